@@ -10,16 +10,21 @@ One "step" = one pass of the hot loop of train_quantized_transformer.py (referen
   AdaLN-Zero on window positions) -> CE -> backward -> [RCCL all-reduce] -> Adam.
 value = image tokens trained per second, whole job (weak scaling: 64 latents / GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--full]
+                    [--dump-outputs DIR]
 
 With --gpus N > 1 and no torchrun environment the script launches its own N ranks
 (`python -m torch.distributed.run --nproc-per-node N ... bench.py ...`) BEFORE anything
 touches a GPU and exits with their code; under torchrun it is one rank of the job.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline`
-(the MFMA GEMM family, timed with HIP events around every launch in a short second
-pass -- the headline loop carries no per-launch events) and `cpu_baseline` (the
-torch-CPU oracle of the same step on the host cores, a bounded sample).
+Prints ONE JSON line on rank 0: the headline figure of W untimed and K timed steps.  Everything
+else is measured only with --full: `roofline` (the MFMA GEMM family, timed with HIP events around
+every launch in a short second pass -- the headline loop carries no per-launch events), `bmu`,
+`cpu_baseline` (the torch-CPU oracle of the same step on the host cores, a bounded sample),
+`allreduce` (N > 1), the side configurations `configs` (config 2 on one GPU) and, for config 3,
+the other cascade orders, the decode step and the conv decoder.  --dump-outputs DIR writes what
+the last timed step left to its caller as DIR/<name>.npy (float32; a fixed, seeded sample of
+the parameters and gradients).
 """
 import argparse
 import json
@@ -73,8 +78,15 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-events", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement also run every side measurement (roofline event pass, BMU "
+                         "launch, CPU oracle, standalone all-reduce, side configurations; for c3 the other cascade "
+                         "orders, the decode step and the conv decoder); a plain run times the steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss; a fixed, seeded sample of the updated "
+                         "parameters and their gradients; for c3 the generated tokens) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip cpu_baseline")
+    ap.add_argument("--no-kernel-events", action="store_true", help="(with --full) skip the roofline event pass")
     ap.add_argument("--precision", choices=["f32", "bf16", "fp8"], default=None,
                     help="f32 = the parity mode and the headline number (default for c2/c4); bf16 / "
                          "fp8 = opt-in reduced precision (Linear GEMMs + attention products on the "
@@ -94,7 +106,7 @@ def parse_args(argv=None):
                          "(csrc/gemm_x3.hip, option gemm_x3): fp32 operands, results and tolerances, reported under its "
                          "own dtype and workload tag")
     ap.add_argument("--no-side-configs", action="store_true",
-                    help="default c2 run on one GPU: do not append the short c3 / c4-shard / c5-shard measurements "
+                    help="--full c2 run on one GPU: do not append the short c3 / c4-shard / c5-shard measurements "
                          "(`configs` object)")
     ap.add_argument("--batch", type=int, default=None, help="override the per-GPU batch")
     return ap.parse_args(argv)
@@ -149,6 +161,28 @@ def stub_main(args):
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE = 1 << 22      # entries per dumped parameter / gradient sample: 16 MiB each in float32
+
+
+def dump_sample_index(total, n=DUMP_SAMPLE, seed=0):
+    """Fixed, seeded sample of n positions in [0, total), one drawn in each of n equal strides (every
+    position when total <= n).  The same for every run and every build of the same configuration."""
+    import numpy as np
+    if total <= n:
+        return np.arange(total, dtype=np.int64)
+    stride = total // n
+    return np.arange(n, dtype=np.int64) * stride + np.random.default_rng(seed).integers(0, stride, n)
+
+
+def dump_outputs(out_dir, arrays):
+    """arrays: name -> numpy array (float32 / float64), written as out_dir/<name>.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def build_models(device, cfg, seed=3):
@@ -267,9 +301,9 @@ def bmu_side_measure(device, K=512):
 def run_c3(args):
     """BASELINE config 3 on one GPU: the cascade of generate_images.py:101-366 -- in the reference's draw order
     (the independent candidates of a chunk run as rows of one batch, every draw numbered as the reference's
-    candidate-after-candidate loop numbers it: same draws -> same tokens), the same with the candidates
-    literally one after the other, and with --batch-beams (draws numbered by row) -- the decode step alone
-    (graph replay) with its weight-streaming roofline, and codebook gather + conv decoder.  `steps` timed
+    candidate-after-candidate loop numbers it: same draws -> same tokens); with --full also the same with the
+    candidates literally one after the other, and with --batch-beams (draws numbered by row) -- the decode step
+    alone (graph replay) with its weight-streaming roofline, and codebook gather + conv decoder.  `steps` timed
     cascades after `warmup` untimed ones; value = accepted image tokens per second in the reference's order."""
     import torch
     sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -291,8 +325,8 @@ def run_c3(args):
     # decode caches it keeps per model (conditioning tables, captured step graphs); `first_call` = the same
     # cascade on freshly built models (nothing to re-use)
     models = [bg.build_stage_model(s_, K, dev) for s_ in range(3)]
-    for name, batched in (("sequential", False), ("first_call", False), ("sequential_one_by_one", False),
-                          ("batched_beams", True)):
+    orders = (("sequential", False), ("first_call", False), ("sequential_one_by_one", False), ("batched_beams", True))
+    for name, batched in orders if args.full else orders[:1]:
         ns.batch_beams = batched
         sampling.ORDERED_ROWS = 0 if name == "sequential_one_by_one" else ordered_rows
         ms_ = None if name == "first_call" else models
@@ -309,7 +343,25 @@ def run_c3(args):
         res[name] = {"accepted_tokens_per_s": round(toks / gen_s, 1), "cascade_ms": round(gen_s * 1e3, 2),
                      "wall_ms": round(dt * 1e3, 1),
                      "stage_tokens_per_s": [st["accepted_tokens_per_s"] for st in stages]}
+        if name == "sequential" and args.dump_outputs:
+            # the last timed cascade's image tokens (last stage, N x 256; exact in float32)
+            dump_outputs(args.dump_outputs, {"tokens": prev.float().cpu().numpy()})
     sampling.ORDERED_ROWS = ordered_rows
+    out = {"metric": METRIC, "value": res["sequential"]["accepted_tokens_per_s"], "unit": "image-tokens/s",
+           "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+           "ms_per_step": res["sequential"]["cascade_ms"], "higher_is_better": True, "scaling": "weak",
+           "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+           "config": {"workload": C3_NAME, "images": N, "num_beam": 4, "beam_width": 4, "window": 256,
+                      "sampler": "fused in-graph sampling kernel (inverse CDF from device-generator uniforms)",
+                      "step": "one cascade = 1344 accepted tokens (value: the reference's draw order -- the 4 "
+                              "independent candidates of a chunk as rows of one batch, each draw numbered as the "
+                              "reference's candidate loop numbers it; sequential_one_by_one: the candidates "
+                              "literally one after the other; batched_beams: draws numbered by row; the stage "
+                              "models are kept for the run as a loaded generator keeps them -- first_call: the "
+                              "same cascade on freshly built models, no decode cache to re-use)"}}
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        return
     # the decode step alone: encoder-decoder stage, 4 and 16 rows, graph replay; algorithmic bytes = the fp32
     # weights one step streams (every Linear of the decoder blocks + classifier; the cond projections are a
     # per-position table row, the embedding one row per sequence)
@@ -350,38 +402,26 @@ def run_c3(args):
         torch.cuda.synchronize()
         img_s = N / ((time.perf_counter() - t0) / 20)
     gbps = wbytes / (step[16] * 1e-3) / 1e9
-    out = {"metric": METRIC, "value": res["sequential"]["accepted_tokens_per_s"], "unit": "image-tokens/s",
-           "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-           "ms_per_step": res["sequential"]["cascade_ms"], "higher_is_better": True, "scaling": "weak",
-           "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-           "config": {"workload": C3_NAME, "images": N, "num_beam": 4, "beam_width": 4, "window": 256,
-                      "sampler": "fused in-graph sampling kernel (inverse CDF from device-generator uniforms)",
-                      "step": "one cascade = 1344 accepted tokens (value: the reference's draw order -- the 4 "
-                              "independent candidates of a chunk as rows of one batch, each draw numbered as the "
-                              "reference's candidate loop numbers it; sequential_one_by_one: the candidates "
-                              "literally one after the other; batched_beams: draws numbered by row; the stage "
-                              "models are kept for the run as a loaded generator keeps them -- first_call: the "
-                              "same cascade on freshly built models, no decode cache to re-use)"},
-           "c3": {"sequential": res["sequential"], "first_call": res["first_call"],
-                  "sequential_one_by_one": res["sequential_one_by_one"],
-                  "batched_beams": res["batched_beams"],
-                  "decode_step_ms_rows4": round(step[4], 4), "decode_step_ms_rows16": round(step[16], 4),
-                  "decoder_images_per_s": round(img_s, 1)},
-           "roofline": {"bound": "hbm", "kernel": "qarig::decode_linear_kernel<*> chain of one encoder-decoder "
-                                                  "decode step (80 dependent launches, 16 rows = 4 images x 4 "
-                                                  "candidates, HIP graph replay)",
-                        "achieved": round(gbps, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                        "frac": round(gbps / HBM_PEAK_GBPS, 4), "traffic": None,
-                        "algorithmic_bytes_per_step": wbytes,
-                        "rows4_GBps": round(wbytes / (step[4] * 1e-3) / 1e9, 1),
-                        "note": "weights streamed once per step / replay time; the step is bound by its ~80 "
-                                "dependent launch boundaries (1.7 us each measured) and memory round trips, "
-                                "not by bytes"}}
+    out["c3"] = {"sequential": res["sequential"], "first_call": res["first_call"],
+                 "sequential_one_by_one": res["sequential_one_by_one"],
+                 "batched_beams": res["batched_beams"],
+                 "decode_step_ms_rows4": round(step[4], 4), "decode_step_ms_rows16": round(step[16], 4),
+                 "decoder_images_per_s": round(img_s, 1)}
+    out["roofline"] = {"bound": "hbm", "kernel": "qarig::decode_linear_kernel<*> chain of one encoder-decoder "
+                                                 "decode step (80 dependent launches, 16 rows = 4 images x 4 "
+                                                 "candidates, HIP graph replay)",
+                       "achieved": round(gbps, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                       "frac": round(gbps / HBM_PEAK_GBPS, 4), "traffic": None,
+                       "algorithmic_bytes_per_step": wbytes,
+                       "rows4_GBps": round(wbytes / (step[4] * 1e-3) / 1e9, 1),
+                       "note": "weights streamed once per step / replay time; the step is bound by its ~80 "
+                               "dependent launch boundaries (1.7 us each measured) and memory round trips, "
+                               "not by bytes"}
     print(json.dumps(out), flush=True)
 
 
 def side_configs():
-    """The default run's `configs` object: BASELINE configs 3, 4 (per-GPU shard) and 5 (per-GPU shard) measured
+    """The --full run's `configs` object: BASELINE configs 3, 4 (per-GPU shard) and 5 (per-GPU shard) measured
     for a few steps each -- and configs 2 and 4 again under the opt-in kernel option gemm_x3 --, every one by this
     script in a child process (started after the headline measurement; the parent only waits), reduced to the
     fields a reader compares."""
@@ -395,7 +435,7 @@ def side_configs():
     for name, flags in runs:
         t0 = time.perf_counter()
         try:
-            r = subprocess.run([sys.executable, os.path.abspath(__file__)] + flags + ["--no-side-configs"],
+            r = subprocess.run([sys.executable, os.path.abspath(__file__)] + flags + ["--full", "--no-side-configs"],
                                capture_output=True, text=True, timeout=150, cwd=ROOT)
             lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
             if r.returncode != 0 or not lines:
@@ -500,11 +540,19 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # what the last timed step hands its caller: the loss, and the parameters and gradients it left in the
+        # optimizer's flat buffers (the same fixed, seeded sample of each; identical on every rank)
+        idx = torch.from_numpy(dump_sample_index(optim.total)).to(device)
+        dump_outputs(args.dump_outputs, {"loss": loss.detach().float().reshape(1).cpu().numpy(),
+                                         "params": optim.flat_param[idx].float().cpu().numpy(),
+                                         "grads": optim.flat_grad[idx].float().cpu().numpy()})
+        del idx
 
-    # second, short pass: HIP events around every GEMM launch (on the launch stream) for the
+    # --full: second, short pass: HIP events around every GEMM launch (on the launch stream) for the
     # roofline object; kept out of the headline loop, which carries no per-launch events
     events = []
-    if not args.no_kernel_events:
+    if args.full and not args.no_kernel_events:
         ev_steps = min(2, args.steps)
         ops.GEMM_EVENTS = []
         t1 = time.perf_counter()
@@ -516,7 +564,7 @@ def main():
 
     # the gradient exchange on its own (the timed loop overlaps it with backward)
     allreduce = None
-    if world > 1:
+    if world > 1 and args.full:
         flat = optim.flat_grad
         parallel.allreduce_flat(flat)
         fence()
@@ -648,10 +696,12 @@ def main():
                     "achieved": round(f8fl / f8ms / 1e9, 2), "peak": PEAK_FP8_MFMA_TFLOPS, "unit": "TFLOP/s",
                     "frac": round(f8fl / f8ms / 1e9 / PEAK_FP8_MFMA_TFLOPS, 4),
                     "share_of_gemm_flops": round(f8fl / fl_all, 3)}
-        out["bmu"] = bmu_side_measure(device)
-        if not args.no_cpu_baseline and world == 1 and args.config == "c2":
+        if args.full:
+            out["bmu"] = bmu_side_measure(device)
+        if args.full and not args.no_cpu_baseline and world == 1 and args.config == "c2":
             out["cpu_baseline"] = cpu_baseline(cfg)
-        if world == 1 and args.config == "c2" and not args.no_side_configs and precision == "f32" and not x3:
+        if args.full and world == 1 and args.config == "c2" and not args.no_side_configs and precision == "f32" \
+                and not x3:
             out["configs"] = side_configs()
         print(json.dumps(out), flush=True)
     if world > 1:

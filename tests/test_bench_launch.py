@@ -35,6 +35,17 @@ def test_bench_gpus1_runs_in_process():
     assert len(lines) == 1 and json.loads(lines[0])["n_gpus"] == 1
 
 
+def test_dump_sample_index_is_fixed_and_in_range():
+    # --dump-outputs samples the flat parameter / gradient buffers at these positions: the same for every run
+    import numpy as np
+    import bench
+    total = 78_226_433
+    a, b = bench.dump_sample_index(total), bench.dump_sample_index(total)
+    assert np.array_equal(a, b) and a.shape == (bench.DUMP_SAMPLE,)
+    assert a.min() >= 0 and a.max() < total and (np.diff(a) > 0).all()
+    assert np.array_equal(bench.dump_sample_index(1000), np.arange(1000))
+
+
 def test_bench_world_mismatch_fails_loudly():
     # under a torchrun-style environment that disagrees with --gpus the rank must abort
     env = {"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"}

@@ -1,5 +1,6 @@
-"""The driver's contract for bench.py: one JSON line with the agreed keys, the BASELINE
-metric string, the roofline and cpu_baseline objects; and __graft_entry__.smoke()."""
+"""The driver's contract for bench.py: one JSON line with the agreed keys and the BASELINE
+metric string; with --full also the roofline and cpu_baseline objects and the side
+configurations; --dump-outputs; and __graft_entry__.smoke()."""
 import json
 import os
 import subprocess
@@ -18,7 +19,7 @@ KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "
 def test_bench_line_contract():
     env = dict(os.environ, QARIG_CPU_BASELINE_SECONDS="2")
     env.pop("QARIG_GEMM_X3", None)      # (the suite may run under the option; the line under test is the default one)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -61,6 +62,35 @@ def test_bench_line_contract():
         assert "gemm_x3" in side[name]["dtype"] and "gemm_x3" in side[name]["workload"]
     assert out["dtype"] == "f32" and "gemm_x3" not in out["config"]["workload"]
     assert side["c4_shard"]["roofline"]["bound"] == side["c5_shard"]["roofline"]["bound"] == "mfma"
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain run times the steps and measures nothing else; --dump-outputs writes the last timed step's loss
+    and the fixed sample of its parameters and gradients."""
+    import numpy as np
+    import bench
+    env = dict(os.environ)
+    env.pop("QARIG_GEMM_X3", None)
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(d)], capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert KEYS - {"roofline", "cpu_baseline", "configs"} <= set(out)
+    assert not {"roofline", "cpu_baseline", "configs", "bmu", "allreduce"} & set(out)
+    assert out["metric"] == json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"]
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["dtype"] == "f32"
+    assert abs(out["value"] - 64 * 256 / (out["ms_per_step"] / 1e3)) < 0.01 * out["value"]
+    files = sorted(os.listdir(d))
+    assert files == ["grads.npy", "loss.npy", "params.npy"]
+    assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+    got = {f[:-4]: np.load(d / f) for f in files}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert got["params"].shape == got["grads"].shape == (bench.DUMP_SAMPLE,)
+    assert abs(float(got["loss"][0]) - out["config"]["loss"]) < 1e-4
+    assert np.abs(got["grads"]).max() > 0
 
 
 def test_graft_entry_smoke():
