@@ -236,7 +236,8 @@ int qarig_decode_linear_f32(const float* X, int64_t ldx, int64_t x_gs, float eps
  * of QARIG_DECODE_CTL_WORDS words -- [0] window index of the token the next step evaluates,
  * [1] window index at which the current chunk of beam_width tokens starts, [2] draws made so far
  * (row of the uniform / forced / log buffers), [3] candidate chunks evaluated at this position,
- * [4] decoder steps since the candidate began (the chunk slot the next draw fills). */
+ * [4] decoder steps since the candidate began (the chunk slot the next draw fills), [5] tokens in the
+ * window step's token ring (qarig_window_*). */
 #define QARIG_DECODE_CTL_WORDS 8
 
 /* First launch of a step: x[b] = table[ids[b]] + pe[len] (models/Transformer.py:154-167; pe may be
@@ -296,6 +297,39 @@ int qarig_decode_commit(int* ctl, int N, int NB, int beam_width, const int64_t* 
 
 /* ctl[1] += beam_width; ctl[0] = ctl[1]; ctl[3] = 0. */
 int qarig_decode_advance(int* ctl, int beam_width, void* stream);
+
+/* ---- Device-resident evaluation of the slid window (generate_images.py:275-290) ----------------
+ * Once the window slides, the reference re-runs the decoder on the last window - 1 tokens with
+ * window-relative positional embeddings (models/Transformer.py:154-167, dec_pos_index = 1..Seq) and reads
+ * the last token's logits.  These entry points keep that evaluation a replay of one captured graph. */
+
+/* 1 when R sequences (1..16), a window of `window` tokens, model width D (a multiple of 4) and H
+ * self-attention heads (head dim 4, 8, 16, 32 or 64) fit the window step, else 0. */
+int qarig_window_step_supported(int R, int window, int D, int H);
+
+/* The window in front of ring length n = ctl[5]: start = n - W1; x[r][s] = table[ring[r][start + s]] +
+ * pe[s] for s < W1 (pe row s: the sinusoid of window position s + 1, models/Transformer.py:154-167), the
+ * row s = W1 of Wp = W1 + 1 repeats s = W1 - 1 (whole 128-row tiles).  rowmap[r * Wp + s] (optional):
+ * the token's row of the stage's conditioning table -- its absolute position, 0 for ring column 0 and
+ * column + pos_off behind it (generate_images.py:306-322 numbers appended tokens cur + tok + 1);
+ * last_map[r] (optional): that of the last real token.  An id outside [0, V), a position outside [0, P)
+ * or a start outside the ring sets *bad_flag and is clamped. */
+int qarig_window_assemble(const int64_t* ring, int64_t ldr, const int* ctl, int R, int W1, int Wp, int D,
+                          int V, const float* table, const float* pe, int P, int pos_off, float* x,
+                          int* rowmap, int* last_map, int* bad_flag, void* stream);
+
+/* Masked self-attention of the window's last real token (models/layers.py:433-474, the last row of the
+ * causal softmax(q k^T / sqrt(d)) v): q (R, H * d), k / v token-major rows of H * d floats, `rows` per
+ * sequence at batch_stride, the first n_keys of them attended (a pad row behind them is ignored);
+ * o = result (* o_mul at row stride ldmul, 0: one row for all). */
+int qarig_window_attention(const float* q, const float* k, const float* v, int R, int H, int d, int n_keys,
+                           int rows, int64_t batch_stride, const float* o_mul, int64_t ldmul, float* o,
+                           void* stream);
+
+/* The sampled token joins the sequence (generate_images.py:306-310, a torch.cat on the host there):
+ * ring[b][ctl[5]] = ids[b], ctl[5] += 1.  A column outside the ring sets *bad_flag and writes nothing. */
+int qarig_window_append(int* ctl, const int64_t* ids, int64_t* ring, int B, int64_t ldr, int* bad_flag,
+                        void* stream);
 
 /* out[N] = column sums of X[M][N] in a fixed order (bias / LayerNorm-affine grads). */
 size_t qarig_colsum_workspace_bytes(int M, int N);

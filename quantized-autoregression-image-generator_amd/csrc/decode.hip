@@ -407,6 +407,7 @@ enum DecCtl : int {
     CTL_DRAW = 2,    // sampling draws made so far (row of the uniform / forced-token / probability-log buffers)
     CTL_CAND = 3,    // candidate chunks of the current chunk position evaluated so far
     CTL_TOK = 4,     // decoder steps since the candidate began = the chunk slot the next draw fills
+    CTL_RING = 5,    // tokens in the window step's token ring (the slid window ends in front of it)
     CTL_WORDS = 8
 };
 
@@ -769,6 +770,66 @@ __global__ void decode_advance_kernel(int* __restrict__ ctl, int bw) {
         ctl[CTL_TOK] = 0;
     }
 }
+
+// ---------------------------------------------------------------------------------------------
+// The slid window (generate_images.py:275-290) from the device-resident token ring: the window is the
+// W1 = window - 1 tokens in front of ring length n = ctl[CTL_RING], start = n - W1.  Token s of sequence r:
+// x[r][s] = E[ring[r][start + s]] + pe[s] (pe row s: the window-relative sinusoid of position s + 1,
+// Transformer.py:154-167) and its row of the stage's conditioning table: the absolute position of ring
+// column j -- 0 for the first token, j + pos_off behind it (the numbering the loop appends).  Wp = W1 + 1
+// adds the duplicate of the last token that makes R x Wp whole 128-row tiles.  Ids outside [0, V),
+// positions outside [0, P) and a window start outside the ring set *bad and are clamped: never dereferenced.
+__global__ __launch_bounds__(256) void window_assemble_kernel(
+    const int64_t* __restrict__ ring, int64_t ldr, const int* __restrict__ ctl, int R, int W1, int Wp, int D, int V,
+    const float* __restrict__ table, const float* __restrict__ pe, int P, int pos_off, float* __restrict__ x,
+    int* __restrict__ rowmap, int* __restrict__ last_map, int* __restrict__ bad) {
+    int start = ctl[CTL_RING] - W1;
+    if (start < 0 || (int64_t)start + W1 > ldr) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) atomicExch(bad, 1);
+        start = (int)min(max((int64_t)start, (int64_t)0), ldr - W1);
+    }
+    const int dq = D / 4;
+    const int64_t total = (int64_t)R * Wp * dq;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t t = i / dq;                     // token row r * Wp + s
+        const int c = (int)(i - t * dq) * 4;
+        const int r = (int)(t / Wp), s = (int)(t - (int64_t)r * Wp);
+        const int j = start + min(s, W1 - 1);         // the pad row repeats the last token and its position
+        const int64_t id = ring[(int64_t)r * ldr + j];
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (id < 0 || id >= V) {
+            if (c == 0) atomicExch(bad, 1);
+        } else {
+            v = ld4(table + id * D + c);
+            const float4 q = ld4(pe + (int64_t)s * D + c);
+            v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w;
+        }
+        *reinterpret_cast<float4*>(x + t * D + c) = v;
+        if (c == 0 && rowmap) {
+            int p = j == 0 ? 0 : j + pos_off;
+            if (p < 0 || p >= P) {
+                atomicExch(bad, 1);
+                p = min(max(p, 0), P - 1);
+            }
+            rowmap[t] = p;
+            if (last_map && s == W1 - 1) last_map[r] = p;
+        }
+    }
+}
+
+// The sampled ids join the ring: ring[b][n] = ids[b], n = ctl[CTL_RING] += 1 (the host's torch.cat of
+// generate_images.py:306-310).  A column outside the ring sets *bad and writes nothing.
+__global__ __launch_bounds__(64) void window_append_kernel(int* __restrict__ ctl, const int64_t* __restrict__ ids,
+                                                           int64_t* __restrict__ ring, int B, int64_t ldr,
+                                                           int* __restrict__ bad) {
+    const int n = ctl[CTL_RING];
+    const bool ok = n >= 0 && n < ldr;
+    for (int b = threadIdx.x; b < B; b += 64)
+        if (ok) ring[(int64_t)b * ldr + n] = ids[b];
+    if (!ok && threadIdx.x == 0) atomicExch(bad, 1);
+    __syncthreads();
+    if (threadIdx.x == 0) ctl[CTL_RING] = n + 1;
+}
 }  // namespace qarig
 
 using namespace qarig;
@@ -1028,5 +1089,59 @@ extern "C" int qarig_decode_advance(int* ctl, int beam_width, void* stream) {
     QARIG_CHECK_ARG(ctl && beam_width > 0, "decode_advance: bad arguments");
     hipLaunchKernelGGL(decode_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, ctl, beam_width);
     QARIG_CHECK_LAUNCH("decode_advance");
+    return QARIG_OK;
+}
+
+extern "C" int qarig_window_step_supported(int R, int window, int D, int H) {
+    if (R < 1 || R > 16 || window < 2 || window > 65536 || D < 4 || D % 4 || H < 1 || D % H) return 0;
+    const int d = D / H;
+    return d == 4 || d == 8 || d == 16 || d == 32 || d == 64;
+}
+
+extern "C" int qarig_window_assemble(const int64_t* ring, int64_t ldr, const int* ctl, int R, int W1, int Wp, int D,
+                                     int V, const float* table, const float* pe, int P, int pos_off, float* x,
+                                     int* rowmap, int* last_map, int* bad_flag, void* stream) {
+    QARIG_CHECK_ARG(ring && ctl && table && pe && x && bad_flag, "window_assemble: null pointer");
+    QARIG_CHECK_ARG(R > 0 && W1 > 0 && (Wp == W1 || (int64_t)Wp == (int64_t)W1 + 1) && D > 0 && D % 4 == 0 && V > 0 && ldr >= W1,
+                    "window_assemble: bad extents (Wp = W1 or W1 + 1, D %% 4 == 0, ldr >= W1)");
+    QARIG_CHECK_ARG(!rowmap || (P > 0 && pos_off >= 0 && pos_off <= 1), "window_assemble: rowmap needs P > 0, pos_off 0 or 1");
+    QARIG_CHECK_ARG(!last_map || rowmap, "window_assemble: last_map needs rowmap");
+    QARIG_CHECK_DIMS("window_assemble", R, Wp, D);
+    QARIG_CHECK_DIMS("window_assemble", V, D);
+    QARIG_CHECK_ARG(qarig_dims_ok({R, ldr}, 1LL << 24, 1LL << 40), "window_assemble: ring too large");
+    auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
+    QARIG_CHECK_ARG(al16(table) && al16(pe) && al16(x), "window_assemble: operands must be 16-B aligned");
+    const int64_t items = (int64_t)R * Wp * (D / 4);
+    const int blocks = (int)((items + 255) / 256 < 2048 ? (items + 255) / 256 : 2048);
+    hipLaunchKernelGGL(window_assemble_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, ring, ldr, ctl, R, W1,
+                       Wp, D, V, table, pe, P, pos_off, x, rowmap, last_map, bad_flag);
+    QARIG_CHECK_LAUNCH("window_assemble");
+    return QARIG_OK;
+}
+
+// The last real query of every window against its keys: decode_attention_kernel in its row-major
+// (token-major) addressing, no appended row, n_keys keys of the `rows` the projections wrote.
+extern "C" int qarig_window_attention(const float* q, const float* k, const float* v, int R, int H, int d,
+                                      int n_keys, int rows, int64_t batch_stride, const float* o_mul, int64_t ldmul,
+                                      float* o, void* stream) {
+    QARIG_CHECK_ARG(q && k && v && o, "window_attention: null pointer");
+    QARIG_CHECK_ARG(d == 4 || d == 8 || d == 16 || d == 32 || d == 64,
+                    "window_attention: head dim %d unsupported (4,8,16,32,64)", d);
+    QARIG_CHECK_ARG(R > 0 && H > 0 && n_keys > 0 && rows >= n_keys, "window_attention: bad extents (0 < n_keys <= rows)");
+    QARIG_CHECK_DIMS("window_attention", R, H, rows);
+    QARIG_CHECK_ARG(batch_stride >= (int64_t)rows * H * d && batch_stride % 4 == 0 && batch_stride <= (1LL << 40),
+                    "window_attention: batch stride shorter than rows * H * d");
+    return qarig_decode_attention(q, nullptr, nullptr, const_cast<float*>(k), const_cast<float*>(v), R, H, d, n_keys,
+                                  nullptr, rows, batch_stride, d, (int64_t)H * d, sqrtf((float)d), o_mul, ldmul, o,
+                                  stream);
+}
+
+extern "C" int qarig_window_append(int* ctl, const int64_t* ids, int64_t* ring, int B, int64_t ldr, int* bad_flag,
+                                   void* stream) {
+    QARIG_CHECK_ARG(ctl && ids && ring && bad_flag, "window_append: null pointer");
+    QARIG_CHECK_ARG(B > 0 && ldr > 0 && qarig_dims_ok({B, ldr}, 1LL << 24, 1LL << 40), "window_append: bad extents");
+    hipLaunchKernelGGL(window_append_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, ctl, ids, ring, B, ldr,
+                       bad_flag);
+    QARIG_CHECK_LAUNCH("window_append");
     return QARIG_OK;
 }

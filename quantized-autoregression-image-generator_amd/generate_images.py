@@ -41,6 +41,11 @@ def parse_args():
     p.add_argument("--no-kv-cache", action="store_true",
                    help="re-run the whole window for every token like the reference instead of "
                         "decoding one token per step from a key/value cache")
+    p.add_argument("--window-graph", action="store_true",
+                   help="(additive) once the sliding window slides, evaluate each token as one replay of a captured "
+                        "graph on the GPU instead of an eager pass over the window.  Applies only to the fused "
+                        "sampler, images x num_beam <= 16 and models with a cache kernel (head dim <= 64); "
+                        "elsewhere it is ignored.")
     return vars(p.parse_args())
 
 
@@ -108,7 +113,8 @@ def main():
                     md["sliding_window"], end_token=k_hr, shift=shift, num_beam=data["num_beam"],
                     beam_width=data["beam_width"], mode="generate",
                     progress=lambda i, t: log(f"{i:,} / {t:,}"), batch_beams=args["batch_beams"],
-                    use_kv_cache=not args["no_kv_cache"], sampler=args["sampler"])
+                    use_kv_cache=not args["no_kv_cache"], sampler=args["sampler"],
+                    window_graph=args["window_graph"])
                 hr_input = hr_input[:, 1:] - shift
             else:                                        # more ranks than images: nothing to generate here
                 hr_input = torch.zeros((0, total_Seq), dtype=torch.int64, device=device)

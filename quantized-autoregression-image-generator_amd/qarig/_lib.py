@@ -87,6 +87,10 @@ SIGNATURES = {
     "qarig_decode_rows": (I, [P, P, P, P, I, I, I, I, I, I, I, I, P]),
     "qarig_decode_commit": (I, [P, I, I, I, P, P, L, P, P]),
     "qarig_decode_advance": (I, [P, I, P]),
+    "qarig_window_step_supported": (I, [I, I, I, I]),
+    "qarig_window_assemble": (I, [P, L, P, I, I, I, I, I, P, P, I, I, P, P, P, P, P]),
+    "qarig_window_attention": (I, [P, P, P, I, I, I, I, I, L, P, L, P, P]),
+    "qarig_window_append": (I, [P, P, P, I, L, P, P]),
     "qarig_attention_bwd": (I, [P, P, P, P, P, P, I, I, I, I, I, I, F, P, P, P, P, P]),
     "qarig_cross_entropy_fwd": (I, [P, P, I, I, P, P, P, P, P]),
     "qarig_mse_workspace_bytes": (Z, []),

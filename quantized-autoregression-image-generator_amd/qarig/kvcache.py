@@ -27,14 +27,17 @@ graph, all reading and writing device state; the host enqueues them without read
 stage is finished.
 
 The cache stops being valid when the window slides (every token's window index shifts);
-`sampling.generate_tokens` falls back to the full-window evaluation from there on.
+`sampling.generate_tokens` falls back to the full-window evaluation from there on.  `WindowStep` keeps that
+evaluation on the device too (opt-in, `generate_tokens(window_graph=True)`): it cannot reuse keys and values
+either -- a slide changes the window-relative positional embedding of every token -- but everything around the
+recomputation is built once per stage and the evaluation itself is one graph replay.
 """
 import os
 from types import SimpleNamespace
 
 import torch
 
-from models.layers import _lin_params, _mlp2_forward
+from models.layers import _lin_params, _mlp2_forward, _norm_forward
 from . import functional as QF
 from . import ops
 
@@ -514,3 +517,175 @@ class DecodeCache:
         """(N, 1 + chunks * beam_width) tokens of the sequences, first token included."""
         s = self._search
         return s.tokens[:, :1 + s.chunks * s.bw].clone()
+
+
+def _mlp2_rows(seq, x, out=None):
+    """The two-layer MLP `seq` on R <= 16 rows x (R, K): the weight-streaming decode kernel when the shapes
+    fit it, the general kernels otherwise.  Returns (R, N) (written into `out` when given)."""
+    (w1, b1), (w2, b2) = _lin_params(seq[0]), _lin_params(seq[1])
+    R, K = x.shape
+    if b1 is not None and b2 is not None and ops.decode_linear_supported(R, w1.shape[0], K, False) and \
+            ops.decode_linear_supported(R, w2.shape[0], w2.shape[1], False):
+        hid = ops.decode_linear(x, w1, b1, seq[0]._act)
+        return ops.decode_linear(hid, w2, b2, seq[1]._act, out=out)
+    y = _mlp2_forward(seq, x.reshape(R, 1, K)).reshape(R, -1)
+    if out is not None:
+        out.copy_(y)
+        return out
+    return y
+
+
+class WindowStep:
+    """One evaluation of the slid window (generate_images.py:275-290): the last `window - 1` tokens of each of
+    `rows` sequences through `model.decode` with window-relative positional embeddings, logits of the last token.
+
+    The tokens live in a device ring (rows, capacity) whose length is the control word ctl[5]
+    (`ops.window_append` adds the sampled ids); the evaluation reads nothing from the host, so it is captured
+    once and replayed:
+      window assembly (embedding + sinusoid, the row of every token in the conditioning table) ->
+      decoder layers 0 .. L-2 on all rows (the model's own layer forwards) ->
+      last layer: norm and the k / v MLPs on all rows, then q, attention, residual, cross-attention and
+      feed-forward on the last real row of each sequence alone -> classifier on those rows.
+    Built once: the conditioning table of positions 0 .. pos_bound with every ScaleLayer / ShiftLayer
+    projection of it (models/layers.py:100-153, 258-304), and the cross-attention k / v of the encoder output
+    for every layer (`rebind` recomputes them for another stage's encoder output).
+    pos_off: the loop's position numbering (1: generate_images.py:306-322, cur + tok + 1; 0: training's)."""
+
+    def __init__(self, model, enc, rows, window, capacity, pos_bound, pos_off, graph=True):
+        table = model.dec_embedding.weight
+        self.model, self.rows, self.window = model, int(rows), int(window)
+        self.dim, dev = table.shape[1], table.device
+        heads = model.decoder_layers[-1].self_attn_block.self_attn.heads
+        if not ops.window_step_supported(self.rows, self.window, self.dim, heads):
+            raise ValueError(f"WindowStep: {rows} rows, window {window}, width {self.dim}, {heads} heads do not fit "
+                             "the window kernels (<= 16 rows, head dim 4 ... 64)")
+        if not all(l.self_attn_block.self_attn.use_masked_attn for l in model.decoder_layers):
+            raise ValueError("WindowStep: needs causal decoder self-attention")
+        R, D = self.rows, self.dim
+        self.W1 = self.window - 1
+        # rows x (window - 1) is no whole number of 128-row GEMM tiles; one duplicate of the last token behind
+        # it makes one and changes nothing before it (causal attention, everything else per token)
+        self.pad = (R * self.W1) % 128 != 0 and (R * (self.W1 + 1)) % 128 == 0
+        self.Wp = self.W1 + int(self.pad)
+        self.pos_off = int(pos_off)
+        self.ring = torch.zeros((R, int(capacity)), dtype=torch.int64, device=dev)
+        self.ctl = torch.zeros(ops.DECODE_CTL_WORDS, dtype=torch.int32, device=dev)
+        self.pe = model._sequence_pe(self.Wp, D, dev)
+        self.x = torch.empty((R, self.Wp, D), dtype=torch.float32, device=dev)
+        self.logits = torch.empty((R, _lin_params(model.classifier[1])[0].shape[0]), dtype=torch.float32, device=dev)
+        self.cond = self.cond_last = self.rowmap = self.last_map = None
+        self.P = 0
+        with torch.no_grad():
+            if model.use_pos_cond:
+                self._build_table(pos_bound)
+            self.cross = [None] * len(model.decoder_layers)
+            self._enc_shape = None if enc is None else tuple(enc.shape)
+            self._cross_kv(enc)
+        self._graph = None
+        if graph:
+            self._capture()
+
+    def _build_table(self, pos_bound):
+        """cond of positions 0 .. P-1 (P: pos_bound in whole 128-row tiles, as Transformer._cond sizes it) and
+        every projection of it, evaluated here once; the graph only gathers rows of them."""
+        model, D, dev = self.model, self.dim, self.ring.device
+        P = (int(pos_bound) + 127) // 128 * 128
+        tab = _mlp2_forward(model.pos_cond_layer, ops.posemb(torch.arange(P, device=dev), D))
+        R, Wp = self.rows, self.Wp
+        self.rowmap = torch.zeros(R * Wp, dtype=torch.int32, device=dev)
+        self.last_map = torch.zeros(R, dtype=torch.int32, device=dev)
+        groups = model._cond_linear_groups()
+        self.cond = QF.CondTable(tab, self.rowmap, (R, Wp), groups=groups)
+        self.cond_last = QF.CondTable(tab, self.last_map, (R, 1), groups=groups)
+        for lin in (l for per in model._cond_linears_per_layer() for l in per):
+            self.cond._proj[id(lin)] = self.cond.projection(lin)
+        self.cond_last._proj = self.cond._proj
+        # the assembly kernel writes in-range rows (clamped, flagged) straight into the maps the consumers read
+        self.cond.idx, self.cond_last.idx = self.rowmap, self.last_map
+        self.P = P
+
+    def _cross_kv(self, enc):
+        for li, layer in enumerate(self.model.decoder_layers):
+            if not layer.use_cross_attn:
+                continue
+            at = layer.cross_attn_block.cross_attn
+            k, v = _mlp2_forward(at.k_block, enc), _mlp2_forward(at.v_block, enc)
+            if self.cross[li] is None:
+                self.cross[li] = (k, v)
+            else:
+                self.cross[li][0].copy_(k)
+                self.cross[li][1].copy_(v)
+
+    @torch.no_grad()
+    def rebind(self, enc):
+        """The step for another stage with the same weights and shapes: the encoder output's cross-attention
+        k / v are recomputed into the tensors the graph reads.  False when its shape differs."""
+        if (None if enc is None else tuple(enc.shape)) != self._enc_shape:
+            return False
+        self._cross_kv(enc)
+        return True
+
+    @torch.no_grad()
+    def load(self, tokens):
+        """tokens (rows, n) int64: the sequences so far; the ring holds them and its length becomes n."""
+        n = tokens.shape[1]
+        if not 0 < n <= self.ring.shape[1]:
+            raise ValueError(f"WindowStep.load: {n} tokens for a ring of {self.ring.shape[1]}")
+        self.ring[:, :n].copy_(tokens)
+        self.ctl[ops.CTL_RING:ops.CTL_RING + 1].fill_(n)
+
+    def append(self, ids):
+        """ids (rows,) int64 join the ring (device-side length)."""
+        ops.window_append(self.ctl, self.ring, ids)
+
+    def rewind(self, n):
+        """The ring's length back to n (a candidate chunk starts over at the chunk position)."""
+        self.ctl[ops.CTL_RING:ops.CTL_RING + 1].fill_(int(n))
+
+    def _capture(self):
+        dev = self.ring.device
+        saved = self.ctl.clone()
+        self.ctl[ops.CTL_RING:ops.CTL_RING + 1].fill_(self.W1)     # a valid window for the warm-up
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side), torch.no_grad():
+            self._forward()                      # kernel loads and workspace growth happen outside the capture
+        torch.cuda.current_stream(dev).wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph), torch.no_grad():
+            self._forward()
+        self.ctl.copy_(saved)
+        self._graph = graph
+
+    @torch.no_grad()
+    def evaluate(self):
+        """Logits (rows, V) of the last token of the window in front of the ring's length (a buffer that the
+        next evaluation overwrites)."""
+        if self._graph is not None:
+            self._graph.replay()
+        else:
+            self._forward()
+        return self.logits
+
+    def _forward(self):
+        model, R, D = self.model, self.rows, self.dim
+        ops.window_assemble(self.ring, self.ctl, model.dec_embedding.weight, self.pe, self.W1, self.pad, self.x,
+                            self.rowmap, self.last_map, self.P, self.pos_off)
+        x, cond = self.x, self.cond
+        layers = model.decoder_layers
+        for li, layer in enumerate(layers[:-1]):
+            x = layer(x=x, cross_cond=None, pos_cond=cond, cross_kv=self.cross[li])
+        layer, last = layers[-1], self.W1 - 1
+        sab = layer.self_attn_block
+        at = sab.self_attn
+        h, _ = _norm_forward(sab.self_attn_norm, x, cond, sab.use_adaln0)
+        k = _mlp2_forward(at.k_block, h)
+        v = _mlp2_forward(at.v_block, h)
+        q = _mlp2_rows(at.q_block, h[:, last].contiguous())
+        o = ops.window_attention(q, k, v, self.W1, at.heads)
+        # from here on only the last real token of each sequence is read (logits[:, -1])
+        x = sab.self_attn_res(x=o.reshape(R, 1, D), x_skip=x[:, last:last + 1].contiguous(), cond=self.cond_last)
+        if layer.use_cross_attn:
+            x = layer.cross_attn_block(x, cross_cond=None, cond=self.cond_last, kv=self.cross[-1])
+        x = layer.feedforward_block(x, cond=self.cond_last)
+        _mlp2_rows(model.classifier, x.reshape(R, D), out=self.logits)

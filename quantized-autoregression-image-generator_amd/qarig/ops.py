@@ -1082,6 +1082,61 @@ def decode_advance(ctl, beam_width):
     check(_lib.load().qarig_decode_advance(ptr(ctl), int(beam_width), stream()), "qarig_decode_advance")
 
 
+CTL_RING = 5                  # include/qarig.h: ctl[5], tokens in the window step's token ring
+
+
+def window_step_supported(R, window, D, heads):
+    return bool(_lib.load().qarig_window_step_supported(int(R), int(window), int(D), int(heads)))
+
+
+def window_assemble(ring, ctl, table, pe, W1, pad, x, rowmap=None, last_map=None, P=0, pos_off=0):
+    """The slid window in front of ring length ctl[5] into x (R, W1 + pad, D) (+ the rows of the conditioning
+    table into rowmap (R * (W1 + pad),) and that of each last real token into last_map (R,)); see
+    include/qarig.h qarig_window_assemble."""
+    require_cuda(ring, ctl, table, pe, x, rowmap, last_map)
+    R, ldr = ring.shape
+    Wp = int(W1) + int(bool(pad))
+    V, D = table.shape
+    assert ring.dtype == torch.int64 and ring.stride(1) == 1 and ctl.dtype == torch.int32 and ctl.numel() > CTL_RING
+    assert table.is_contiguous() and pe.is_contiguous() and pe.shape[0] >= Wp and pe.shape[1] == D
+    assert x.shape == (R, Wp, D) and x.is_contiguous() and x.dtype == torch.float32
+    for t, n in ((rowmap, R * Wp), (last_map, R)):
+        assert t is None or (t.dtype == torch.int32 and t.numel() == n and t.is_contiguous())
+    check(_lib.load().qarig_window_assemble(ptr(ring), ring.stride(0), ptr(ctl), R, int(W1), Wp, D, V, ptr(table),
+                                            ptr(pe), int(P), int(pos_off), ptr(x), ptr(rowmap), ptr(last_map),
+                                            ptr(_bad_flag(table.device)), stream()), "qarig_window_assemble")
+
+
+def window_attention(q, k, v, n_keys, heads, o_mul=None, out=None):
+    """q (R, D): the last real token of each window; k / v (R, rows, D) token-major (rows >= n_keys; rows past
+    n_keys -- the pad row -- are not attended).  Returns o (R, D)."""
+    require_cuda(q, k, v, o_mul, out)
+    R, D = q.shape
+    rows = k.shape[1]
+    assert k.shape == v.shape and k.shape[0] == R and k.shape[2] == D and k.stride() == v.stride()
+    assert k.stride(2) == 1 and k.stride(1) == D and q.is_contiguous()
+    o = out if out is not None else torch.empty_like(q)
+    assert o.shape == q.shape and o.is_contiguous()
+    ldmul = 0
+    if o_mul is not None:
+        assert o_mul.shape in (q.shape, (D,)) and o_mul.is_contiguous()
+        ldmul = D if o_mul.dim() == 2 else 0
+    check(_lib.load().qarig_window_attention(ptr(q), ptr(k), ptr(v), R, int(heads), D // int(heads), int(n_keys),
+                                             rows, k.stride(0), ptr(o_mul), ldmul, ptr(o), stream()),
+          "qarig_window_attention")
+    return o
+
+
+def window_append(ctl, ring, ids):
+    """ring[b][ctl[5]] = ids[b], ctl[5] += 1."""
+    require_cuda(ctl, ring, ids)
+    B, ldr = ring.shape
+    assert ring.dtype == torch.int64 and ring.stride(1) == 1 and ctl.dtype == torch.int32 and ctl.numel() > CTL_RING
+    assert ids.dtype == torch.int64 and ids.numel() == B and ids.is_contiguous()
+    check(_lib.load().qarig_window_append(ptr(ctl), ptr(ids), ptr(ring), B, ring.stride(0),
+                                          ptr(_bad_flag(ring.device)), stream()), "qarig_window_append")
+
+
 def attention_bwd(q, k, v, o, dO, lse, heads, causal, scale_dim=None):
     N, Sq, D = q.shape
     Sk = k.shape[1]

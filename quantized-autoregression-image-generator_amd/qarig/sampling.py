@@ -17,7 +17,7 @@ import os
 import torch
 
 from . import ops
-from .kvcache import DecodeCache
+from .kvcache import DecodeCache, WindowStep
 
 
 def _sample(logits, temperature, end_token, mode, rows, comb):
@@ -97,6 +97,7 @@ DECODE_CACHE_SLOTS = 8
 
 def decode_cache_clear():
     _DECODE_CACHES.clear()
+    _WINDOW_STEPS.clear()
 
 
 def _weights_key(model):
@@ -122,6 +123,83 @@ def decode_cache(model, enc, batch, limit, positions):
         _DECODE_CACHES.pop(next(iter(_DECODE_CACHES)))
     _DECODE_CACHES[slot] = (weakref.ref(model), wkey, cache)
     return cache
+
+
+# Window steps (kvcache.WindowStep: the slid window's evaluation as one captured graph, generate_tokens(
+# window_graph=True)) kept per model like the decode caches.  Their key adds ops.LP_EPOCH to the weights' state:
+# every write into the flat parameter buffer (FlatAdam's steps, load_state_dict, parallel.broadcast_params) bumps
+# it, and the step holds projections of the weights (conditioning table, cross-attention k / v).
+_WINDOW_STEPS = {}
+WINDOW_STEP_SLOTS = 4
+
+
+def window_step(model, enc, rows, window, capacity, pos_bound, pos_off):
+    """A WindowStep for these shapes -- a kept one re-bound to `enc` when the weights have not changed since it
+    was built, a new one otherwise."""
+    import weakref
+    slot = (id(model), rows, window, capacity, pos_bound, pos_off, None if enc is None else tuple(enc.shape))
+    wkey = (_weights_key(model), ops.LP_EPOCH)
+    hit = _WINDOW_STEPS.pop(slot, None)
+    if hit is not None and hit[0]() is model and hit[1] == wkey and hit[2].rebind(enc):
+        step = hit[2]
+    else:
+        hit = None
+        step = WindowStep(model, enc, rows, window, capacity, pos_bound, pos_off)
+    if len(_WINDOW_STEPS) >= WINDOW_STEP_SLOTS:
+        _WINDOW_STEPS.pop(next(iter(_WINDOW_STEPS)))
+    _WINDOW_STEPS[slot] = (weakref.ref(model), wkey, step)
+    return step
+
+
+def _window_graph_fits(model, cache, hr_input, sliding_window, beam_width, stop_len):
+    """The window step applies to this tail: a Transformer whose evaluation rows (images x candidates) and
+    self-attention heads fit the window kernels, and an evaluation of the tail slides the window."""
+    s = cache._search
+    if s is None or not hasattr(model, "_cond"):
+        return False
+    heads = model.decoder_layers[-1].self_attn_block.self_attn.heads
+    if s.N * s.NB > DECODE_ROWS or not ops.window_step_supported(s.N * s.NB, sliding_window, cache.dim, heads):
+        return False
+    cur = hr_input.shape[1]
+    chunks = max(0, -(-(stop_len - cur) // beam_width))
+    return chunks > 0 and cur + chunks * beam_width - 1 >= sliding_window
+
+
+def _window_tail(model, cache, hr_input, enc, sliding_window, beam_width, progress, total_seq, stop_len, pos_off,
+                 pos_bound):
+    """_fused_tail with the slid evaluations replayed from a WindowStep's graph: the same draws, decisions and
+    draw numbers (every launch of the search is the one _fused_tail enqueues), the tokens in the step's device
+    ring instead of host-side torch.cat.  Evaluations that still fit the window replay the cache's step graph as
+    there.  Enqueues only; nothing is read back."""
+    s = cache._search
+    N, NB, bw, ctl = s.N, s.NB, s.bw, cache.ctl
+    enc_eval = enc.repeat_interleave(NB, dim=0) if (enc is not None and NB > 1) else enc
+    step = window_step(model, enc_eval, N * NB, sliding_window, stop_len + bw, pos_bound, pos_off)
+    step.load(hr_input.repeat_interleave(NB, dim=0) if NB > 1 else hr_input)
+    cur = hr_input.shape[1]
+    while cur < stop_len:
+        for _ in range(s.candidates):
+            step.rewind(cur)
+            for tok in range(bw):
+                n = cur + tok                    # tokens in the sequence; the next one is drawn from the last's logits
+                if n - 1 < cache.max_len and n < sliding_window:
+                    s.ids.copy_(step.ring[:, n - 1])
+                    ctl[0:1].fill_(n - 1)
+                    s.g_step.replay()
+                    logits = s.logits
+                else:
+                    logits = step.evaluate()
+                ops.decode_sample(logits, s.T, s.end, s.gen, s.shift, s.uniforms, ctl, tok, bw, s.ids, s.chunk,
+                                  s.comb, forced=s.forced, probs_log=s.probs, inc_len=False, beams=s.beams)
+                step.append(s.ids)
+            ops.decode_decide(ctl, N, NB, bw, s.comb, s.chunk, s.best_p, s.best_chunk, s.take, draws=s.per_set)
+        ops.decode_advance(ctl, bw)
+        s.used += s.candidates * s.per_set
+        step.ring.view(N, NB, -1)[:, :, cur:cur + bw].copy_(s.best_chunk[:, None, :])     # the kept chunk
+        cur += bw
+        if progress is not None:
+            progress(cur - 1, total_seq)
+    return step.ring[::NB, :cur].clone()
 
 
 def _generate_fused(model, hr_input, enc, total_seq, temperature, use_sliding_window,
@@ -315,12 +393,15 @@ def _generate_cached(model, hr_input, enc, total_seq, temperature, use_sliding_w
 @torch.no_grad()
 def generate_tokens(model, hr_input, lr_input, total_seq, temperature, use_sliding_window,
                     sliding_window, end_token, shift=0, num_beam=1, beam_width=1, mode="generate",
-                    progress=None, batch_beams=False, use_kv_cache=True, sampler=None):
+                    progress=None, batch_beams=False, use_kv_cache=True, sampler=None, window_graph=False):
     """hr_input: (N, S0) int64 conditioning/start tokens.  Returns the extended (N, S) tensor
     (first tokens included; callers strip them and undo `shift`).  use_kv_cache: evaluate one
     token per step from a key/value cache until the window starts to slide (same logits up
     to fp32 summation order); False re-runs the window for every token like the reference.
-    sampler: "fused" / "torch" for the cached loop (DEFAULT_SAMPLER)."""
+    sampler: "fused" / "torch" for the cached loop (DEFAULT_SAMPLER).
+    window_graph (opt-in): with the fused sampler, up to DECODE_ROWS rows (images x candidates) and a model the
+    window kernels take, every evaluation after the window slides is a replay of one captured graph
+    (kvcache.WindowStep) instead of an eager model.decode of the window; other cases ignore it."""
     assert mode in ("generate", "train")
     device = hr_input.device
     N = hr_input.shape[0]
@@ -340,7 +421,8 @@ def generate_tokens(model, hr_input, lr_input, total_seq, temperature, use_slidi
             sub_progress = progress if g0 + group >= N else None
             outs.append(generate_tokens(model, hr_input[sub], None if lr_input is None else lr_input[sub], total_seq,
                                         temperature, use_sliding_window, sliding_window, end_token, shift, num_beam,
-                                        beam_width, mode, sub_progress, batch_beams, use_kv_cache, sampler))
+                                        beam_width, mode, sub_progress, batch_beams, use_kv_cache, sampler,
+                                        window_graph=window_graph))
         return torch.cat(outs, dim=0)
     enc = model.encode(lr_input) if model.use_encoder else None
     pos = torch.zeros((N, 1), device=device) if use_sliding_window else None
@@ -363,9 +445,15 @@ def generate_tokens(model, hr_input, lr_input, total_seq, temperature, use_slidi
     pos_bound = stop_len + beam_width + pos_off + 1
     if cache is not None and cache._search is not None:
         tail = _Timer()
-        hr_input = _fused_tail(model, cache, hr_input, pos, enc, use_sliding_window, sliding_window, beam_width,
-                               progress, total_seq, stop_len, pos_off, pos_bound)
-        tail.mark("windowed tail (fused draws)")
+        if window_graph and use_sliding_window and \
+                _window_graph_fits(model, cache, hr_input, sliding_window, beam_width, stop_len):
+            hr_input = _window_tail(model, cache, hr_input, enc, sliding_window, beam_width, progress, total_seq,
+                                    stop_len, pos_off, pos_bound)
+            tail.mark("windowed tail (window graph)")
+        else:
+            hr_input = _fused_tail(model, cache, hr_input, pos, enc, use_sliding_window, sliding_window, beam_width,
+                                   progress, total_seq, stop_len, pos_off, pos_bound)
+            tail.mark("windowed tail (fused draws)")
         tail.report()
         if FUSED_DEBUG is not None:
             FUSED_DEBUG["probs"] = cache._search.probs
