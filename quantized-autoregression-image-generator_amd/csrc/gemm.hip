@@ -112,6 +112,20 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_kernel(SA sa, SB sb, GemmEpi
 // The k-loop of the prefetch kernels: tiles [0, nk) of BK from k_begin, of the 128 x 128 block at
 // (m0, n0), through the 4-stage ring at `lds` (64 KB); `tt` = thread index among the ring's 256.
 // Contains workgroup barriers: every wave of the workgroup runs it with the same nk.
+//
+// Ablation builds (tools/gemm_ablation.py; never the library's default build) price the parts of the
+// k-loop one at a time.  Their results are wrong by design and nothing may consume them; none of them
+// reads or writes anything the full loop does not:
+//   QARIG_RING_ABL_NODMA     the prologue fills the 4 stages once (and waits for them); the loop issues
+//                            no DMA and runs over the stale stages
+//   QARIG_RING_ABL_NOBAR     (with NODMA) no barrier per k-tile either
+//   QARIG_RING_ABL_NOREAD    no fragment ds_reads in the loop: every tile multiplies the prologue's registers
+//   QARIG_RING_ABL_NOEPI     (gemm_dma_pf_kernel) no epilogue stores
+//   QARIG_RING_STAMPS        diagnostic: s_memtime / s_memrealtime around the k-loop, workgroup 0..4095,
+//                            into a buffer of their own (qarig_ring_stamps_read)
+#if defined(QARIG_RING_ABL_NOBAR) && !defined(QARIG_RING_ABL_NODMA)
+#error "QARIG_RING_ABL_NOBAR needs QARIG_RING_ABL_NODMA: the barrier orders the DMA refills"
+#endif
 template <bool AKC, bool BKC>
 __device__ __forceinline__ void pf_ring(Acc& acc, float& rs, const bool do_rs, float* lds,
                                         const float* __restrict__ A, int64_t lda,
@@ -158,7 +172,11 @@ __device__ __forceinline__ void pf_ring(Acc& acc, float& rs, const bool do_rs, f
         issue(1, 1);
         issue(2, 2);
         issue(3, 3);
+#ifdef QARIG_RING_ABL_NODMA
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the four stages, once
+#else
         asm volatile("s_waitcnt vmcnt(12)" ::: "memory");      // tile 0 landed (1, 2, 3 in flight)
+#endif
         __builtin_amdgcn_s_barrier();
         Frags8 P, Q;
         frags_read_s<AKC, BKC, 0>(P, fb);
@@ -166,15 +184,31 @@ __device__ __forceinline__ void pf_ring(Acc& acc, float& rs, const bool do_rs, f
         __builtin_amdgcn_sched_barrier(0);
         if (do_rs) QARIG_PF_ROWSUM(0)
         int t = 0;
+#ifdef QARIG_RING_ABL_NODMA
+#define QARIG_PF_ISSUE(T, S)
+#else
+#define QARIG_PF_ISSUE(T, S) issue(T, S);
+#endif
+#ifdef QARIG_RING_ABL_NOBAR
+#define QARIG_PF_BARRIER()
+#else
+#define QARIG_PF_BARRIER() __builtin_amdgcn_s_barrier();
+#endif
+#ifdef QARIG_RING_ABL_NOREAD
+#define QARIG_PF_READ(NXT, S)
+#define QARIG_PF_CUR(CUR) P
+#else
+#define QARIG_PF_READ(NXT, S) frags_read_s<AKC, BKC, (S + 1) % 4>(NXT, fb); __builtin_amdgcn_sched_barrier(0);
+#define QARIG_PF_CUR(CUR) CUR
+#endif
         // body for tile t (stage S = t % 4) with its fragments in CUR; leaves tile t+1's in NXT
 #define QARIG_PF_BODY(CUR, NXT, S)                                                                \
         {                                                                                         \
             asm volatile("s_waitcnt vmcnt(8)" ::: "memory");   /* tile t+1 landed; t+2, t+3 in flight */ \
-            __builtin_amdgcn_s_barrier();      /* ... for everyone; all reads of tile t retired */  \
-            issue(t + 4, S);                   /* into the stage tile t has just vacated */        \
-            frags_read_s<AKC, BKC, (S + 1) % 4>(NXT, fb);                                         \
-            __builtin_amdgcn_sched_barrier(0);                                                    \
-            frags_mma(acc, CUR);                                                                  \
+            QARIG_PF_BARRIER()                 /* ... for everyone; all reads of tile t retired */  \
+            QARIG_PF_ISSUE(t + 4, S)           /* into the stage tile t has just vacated */        \
+            QARIG_PF_READ(NXT, S)                                                                 \
+            frags_mma(acc, QARIG_PF_CUR(CUR));                                                    \
             frags_wait(NXT);                                                                      \
             __builtin_amdgcn_sched_barrier(0);                                                    \
             if (do_rs && t + 1 < nk) QARIG_PF_ROWSUM((S + 1) % 4)                                 \
@@ -190,10 +224,19 @@ __device__ __forceinline__ void pf_ring(Acc& acc, float& rs, const bool do_rs, f
         if (t < nk) QARIG_PF_BODY(Q, P, 1)
         if (t < nk) QARIG_PF_BODY(P, Q, 2)
 #undef QARIG_PF_BODY
+#undef QARIG_PF_ISSUE
+#undef QARIG_PF_BARRIER
+#undef QARIG_PF_READ
+#undef QARIG_PF_CUR
 #undef QARIG_PF_ROWSUM
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
 }
+
+#ifdef QARIG_RING_STAMPS
+constexpr int RING_STAMP_SLOTS = 4096;
+__device__ uint64_t g_ring_stamps[4 * RING_STAMP_SLOTS];   // {memtime, memrealtime} before / after the k-loop
+#endif
 
 template <bool AKC, bool BKC>
 __global__ __launch_bounds__(NTHREADS, 2) void gemm_dma_pf_kernel(const float* __restrict__ A, int64_t lda,
@@ -235,9 +278,22 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_dma_pf_kernel(const float* _
     acc_zero(acc);
     float rs = 0.0f;
     const bool do_rs = !AKC && ep.rowsum != nullptr && tn == 0 && tid < 128;
+#ifdef QARIG_RING_STAMPS
+    const uint64_t c0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
+#endif
     pf_ring<AKC, BKC>(acc, rs, do_rs, lds, A, lda, B, ldb, m0, n0, k_begin, nk, wave, lane, tid);
+#ifdef QARIG_RING_STAMPS
+    const uint64_t c1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
+    if (tid == 0 && blockIdx.x < RING_STAMP_SLOTS) {
+        uint64_t* q = g_ring_stamps + 4 * blockIdx.x;
+        q[0] = c0; q[1] = r0; q[2] = c1; q[3] = r1;
+    }
+#endif
     if (do_rs) ep.rowsum[(int64_t)z * M + m0 + tid] = rs;
     __syncthreads();                      // ring no longer in use: the epilogue stages through it
+#ifdef QARIG_RING_ABL_NOEPI
+    if (M != -1) return;                  // (never true at run time: keeps the accumulators live)
+#endif
     // (flat grid: blockIdx.z == 0, the slab offset is folded into the pointer)
     gemm_epilogue_wide<2>(acc, ep, lds, m0, n0, M, N, splitk, xcd_splits && slabs ? slabs + (int64_t)z * M * N : slabs);
 }
@@ -692,6 +748,19 @@ __global__ __launch_bounds__(1024) void gemm_skinny_kernel(const float* __restri
 }  // namespace qarig
 
 using namespace qarig;
+
+#ifdef QARIG_RING_STAMPS
+// diagnostic build only (not declared in include/qarig.h): copies the stamps of gemm_dma_pf_kernel's last
+// launches ({memtime, memrealtime} before and after the k-loop, per workgroup 0..4095) to host memory and
+// clears them
+extern "C" int qarig_ring_stamps_read(uint64_t* host, int slots) {
+    const size_t n = 4 * (size_t)min(slots, RING_STAMP_SLOTS) * sizeof(uint64_t);
+    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_ring_stamps), n, 0, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    static uint64_t zeros[4 * RING_STAMP_SLOTS];
+    return hipMemcpyToSymbol(HIP_SYMBOL(g_ring_stamps), zeros, sizeof(zeros), 0, hipMemcpyHostToDevice) == hipSuccess
+               ? 0 : -1;
+}
+#endif
 
 extern "C" size_t qarig_gemm_workspace_bytes(int M, int N, int splitk) {
     if (M < 1 || N < 1 || splitk > (1 << 16)) return 0;

@@ -144,10 +144,13 @@ using namespace qarig;
 // rows 28.9 -> 20.7, 1024 x 512 x 512 23.3 -> 14.6, 1024 x 2048 x 512 34.0 -> 29.0; with K = 2048 on 32-64 tiles
 // of 128 the split-K ring kernels are as fast or faster (2048 x 512 x 2048: 50.6 against 50.0-60 us): this
 // register-staged loop reaches ~70 TF where the LDS-DMA ring reaches ~90 on a quarter of the chip plus a reduce.
+// The "very few tiles" case stops at K = 2048: the 512 x 512 weight gradient over 16,384 rows (16 tiles of 128)
+// went to 256 workgroups that each walked 4,096 k on this loop (164 us, 52 TF); the ring at 32 splits of 512
+// takes it in 79 us (profiles/r05_bench_c2_tile64_ab.txt).
 extern "C" int qarig_gemm_tile64(int M, int N, int K) {
     if (g_qarig_opt.gemm_tile64 == 0 || M < 64 || N < 64 || K < 16 || M % 64 || N % 64 || K % 16) return 0;
     const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128);
-    return g_qarig_opt.gemm_tile64 == 1 || (t128 < 192 && (K <= 1024 || t128 <= 16));
+    return g_qarig_opt.gemm_tile64 == 1 || (t128 < 192 && (K <= 1024 || (t128 <= 16 && K <= 2048)));
 }
 
 int qarig_gemm64_launch(const float* A, int64_t lda, int a_kcontig, const float* B, int64_t ldb, int b_kcontig,

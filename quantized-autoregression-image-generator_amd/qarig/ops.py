@@ -670,7 +670,8 @@ def pick_splitk(M, N, K):
             s -= 1
         return max(1, s)
     # (a 512 x 512 gradient over 2,048 rows -- 16 tiles -- measured 40 us in 4 slices of 512 rows and
-    # 29 us in 8 of 256: with few tiles the slices may be as short as 16 k-tiles)
+    # 29 us in 8 of 256: with few tiles the slices may be as short as 16 k-tiles; over 16,384 rows the same
+    # gradient comes here -- qarig_gemm_tile64 stops at K = 2048 -- and runs 32 slices of 512 in 79 us)
     s = max(1, min(max(1, 512 // tiles), K // (256 if tiles <= 32 else 512), 32))
     # slices that divide K into whole 16-deep tiles keep the launch on the interior kernels
     # (the padded classifier's 640 x 2048 output over K = 16384 asked for 6: 2736-deep slices
