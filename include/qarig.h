@@ -161,6 +161,41 @@ int qarig_gemm_f8(const void* A, int64_t lda, const void* B, int64_t ldb, const 
                   const float* residual, int64_t ldr, float* preact, int64_t ldp, int act, void* Cb,
                   int64_t ldcb, void* Pb, int64_t ldpb, void* stream);
 
+/* MX-e4m3 ("mxfp8" mode: every product of the reduced-precision Linear nodes, forward and backward;
+ * models/layers.py:234-254, 330-340, 389-418).  The format (OCP microscaling, e4m3 elements):
+ *  - elements are OCP e4m3fn bytes; each block of 32 consecutive elements along the product's
+ *    reduction dimension has one e8m0 scale byte E = e + 127 (value 2^e);
+ *  - e is the smallest integer with max|x| over the block <= 448 * 2^e (no element saturates),
+ *    clamped to [-127, 127]; an all-zero block has e = 0;
+ *  - element = round-to-nearest-even of x * 2^-e to e4m3fn (the multiplication is exact in fp32);
+ *  - non-finite input is out of scope: a NaN does not enter its block's maximum and quantises to the
+ *    e4m3 NaN byte; an infinity gives its block e = 120 and unspecified elements.
+ * Every operand is a (rows, K) byte matrix blocked along K with scales (rows, K/32):
+ *  - row form of a tensor (R, C): as stored, blocked along C, scales (R, C/32);
+ *  - transposed form: (C, Rp), Rp = R rounded up to 128, blocked along R, scales (C, Rp/32); the
+ *    padding columns are zero (scale byte 127).
+ * forward x W^T = (x row, W row); input gradient dT W = (dT row, W transposed); weight gradient
+ * dT^T x = (dT transposed, x transposed): every product is NT on one kernel.
+ * qarig_mx_quant: one pass over src (fp32, or bf16 with src_is_bf16; row stride ld elements,
+ * C % 128 == 0) writing any of the row form (q, q_scale), the transposed form (qt, qt_scale) and
+ * colsum (+)= the fp32 column sums (workspace: qarig_mx_quant_workspace_bytes, needed with colsum).
+ * qarig_gemm_mx: C = epilogue(sum_k A[m][k] B[n][k]) on v_mfma_scale_f32_32x32x64_f8f6f4 with
+ * the scale bytes applied in the instruction; A, B bytes (lda / ldb in bytes), sA (M, K/32), sB
+ * (N, K/32) (ldsa / ldsb in bytes); epilogue, split-K (workspace: qarig_gemm_mx_workspace_bytes)
+ * and accumulate as qarig_gemm_lp.  Shapes: qarig_gemm_mx_supported. */
+size_t qarig_mx_quant_workspace_bytes(int R, int C);
+int qarig_mx_quant(const void* src, int64_t ld, int src_is_bf16, int R, int C, void* q, void* q_scale,
+                   void* qt, void* qt_scale, float* colsum, int accumulate, void* workspace,
+                   size_t ws_bytes, void* stream);
+int qarig_gemm_mx_supported(int M, int N, int K, int splitk);
+size_t qarig_gemm_mx_workspace_bytes(int M, int N, int splitk);
+int qarig_gemm_mx(const void* A, int64_t lda, const void* sA, int64_t ldsa, const void* B, int64_t ldb,
+                  const void* sB, int64_t ldsb, float* C, int64_t ldc, int M, int N, int K,
+                  const float* bias, const float* residual, int64_t ldr, float* preact, int64_t ldp,
+                  int act, const void* gradz, int64_t ldz, int gradz_is_bf16, int gact, int splitk,
+                  int accumulate, void* Cb, int64_t ldcb, void* Pb, int64_t ldpb, void* workspace,
+                  size_t ws_bytes, void* stream);
+
 /* Operand conversion of the reduced-precision mode (no reference counterpart): fp32 -> bf16,
  * round to nearest even; n contiguous elements, or the transpose (C, R) of a (R, C) matrix
  * with row stride ld (the W^T shadow of an nn.Linear weight). */

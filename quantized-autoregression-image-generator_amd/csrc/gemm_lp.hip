@@ -457,24 +457,84 @@ struct F8Frag {
         return i32x8_f8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
     }
 };
+// MX: the block-scaled instruction takes its 64 k as four 16-byte groups -- bytes 0-15 of lanes 0-31,
+// bytes 0-15 of lanes 32-63, bytes 16-31 of lanes 0-31, bytes 16-31 of lanes 32-63 -- and scales
+// the first 32 with the byte of lanes 0-31, the last 32 with that of lanes 32-63 (measured on exact
+// data: tests/test_gpu_mxfp8.py).  So lane l holds k = 64 ks + 16 (l >> 5) ... + 15 and 64 ks + 32 +
+// 16 (l >> 5) ... + 15 there, and each 32-block of memory meets one scale.  (Unscaled, any order
+// that A and B share gives the same sums.)
+template <bool MX = false>
 __device__ __forceinline__ void f8_frag(const bf16_t* tile, int x0, int ks, int lane, F8Frag& f) {
     const int r = x0 + (lane & 31);
-    const int c0 = ks * 4 + (lane >> 5) * 2;
+    const int c0 = MX ? ks * 4 + (lane >> 5) : ks * 4 + (lane >> 5) * 2;
+    const int c1 = MX ? c0 + 2 : c0 + 1;
     const unsigned base = lds_addr_lp(tile) + r * 128;
-    const unsigned a0 = base + (((c0) ^ ((r >> 1) & 7)) << 4), a1 = base + (((c0 + 1) ^ ((r >> 1) & 7)) << 4);
+    const unsigned a0 = base + (((c0) ^ ((r >> 1) & 7)) << 4), a1 = base + (((c1) ^ ((r >> 1) & 7)) << 4);
     asm volatile("ds_read_b128 %0, %1" : "=v"(f.lo) : "v"(a0));
     asm volatile("ds_read_b128 %0, %1" : "=v"(f.hi) : "v"(a1));
 }
 
+// MX (OCP microscaling, include/qarig.h "MX-e4m3"): the same loops with a compile-time MX switch.
+// Each operand then carries one e8m0 scale byte per 32 elements along k, row-major (rows, K/32); a
+// 128-deep k-tile needs 4 contiguous bytes of each row.  In k-step ks, lanes 0-31 feed the scale
+// byte of block 2 ks of their row and lanes 32-63 that of block 2 ks + 1 (f8_frag<true> lays the
+// bytes out to match) to v_mfma_scale_f32_32x32x64_f8f6f4 (op_sel 0: the byte sits in bits 0-7), the
+// hardware multiplies every 32-product group by 2^(Ea - 127) 2^(Eb - 127), and the epilogue has no
+// dequantisation factor.  The scale dwords ride in the operand ring (mx_stage_scales).  MX
+// products also take split-K (blockIdx.z slices of K, fp32 slabs reduced by qarig_slab_reduce_f32).
+// MX = false is the per-tensor kernel as it was (its machine code is unchanged).
+struct MxScales {
+    const unsigned char* sa; int64_t ldsa;   // (M, K/32) scale bytes of A, row stride in bytes
+    const unsigned char* sb; int64_t ldsb;   // (N, K/32) of B
+    int splitk; float* slabs;
+};
+// A k-tile's scales travel with its operand tiles: this wave's DMA of ROWS x 4 bytes of A (waves
+// 0..ROWS/64-1) or of B (the next ROWS/64 waves), 64 rows per instruction, into the stage's scale image
+// [A rows][B rows] of dwords; the loop's vmcnt wait and barrier cover it like the operand tiles.
+template <int ROWS>
+__device__ __forceinline__ void mx_stage_scales(const MxScales& mx, int m0, int n0, int k0, bf16_t* img,
+                                                int wave, int lane) {
+    constexpr int PER = ROWS / 64;
+    if (wave < 2 * PER) {
+        const bool b = wave >= PER;
+        const int r = (b ? wave - PER : wave) * 64 + lane;
+        const unsigned char* src = b ? mx.sb + (int64_t)(n0 + r) * mx.ldsb : mx.sa + (int64_t)(m0 + r) * mx.ldsa;
+        __builtin_amdgcn_global_load_lds((glb_ptr_lp)(src + (k0 >> 5)), (lds_ptr_lp)(img + wave * 128), 4, 0, 0);
+    }
+}
+// This lane's byte address in a stage's scale image: row `row` of the A (b = 0) or B half, byte
+// lane >> 5; fragment i of k-step ks then reads byte offset 128 i + 2 ks (an immediate, so the loop
+// keeps one address register per operand).  Inline asm like the fragment reads: the value is
+// consumed behind the lgkmcnt wait.
+__device__ __forceinline__ unsigned mx_scale_addr(const bf16_t* img, int row, int lane) {
+    return lds_addr_lp(img) + row * 4 + (lane >> 5);
+}
+template <int OFF>
+__device__ __forceinline__ void mx_scale_read(unsigned addr, int& v) {
+    asm volatile("ds_read_u8 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
+}
+// The MX kernels take the MxScales as one more argument; the per-tensor instantiations
+// (gemm_f8_kernel<false>) keep the argument list the kernels always had.
+__device__ __forceinline__ MxScales mx_scales() { return MxScales{}; }
+__device__ __forceinline__ MxScales mx_scales(const MxScales& m) { return m; }
+
+template <bool MX, class... MxArg>
 __global__ __launch_bounds__(NTHREADS, 2) void gemm_f8_kernel(const unsigned char* __restrict__ A, int64_t lda,
                                                               const unsigned char* __restrict__ B, int64_t ldb,
-                                                              GemmEpilogue ep, int M, int N, int K, int tiles_n) {
+                                                              GemmEpilogue ep, int M, int N, int K, int tiles_n,
+                                                              MxArg... mx_arg) {
+    const MxScales mx = mx_scales(mx_arg...);
     constexpr int FBK = 128;                                             // bytes = elements per k-tile
-    __shared__ __attribute__((aligned(16))) bf16_t lds[2 * LP_STAGE];   // 64 KB: 2 workgroups per CU
+    constexpr int SC = MX ? 2 * 128 * 4 / 2 : 0;                         // scale image per stage (bf16_t units)
+    __shared__ __attribute__((aligned(16))) bf16_t lds[2 * LP_STAGE + 2 * SC];   // 64 KB (+2 KB MX): 2 per CU
+    bf16_t* const scl = lds + 2 * LP_STAGE;
+    // MX split-K: blockIdx.z takes K / splitk (the host keeps that a multiple of 128)
+    const bool split = MX && mx.splitk > 1;
+    const int k_begin = split ? (int)blockIdx.z * (K / mx.splitk) : 0;
+    const int nk = (split ? K / mx.splitk : K) / FBK;
     const int tile = xcd_remap(blockIdx.x, gridDim.x);
     const int tm = tile / tiles_n, tn = tile - tm * tiles_n;
     const int m0 = tm * BM, n0 = tn * BN;
-    const int nk = K / FBK;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
@@ -486,16 +546,18 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_f8_kernel(const unsigned cha
     Acc acc;
     acc_zero(acc);
     if (nk > 0) {
-        lp_stage<false>(A2, lda2, m0, 0, lds, wave, lane);
-        lp_stage<false>(B2, ldb2, n0, 0, lds + LP_OP, wave, lane);
+        lp_stage<false>(A2, lda2, m0, k_begin / 2, lds, wave, lane);
+        lp_stage<false>(B2, ldb2, n0, k_begin / 2, lds + LP_OP, wave, lane);
+        if constexpr (MX) mx_stage_scales<128>(mx, m0, n0, k_begin, scl, wave, lane);
         for (int kt = 0; kt < nk; ++kt) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             const int st = kt & 1;
             if (kt + 1 < nk) {
-                const int kn = (kt + 1) * (FBK / 2);
+                const int kn = k_begin / 2 + (kt + 1) * (FBK / 2);
                 lp_stage<false>(A2, lda2, m0, kn, lds + (st ^ 1) * LP_STAGE, wave, lane);
                 lp_stage<false>(B2, ldb2, n0, kn, lds + (st ^ 1) * LP_STAGE + LP_OP, wave, lane);
+                if constexpr (MX) mx_stage_scales<128>(mx, m0, n0, 2 * kn, scl + (st ^ 1) * SC, wave, lane);
             }
             const bf16_t* ta = lds + st * LP_STAGE;
             const bf16_t* tb = ta + LP_OP;
@@ -504,9 +566,22 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_f8_kernel(const unsigned cha
             for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
-                    f8_frag(ta, wm * 64 + i * 32, ks, lane, fa[ks][i]);
-                    f8_frag(tb, wn * 64 + i * 32, ks, lane, fb[ks][i]);
+                    f8_frag<MX>(ta, wm * 64 + i * 32, ks, lane, fa[ks][i]);
+                    f8_frag<MX>(tb, wn * 64 + i * 32, ks, lane, fb[ks][i]);
                 }
+            int ea[2][2], eb[2][2];
+            if constexpr (MX) {
+                const unsigned sa = mx_scale_addr(scl + st * SC, wm * 64 + (lane & 31), lane);
+                const unsigned sb = mx_scale_addr(scl + st * SC, 128 + wn * 64 + (lane & 31), lane);
+                mx_scale_read<0>(sa, ea[0][0]);
+                mx_scale_read<128>(sa, ea[0][1]);
+                mx_scale_read<2>(sa, ea[1][0]);
+                mx_scale_read<130>(sa, ea[1][1]);
+                mx_scale_read<0>(sb, eb[0][0]);
+                mx_scale_read<128>(sb, eb[0][1]);
+                mx_scale_read<2>(sb, eb[1][0]);
+                mx_scale_read<130>(sb, eb[1][1]);
+            }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -514,26 +589,41 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_f8_kernel(const unsigned cha
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        acc.t[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
-                            fa[ks][i].value(), fb[ks][j].value(), acc.t[i][j], 0, 0, 0, 0, 0, 0);
+                    for (int j = 0; j < 2; ++j) {
+                        if constexpr (MX)
+                            acc.t[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
+                                fa[ks][i].value(), fb[ks][j].value(), acc.t[i][j], 0, 0, 0, ea[ks][i], 0, eb[ks][j]);
+                        else
+                            acc.t[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
+                                fa[ks][i].value(), fb[ks][j].value(), acc.t[i][j], 0, 0, 0, 0, 0, 0);
+                    }
         }
     }
     __syncthreads();
-    gemm_epilogue_wide<2>(acc, ep, reinterpret_cast<float*>(lds), m0, n0, M, N, 1, nullptr);
+    if constexpr (MX)
+        gemm_epilogue_wide<2>(acc, ep, reinterpret_cast<float*>(lds), m0, n0, M, N, mx.splitk, mx.slabs);
+    else
+        gemm_epilogue_wide<2>(acc, ep, reinterpret_cast<float*>(lds), m0, n0, M, N, 1, nullptr);
 }
 
 // The e4m3 product on the 256 x 256 tile of gemm_lp_big_kernel (128 bytes deep per k-tile: the
 // same 64 KB stage images, lpb_stage<false> on the bytes).
+template <bool MX, class... MxArg>
 __global__ __launch_bounds__(1024, 1) void gemm_f8_big_kernel(const unsigned char* __restrict__ A, int64_t lda,
                                                               const unsigned char* __restrict__ B, int64_t ldb,
-                                                              GemmEpilogue ep, int M, int N, int K, int tiles_n) {
+                                                              GemmEpilogue ep, int M, int N, int K, int tiles_n,
+                                                              MxArg... mx_arg) {
+    const MxScales mx = mx_scales(mx_arg...);
     constexpr int FBK = 128;
-    extern __shared__ __attribute__((aligned(16))) bf16_t ldsf[];   // 2 x 64 KB
+    constexpr int SC = MX ? 2 * LPB * 4 / 2 : 0;                    // scale image per stage (bf16_t units)
+    extern __shared__ __attribute__((aligned(16))) bf16_t ldsf[];   // 2 x 64 KB (+ 2 x 2 KB MX)
+    bf16_t* const scl = ldsf + 2 * LPB_STAGE;
+    const bool split = MX && mx.splitk > 1;
+    const int k_begin = split ? (int)blockIdx.z * (K / mx.splitk) : 0;
+    const int nk = (split ? K / mx.splitk : K) / FBK;
     const int tile = xcd_remap(blockIdx.x, gridDim.x);
     const int tm = tile / tiles_n, tn = tile - tm * tiles_n;
     const int m0 = tm * LPB, n0 = tn * LPB;
-    const int nk = K / FBK;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3;
@@ -544,16 +634,18 @@ __global__ __launch_bounds__(1024, 1) void gemm_f8_big_kernel(const unsigned cha
     Acc acc;
     acc_zero(acc);
     if (nk > 0) {
-        lpb_stage<false>(A2, lda2, m0, 0, ldsf, wave, lane);
-        lpb_stage<false>(B2, ldb2, n0, 0, ldsf + LPB_OP, wave, lane);
+        lpb_stage<false>(A2, lda2, m0, k_begin / 2, ldsf, wave, lane);
+        lpb_stage<false>(B2, ldb2, n0, k_begin / 2, ldsf + LPB_OP, wave, lane);
+        if constexpr (MX) mx_stage_scales<LPB>(mx, m0, n0, k_begin, scl, wave, lane);
         for (int kt = 0; kt < nk; ++kt) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             const int st = kt & 1;
             if (kt + 1 < nk) {
-                const int kn = (kt + 1) * (FBK / 2);
+                const int kn = k_begin / 2 + (kt + 1) * (FBK / 2);
                 lpb_stage<false>(A2, lda2, m0, kn, ldsf + (st ^ 1) * LPB_STAGE, wave, lane);
                 lpb_stage<false>(B2, ldb2, n0, kn, ldsf + (st ^ 1) * LPB_STAGE + LPB_OP, wave, lane);
+                if constexpr (MX) mx_stage_scales<LPB>(mx, m0, n0, 2 * kn, scl + (st ^ 1) * SC, wave, lane);
             }
             const bf16_t* ta = ldsf + st * LPB_STAGE;
             const bf16_t* tb = ta + LPB_OP;
@@ -562,24 +654,49 @@ __global__ __launch_bounds__(1024, 1) void gemm_f8_big_kernel(const unsigned cha
                 F8Frag fa[2], fb[2];
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
-                    f8_frag(ta, wm * 64 + i * 32, ks, lane, fa[i]);
-                    f8_frag(tb, wn * 64 + i * 32, ks, lane, fb[i]);
+                    f8_frag<MX>(ta, wm * 64 + i * 32, ks, lane, fa[i]);
+                    f8_frag<MX>(tb, wn * 64 + i * 32, ks, lane, fb[i]);
+                }
+                int ea[2], eb[2];
+                if constexpr (MX) {
+                    const unsigned sa = mx_scale_addr(scl + st * SC, wm * 64 + (lane & 31), lane);
+                    const unsigned sb = mx_scale_addr(scl + st * SC, LPB + wn * 64 + (lane & 31), lane);
+                    if (ks == 0) {
+                        mx_scale_read<0>(sa, ea[0]);
+                        mx_scale_read<128>(sa, ea[1]);
+                        mx_scale_read<0>(sb, eb[0]);
+                        mx_scale_read<128>(sb, eb[1]);
+                    } else {
+                        mx_scale_read<2>(sa, ea[0]);
+                        mx_scale_read<130>(sa, ea[1]);
+                        mx_scale_read<2>(sb, eb[0]);
+                        mx_scale_read<130>(sb, eb[1]);
+                    }
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        acc.t[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
-                            fa[i].value(), fb[j].value(), acc.t[i][j], 0, 0, 0, 0, 0, 0);
+                    for (int j = 0; j < 2; ++j) {
+                        if constexpr (MX)
+                            acc.t[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
+                                fa[i].value(), fb[j].value(), acc.t[i][j], 0, 0, 0, ea[i], 0, eb[j]);
+                        else
+                            acc.t[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
+                                fa[i].value(), fb[j].value(), acc.t[i][j], 0, 0, 0, 0, 0, 0);
+                    }
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
     }
     __syncthreads();
-    gemm_epilogue_wave(acc, ep, reinterpret_cast<float*>(ldsf) + wave * (32 * 64), m0 + wm * 64, n0 + wn * 64,
-                       M, N, 1, nullptr);
+    if constexpr (MX)   // the epilogue of gemm_lp_big_kernel (the bf16 nodes' big-tile products)
+        gemm_epilogue_wave<2, Acc, 1>(acc, ep, reinterpret_cast<float*>(ldsf) + wave * (32 * 64), m0 + wm * 64,
+                                      n0 + wn * 64, M, N, mx.splitk, mx.slabs);
+    else
+        gemm_epilogue_wave(acc, ep, reinterpret_cast<float*>(ldsf) + wave * (32 * 64), m0 + wm * 64, n0 + wn * 64,
+                           M, N, 1, nullptr);
 }
 
 // |x| maximum of a tensor as the bit pattern of a non-negative float (they order like
@@ -616,6 +733,116 @@ __global__ __launch_bounds__(256) void cast_fp8_kernel(const float* __restrict__
         int p = __builtin_amdgcn_cvt_pk_fp8_f32(v.x * scale, v.y * scale, 0, false);
         p = __builtin_amdgcn_cvt_pk_fp8_f32(v.z * scale, v.w * scale, p, true);
         dst[i] = (unsigned)p;
+    }
+}
+
+// ---- MX-e4m3 quantiser (format: include/qarig.h) ----------------------------------------------
+// e8m0 exponent of a 32-element block with maximum |x| = amax: the smallest e with amax <= 448 2^e,
+// clamped to [-127, 127]; 0 for an all-zero block.  amax = 1.m 2^p: e = p - 8, plus one when
+// 1.m > 1.75 (448 = 1.75 2^8).  Subnormal maxima give p - 8 < -127 and clamp.
+__device__ __forceinline__ int mx_exponent(float amax) {
+    const unsigned u = __float_as_uint(amax);
+    if (u == 0u) return 0;
+    const int e = (int)(u >> 23) - 135 + ((u & 0x7fffffu) > 0x600000u ? 1 : 0);
+    return e < -127 ? -127 : (e > 127 ? 127 : e);
+}
+// 2^-e as an fp32 (normal for every e this format produces from finite input: e <= 121)
+__device__ __forceinline__ float mx_inv_scale(int e) { return __uint_as_float((unsigned)(127 - e) << 23); }
+// four e4m3 bytes of x * 2^-e, round to nearest even
+__device__ __forceinline__ unsigned mx_pack4(float4 v, float s) {
+    int p = __builtin_amdgcn_cvt_pk_fp8_f32(v.x * s, v.y * s, 0, false);
+    p = __builtin_amdgcn_cvt_pk_fp8_f32(v.z * s, v.w * s, p, true);
+    return (unsigned)p;
+}
+
+// One pass over a 64-row x 128-column tile of src (R, C) (fp32, or bf16 with BF), each output optional:
+//   q  (R, C) bytes + qs (R, C/32): the row form, blocks of 32 columns of one row;
+//   qt (C, Rp) bytes + qts (C, Rp/32): the transposed form, blocks of 32 rows of one column
+//      (Rp = R rounded up to 128; rows R..Rp-1 are zeros with scale byte 127);
+//   part[blockIdx.y][C]: the tile's column sums (fp32; colsum_reduce_kernel adds the tiles up).
+// Phase 1: each wave takes 16 rows, a row per 32 lanes per instruction (float4 each), so a row
+// block is 8 lanes and its maximum is three xor-shuffles; the fp32 tile goes to LDS.  Phase 2:
+// thread (column, 32-row half) quantises one transposed block from LDS into a byte image, which
+// phase 3 stores as 64-byte column segments.
+constexpr int MXQ_R = 64, MXQ_C = 128;
+template <bool BF>
+__global__ __launch_bounds__(256) void mx_quant_kernel(const void* __restrict__ src_, int64_t ld, int R, int C,
+                                                       unsigned char* __restrict__ q, unsigned char* __restrict__ qs,
+                                                       unsigned char* __restrict__ qt, unsigned char* __restrict__ qts,
+                                                       int Rp, float* __restrict__ part) {
+    __shared__ float4 tile[MXQ_R][MXQ_C / 4];                 // 32 KB
+    __shared__ unsigned tq[MXQ_C][MXQ_R / 4 + 1];             // transposed bytes (+1: odd dword pitch)
+    __shared__ float4 red[3][MXQ_C / 4];
+    const int r0 = blockIdx.y * MXQ_R, c0 = blockIdx.x * MXQ_C;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int cl = lane & 31;                                  // float4 column within the tile
+    const int c = c0 + 4 * cl;
+    float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 2
+    for (int it = 0; it < 8; ++it) {
+        const int rl = wave * 16 + it * 2 + (lane >> 5);
+        const int r = r0 + rl;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (r < R) {
+            if constexpr (BF) {
+                const uint2 b = *reinterpret_cast<const uint2*>(reinterpret_cast<const bf16_t*>(src_) + (int64_t)r * ld + c);
+                v = make_float4(bf16_bits_to_f32(b.x & 0xffffu), bf16_bits_to_f32(b.x >> 16),
+                                bf16_bits_to_f32(b.y & 0xffffu), bf16_bits_to_f32(b.y >> 16));
+            } else {
+                v = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(src_) + (int64_t)r * ld + c);
+            }
+        }
+        tile[rl][cl] = v;
+        sum.x += v.x; sum.y += v.y; sum.z += v.z; sum.w += v.w;
+        if (q && r < R) {
+            float m = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
+            m = fmaxf(m, __shfl_xor(m, 1, 64));
+            m = fmaxf(m, __shfl_xor(m, 2, 64));
+            m = fmaxf(m, __shfl_xor(m, 4, 64));
+            const int e = mx_exponent(m);
+            *reinterpret_cast<unsigned*>(q + (int64_t)r * C + c) = mx_pack4(v, mx_inv_scale(e));
+            if ((lane & 7) == 0) qs[(int64_t)r * (C / 32) + c / 32] = (unsigned char)(e + 127);
+        }
+    }
+    if (part) {
+        sum.x += __shfl_xor(sum.x, 32, 64); sum.y += __shfl_xor(sum.y, 32, 64);
+        sum.z += __shfl_xor(sum.z, 32, 64); sum.w += __shfl_xor(sum.w, 32, 64);
+        if (wave > 0 && lane < 32) red[wave - 1][cl] = sum;
+    }
+    __syncthreads();
+    if (part && wave == 0 && lane < 32) {
+#pragma unroll
+        for (int g = 0; g < 3; ++g) {
+            const float4 t = red[g][cl];
+            sum.x += t.x; sum.y += t.y; sum.z += t.z; sum.w += t.w;
+        }
+        *reinterpret_cast<float4*>(part + (int64_t)blockIdx.y * C + c) = sum;
+    }
+    if (!qt) return;
+    {
+        const int col = threadIdx.x & (MXQ_C - 1), half = threadIdx.x >> 7;
+        const float* tf = reinterpret_cast<const float*>(tile);
+        float m = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 32; ++i) m = fmaxf(m, fabsf(tf[(half * 32 + i) * MXQ_C + col]));
+        const int e = mx_exponent(m);
+        const float s = mx_inv_scale(e);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int rr = half * 32 + 4 * i;
+            const float4 v = make_float4(tf[rr * MXQ_C + col], tf[(rr + 1) * MXQ_C + col],
+                                         tf[(rr + 2) * MXQ_C + col], tf[(rr + 3) * MXQ_C + col]);
+            tq[col][half * 8 + i] = mx_pack4(v, s);
+        }
+        qts[(int64_t)(c0 + col) * (Rp / 32) + r0 / 32 + half] = (unsigned char)(e + 127);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int chunk = h * 256 + threadIdx.x;            // 16-B chunk: column chunk / 4, part chunk % 4
+        const int col = chunk >> 2, pc = chunk & 3;
+        const uint4 v = make_uint4(tq[col][pc * 4], tq[col][pc * 4 + 1], tq[col][pc * 4 + 2], tq[col][pc * 4 + 3]);
+        *reinterpret_cast<uint4*>(qt + (int64_t)(c0 + col) * Rp + r0 + pc * 16) = v;
     }
 }
 
@@ -1022,18 +1249,145 @@ extern "C" int qarig_gemm_f8(const void* A, int64_t lda, const void* B, int64_t 
         constexpr int BIG_LDS = 2 * LPB_STAGE * (int)sizeof(bf16_t);
         static bool attr_set = false;
         if (!attr_set) {
-            (void)hipFuncSetAttribute((const void*)gemm_f8_big_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+            (void)hipFuncSetAttribute((const void*)gemm_f8_big_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                       BIG_LDS);
             attr_set = true;
         }
-        hipLaunchKernelGGL(gemm_f8_big_kernel, dim3((M / LPB) * (N / LPB)), dim3(1024), BIG_LDS,
+        hipLaunchKernelGGL(gemm_f8_big_kernel<false>, dim3((M / LPB) * (N / LPB)), dim3(1024), BIG_LDS,
                            (hipStream_t)stream, (const unsigned char*)A, lda, (const unsigned char*)B, ldb, ep, M,
                            N, K, N / LPB);
         QARIG_CHECK_LAUNCH("gemm_f8 big");
         return QARIG_OK;
     }
-    hipLaunchKernelGGL(gemm_f8_kernel, dim3(tiles_m * tiles_n), dim3(NTHREADS), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(gemm_f8_kernel<false>, dim3(tiles_m * tiles_n), dim3(NTHREADS), 0, (hipStream_t)stream,
                        (const unsigned char*)A, lda, (const unsigned char*)B, ldb, ep, M, N, K, tiles_n);
     QARIG_CHECK_LAUNCH("gemm_f8");
+    return QARIG_OK;
+}
+
+// ---- MX-e4m3 operands (include/qarig.h): quantiser and block-scaled GEMM ----------------------
+extern "C" size_t qarig_mx_quant_workspace_bytes(int R, int C) {
+    if (R < 1 || C < 1 || R > (1 << 24) || C > (1 << 24)) return 0;
+    return (size_t)((R + 127) / 128 * 2) * C * sizeof(float);
+}
+
+// One pass over src (R, C) (fp32, or bf16 when src_is_bf16; row stride ld elements), writing any of:
+// the row form q (R, C) + q_scale (R, C/32); the transposed form qt (C, Rp) + qt_scale (C, Rp/32),
+// Rp = R rounded up to 128, zero padded; colsum[c] (+)= sum_r src[r][c] (fp32, fixed order).
+// C % 128 == 0.  Replaces the operand casts of the reduced-precision Linear products
+// (models/layers.py:234-254, 330-340, 389-418) and, for colsum, the bias gradient of
+// models/layers.py:243-250 (as qarig_cast_colsum does for bf16).
+extern "C" int qarig_mx_quant(const void* src, int64_t ld, int src_is_bf16, int R, int C, void* q, void* q_scale,
+                              void* qt, void* qt_scale, float* colsum, int accumulate, void* workspace,
+                              size_t ws_bytes, void* stream) {
+    QARIG_CHECK_ARG(src && R > 0 && C > 0 && C % MXQ_C == 0 && ld >= C, "mx_quant: bad arguments (C %% 128 == 0)");
+    QARIG_CHECK_DIMS("mx_quant", R, C);
+    QARIG_CHECK_ARG((q != nullptr) == (q_scale != nullptr) && (qt != nullptr) == (qt_scale != nullptr) &&
+                        (q || qt || colsum), "mx_quant: each form needs its bytes and its scales");
+    QARIG_CHECK_ARG(((uintptr_t)src & (src_is_bf16 ? 7 : 15)) == 0 && ld % 4 == 0 && ((uintptr_t)q & 3) == 0 &&
+                        ((uintptr_t)qt & 15) == 0, "mx_quant: misaligned buffers");
+    const int Rp = (R + 127) / 128 * 128;
+    const int chunks = Rp / MXQ_R;
+    if (colsum && (!workspace || ws_bytes < qarig_mx_quant_workspace_bytes(R, C))) {
+        qarig_set_error("mx_quant: workspace too small");
+        return QARIG_ERR_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    float* part = colsum ? (float*)workspace : nullptr;
+    dim3 grid(C / MXQ_C, chunks), block(256);
+    if (src_is_bf16)
+        hipLaunchKernelGGL(mx_quant_kernel<true>, grid, block, 0, st, src, ld, R, C, (unsigned char*)q,
+                           (unsigned char*)q_scale, (unsigned char*)qt, (unsigned char*)qt_scale, Rp, part);
+    else
+        hipLaunchKernelGGL(mx_quant_kernel<false>, grid, block, 0, st, src, ld, R, C, (unsigned char*)q,
+                           (unsigned char*)q_scale, (unsigned char*)qt, (unsigned char*)qt_scale, Rp, part);
+    QARIG_CHECK_LAUNCH("mx_quant");
+    if (colsum) {
+        hipLaunchKernelGGL(colsum_reduce_kernel, dim3((C + 63) / 64), dim3(256), 0, st, (const float*)part, chunks,
+                           C, colsum, accumulate);
+        QARIG_CHECK_LAUNCH("mx_quant colsum");
+    }
+    return QARIG_OK;
+}
+
+// 1 when C = A B^T on MX operands can run: M, N % 128 == 0, K % splitk == 0, (K / splitk) % 128 == 0.
+extern "C" int qarig_gemm_mx_supported(int M, int N, int K, int splitk) {
+    if (splitk < 1) splitk = 1;
+    if (!qarig_dims_ok({M, N}) || !qarig_dims_ok({M, K}) || !qarig_dims_ok({N, K}) || splitk > 4096) return 0;
+    return M > 0 && N > 0 && K > 0 && M % BM == 0 && N % BN == 0 && K % splitk == 0 && (K / splitk) % 128 == 0;
+}
+
+extern "C" size_t qarig_gemm_mx_workspace_bytes(int M, int N, int splitk) {
+    return qarig_gemm_lp_workspace_bytes(M, N, splitk);
+}
+
+// C / Cb = epilogue(sum_k A[m][k] B[n][k]) with A (M, K) and B (N, K) in MX-e4m3 row form (bytes,
+// lda / ldb in bytes) and their scales sA (M, K/32), sB (N, K/32) (row strides ldsa / ldsb in bytes).
+// Epilogue arguments, split-K and accumulate as qarig_gemm_lp.  Replaces the Linear contractions of
+// models/layers.py:234-254, 330-340, 389-418 (forward, input and weight gradients) in "mxfp8" mode.
+extern "C" int qarig_gemm_mx(const void* A, int64_t lda, const void* sA, int64_t ldsa, const void* B, int64_t ldb,
+                             const void* sB, int64_t ldsb, float* C, int64_t ldc, int M, int N, int K,
+                             const float* bias, const float* residual, int64_t ldr, float* preact, int64_t ldp,
+                             int act, const void* gradz, int64_t ldz, int gradz_is_bf16, int gact, int splitk,
+                             int accumulate, void* Cb, int64_t ldcb, void* Pb, int64_t ldpb, void* workspace,
+                             size_t ws_bytes, void* stream) {
+    QARIG_CHECK_ARG(A && B && sA && sB && (C || Cb), "gemm_mx: null operand");
+    QARIG_CHECK_ARG(act >= 0 && act <= 3 && gact >= 0 && gact <= 3, "gemm_mx: bad activation id");
+    if (splitk < 1) splitk = 1;
+    QARIG_CHECK_ARG(qarig_gemm_mx_supported(M, N, K, splitk),
+                    "gemm_mx: needs M,N %% 128 == 0 and K/splitk %% 128 == 0 (M=%d N=%d K=%d splitk=%d)", M, N,
+                    K, splitk);
+    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+    QARIG_CHECK_ARG(al16(A) && al16(B) && lda % 16 == 0 && ldb % 16 == 0 && lda >= K && ldb >= K,
+                    "gemm_mx: operands 16-B aligned, ld %% 16");
+    QARIG_CHECK_ARG(((uintptr_t)sA & 3) == 0 && ((uintptr_t)sB & 3) == 0 && ldsa % 4 == 0 && ldsb % 4 == 0 &&
+                        ldsa >= K / 32 && ldsb >= K / 32, "gemm_mx: scales 4-B aligned, ld %% 4");
+    auto ok4 = [&](const void* p, int64_t ld) { return !p || (al16(p) && ld % 4 == 0); };
+    QARIG_CHECK_ARG(ok4(C, ldc) && ok4(bias, 4) && ok4(residual, ldr) && ok4(preact, ldp) &&
+                        (gradz_is_bf16 ? (!gradz || (((uintptr_t)gradz & 7) == 0 && ldz % 4 == 0)) : ok4(gradz, ldz)),
+                    "gemm_mx: fp32 epilogue tensors 16-B aligned, ld %% 4");
+    QARIG_CHECK_ARG((!Cb || (((uintptr_t)Cb & 7) == 0 && ldcb % 4 == 0)) &&
+                        (!Pb || (((uintptr_t)Pb & 7) == 0 && ldpb % 4 == 0)),
+                    "gemm_mx: bf16 outputs 8-B aligned, ld %% 4");
+    if (accumulate) {
+        QARIG_CHECK_ARG(C && !bias && !residual && !preact && !gradz && act == ACT_NONE && !Cb && !Pb,
+                        "gemm_mx: accumulate supports the plain epilogue only");
+        if (splitk == 1) { residual = C; ldr = ldc; }
+    }
+    if (splitk > 1) {
+        QARIG_CHECK_ARG(C && !bias && !residual && !preact && !gradz && act == ACT_NONE && !Cb && !Pb,
+                        "gemm_mx: split-K supports the plain epilogue only");
+        if (!workspace || ws_bytes < qarig_gemm_mx_workspace_bytes(M, N, splitk)) {
+            qarig_set_error("gemm_mx: workspace too small");
+            return QARIG_ERR_WORKSPACE;
+        }
+    }
+    GemmEpilogue ep{C, ldc, bias, residual, ldr, preact, ldp, act,
+                    gradz_is_bf16 ? nullptr : (const float*)gradz, ldz, gact, nullptr,
+                    (unsigned short*)Cb, ldcb, (unsigned short*)Pb, ldpb,
+                    gradz_is_bf16 ? (const unsigned short*)gradz : nullptr, ldz, nullptr, nullptr};
+    MxScales mx{(const unsigned char*)sA, ldsa, (const unsigned char*)sB, ldsb, splitk, (float*)workspace};
+    hipStream_t st = (hipStream_t)stream;
+    const int big_env = g_qarig_opt.lp_big;
+    const long big_tiles = (long)(M / LPB) * (N / LPB) * splitk;
+    if (M % LPB == 0 && N % LPB == 0 && big_env != 0 && (big_env == 1 || big_tiles >= 224)) {
+        constexpr int BIG_LDS = 2 * LPB_STAGE * (int)sizeof(bf16_t) + 2 * 2 * LPB * 4;   // + scale images
+        static bool attr_set = false;
+        if (!attr_set) {
+            (void)hipFuncSetAttribute((const void*)gemm_f8_big_kernel<true, MxScales>,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, BIG_LDS);
+            attr_set = true;
+        }
+        hipLaunchKernelGGL((gemm_f8_big_kernel<true, MxScales>), dim3((M / LPB) * (N / LPB), 1, splitk), dim3(1024),
+                           BIG_LDS, st, (const unsigned char*)A, lda, (const unsigned char*)B, ldb, ep, M, N, K,
+                           N / LPB, mx);
+        QARIG_CHECK_LAUNCH("gemm_mx big");
+    } else {
+        hipLaunchKernelGGL((gemm_f8_kernel<true, MxScales>), dim3((M / BM) * (N / BN), 1, splitk), dim3(NTHREADS), 0,
+                           st, (const unsigned char*)A, lda, (const unsigned char*)B, ldb, ep, M, N, K, N / BN, mx);
+        QARIG_CHECK_LAUNCH("gemm_mx");
+    }
+    if (splitk > 1)
+        return qarig_slab_reduce_f32((const float*)workspace, C, ldc, M, N, splitk, accumulate, stream);
     return QARIG_OK;
 }

@@ -124,7 +124,7 @@ def _lp():
 
 def linear_act(x, weight, bias=None, residual=None, act=0):
     if ops.lp_mode() and not _no_grad() and _lp().linear_supported(x, weight):
-        return _lp()._LinearActLP.apply(x, weight, bias, residual, act)
+        return _lp().linear_node(x, weight, bias, residual, act)
     if _no_grad():   # inference: straight to the kernel, no autograd node, no saved tensors
         require_cuda(x, weight)
         r2 = _2d(f32c(residual)) if residual is not None else None
@@ -218,7 +218,7 @@ class _MLP2(torch.autograd.Function):
 
 def mlp2(x, w1, b1, w2, b2, act1, act2=0):
     if ops.lp_mode() and not _no_grad() and _lp().mlp2_supported(x, w1, w2):
-        return _lp()._MLP2LP.apply(x, w1, b1, w2, b2, act1, act2)
+        return _lp().mlp2_node(x, w1, b1, w2, b2, act1, act2)
     if _no_grad():
         require_cuda(x, w1, w2)
         h = ops.gemm(_2d(f32c(x)), w1, bias=b1, act=act1)
@@ -425,7 +425,7 @@ def mlp2x3(x, blocks_params, act1, act2=0, _grouped=True):
         return _MLP2xG.apply(x, act1, act2, *[t for p in blocks_params for t in p])
     if ops.lp_mode() and all(_lp().mlp2_supported(x, p[0], p[2]) and p[2].shape[0] % 128 == 0
                                        for p in blocks_params):
-        return _lp()._MLP2x3LP.apply(x, act1, act2, *[t for p in blocks_params for t in p])
+        return _lp().mlp2x3_node(x, act1, act2, [t for p in blocks_params for t in p])
     return _MLP2x3.apply(x, act1, act2, *[t for p in blocks_params for t in p])
 
 

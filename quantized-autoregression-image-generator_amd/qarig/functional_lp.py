@@ -315,3 +315,273 @@ def linear_supported(x, weight):
     M = x.numel() // x.shape[-1]
     N, K = weight.shape
     return (ops.lp_mode() and M >= 1024 and _ok(M, N, K) and _ok(M, K, N) and _ok(N, K, M))
+
+
+# ---- "mxfp8": every product on MX-e4m3 operands ---------------------------------------------------
+def _mx_splitk(tiles, K):
+    """K slices for an MX weight gradient: the bf16 rule (_wgrad), on whole 128-deep tiles."""
+    bt = tiles
+    s = 1
+    while bt * s < 224 and s < 32:
+        s *= 2
+    while s > 1 and (K % s or (K // s) % 128):
+        s -= 1
+    return s
+
+
+def _mx_wgrad(dTt, xt, w, Np, K, n_rows):
+    """dW (n_rows, K) = dT^T x from the transposed forms dTt (Np, Mp) and xt (K, Mp), accumulated into
+    w.grad when it is a FlatAdam slot."""
+    Mp = xt.q.shape[1]
+    sk = _mx_splitk((Np // 128) * (K // 128), Mp)
+    slot = _grad_slot(w)
+    if slot is not None and Np == n_rows:
+        ops.gemm_mx(dTt, xt, Np, K, Mp, C=slot, splitk=sk, accumulate=True)
+        _report_done(w)
+        return None
+    dw = torch.empty((Np, K), dtype=torch.float32, device=xt.q.device)
+    ops.gemm_mx(dTt, xt, Np, K, Mp, C=dw, splitk=sk)
+    dw = dw[:n_rows]
+    if slot is not None:
+        slot.add_(dw)
+        _report_done(w)
+        return None
+    return dw
+
+
+def _mx_grad_in(dT, b, n):
+    """Row and transposed forms of an incoming gradient dT (M, Np) and, from the same pass, the bias
+    gradient (first n columns): (row form, transposed form, db or None)."""
+    Np = dT.shape[1]
+    slot = _grad_slot(b) if b is not None else None
+    if b is None:
+        rf, tf = ops.mx_quant(dT, row=True, transposed=True)
+        return rf, tf, None
+    if slot is not None and Np == n:
+        rf, tf = ops.mx_quant(dT, row=True, transposed=True, colsum=slot, accumulate=True)
+        _report_done(b)
+        return rf, tf, None
+    tmp = torch.empty(Np, dtype=torch.float32, device=dT.device)
+    rf, tf = ops.mx_quant(dT, row=True, transposed=True, colsum=tmp)
+    if slot is not None:
+        slot.add_(tmp[:n])
+        _report_done(b)
+        return rf, tf, None
+    return rf, tf, tmp[:n]
+
+
+def _mlp_mx_fwd(xr, M, K, w1, b1, w2, b2, act1, act2, Np, device):
+    """The two forward products of one MLP from x's row form: (y (M, Np) fp32, t2 or None, t1b,
+    h's transposed form)."""
+    H = w1.shape[0]
+    w1r, _ = ops.mx_weight(w1)
+    w2r, _ = ops.mx_weight(w2, Np)
+    hb = torch.empty((M, H), dtype=torch.bfloat16, device=device)
+    t1b = torch.empty((M, H), dtype=torch.bfloat16, device=device) if act1 else None
+    ops.gemm_mx(xr, w1r, M, H, K, bias=b1, act=act1, Cb=hb, Pb=t1b)
+    hr, ht = ops.mx_quant(hb, row=True, transposed=True)
+    y = torch.empty((M, Np), dtype=torch.float32, device=device)
+    t2 = torch.empty((M, Np), dtype=torch.float32, device=device) if act2 else None
+    b2p = b2
+    if Np != w2.shape[0] and b2 is not None:
+        b2p = torch.zeros(Np, dtype=torch.float32, device=device)
+        b2p[:w2.shape[0]].copy_(b2.detach())
+    ops.gemm_mx(hr, w2r, M, Np, H, C=y, bias=b2p, preact=t2, act=act2)
+    return y, t2, t1b, ht
+
+
+def _mlp_mx_bwd(dT2, w1, b1, w2, b2, t1b, ht, xt, act1, N, Np, need, dx):
+    """Backward of one MLP from dT2 (M, Np) fp32; need = needs_input_grad of (x, w1, b1, w2, b2).
+    dx: None (no input gradient), or (tensor, accumulate).  Returns (dw1, db1, dw2, db2)."""
+    M = dT2.shape[0]
+    H, K = w1.shape
+    d2r, d2t, db2 = _mx_grad_in(dT2, b2 if need[4] else None, N)
+    _, w2t = ops.mx_weight(w2, Np)
+    dT1b = torch.empty((M, H), dtype=torch.bfloat16, device=dT2.device)
+    ops.gemm_mx(d2r, w2t, M, H, Np, gradz=t1b if act1 else None, gact=act1, Cb=dT1b)
+    dw2 = _mx_wgrad(d2t, ht, w2, Np, H, N) if need[3] else None
+    del d2r, d2t
+    d1r, d1t, db1 = _mx_grad_in(dT1b, b1 if need[2] else None, H)
+    if dx is not None:
+        _, w1t = ops.mx_weight(w1)
+        ops.gemm_mx(d1r, w1t, M, K, H, C=dx[0], accumulate=dx[1])
+    dw1 = _mx_wgrad(d1t, xt, w1, H, K, H) if need[1] else None
+    return dw1, db1, dw2, db2
+
+
+class _MLP2MX(torch.autograd.Function):
+    """y = act2(act1(x W1^T + b1) W2^T + b2), all six products on MX-e4m3 operands."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, act1, act2):
+        require_cuda(x, w1, w2)
+        shp = x.shape
+        x2 = _2d(f32c(x))
+        M, K = x2.shape
+        N = w2.shape[0]
+        Np = _pad128(N)
+        xr, xt = ops.mx_quant(x2, row=True, transposed=True)
+        y, t2, t1b, ht = _mlp_mx_fwd(xr, M, K, w1, b1, w2, b2, act1, act2, Np, x2.device)
+        ctx.save_for_backward(xt.q, xt.s, ht.q, ht.s, t1b if t1b is not None else ht.q,
+                              t2 if t2 is not None else ht.q)
+        ctx.cfg = (act1, act2, N, Np, shp)
+        ctx.params = (w1, b1, w2, b2)
+        if Np != N:
+            y = y[:, :N].contiguous()
+        return y.reshape(*shp[:-1], N)
+
+    @staticmethod
+    def backward(ctx, dy):
+        xq, xs, hq, hs, t1b, t2 = ctx.saved_tensors
+        act1, act2, N, Np, shp = ctx.cfg
+        w1, b1, w2, b2 = ctx.params
+        dy2 = _2d(f32c(dy))
+        M = dy2.shape[0]
+        if Np != N:
+            pad = torch.zeros((M, Np), dtype=torch.float32, device=dy2.device)
+            pad[:, :N].copy_(dy2)
+            dy2 = pad
+        dT2 = ops.act_bwd(dy2, t2, act2) if act2 else dy2
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty((M, w1.shape[1]), dtype=torch.float32, device=dy2.device)
+        need = [ctx.needs_input_grad[i] for i in range(5)]
+        dw1, db1, dw2, db2 = _mlp_mx_bwd(dT2, w1, b1, w2, b2, t1b if act1 else None, ops.MxOperand(hq, hs),
+                                         ops.MxOperand(xq, xs), act1, N, Np, need,
+                                         (dx, False) if dx is not None else None)
+        if dx is not None:
+            dx = dx.reshape(shp)
+        return dx, dw1, db1, dw2, db2, None, None
+
+
+class _MLP2x3MX(torch.autograd.Function):
+    """The q, k, v MLPs on their common input in "mxfp8": one quantisation of the input, the three
+    input gradients accumulated by the GEMM epilogues into one tensor."""
+
+    @staticmethod
+    def forward(ctx, x, act1, act2, *params):
+        require_cuda(x, *params)
+        shp = x.shape
+        x2 = _2d(f32c(x))
+        M, K = x2.shape
+        xr, xt = ops.mx_quant(x2, row=True, transposed=True)
+        outs, saved = [], [xt.q, xt.s]
+        for i in range(3):
+            w1, b1, w2, b2 = params[4 * i:4 * i + 4]
+            N = w2.shape[0]
+            y, t2, t1b, ht = _mlp_mx_fwd(xr, M, K, w1, b1, w2, b2, act1, act2, N, x2.device)
+            outs.append(y.reshape(*shp[:-1], N))
+            saved += [ht.q, ht.s, t1b if t1b is not None else ht.q, t2 if t2 is not None else ht.q]
+        ctx.save_for_backward(*saved)
+        ctx.cfg = (act1, act2, shp)
+        ctx.params = params
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *dys):
+        saved = ctx.saved_tensors
+        act1, act2, shp = ctx.cfg
+        xt = ops.MxOperand(saved[0], saved[1])
+        K = ctx.params[0].shape[1]
+        grads = []
+        dx = None
+        for i in range(3):
+            w1, b1, w2, b2 = ctx.params[4 * i:4 * i + 4]
+            hq, hs, t1b, t2 = saved[2 + 4 * i:6 + 4 * i]
+            N = w2.shape[0]
+            ni = 3 + 4 * i
+            dy2 = _2d(f32c(dys[i]))
+            M = dy2.shape[0]
+            dT2 = ops.act_bwd(dy2, t2, act2) if act2 else dy2
+            dxa = None
+            if ctx.needs_input_grad[0]:
+                first = dx is None
+                if first:
+                    dx = torch.empty((M, K), dtype=torch.float32, device=dy2.device)
+                dxa = (dx, not first)
+            need = [ctx.needs_input_grad[0]] + [ctx.needs_input_grad[ni + j] for j in range(4)]
+            grads += list(_mlp_mx_bwd(dT2, w1, b1, w2, b2, t1b if act1 else None, ops.MxOperand(hq, hs), xt,
+                                      act1, N, N, need, dxa))
+        if dx is not None:
+            dx = dx.reshape(shp)
+        return (dx, None, None, *grads)
+
+
+class _LinearActMX(torch.autograd.Function):
+    """y = act(x W^T + b [+ residual]), the three products on MX-e4m3 operands."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual, act):
+        require_cuda(x, weight)
+        shp = x.shape
+        x2 = _2d(f32c(x))
+        M, K = x2.shape
+        N = weight.shape[0]
+        xr, xt = ops.mx_quant(x2, row=True, transposed=True)
+        wr, _ = ops.mx_weight(weight)
+        r2 = _2d(f32c(residual)) if residual is not None else None
+        y = torch.empty((M, N), dtype=torch.float32, device=x2.device)
+        t = torch.empty((M, N), dtype=torch.float32, device=x2.device) if act else None
+        ops.gemm_mx(xr, wr, M, N, K, C=y, bias=bias, residual=r2, preact=t, act=act)
+        ctx.save_for_backward(xt.q, xt.s, t if t is not None else xt.q)
+        ctx.cfg = (act, residual is not None, shp)
+        ctx.params = (weight, bias)
+        return y.reshape(*shp[:-1], N)
+
+    @staticmethod
+    def backward(ctx, dy):
+        xq, xs, t = ctx.saved_tensors
+        act, has_res, shp = ctx.cfg
+        weight, bias = ctx.params
+        N, K = weight.shape
+        dy2 = _2d(f32c(dy))
+        M = dy2.shape[0]
+        dT = ops.act_bwd(dy2, t, act) if act else dy2
+        dr_, dt_, db = _mx_grad_in(dT, bias if (bias is not None and ctx.needs_input_grad[2]) else None, N)
+        dx = dw = dr = None
+        if ctx.needs_input_grad[0]:
+            _, wt = ops.mx_weight(weight)
+            dx = torch.empty((M, K), dtype=torch.float32, device=dy2.device)
+            ops.gemm_mx(dr_, wt, M, K, N, C=dx)
+            dx = dx.reshape(shp)
+        if ctx.needs_input_grad[1]:
+            dw = _mx_wgrad(dt_, ops.MxOperand(xq, xs), weight, N, K, N)
+        if has_res and ctx.needs_input_grad[3]:
+            dr = dT.reshape(dy.shape)
+        return dx, dw, db, dr, None
+
+
+def _mx(M, N, K):
+    return ops.mx_supported(M, N, K, 1)
+
+
+def _mlp_mx_ok(M, K, H, N):
+    """Every product of an MLP node on the MX kernel (quantised tensors need 128-multiple widths)."""
+    Np, Mp = _pad128(N), _pad128(M)
+    return (_mx(M, H, K) and _mx(M, Np, H) and _mx(M, H, Np) and _mx(M, K, H) and _mx(Np, H, Mp)
+            and _mx(H, K, Mp))
+
+
+def mlp2_node(x, w1, b1, w2, b2, act1, act2):
+    """The reduced-precision MLP node of the current mode (callers checked mlp2_supported)."""
+    M = x.numel() // x.shape[-1]
+    if ops.PRECISION == "mxfp8" and _mlp_mx_ok(M, w1.shape[1], w1.shape[0], w2.shape[0]):
+        return _MLP2MX.apply(x, w1, b1, w2, b2, act1, act2)
+    return _MLP2LP.apply(x, w1, b1, w2, b2, act1, act2)
+
+
+def mlp2x3_node(x, act1, act2, flat_params):
+    M = x.numel() // x.shape[-1]
+    if ops.PRECISION == "mxfp8" and all(
+            _mlp_mx_ok(M, flat_params[4 * i].shape[1], flat_params[4 * i].shape[0], flat_params[4 * i + 2].shape[0])
+            and flat_params[4 * i + 2].shape[0] % 128 == 0 for i in range(3)):
+        return _MLP2x3MX.apply(x, act1, act2, *flat_params)
+    return _MLP2x3LP.apply(x, act1, act2, *flat_params)
+
+
+def linear_node(x, weight, bias, residual, act):
+    M = x.numel() // x.shape[-1]
+    N, K = weight.shape
+    if ops.PRECISION == "mxfp8" and _mx(M, N, K) and _mx(M, K, N) and _mx(N, K, _pad128(M)):
+        return _LinearActMX.apply(x, weight, bias, residual, act)
+    return _LinearActLP.apply(x, weight, bias, residual, act)

@@ -134,13 +134,15 @@ GEMM_EVENTS = None
 # (opt-in: Linear-layer contractions on the bf16 MFMA with fp32 accumulation and fp32
 # tensors; BASELINE config 5 direction, tolerance stated in tests/test_gpu_bf16.py).
 # QARIG_PRECISION in the environment sets the default.
+# "fp8" adds per-tensor e4m3 forward products to "bf16"; "mxfp8" runs every product of the Linear
+# nodes (forward and both gradients) on block-scaled MX-e4m3 operands (include/qarig.h).
 PRECISION = os.environ.get("QARIG_PRECISION", "f32")
-PRECISIONS = ("f32", "bf16", "fp8")
+PRECISIONS = ("f32", "bf16", "fp8", "mxfp8")
 
 
 def lp_mode():
-    """bf16 storage / bf16-MFMA nodes active ("bf16", and "fp8" which adds e4m3 forward products)."""
-    return PRECISION in ("bf16", "fp8")
+    """bf16 storage / bf16-MFMA nodes active ("bf16"; "fp8" and "mxfp8" build on it)."""
+    return PRECISION in ("bf16", "fp8", "mxfp8")
 
 
 def set_precision(name):
@@ -318,6 +320,103 @@ def gemm_f8(A8, inv_a, B8, inv_b, M, N, K, C=None, bias=None, residual=None, pre
         ev1 = torch.cuda.Event(enable_timing=True)
         ev1.record()
         GEMM_EVENTS.append((2.0 * M * N * K, ev0, ev1, "f8"))
+
+
+class MxOperand:
+    """An MX-e4m3 operand (include/qarig.h): q (rows, K) e4m3 bytes as torch.uint8, s (rows, K/32) e8m0
+    scale bytes.  `rows` is the logical row count of the product operand."""
+    __slots__ = ("q", "s")
+
+    def __init__(self, q, s):
+        self.q, self.s = q, s
+
+
+def mx_quant(x, row=True, transposed=False, colsum=None, accumulate=False):
+    """One pass over x (R, C) (fp32 or bf16, row-contiguous, C % 128 == 0): (row form or None,
+    transposed form or None) as MxOperand; with `colsum` (fp32 (C,)) the column sums of x are
+    written into it (added with `accumulate`)."""
+    assert x.dim() == 2 and x.stride(1) == 1 and x.dtype in (torch.float32, torch.bfloat16)
+    R, C = x.shape
+    Rp = (R + 127) // 128 * 128
+    dev = x.device
+    rf = MxOperand(torch.empty((R, C), dtype=torch.uint8, device=dev),
+                   torch.empty((R, C // 32), dtype=torch.uint8, device=dev)) if row else None
+    tf = MxOperand(torch.empty((C, Rp), dtype=torch.uint8, device=dev),
+                   torch.empty((C, Rp // 32), dtype=torch.uint8, device=dev)) if transposed else None
+    lib = _lib.load()
+    ws, nws = None, 0
+    if colsum is not None:
+        assert colsum.shape == (C,) and colsum.is_contiguous() and colsum.dtype == torch.float32
+        ws = workspace(lib.qarig_mx_quant_workspace_bytes(R, C), dev, "colsum")
+        nws = ws.numel()
+    check(lib.qarig_mx_quant(ptr(x), x.stride(0), int(x.dtype == torch.bfloat16), R, C,
+                             ptr(rf.q if rf else None), ptr(rf.s if rf else None),
+                             ptr(tf.q if tf else None), ptr(tf.s if tf else None), ptr(colsum), int(accumulate),
+                             ptr(ws), nws, stream()), "qarig_mx_quant")
+    return rf, tf
+
+
+def mx_supported(M, N, K, splitk=1):
+    return bool(_lib.load().qarig_gemm_mx_supported(int(M), int(N), int(K), int(splitk)))
+
+
+def gemm_mx(A, B, M, N, K, C=None, bias=None, residual=None, preact=None, act=0, gradz=None, gact=0, splitk=1,
+            accumulate=False, Cb=None, Pb=None):
+    """C = epilogue(A B^T) on MX-e4m3 operands (include/qarig.h qarig_gemm_mx): A, B MxOperand with
+    (M, K) and (N, K) bytes; epilogue options as gemm_lp."""
+    lib = _lib.load()
+    ws, nws = None, 0
+    if splitk > 1:
+        nws = lib.qarig_gemm_mx_workspace_bytes(M, N, splitk)
+        ws = workspace(nws, A.q.device, "gemm")
+        nws = ws.numel()
+    if GEMM_EVENTS is not None:
+        ev0 = torch.cuda.Event(enable_timing=True)
+        ev0.record()
+    check(lib.qarig_gemm_mx(
+        ptr(A.q), A.q.stride(0), ptr(A.s), A.s.stride(0), ptr(B.q), B.q.stride(0), ptr(B.s), B.s.stride(0),
+        ptr(C), C.stride(0) if C is not None else 0, M, N, K, ptr(bias),
+        ptr(residual), residual.stride(0) if residual is not None else 0,
+        ptr(preact), preact.stride(0) if preact is not None else 0, act,
+        ptr(gradz), gradz.stride(0) if gradz is not None else 0,
+        int(gradz is not None and gradz.dtype == torch.bfloat16), gact, splitk, int(accumulate),
+        ptr(Cb), Cb.stride(0) if Cb is not None else 0, ptr(Pb), Pb.stride(0) if Pb is not None else 0,
+        ptr(ws), nws, stream()), "qarig_gemm_mx")
+    if GEMM_EVENTS is not None:
+        ev1 = torch.cuda.Event(enable_timing=True)
+        ev1.record()
+        outs = "+".join(n for n, t in (("C", C), ("P", preact), ("Cb", Cb), ("Pb", Pb)) if t is not None)
+        ins = "".join(n for n, t in (("b", bias), ("r", residual), ("z", gradz)) if t is not None)
+        hbm = 1.03 * (M * K + N * K) + M * N * (4.0 * (C is not None) * (2 if accumulate and splitk == 1 else 1) +
+                                               4.0 * (preact is not None) + 2.0 * (Cb is not None) +
+                                               2.0 * (Pb is not None) + 4.0 * (residual is not None) +
+                                               (0 if gradz is None else gradz.element_size()))
+        GEMM_EVENTS.append((2.0 * M * N * K, ev0, ev1, "",
+                            f"mx NT {M}x{N}x{K} sk{splitk} out {outs} in {ins or '-'} act{act}", hbm))
+
+
+def mx_weight(w, pad_rows=0):
+    """(row form, transposed form) of a weight (N, K) -- zero-padded to pad_rows output rows when
+    given -- cached until the next optimiser step under the keys of the bf16 shadows (address,
+    shape, version, LP_EPOCH); rebuilt on every call under stream capture, so that a replayed
+    graph quantises the weights the optimiser has just written."""
+    src = getattr(w, "_qarig_src", w)
+    Np = pad_rows or w.shape[0]
+    capturing = torch.cuda.is_current_stream_capturing()
+    key = ("mx", w.data_ptr(), tuple(w.shape), Np, w._version, LP_EPOCH)
+    if not capturing:
+        hit = _lp_get(key, src)
+        if hit is not None:
+            return hit
+    wd = w.detach()
+    if Np != w.shape[0]:
+        wp = torch.zeros((Np, w.shape[1]), dtype=torch.float32, device=w.device)
+        wp[:w.shape[0]].copy_(wd)
+        wd = wp
+    out = mx_quant(wd if wd.is_contiguous() else wd.contiguous(), row=True, transposed=True)
+    if not capturing:
+        _lp_put(key, src, out)
+    return out
 
 
 def cast_transpose_bf16(x, cache=False):
