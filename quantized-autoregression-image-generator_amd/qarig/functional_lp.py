@@ -91,6 +91,31 @@ def _splitk(tiles, K):
     return s
 
 
+def _grad_into(p, n, Np, alloc, run):
+    """The gradient of parameter p from a kernel that writes Np >= n rows (entries) of it:
+    run(out, accumulate) launches it.  Accumulated straight into p.grad when that is a FlatAdam slot
+    of the kernel's extent, else through a temporary from alloc().  Returns (gradient, or None when
+    it went into the slot; what run returned)."""
+    slot = _grad_slot(p)
+    if slot is not None and Np == n:
+        r = run(slot, True)
+        _report_done(p)
+        return None, r
+    tmp = alloc()
+    r = run(tmp, False)
+    g = tmp[:n]
+    if slot is not None:
+        slot.add_(g)
+        _report_done(p)
+        return None, r
+    return g, r
+
+
+def _wgrad_into(w, Np, K, n_rows, device, gemm):
+    """dW (n_rows, K) of w from gemm(C, accumulate), which writes (Np, K)."""
+    return _grad_into(w, n_rows, Np, lambda: torch.empty((Np, K), dtype=torch.float32, device=device), gemm)[0]
+
+
 def _wgrad(dTb, xb, w, n_rows):
     """dW (n_rows, K) = dT^T x over the token rows, fp32, accumulated into w.grad when it is a
     FlatAdam slot; dTb (M, Np >= n_rows) and xb (M, K) are the row-major bf16 activations."""
@@ -106,39 +131,51 @@ def _wgrad(dTb, xb, w, n_rows):
             s *= 2
         if bt >= 16 and M % s == 0 and (M // s) % 64 == 0 and M // s >= 1024:
             sk = s
-    slot = _grad_slot(w)
-    if slot is not None and Np == n_rows:
-        ops.gemm_lp(dTb, xb, 1, Np, K, M, C=slot, splitk=sk, accumulate=True)
-        _report_done(w)
-        return None
-    dw = torch.empty((Np, K), dtype=torch.float32, device=xb.device)
-    ops.gemm_lp(dTb, xb, 1, Np, K, M, C=dw, splitk=sk)
-    dw = dw[:n_rows]
-    if slot is not None:
-        slot.add_(dw)
-        _report_done(w)
-        return None
-    return dw
+    return _wgrad_into(w, Np, K, n_rows, xb.device,
+                       lambda C, acc: ops.gemm_lp(dTb, xb, 1, Np, K, M, C=C, splitk=sk, accumulate=acc))
 
 
 def _bias_grad(src, b, n, want_cast):
     """Column sums of src (M, Np) -> bias gradient (first n columns); returns (db or None,
     bf16 copy of src or None)."""
     Np = src.shape[1]
-    slot = _grad_slot(b) if b is not None else None
     if b is None:
         return None, (ops.cast_bf16(src) if want_cast else None)
-    if slot is not None and Np == n:
-        cb = ops.cast_colsum(src, slot, accumulate=True, want_cast=want_cast)
-        _report_done(b)
-        return None, cb
-    tmp = torch.zeros(Np, dtype=torch.float32, device=src.device)
-    cb = ops.cast_colsum(src, tmp, accumulate=False, want_cast=want_cast)
-    if slot is not None:
-        slot.add_(tmp[:n])
-        _report_done(b)
-        return None, cb
-    return tmp[:n], cb
+    return _grad_into(b, n, Np, lambda: torch.zeros(Np, dtype=torch.float32, device=src.device),
+                      lambda out, acc: ops.cast_colsum(src, out, accumulate=acc, want_cast=want_cast))
+
+
+def _mlp_lp_fwd(xq, xb, M, K, w1, b1, w2, b2, act1, act2, Np, device):
+    """The two forward products of one MLP from x's bf16 copy (or its e4m3 form xq): (y (M, Np)
+    fp32, t2 or None, t1b or None, hb)."""
+    H, N = w1.shape[0], w2.shape[0]
+    hb = torch.empty((M, H), dtype=torch.bfloat16, device=device)
+    t1b = torch.empty((M, H), dtype=torch.bfloat16, device=device) if act1 else None
+    _fwd_nt(xq, xb, w1, M, H, K, bias=b1, act=act1, Cb=hb, Pb=t1b)
+    y = torch.empty((M, Np), dtype=torch.float32, device=device)
+    t2 = torch.empty((M, Np), dtype=torch.float32, device=device) if act2 else None
+    b2p = b2
+    if Np != N and b2 is not None:
+        b2p = torch.zeros(Np, dtype=torch.float32, device=device)
+        b2p[:N].copy_(b2.detach())
+    ops.gemm_lp(hb, _shadow(w2, pad_rows=Np), 0, M, Np, H, C=y, bias=b2p, preact=t2, act=act2)
+    return y, t2, t1b, hb
+
+
+def _mlp_lp_bwd(dT2, w1, b1, w2, b2, t1b, hb, xb, act1, N, Np, need, dx):
+    """Backward of one MLP from dT2 (M, Np) fp32; need = needs_input_grad of (x, w1, b1, w2, b2).
+    dx: None (no input gradient), or (tensor, accumulate).  Returns (dw1, db1, dw2, db2)."""
+    M = dT2.shape[0]
+    H, K = w1.shape
+    db2, dT2b = _bias_grad(dT2, b2 if need[4] else None, N, True)
+    dT1b = torch.empty((M, H), dtype=torch.bfloat16, device=dT2.device)
+    ops.gemm_lp(dT2b, _shadow(w2, pad_rows=Np), 2, M, H, Np, gradz=t1b if act1 else None, gact=act1, Cb=dT1b)
+    dw2 = _wgrad(dT2b, hb, w2, N) if need[3] else None
+    db1, _ = _bias_grad(dT1b, b1 if need[2] else None, H, False)
+    if dx is not None:
+        ops.gemm_lp(dT1b, _shadow(w1), 2, M, K, H, C=dx[0], accumulate=dx[1])
+    dw1 = _wgrad(dT1b, xb, w1, H) if need[1] else None
+    return dw1, db1, dw2, db2
 
 
 class _MLP2LP(torch.autograd.Function):
@@ -150,19 +187,10 @@ class _MLP2LP(torch.autograd.Function):
         shp = x.shape
         x2 = _2d(f32c(x))
         M, K = x2.shape
-        H, N = w1.shape[0], w2.shape[0]
+        N = w2.shape[0]
         Np = _pad128(N)
-        xb, xq = _cast_in(x2, [(M, H, K)])
-        hb = torch.empty((M, H), dtype=torch.bfloat16, device=x2.device)
-        t1b = torch.empty((M, H), dtype=torch.bfloat16, device=x2.device) if act1 else None
-        _fwd_nt(xq, xb, w1, M, H, K, bias=b1, act=act1, Cb=hb, Pb=t1b)
-        y = torch.empty((M, Np), dtype=torch.float32, device=x2.device)
-        t2 = torch.empty((M, Np), dtype=torch.float32, device=x2.device) if act2 else None
-        b2p = b2
-        if Np != N and b2 is not None:
-            b2p = torch.zeros(Np, dtype=torch.float32, device=x2.device)
-            b2p[:N].copy_(b2.detach())
-        ops.gemm_lp(hb, _shadow(w2, pad_rows=Np), 0, M, Np, H, C=y, bias=b2p, preact=t2, act=act2)
+        xb, xq = _cast_in(x2, [(M, w1.shape[0], K)])
+        y, t2, t1b, hb = _mlp_lp_fwd(xq, xb, M, K, w1, b1, w2, b2, act1, act2, Np, x2.device)
         ctx.save_for_backward(xb, t1b if t1b is not None else hb, hb, t2 if t2 is not None else hb)
         ctx.cfg = (act1, act2, N, Np, shp)
         ctx.params = (w1, b1, w2, b2)
@@ -176,25 +204,17 @@ class _MLP2LP(torch.autograd.Function):
         act1, act2, N, Np, shp = ctx.cfg
         w1, b1, w2, b2 = ctx.params
         M, K = xb.shape
-        H = hb.shape[1]
         dy2 = _2d(f32c(dy))
         if Np != N:
             pad = torch.zeros((M, Np), dtype=torch.float32, device=dy2.device)
             pad[:, :N].copy_(dy2)
             dy2 = pad
         dT2 = ops.act_bwd(dy2, t2, act2) if act2 else dy2
-        db2, dT2b = _bias_grad(dT2, b2 if ctx.needs_input_grad[4] else None, N, True)
-        dT1b = torch.empty((M, H), dtype=torch.bfloat16, device=dy2.device)
-        ops.gemm_lp(dT2b, _shadow(w2, pad_rows=Np), 2, M, H, Np,
-                    gradz=t1b if act1 else None, gact=act1, Cb=dT1b)
-        dw2 = _wgrad(dT2b, hb, w2, N) if ctx.needs_input_grad[3] else None
-        db1, _ = _bias_grad(dT1b, b1 if ctx.needs_input_grad[2] else None, H, False)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty((M, K), dtype=torch.float32, device=dy2.device)
-            ops.gemm_lp(dT1b, _shadow(w1), 2, M, K, H, C=dx)
+        dx = torch.empty((M, K), dtype=torch.float32, device=dy2.device) if ctx.needs_input_grad[0] else None
+        dw1, db1, dw2, db2 = _mlp_lp_bwd(dT2, w1, b1, w2, b2, t1b, hb, xb, act1, N, Np, ctx.needs_input_grad[:5],
+                                         (dx, False) if dx is not None else None)
+        if dx is not None:
             dx = dx.reshape(shp)
-        dw1 = _wgrad(dT1b, xb, w1, H) if ctx.needs_input_grad[1] else None
         return dx, dw1, db1, dw2, db2, None, None
 
 
@@ -212,15 +232,10 @@ class _MLP2x3LP(torch.autograd.Function):
         outs, saved = [], [xb]
         for i in range(3):
             w1, b1, w2, b2 = params[4 * i:4 * i + 4]
-            H, N = w1.shape[0], w2.shape[0]
-            hb = torch.empty((M, H), dtype=torch.bfloat16, device=x2.device)
-            t1b = torch.empty((M, H), dtype=torch.bfloat16, device=x2.device) if act1 else hb
-            _fwd_nt(xq, xb, w1, M, H, K, bias=b1, act=act1, Cb=hb, Pb=t1b if act1 else None)
-            y = torch.empty((M, N), dtype=torch.float32, device=x2.device)
-            t2 = torch.empty((M, N), dtype=torch.float32, device=x2.device) if act2 else None
-            ops.gemm_lp(hb, _shadow(w2), 0, M, N, H, C=y, bias=b2, preact=t2, act=act2)
+            N = w2.shape[0]
+            y, t2, t1b, hb = _mlp_lp_fwd(xq, xb, M, K, w1, b1, w2, b2, act1, act2, N, x2.device)
             outs.append(y.reshape(*shp[:-1], N))
-            saved += [t1b, hb, t2 if t2 is not None else hb]
+            saved += [t1b if t1b is not None else hb, hb, t2 if t2 is not None else hb]
         ctx.save_for_backward(*saved)
         ctx.cfg = (act1, act2, shp)
         ctx.params = params
@@ -237,24 +252,16 @@ class _MLP2x3LP(torch.autograd.Function):
         for i in range(3):
             w1, b1, w2, b2 = ctx.params[4 * i:4 * i + 4]
             t1b, hb, t2 = saved[1 + 3 * i:4 + 3 * i]
-            H, N = w1.shape[0], w2.shape[0]
+            N = w2.shape[0]
             ni = 3 + 4 * i
             dy2 = _2d(f32c(dys[i]))
             dT2 = ops.act_bwd(dy2, t2, act2) if act2 else dy2
-            db2, dT2b = _bias_grad(dT2, b2 if ctx.needs_input_grad[ni + 3] else None, N, True)
-            dT1b = torch.empty((M, H), dtype=torch.bfloat16, device=dy2.device)
-            ops.gemm_lp(dT2b, _shadow(w2), 2, M, H, N, gradz=t1b if act1 else None,
-                        gact=act1, Cb=dT1b)
-            dw2 = _wgrad(dT2b, hb, w2, N) if ctx.needs_input_grad[ni + 2] else None
-            db1, _ = _bias_grad(dT1b, b1 if ctx.needs_input_grad[ni + 1] else None, H, False)
-            if ctx.needs_input_grad[0]:
-                if dx is None:
-                    dx = torch.empty((M, K), dtype=torch.float32, device=dy2.device)
-                    ops.gemm_lp(dT1b, _shadow(w1), 2, M, K, H, C=dx)
-                else:
-                    ops.gemm_lp(dT1b, _shadow(w1), 2, M, K, H, C=dx, accumulate=True)
-            dw1 = _wgrad(dT1b, xb, w1, H) if ctx.needs_input_grad[ni] else None
-            grads += [dw1, db1, dw2, db2]
+            first = dx is None
+            if ctx.needs_input_grad[0] and first:
+                dx = torch.empty((M, K), dtype=torch.float32, device=dy2.device)
+            need = (ctx.needs_input_grad[0], *ctx.needs_input_grad[ni:ni + 4])
+            grads += _mlp_lp_bwd(dT2, w1, b1, w2, b2, t1b, hb, xb, act1, N, N, need,
+                                 (dx, not first) if dx is not None else None)
         if dx is not None:
             dx = dx.reshape(shp)
         return (dx, None, None, *grads)
@@ -334,40 +341,20 @@ def _mx_wgrad(dTt, xt, w, Np, K, n_rows):
     w.grad when it is a FlatAdam slot."""
     Mp = xt.q.shape[1]
     sk = _mx_splitk((Np // 128) * (K // 128), Mp)
-    slot = _grad_slot(w)
-    if slot is not None and Np == n_rows:
-        ops.gemm_mx(dTt, xt, Np, K, Mp, C=slot, splitk=sk, accumulate=True)
-        _report_done(w)
-        return None
-    dw = torch.empty((Np, K), dtype=torch.float32, device=xt.q.device)
-    ops.gemm_mx(dTt, xt, Np, K, Mp, C=dw, splitk=sk)
-    dw = dw[:n_rows]
-    if slot is not None:
-        slot.add_(dw)
-        _report_done(w)
-        return None
-    return dw
+    return _wgrad_into(w, Np, K, n_rows, xt.q.device,
+                       lambda C, acc: ops.gemm_mx(dTt, xt, Np, K, Mp, C=C, splitk=sk, accumulate=acc))
 
 
 def _mx_grad_in(dT, b, n):
     """Row and transposed forms of an incoming gradient dT (M, Np) and, from the same pass, the bias
     gradient (first n columns): (row form, transposed form, db or None)."""
     Np = dT.shape[1]
-    slot = _grad_slot(b) if b is not None else None
     if b is None:
         rf, tf = ops.mx_quant(dT, row=True, transposed=True)
         return rf, tf, None
-    if slot is not None and Np == n:
-        rf, tf = ops.mx_quant(dT, row=True, transposed=True, colsum=slot, accumulate=True)
-        _report_done(b)
-        return rf, tf, None
-    tmp = torch.empty(Np, dtype=torch.float32, device=dT.device)
-    rf, tf = ops.mx_quant(dT, row=True, transposed=True, colsum=tmp)
-    if slot is not None:
-        slot.add_(tmp[:n])
-        _report_done(b)
-        return rf, tf, None
-    return rf, tf, tmp[:n]
+    db, (rf, tf) = _grad_into(b, n, Np, lambda: torch.empty(Np, dtype=torch.float32, device=dT.device),
+                              lambda out, acc: ops.mx_quant(dT, row=True, transposed=True, colsum=out, accumulate=acc))
+    return rf, tf, db
 
 
 def _mlp_mx_fwd(xr, M, K, w1, b1, w2, b2, act1, act2, Np, device):

@@ -302,24 +302,67 @@ def f8_supported(M, N, K):
     return bool(_lib.load().qarig_gemm_f8_supported(M, N, K))
 
 
+def _ld(t):
+    return t.stride(0) if t is not None else 0
+
+
+def _epilogue_args(C, M, N, K, bias, residual, preact, act, Cb, Pb, grad=()):
+    """The epilogue arguments that qarig_gemm_lp / _f8 / _mx share, in their order: C, the extents, bias,
+    residual, pre-activation, act, [`grad`: gradz, gact, splitk, accumulate -- not for _f8], Cb, Pb."""
+    if grad:
+        gradz, gact, splitk, accumulate = grad
+        grad = (ptr(gradz), _ld(gradz), int(gradz is not None and gradz.dtype == torch.bfloat16), gact, splitk,
+                int(accumulate))
+    return (ptr(C), _ld(C), M, N, K, ptr(bias), ptr(residual), _ld(residual), ptr(preact), _ld(preact), act,
+            *grad, ptr(Cb), _ld(Cb), ptr(Pb), _ld(Pb))
+
+
+def _splitk_workspace(nbytes_fn, M, N, splitk, device):
+    """(workspace, its size) for the fp32 slabs of a split-K product; (None, 0) without split-K."""
+    if splitk <= 1:
+        return None, 0
+    ws = workspace(nbytes_fn(M, N, splitk), device, "gemm")
+    return ws, ws.numel()
+
+
+def _event_begin():
+    """Start event of a GEMM_EVENTS record (None when nothing is recorded)."""
+    if GEMM_EVENTS is None:
+        return None
+    ev0 = torch.cuda.Event(enable_timing=True)
+    ev0.record()
+    return ev0
+
+
+def _event_end(ev0, M, N, K, tail):
+    """Appends (flops, start, end, *tail()) to GEMM_EVENTS."""
+    if ev0 is None or GEMM_EVENTS is None:
+        return
+    ev1 = torch.cuda.Event(enable_timing=True)
+    ev1.record()
+    GEMM_EVENTS.append((2.0 * M * N * K, ev0, ev1, *tail()))
+
+
+def _lp_event_tail(what, operand_bytes, M, N, K, C, bias, residual, preact, act, gradz, splitk, accumulate, Cb, Pb):
+    """("", description, HBM bytes) of a reduced-precision product for its GEMM_EVENTS record."""
+    outs = "+".join(n for n, t in (("C", C), ("P", preact), ("Cb", Cb), ("Pb", Pb)) if t is not None)
+    ins = "".join(n for n, t in (("b", bias), ("r", residual), ("z", gradz)) if t is not None)
+    hbm = operand_bytes * (M * K + N * K) + M * N * (4.0 * (C is not None) * (2 if accumulate and splitk == 1 else 1) +
+                                                     4.0 * (preact is not None) + 2.0 * (Cb is not None) +
+                                                     2.0 * (Pb is not None) + 4.0 * (residual is not None) +
+                                                     (0 if gradz is None else gradz.element_size()))
+    return "", f"{what} {M}x{N}x{K} sk{splitk} out {outs} in {ins or '-'} act{act}", hbm
+
+
 def gemm_f8(A8, inv_a, B8, inv_b, M, N, K, C=None, bias=None, residual=None, preact=None, act=0,
             Cb=None, Pb=None):
     """Forward product on e4m3 operands (include/qarig.h qarig_gemm_f8): C = epilogue(inv_a * inv_b *
     A8 B8^T), A8 (M,K) and B8 (N,K) uint8 from cast_fp8."""
-    if GEMM_EVENTS is not None:
-        ev0 = torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev0 = _event_begin()
     check(_lib.load().qarig_gemm_f8(
         ptr(A8), A8.stride(0), ptr(B8), B8.stride(0), ptr(inv_a), ptr(inv_b),
-        ptr(C), C.stride(0) if C is not None else 0, M, N, K, ptr(bias),
-        ptr(residual), residual.stride(0) if residual is not None else 0,
-        ptr(preact), preact.stride(0) if preact is not None else 0, act,
-        ptr(Cb), Cb.stride(0) if Cb is not None else 0, ptr(Pb), Pb.stride(0) if Pb is not None else 0,
-        stream()), "qarig_gemm_f8")
-    if GEMM_EVENTS is not None:
-        ev1 = torch.cuda.Event(enable_timing=True)
-        ev1.record()
-        GEMM_EVENTS.append((2.0 * M * N * K, ev0, ev1, "f8"))
+        *_epilogue_args(C, M, N, K, bias, residual, preact, act, Cb, Pb), stream()), "qarig_gemm_f8")
+    _event_end(ev0, M, N, K, lambda: ("f8",))
 
 
 class MxOperand:
@@ -365,34 +408,14 @@ def gemm_mx(A, B, M, N, K, C=None, bias=None, residual=None, preact=None, act=0,
     """C = epilogue(A B^T) on MX-e4m3 operands (include/qarig.h qarig_gemm_mx): A, B MxOperand with
     (M, K) and (N, K) bytes; epilogue options as gemm_lp."""
     lib = _lib.load()
-    ws, nws = None, 0
-    if splitk > 1:
-        nws = lib.qarig_gemm_mx_workspace_bytes(M, N, splitk)
-        ws = workspace(nws, A.q.device, "gemm")
-        nws = ws.numel()
-    if GEMM_EVENTS is not None:
-        ev0 = torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ws, nws = _splitk_workspace(lib.qarig_gemm_mx_workspace_bytes, M, N, splitk, A.q.device)
+    ev0 = _event_begin()
     check(lib.qarig_gemm_mx(
         ptr(A.q), A.q.stride(0), ptr(A.s), A.s.stride(0), ptr(B.q), B.q.stride(0), ptr(B.s), B.s.stride(0),
-        ptr(C), C.stride(0) if C is not None else 0, M, N, K, ptr(bias),
-        ptr(residual), residual.stride(0) if residual is not None else 0,
-        ptr(preact), preact.stride(0) if preact is not None else 0, act,
-        ptr(gradz), gradz.stride(0) if gradz is not None else 0,
-        int(gradz is not None and gradz.dtype == torch.bfloat16), gact, splitk, int(accumulate),
-        ptr(Cb), Cb.stride(0) if Cb is not None else 0, ptr(Pb), Pb.stride(0) if Pb is not None else 0,
+        *_epilogue_args(C, M, N, K, bias, residual, preact, act, Cb, Pb, (gradz, gact, splitk, accumulate)),
         ptr(ws), nws, stream()), "qarig_gemm_mx")
-    if GEMM_EVENTS is not None:
-        ev1 = torch.cuda.Event(enable_timing=True)
-        ev1.record()
-        outs = "+".join(n for n, t in (("C", C), ("P", preact), ("Cb", Cb), ("Pb", Pb)) if t is not None)
-        ins = "".join(n for n, t in (("b", bias), ("r", residual), ("z", gradz)) if t is not None)
-        hbm = 1.03 * (M * K + N * K) + M * N * (4.0 * (C is not None) * (2 if accumulate and splitk == 1 else 1) +
-                                               4.0 * (preact is not None) + 2.0 * (Cb is not None) +
-                                               2.0 * (Pb is not None) + 4.0 * (residual is not None) +
-                                               (0 if gradz is None else gradz.element_size()))
-        GEMM_EVENTS.append((2.0 * M * N * K, ev0, ev1, "",
-                            f"mx NT {M}x{N}x{K} sk{splitk} out {outs} in {ins or '-'} act{act}", hbm))
+    _event_end(ev0, M, N, K, lambda: _lp_event_tail("mx NT", 1.03, M, N, K, C, bias, residual, preact, act, gradz,
+                                                    splitk, accumulate, Cb, Pb))
 
 
 def mx_weight(w, pad_rows=0):
@@ -461,34 +484,14 @@ def gemm_lp(A_bf, B_bf, layout, M, N, K, C=None, bias=None, residual=None, preac
             gact=0, splitk=1, accumulate=False, Cb=None, Pb=None):
     """Raw reduced-precision GEMM on bf16 operands (include/qarig.h qarig_gemm_lp)."""
     lib = _lib.load()
-    ws, nws = None, 0
-    if splitk > 1:
-        nws = lib.qarig_gemm_lp_workspace_bytes(M, N, splitk)
-        ws = workspace(nws, A_bf.device, "gemm")
-        nws = ws.numel()
-    if GEMM_EVENTS is not None:
-        ev0 = torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ws, nws = _splitk_workspace(lib.qarig_gemm_lp_workspace_bytes, M, N, splitk, A_bf.device)
+    ev0 = _event_begin()
     check(lib.qarig_gemm_lp(
         ptr(A_bf), A_bf.stride(0), ptr(B_bf), B_bf.stride(0), layout,
-        ptr(C), C.stride(0) if C is not None else 0, M, N, K, ptr(bias),
-        ptr(residual), residual.stride(0) if residual is not None else 0,
-        ptr(preact), preact.stride(0) if preact is not None else 0, act,
-        ptr(gradz), gradz.stride(0) if gradz is not None else 0,
-        int(gradz is not None and gradz.dtype == torch.bfloat16), gact, splitk, int(accumulate),
-        ptr(Cb), Cb.stride(0) if Cb is not None else 0, ptr(Pb), Pb.stride(0) if Pb is not None else 0,
+        *_epilogue_args(C, M, N, K, bias, residual, preact, act, Cb, Pb, (gradz, gact, splitk, accumulate)),
         ptr(ws), nws, stream()), "qarig_gemm_lp")
-    if GEMM_EVENTS is not None:
-        ev1 = torch.cuda.Event(enable_timing=True)
-        ev1.record()
-        outs = "+".join(n for n, t in (("C", C), ("P", preact), ("Cb", Cb), ("Pb", Pb)) if t is not None)
-        ins = "".join(n for n, t in (("b", bias), ("r", residual), ("z", gradz)) if t is not None)
-        hbm = 2.0 * (M * K + N * K) + M * N * (4.0 * (C is not None) * (2 if accumulate and splitk == 1 else 1) +
-                                               4.0 * (preact is not None) + 2.0 * (Cb is not None) +
-                                               2.0 * (Pb is not None) + 4.0 * (residual is not None) +
-                                               (0 if gradz is None else gradz.element_size()))
-        GEMM_EVENTS.append((2.0 * M * N * K, ev0, ev1, "",
-                            f"lp {('NT', 'TN', 'NN')[layout]} {M}x{N}x{K} sk{splitk} out {outs} in {ins or '-'} act{act}", hbm))
+    _event_end(ev0, M, N, K, lambda: _lp_event_tail(f"lp {('NT', 'TN', 'NN')[layout]}", 2.0, M, N, K, C, bias,
+                                                    residual, preact, act, gradz, splitk, accumulate, Cb, Pb))
 
 
 def _gemm_lp(lib, A, B, a_kcontig, b_kcontig, C, pre, M, N, K, bias, residual, act, gradz, gact, splitk,
