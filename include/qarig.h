@@ -137,7 +137,14 @@ int qarig_gemm_f32_grouped(int groups, const float* const* A, int64_t lda, int a
  * reduction-major (input gradient dT W on the weight shadow exactly as stored: no W^T copy).
  * A, B: bf16 (16-bit) elements, lda / ldb in elements.
  * C: fp32 output (may be NULL when Cb is given); Cb / Pb: optional bf16 copies of the output /
- * of the saved pre-activation for a consumer GEMM.  Shapes: qarig_gemm_lp_supported. */
+ * of the saved pre-activation for a consumer GEMM.  Shapes: qarig_gemm_lp_supported.
+ * Every matrix argument of qarig_gemm_lp / _f8 / _mx has a leading dimension of its own (a view of a
+ * larger buffer is a valid argument) under these rules, QARIG_ERR_ARG otherwise, nothing written:
+ *  - A, B: 16-B aligned; lda, ldb % 8 elements (bf16) / % 16 bytes (e4m3; qarig_gemm_mx also
+ *    lda, ldb >= K);
+ *  - MX scale bytes sA, sB: 4-B aligned, ldsa, ldsb % 4 and >= K / 32;
+ *  - C, bias, residual, preact and an fp32 gradz: 16-B aligned, leading dimension % 4;
+ *  - Cb, Pb and a bf16 gradz: 8-B aligned, leading dimension % 4. */
 int qarig_gemm_lp_supported(int M, int N, int K, int splitk);
 size_t qarig_gemm_lp_workspace_bytes(int M, int N, int splitk);
 int qarig_gemm_lp(const void* A, int64_t lda, const void* B, int64_t ldb, int layout, float* C,
