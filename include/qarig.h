@@ -73,15 +73,32 @@ int qarig_bmu_fwd_prepared(const float* x, int N, int C, int H, int W, int pH, i
  * qarig_bmu_fwd takes this form by itself where it applies (D <= 16, D % 4 == 0, K % 32 == 0,
  * K <= 1024, >= 24576 rows); this entry forces it and counts the re-scanned rows into
  * uncertified[0] (device unsigned[8], caller-zeroed, may be NULL; [1..3] += clock64() cycles of the
- * staging / scan / finish phases of every block, [4] += blocks: tools/bmu_bench.py).  models/Codebook.py:77-99. */
+ * staging / scan / finish phases of every block, [4] += blocks: tools/bmu_bench.py).  K <= 1024: one
+ * LDS image holds the whole codebook.  models/Codebook.py:77-99. */
 int qarig_bmu_fwd_coarse(const float* x, int N, int C, int H, int W, int pH, int pW,
                          const float* codebook, int K, int D, int64_t* out_idx,
                          unsigned* uncertified, const void* prepared, void* stream);
+/* The same for every K the coarse form takes (K % 32 == 0, 32 <= K <= 16384).  Beyond 1,024 codes the
+ * codebook goes through LDS in chunks of whole 32-code tiles over a (row block) x (chunk group) grid; every
+ * (row, group) leaves its partial (coarse minimum, index, second-smallest) and every chunk its max |w|^2 and
+ * inexact flag in `workspace` (qarig_bmu_coarse_workspace_bytes(rows, K) bytes; 0 and unused for K <= 1024),
+ * and a finalize kernel merges them in code order, applies the same certificate and re-scans the other rows,
+ * one wave per row, against the fp32 codebook: the same bit-identical indices.  uncertified as above
+ * (re-scanned rows are counted by the finalize kernel; [5] += its clock64() cycles per block, [6] += its
+ * blocks).  qarig_bmu_fwd takes this form only under option bmu_coarse = 1.  Returns the workspace error
+ * when ws_bytes is too small. */
+size_t qarig_bmu_coarse_workspace_bytes(int64_t rows, int K);
+int qarig_bmu_fwd_coarse_ws(const float* x, int N, int C, int H, int W, int pH, int pW,
+                            const float* codebook, int K, int D, int64_t* out_idx,
+                            unsigned* uncertified, const void* prepared, void* workspace,
+                            size_t ws_bytes, void* stream);
 /* The staged form of a codebook for `prepared` above (may be NULL: every workgroup then stages the
  * codebook itself): qarig_bmu_prepare_bytes(K, D) bytes (0 = the coarse form does not apply), written
  * by qarig_bmu_prepare.  A frozen codebook -- tokenising a dataset (generate_fmap_dataset.py /
  * train_quantized_transformer.py:412-421 call get_patches_bmu with fixed codebooks every step) -- is
- * prepared once; its image must be rebuilt after the codebook changes. */
+ * prepared once; its image must be rebuilt after the codebook changes.  K <= 1024: K * 100 + 16 bytes
+ * (three planes of bf16 pieces, |w|^2, max |w|^2 and an inexact flag); 1024 < K <= 16384: that layout per
+ * 512-code chunk, chunk after chunk (the chunking of an image is fixed: a search given one uses it). */
 size_t qarig_bmu_prepare_bytes(int K, int D);
 int qarig_bmu_prepare(const float* codebook, int K, int D, void* image, void* stream);
 

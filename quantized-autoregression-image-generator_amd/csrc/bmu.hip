@@ -1122,7 +1122,8 @@ __global__ __launch_bounds__(256) void bmu_fewrows_argmin_kernel(const float* __
 using namespace qarig;
 
 // ---------------------------------------------------------------------------------------------
-// Coarse pass on the bf16 MFMA + certificate + exact re-scan (D <= 16, K <= 1024, K % 32 == 0).
+// Coarse pass on the bf16 MFMA + certificate + exact re-scan (D <= 16, K % 32 == 0; K <= 1024: bmu_coarse_kernel,
+// the whole codebook in one LDS image; up to 16384 codes: bmu_coarse_chunk_kernel + bmu_coarse_finalize_kernel below).
 //
 // The exact kernels above run at the SUM of their fp32-MFMA and vector-ALU cycles (the two do not
 // overlap on this chip: DESIGN 10) -- 9 MFMAs of 64 cycles and a 16-candidate scan per 32 x 32
@@ -1208,6 +1209,91 @@ __device__ __forceinline__ float bmu_join3(uint32_t H, uint32_t M, uint32_t L, i
 // far below eps to above 4 eps.
 constexpr float BMU_COARSE_EPS = 1e-5f;
 
+// A prepared image (or one chunk of it) into LDS without a register round trip: 1 KiB per wave instruction, every
+// piece in flight at once; the last partial KiB through registers.  The caller waits (vmcnt(0)) before its barrier.
+__device__ __forceinline__ void bmu_image_to_lds(const unsigned char* __restrict__ image_in, size_t image_bytes,
+                                                 unsigned char* lds_raw) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n16 = (int)(image_bytes >> 4);
+    const int nblk = n16 >> 6;
+    for (int b = wave; b < nblk; b += NTHREADS / 64)
+        __builtin_amdgcn_global_load_lds(
+            (__attribute__((address_space(1))) const void*)(image_in + ((size_t)b * 64 + lane) * 16),
+            (__attribute__((address_space(3))) void*)(lds_raw + (size_t)b * 1024), 16, 0, 0);
+    const uint4* src = reinterpret_cast<const uint4*>(image_in);
+    uint4* dst = reinterpret_cast<uint4*>(lds_raw);
+    if (nblk * 64 + tid < n16) dst[nblk * 64 + tid] = src[nblk * 64 + tid];
+}
+
+// Codes kbase .. kbase + kn - 1 of the fp32 codebook into the LDS image of a kn-code codebook: -2w split three
+// ways, |w|^2 chain (accumulator order); two codes per pass with all eight 16-B loads in flight.  w2max / inexact:
+// this thread's share of max |w|^2 and of "some piece does not add up / a non-finite code".
+__device__ __forceinline__ void bmu_stage_codes(const float* __restrict__ w, int D, int kbase, int kn,
+                                                bmu_u32x4* frag, int plane, float* W2, float& w2max, int& inexact) {
+    const int tid = threadIdx.x;
+    for (int k0 = tid; k0 < kn; k0 += 2 * NTHREADS) {
+        float4 raw[2][4];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int k = min(k0 + u * NTHREADS, kn - 1);
+            const float4* wk4 = reinterpret_cast<const float4*>(w + (int64_t)(kbase + k) * D);   // host: D % 4 == 0, 16-B aligned
+#pragma unroll
+            for (int q = 0; q < 4; ++q) raw[u][q] = 4 * q < D ? wk4[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int k = k0 + u * NTHREADS;
+            if (k >= kn) break;
+            float v[16];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                v[4 * q] = raw[u][q].x; v[4 * q + 1] = raw[u][q].y; v[4 * q + 2] = raw[u][q].z; v[4 * q + 3] = raw[u][q].w;
+            }
+            float w2 = 0.0f;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) w2 = e < D ? fmaf(v[e], v[e], w2) : w2;
+            W2[bmu_w2_at(k)] = w2;
+            w2max = fmaxf(w2max, w2);
+            if (!(w2 <= 3.0e38f)) inexact = 1;          // a NaN / Inf code: the definition's clamp decides, exactly
+            const int T = k >> 5, c = k & 31;
+#pragma unroll
+            for (int hh = 0; hh < 2; ++hh) {
+                bmu_u32x4 H, M, L;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    uint32_t a, b, cc;
+                    if (!bmu_split3(-2.0f * v[8 * hh + 2 * q], -2.0f * v[8 * hh + 2 * q + 1], a, b, cc)) inexact = 1;
+                    H[q] = a; M[q] = b; L[q] = cc;
+                }
+                const int at = (T * 2 + hh) * 32 + c;
+                frag[at] = H;
+                frag[plane + at] = M;
+                frag[2 * plane + at] = L;
+            }
+        }
+    }
+}
+
+// The coarse scan of nt 32-code tiles of an LDS image against this lane's half patch row (three bf16 pieces):
+// (min, second-smallest) of t~, the minimum carrying its register number in its low four bits, and the tile --
+// counted from the image's first -- in which the minimum fell (-1: none).  One inline-asm statement
+// (tools/gen_bmu_scan.py writes it and documents its registers).
+__device__ __forceinline__ void bmu_coarse_scan(const bmu_u32x4* frag, int plane, const float* W2, int NT, int h, int cl,
+                                                const bmu_u32x4& XH, const bmu_u32x4& XM, const bmu_u32x4& XL,
+                                                float& best, float& sec, int& tidx) {
+    const bmu_bf16x8 bXH = __builtin_bit_cast(bmu_bf16x8, XH), bXM = __builtin_bit_cast(bmu_bf16x8, XM),
+                     bXL = __builtin_bit_cast(bmu_bf16x8, XL);
+    const unsigned f0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const void*)(frag + h * 32 + cl);
+    const unsigned wa = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const void*)(W2 + h * 16);
+    const int plane_bytes = __builtin_amdgcn_readfirstlane(plane * 16), nt = __builtin_amdgcn_readfirstlane(NT);
+    int st_, su_;
+    asm volatile(
+#include "bmu_scan_asm.inc"
+        : [best] "=&v"(best), [sec] "=&v"(sec), [tidx] "=&v"(tidx), [t] "=&s"(st_), [u] "=&s"(su_)
+        : [xh] "v"(bXH), [xm] "v"(bXM), [xl] "v"(bXL), [f0] "v"(f0), [pl] "s"(plane_bytes), [w] "v"(wa), [nt] "s"(nt)
+        : "vcc", "scc", "memory", BMU_SCAN_CLOBBERS);
+}
+
 // PREP: stages the image of a codebook (what every block of the search kernel builds in LDS) into
 // `image` instead: [3 planes: K x 96 B][|w|^2 in accumulator order: K x 4 B][max |w|^2, inexact flag: 8 B].  A frozen
 // codebook (tokenising a dataset, the Transformer training loop) is prepared once and its image
@@ -1254,62 +1340,12 @@ __global__ __launch_bounds__(NTHREADS, 2) void bmu_coarse_kernel(PatchGeom g, Pa
     int inexact = 0;
     const size_t image_bytes = (size_t)K * 100;               // planes + |w|^2 (a multiple of 16: K % 32 == 0)
     if (!PREP && image_in) {
-        // a prepared image: global -> LDS without a register round trip (1 KiB per wave instruction, every piece
-        // of the image in flight at once); the last partial KiB through registers
-        const int n16 = (int)(image_bytes >> 4);
-        const int nblk = n16 >> 6;
-        for (int b = wave; b < nblk; b += NTHREADS / 64)
-            __builtin_amdgcn_global_load_lds(
-                (__attribute__((address_space(1))) const void*)(image_in + ((size_t)b * 64 + lane) * 16),
-                (__attribute__((address_space(3))) void*)(lds_raw + (size_t)b * 1024), 16, 0, 0);
-        const uint4* src = reinterpret_cast<const uint4*>(image_in);
-        uint4* dst = reinterpret_cast<uint4*>(lds_raw);
-        if (nblk * 64 + tid < n16) dst[nblk * 64 + tid] = src[nblk * 64 + tid];
+        bmu_image_to_lds(image_in, image_bytes, lds_raw);
         const float* hdr = reinterpret_cast<const float*>(image_in + image_bytes);
         w2max = hdr[0];
         inexact = hdr[1] != 0.0f;
     } else
-    for (int k0 = tid; k0 < K; k0 += 2 * NTHREADS) {
-        float4 raw[2][4];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int k = min(k0 + u * NTHREADS, K - 1);
-            const float4* wk4 = reinterpret_cast<const float4*>(w + (int64_t)k * D);   // host: D % 4 == 0, 16-B aligned
-#pragma unroll
-            for (int q = 0; q < 4; ++q) raw[u][q] = 4 * q < D ? wk4[q] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int k = k0 + u * NTHREADS;
-            if (k >= K) break;
-            float v[16];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                v[4 * q] = raw[u][q].x; v[4 * q + 1] = raw[u][q].y; v[4 * q + 2] = raw[u][q].z; v[4 * q + 3] = raw[u][q].w;
-            }
-            float w2 = 0.0f;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) w2 = e < D ? fmaf(v[e], v[e], w2) : w2;
-            W2[bmu_w2_at(k)] = w2;
-            w2max = fmaxf(w2max, w2);
-            if (!(w2 <= 3.0e38f)) inexact = 1;          // a NaN / Inf code: the definition's clamp decides, exactly
-            const int T = k >> 5, c = k & 31;
-#pragma unroll
-            for (int hh = 0; hh < 2; ++hh) {
-                bmu_u32x4 H, M, L;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    uint32_t a, b, cc;
-                    if (!bmu_split3(-2.0f * v[8 * hh + 2 * q], -2.0f * v[8 * hh + 2 * q + 1], a, b, cc)) inexact = 1;
-                    H[q] = a; M[q] = b; L[q] = cc;
-                }
-                const int at = (T * 2 + hh) * 32 + c;
-                frag[at] = H;
-                frag[plane + at] = M;
-                frag[2 * plane + at] = L;
-            }
-        }
-    }
+        bmu_stage_codes(w, D, 0, K, frag, plane, W2, w2max, inexact);
     float x2a = 0.0f;
     bmu_u32x4 XH = {0u, 0u, 0u, 0u}, XM = XH, XL = XH;
     if constexpr (!PREP) {
@@ -1359,17 +1395,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void bmu_coarse_kernel(PatchGeom g, Pa
     float best = INFINITY, sec = INFINITY;
     int tidx = -1;
     if constexpr (!PREP) {
-        const bmu_bf16x8 bXH = __builtin_bit_cast(bmu_bf16x8, XH), bXM = __builtin_bit_cast(bmu_bf16x8, XM),
-                         bXL = __builtin_bit_cast(bmu_bf16x8, XL);
-        const unsigned f0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const void*)(frag + h * 32 + cl);
-        const unsigned wa = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const void*)(W2 + h * 16);
-        const int plane_bytes = __builtin_amdgcn_readfirstlane(plane * 16), nt = __builtin_amdgcn_readfirstlane(NT);
-        int st_, su_;
-        asm volatile(
-#include "bmu_scan_asm.inc"
-            : [best] "=&v"(best), [sec] "=&v"(sec), [tidx] "=&v"(tidx), [t] "=&s"(st_), [u] "=&s"(su_)
-            : [xh] "v"(bXH), [xm] "v"(bXM), [xl] "v"(bXL), [f0] "v"(f0), [pl] "s"(plane_bytes), [w] "v"(wa), [nt] "s"(nt)
-            : "vcc", "scc", "memory", BMU_SCAN_CLOBBERS);
+        bmu_coarse_scan(frag, plane, W2, NT, h, cl, XH, XM, XL, best, sec, tidx);
     }
     const int ridx = (int)(__float_as_uint(best) & 15u);
     const long long tc2 = stats ? clock64() : 0;
@@ -1453,9 +1479,278 @@ __global__ __launch_bounds__(NTHREADS, 2) void bmu_coarse_kernel(PatchGeom g, Pa
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Codebooks beyond one LDS image (1024 < K <= 16384): the same coarse pass over a grid of (128-row block) x
+// (group of code chunks).  A chunk is a whole number of 32-code tiles, at most BMU_CHUNK_MAX codes, and is staged,
+// split and scanned exactly as the single-image kernel does with a codebook of that many codes (same LDS image,
+// same scan loop with the chunk's tile count; the chunk's first tile is added to the minimum's tile afterwards).
+// A workgroup walks the chunks of its group in ascending order -- re-staging between two barriers -- and merges
+// each chunk's (min, first index, second-smallest) into its running state with bmu_merge; the group's state per row
+// goes to the workspace, as do every chunk's own max |w|^2 and inexact flag (written by row block 0).  No atomics:
+// bmu_coarse_finalize_kernel merges a row's partials in group order.  A row whose split of x is inexact leaves
+// NaN in its |x|^2 slot, which no certificate survives.
+// The prepared image of such a codebook is chunk-major: chunk c = [3 planes][|w|^2 in accumulator order][max |w|^2,
+// inexact flag, 8 B of padding] of its own codes at byte c * (100 * chunk + 16): the single-image layout per chunk.
+constexpr int BMU_CHUNK_MAX = 512;        // codes per chunk; also the chunk of every prepared image with K > 1024
+constexpr int BMU_CHUNK_MIN = 128;        // (launches with few rows: more, smaller chunks)
+constexpr int BMU_CHUNK_PAD = 2048 + 64;  // LDS behind the image: the scan loop pre-loads two tiles past the last
+                                          // (2 KiB beyond the third plane's end, of which the |w|^2 cover 4 B per
+                                          // code), + 16 floats of reductions
+constexpr int BMU_FIN_ROWS = 64;          // rows per workgroup of the finalize kernel
+constexpr int BMU_K_MAX = 16384;          // largest codebook the chunked form takes
+constexpr int BMU_CHUNKED_AUTO_ROWS = INT_MAX;   // auto dispatch takes the chunked form from this many rows (measured)
+
+__global__ __launch_bounds__(NTHREADS, 2) void bmu_coarse_chunk_kernel(PatchGeom g, PatchOffsets po,
+                                                                       const float* __restrict__ w, int K,
+                                                                       int chunk, int nchunks, int per_group,
+                                                                       const unsigned char* __restrict__ image_in,
+                                                                       float* __restrict__ part_d,
+                                                                       int* __restrict__ part_i,
+                                                                       float* __restrict__ part_s,
+                                                                       float* __restrict__ part_x2,
+                                                                       float* __restrict__ chunk_hdr,
+                                                                       unsigned* __restrict__ stats) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    bmu_u32x4* frag = reinterpret_cast<bmu_u32x4*>(lds_raw);
+    float* red = reinterpret_cast<float*>(lds_raw + (size_t)chunk * 100 + 2048);     // [8] reductions
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int h = lane >> 5, cl = lane & 31;
+    const int p0 = blockIdx.x * 128;
+    const int D = g.D;
+    const long long tc0 = stats ? clock64() : 0;
+
+    // ---- this lane's half patch row, split three ways (as bmu_coarse_kernel)
+    const int prow = p0 + wave * 32 + cl;
+    const bool live = prow < g.R;
+    float xv[8];
+    {
+        const float* px = g.x + patch_row_base_fast(g, po, live ? prow : g.R - 1);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int off = h ? po.off[8 + q] : po.off[q];
+            xv[q] = px[off];
+        }
+    }
+    const int c_begin = blockIdx.y * per_group, c_end = min(nchunks, c_begin + per_group);
+    BmuState run{INFINITY, INT_MAX, INFINITY};
+    float x2a = 0.0f;
+    int x_inexact = 0;
+    bmu_u32x4 XH = {0u, 0u, 0u, 0u}, XM = XH, XL = XH;
+    long long t_stage = 0, t_scan = 0, tc1 = tc0;
+    for (int c = c_begin; c < c_end; ++c) {
+        const int kbase = c * chunk;
+        const int kn = min(chunk, K - kbase);                   // a multiple of 32
+        const int NT = kn >> 5, plane = NT * 64;
+        float* W2 = reinterpret_cast<float*>(frag + 3 * plane);
+        float w2max = 0.0f;
+        int inexact = 0;
+        if (c != c_begin) __syncthreads();                      // the previous chunk's scan has read its image
+        if (image_in) {
+            const unsigned char* img = image_in + (size_t)c * ((size_t)chunk * 100 + 16);
+            bmu_image_to_lds(img, (size_t)kn * 100, lds_raw);
+            const float* hdr = reinterpret_cast<const float*>(img + (size_t)kn * 100);
+            w2max = hdr[0];
+            inexact = hdr[1] != 0.0f;
+        } else
+            bmu_stage_codes(w, D, kbase, kn, frag, plane, W2, w2max, inexact);
+        if (c == c_begin) {                                     // under the first chunk's loads
+#pragma unroll
+            for (int q = 0; q < 8; ++q) xv[q] = 8 * h + q < D ? xv[q] : 0.0f;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                uint32_t a, b, cc;
+                if (!bmu_split3(xv[2 * q], xv[2 * q + 1], a, b, cc)) x_inexact = 1;
+                XH[q] = a; XM[q] = b; XL[q] = cc;
+                x2a += xv[2 * q] * xv[2 * q] + xv[2 * q + 1] * xv[2 * q + 1];
+            }
+            x2a += __shfl_xor(x2a, 32);
+            x_inexact |= __shfl_xor(x_inexact, 32);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // the image's DMA has landed before the barrier publishes it
+        if (!image_in) {                                        // (uniform) the chunk's max |w|^2 and inexact flag
+            w2max = wave_max(w2max);
+            inexact = __any(inexact);
+            if (lane == 0) { red[wave] = w2max; red[4 + wave] = inexact ? 1.0f : 0.0f; }
+        }
+        __syncthreads();
+        if (blockIdx.x == 0 && tid == 0) {
+            if (!image_in) {
+                w2max = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+                inexact = (red[4] + red[5] + red[6] + red[7]) != 0.0f;
+            }
+            chunk_hdr[2 * c] = w2max;
+            chunk_hdr[2 * c + 1] = inexact ? 1.0f : 0.0f;
+        }
+        const long long tc2 = stats ? clock64() : 0;
+        float best, sec;
+        int tidx;
+        bmu_coarse_scan(frag, plane, W2, NT, h, cl, XH, XM, XL, best, sec, tidx);
+        const int ridx = (int)(__float_as_uint(best) & 15u);
+        const int idx = tidx < 0 ? INT_MAX : kbase + tidx * 32 + 4 * h + (ridx & 3) + 8 * (ridx >> 2);
+        run = bmu_merge(run, BmuState{best, idx, sec});
+        if (stats) {
+            const long long tc3 = clock64();
+            t_stage += tc2 - tc1;
+            t_scan += tc3 - tc2;
+            tc1 = tc3;
+        }
+    }
+    // ---- the two lane halves of a row hold disjoint codes; the group's state per row goes to the workspace
+    run = bmu_merge(run, BmuState{__shfl_xor(run.d2, 32), __shfl_xor(run.idx, 32), __shfl_xor(run.sec, 32)});
+    if (live && h == 0) {
+        const int64_t o = (int64_t)blockIdx.y * g.R + prow;
+        part_d[o] = run.d2;
+        part_i[o] = run.idx;
+        part_s[o] = run.sec;
+        if (blockIdx.y == 0) part_x2[prow] = x_inexact ? NAN : x2a;
+    }
+    if (stats && tid == 0) {
+        atomicAdd(stats + 1, (unsigned)t_stage);
+        atomicAdd(stats + 2, (unsigned)t_scan);
+        atomicAdd(stats + 3, (unsigned)(clock64() - tc1));
+        atomicAdd(stats + 4, 1u);
+    }
+}
+
+// One block per chunk of the prepared image of a K > 1024 codebook (no reduction across blocks: the search's
+// finalize takes the maximum over the chunk headers).
+__global__ __launch_bounds__(NTHREADS) void bmu_coarse_prepare_chunks_kernel(const float* __restrict__ w, int K, int D,
+                                                                             int chunk,
+                                                                             unsigned char* __restrict__ image_out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    bmu_u32x4* frag = reinterpret_cast<bmu_u32x4*>(lds_raw);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int kbase = blockIdx.x * chunk;
+    const int kn = min(chunk, K - kbase);
+    const int plane = (kn >> 5) * 64;
+    float* W2 = reinterpret_cast<float*>(frag + 3 * plane);
+    float* red = reinterpret_cast<float*>(lds_raw + (size_t)chunk * 100);
+    float w2max = 0.0f;
+    int inexact = 0;
+    bmu_stage_codes(w, D, kbase, kn, frag, plane, W2, w2max, inexact);
+    w2max = wave_max(w2max);
+    inexact = __any(inexact);
+    if (lane == 0) { red[wave] = w2max; red[4 + wave] = inexact ? 1.0f : 0.0f; }
+    __syncthreads();
+    unsigned char* img = image_out + (size_t)blockIdx.x * ((size_t)chunk * 100 + 16);
+    const uint4* src = reinterpret_cast<const uint4*>(lds_raw);
+    uint4* dst = reinterpret_cast<uint4*>(img);
+    for (int i = tid; i < kn * 100 / 16; i += NTHREADS) dst[i] = src[i];
+    if (tid == 0) {
+        float* hdr = reinterpret_cast<float*>(img + (size_t)kn * 100);
+        hdr[0] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+        hdr[1] = (red[4] + red[5] + red[6] + red[7]) != 0.0f ? 1.0f : 0.0f;
+        hdr[2] = hdr[3] = 0.0f;
+    }
+}
+
+// Finalize of the chunked coarse pass, BMU_FIN_ROWS rows per workgroup.  Wave 0: a row per lane -- its partials
+// merged in group (= ascending code) order, max |w|^2 over all chunks, the unchanged certificate; certified rows are
+// written, the others listed.  Then every wave takes listed rows (wave v the v-th, v+4-th, ...: no barrier, no
+// cooperation inside the block) and re-scans them with the literal definition against the fp32 codebook in memory,
+// lane l codes l, l + 64, ... ascending, (d, index) reduced with the first-index rule.
+__global__ __launch_bounds__(256) void bmu_coarse_finalize_kernel(PatchGeom g, PatchOffsets po,
+                                                                  const float* __restrict__ w, int K,
+                                                                  const float* __restrict__ part_d,
+                                                                  const int* __restrict__ part_i,
+                                                                  const float* __restrict__ part_s,
+                                                                  const float* __restrict__ part_x2,
+                                                                  const float* __restrict__ chunk_hdr,
+                                                                  int ngroups, int nchunks,
+                                                                  int64_t* __restrict__ out,
+                                                                  unsigned* __restrict__ stats) {
+    __shared__ int list[BMU_FIN_ROWS];
+    __shared__ int nlist;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int D = g.D;
+    const long long tc0 = stats ? clock64() : 0;
+    if (wave == 0) {
+        float w2max = 0.0f;
+        int inexact = 0;
+        for (int c = lane; c < nchunks; c += 64) {
+            w2max = fmaxf(w2max, chunk_hdr[2 * c]);
+            inexact |= chunk_hdr[2 * c + 1] != 0.0f;
+        }
+        w2max = wave_max(w2max);
+        inexact = __any(inexact);
+        const int row = blockIdx.x * BMU_FIN_ROWS + lane;
+        int flag = 0;
+        if (row < g.R) {
+            BmuState st{part_d[row], part_i[row], part_s[row]};
+            for (int z = 1; z < ngroups; ++z) {
+                const int64_t o = (int64_t)z * g.R + row;
+                st = bmu_merge(st, BmuState{part_d[o], part_i[o], part_s[o]});
+            }
+            const float eps = BMU_COARSE_EPS * (1.001f * part_x2[row] + 2.0f * w2max);   // NaN: x's split was inexact
+            const bool certified = !inexact && (st.sec - st.d2 > 3.0f * eps);
+            if (certified) out[row] = (int64_t)st.idx;
+            flag = !certified;
+        }
+        const unsigned long long m = __ballot(flag);
+        if (flag) list[__popcll(m & ((1ull << lane) - 1ull))] = row;
+        if (lane == 0) {
+            nlist = __popcll(m);
+            if (stats && m) atomicAdd(stats, (unsigned)__popcll(m));
+        }
+    }
+    __syncthreads();
+    const int n = nlist;
+    for (int i = wave; i < n; i += 4) {
+        const int row = list[i];
+        const float* px = g.x + patch_row_base(g, row);
+        float xs[16];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const float v = px[po.off[e]];                      // (po.off[e >= D] = po.off[0]: a valid address)
+            xs[e] = e < D ? v : 0.0f;
+        }
+        float x2 = 0.0f;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) x2 = e < D ? fmaf(xs[e], xs[e], x2) : x2;
+        float bd = INFINITY;
+        int bi = INT_MAX;
+#pragma unroll 2
+        for (int k = lane; k < K; k += 64) {
+            const float4* wk4 = reinterpret_cast<const float4*>(w + (int64_t)k * D);   // host: D % 4 == 0, 16-B aligned
+            float v[16];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float4 t = 4 * q < D ? wk4[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+                v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
+            }
+            float w2 = 0.0f, acc = 0.0f;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) w2 = e < D ? fmaf(v[e], v[e], w2) : w2;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc = e < D ? fmaf(-2.0f * v[e], xs[e], acc) : acc;
+            const float d = sqrtf(fmaxf((acc + w2) + x2, 0.0f));
+            if (d < bd) { bd = d; bi = k; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float s2 = __shfl_xor(bd, o);
+            const int i2 = __shfl_xor(bi, o);
+            if (s2 < bd || (s2 == bd && i2 < bi)) { bd = s2; bi = i2; }
+        }
+        if (lane == 0) out[row] = bi == INT_MAX ? 0 : (int64_t)bi;
+    }
+    if (stats && tid == 0) {
+        atomicAdd(stats + 5, (unsigned)(clock64() - tc0));
+        atomicAdd(stats + 6, 1u);
+    }
+}
+
 static int bmu_code_tiles(int K) { return (K + BM - 1) / BM; }
 
 static constexpr int FEWROWS_MAX = 128, FEWROWS_MIN_D = 512;
+
+// Workspace of the chunked coarse pass: per (group, row) partial (min, index, second) for up to K / BMU_CHUNK_MIN
+// groups, |x|^2 per row, (max |w|^2, inexact) per chunk.  0 where one LDS image holds the codebook (K <= 1024).
+extern "C" size_t qarig_bmu_coarse_workspace_bytes(int64_t rows, int K) {
+    if (rows < 0 || rows > (1LL << 31) || K <= 1024 || K > BMU_K_MAX || K % 32) return 0;
+    const size_t gmax = (size_t)(K + BMU_CHUNK_MIN - 1) / BMU_CHUNK_MIN;
+    return gmax * (size_t)rows * 12 + (size_t)rows * 4 + gmax * 8 + 64;
+}
 
 extern "C" size_t qarig_bmu_workspace_bytes(int64_t rows, int K) {
     if (rows < 0 || rows > (1LL << 31) || K < 1 || K > (1 << 24)) return 0;     // refused by qarig_bmu_fwd
@@ -1463,11 +1758,18 @@ extern "C" size_t qarig_bmu_workspace_bytes(int64_t rows, int K) {
     size_t need = (size_t)bmu_code_tiles(K) * (size_t)rows * 12 + (size_t)rows * 4 + 64;
     // few-rows form: rows x K dot products + |w|^2 + |x|^2
     if (rows <= FEWROWS_MAX) need = need > ((size_t)rows * K + K + rows) * 4 ? need : ((size_t)rows * K + K + rows) * 4;
-    return need;
+    // chunked coarse pass (K > 1024): the same partials for up to K / BMU_CHUNK_MIN groups + a header per chunk
+    const size_t chunked = qarig_bmu_coarse_workspace_bytes(rows, K);
+    return need > chunked ? need : chunked;
 }
 
 static bool bmu_coarse_ok(const PatchGeom& g, int K, const float* codebook) {
     return g.D <= 16 && g.D % 4 == 0 && K % 32 == 0 && K >= 32 && K <= 1024 && g.R > 25 &&
+           (((uintptr_t)codebook) & 15) == 0;
+}
+
+static bool bmu_coarse_chunked_ok(const PatchGeom& g, int K, const float* codebook) {
+    return g.D <= 16 && g.D % 4 == 0 && K % 32 == 0 && K > 1024 && K <= BMU_K_MAX && g.R > 25 &&
            (((uintptr_t)codebook) & 15) == 0;
 }
 
@@ -1509,16 +1811,62 @@ static int bmu_coarse_launch(const PatchGeom& g, const float* codebook, int K, i
     return QARIG_OK;
 }
 
-// Image of a codebook for qarig_bmu_fwd_coarse (its `prepared` argument): bytes, and the one-block kernel
-// that writes it.  0 bytes = the coarse form does not take this codebook.
+// Grid of the chunked form.  Chunk size: the image's (fixed per codebook) when there is one, else halved from
+// BMU_CHUNK_MAX while rows x chunks leave the chip under two workgroups per CU; chunks per workgroup: doubled while
+// the grid still has those 512 workgroups (many rows: a workgroup stages its patch rows once for several chunks).
+struct BmuChunkPlan { int chunk, nchunks, per_group, ngroups; };
+static BmuChunkPlan bmu_chunk_plan(int R, int K, bool image) {
+    const int64_t rb = (R + 127) / 128;
+    int chunk = BMU_CHUNK_MAX;
+    if (!image)
+        while (chunk > BMU_CHUNK_MIN && rb * ((K + chunk - 1) / chunk) < 512) chunk /= 2;
+    const int nchunks = (K + chunk - 1) / chunk;
+    int per = 1;
+    while (per < nchunks && rb * ((nchunks + 2 * per - 1) / (2 * per)) >= 512) per *= 2;
+    return {chunk, nchunks, per, (nchunks + per - 1) / per};
+}
+
+static int bmu_coarse_chunked_launch(const PatchGeom& g, const float* codebook, int K, int64_t* out_idx,
+                                     unsigned* stats, const void* image, void* workspace, hipStream_t st) {
+    PatchOffsets po;
+    bmu_patch_offsets(g, po);
+    const BmuChunkPlan pl = bmu_chunk_plan(g.R, K, image != nullptr);
+    float* part_d = (float*)workspace;
+    int* part_i = (int*)(part_d + (size_t)pl.ngroups * g.R);
+    float* part_s = (float*)(part_i + (size_t)pl.ngroups * g.R);
+    float* part_x2 = part_s + (size_t)pl.ngroups * g.R;
+    float* chunk_hdr = part_x2 + g.R;
+    const size_t shm = (size_t)pl.chunk * 100 + BMU_CHUNK_PAD;
+    hipLaunchKernelGGL(bmu_coarse_chunk_kernel, dim3((g.R + 127) / 128, pl.ngroups), dim3(NTHREADS), shm, st, g, po,
+                       codebook, K, pl.chunk, pl.nchunks, pl.per_group, (const unsigned char*)image, part_d, part_i,
+                       part_s, part_x2, chunk_hdr, stats);
+    QARIG_CHECK_LAUNCH("bmu coarse chunks");
+    hipLaunchKernelGGL(bmu_coarse_finalize_kernel, dim3((g.R + BMU_FIN_ROWS - 1) / BMU_FIN_ROWS), dim3(256), 0, st, g,
+                       po, codebook, K, part_d, part_i, part_s, part_x2, chunk_hdr, pl.ngroups, pl.nchunks, out_idx,
+                       stats);
+    QARIG_CHECK_LAUNCH("bmu coarse finalize");
+    return QARIG_OK;
+}
+
+// Image of a codebook for qarig_bmu_fwd_coarse / _coarse_ws / _prepared (their `prepared` argument): bytes, and the
+// kernel that writes it (one block; one block per chunk for K > 1024).  0 bytes = the coarse form does not take this
+// codebook.  K <= 1024: K x 100 B + 16; beyond: that layout per BMU_CHUNK_MAX-code chunk, chunk after chunk.
 extern "C" size_t qarig_bmu_prepare_bytes(int K, int D) {
-    if (D < 1 || D > 16 || D % 4 || K < 32 || K > 1024 || K % 32) return 0;
-    return (size_t)K * 100 + 16;
+    if (D < 1 || D > 16 || D % 4 || K < 32 || K > BMU_K_MAX || K % 32) return 0;
+    if (K <= 1024) return (size_t)K * 100 + 16;
+    return (size_t)K * 100 + (size_t)((K + BMU_CHUNK_MAX - 1) / BMU_CHUNK_MAX) * 16;
 }
 extern "C" int qarig_bmu_prepare(const float* codebook, int K, int D, void* image, void* stream) {
     QARIG_CHECK_ARG(codebook && image, "bmu_prepare: null pointer");
     QARIG_CHECK_ARG(qarig_bmu_prepare_bytes(K, D) != 0 && (((uintptr_t)codebook | (uintptr_t)image) & 15) == 0,
-                    "bmu_prepare: needs D <= 16, D %% 4 == 0, K %% 32 == 0, 32 <= K <= 1024, 16-B aligned pointers");
+                    "bmu_prepare: needs D <= 16, D %% 4 == 0, K %% 32 == 0, 32 <= K <= 16384, 16-B aligned pointers");
+    if (K > 1024) {
+        hipLaunchKernelGGL(bmu_coarse_prepare_chunks_kernel, dim3((K + BMU_CHUNK_MAX - 1) / BMU_CHUNK_MAX),
+                           dim3(NTHREADS), (size_t)BMU_CHUNK_MAX * 100 + 64, (hipStream_t)stream, codebook, K, D,
+                           BMU_CHUNK_MAX, (unsigned char*)image);
+        QARIG_CHECK_LAUNCH("bmu prepare chunks");
+        return QARIG_OK;
+    }
     PatchGeom g{nullptr, 1, 1, 1, 1, 1, 1, 1, 1, D, 1};
     PatchOffsets po{};
     const size_t shm = bmu_coarse_lds(K);
@@ -1531,10 +1879,10 @@ extern "C" int qarig_bmu_prepare(const float* codebook, int K, int D, void* imag
 
 // The coarse-pass form on its own (tests, benchmarks): fails where qarig_bmu_fwd would fall back to
 // the exact kernels; *uncertified (device, caller-zeroed, may be NULL) += rows that took the exact
-// re-scan.
-extern "C" int qarig_bmu_fwd_coarse(const float* x, int N, int C, int H, int W, int pH, int pW,
-                                    const float* codebook, int K, int D, int64_t* out_idx,
-                                    unsigned* uncertified, const void* prepared, void* stream) {
+// re-scan.  chunked: K > 1024 allowed (through the workspace).
+static int bmu_coarse_entry(const float* x, int N, int C, int H, int W, int pH, int pW, const float* codebook, int K,
+                            int D, int64_t* out_idx, unsigned* uncertified, const void* prepared, bool chunked,
+                            void* workspace, size_t ws_bytes, void* stream) {
     QARIG_CHECK_ARG(x && codebook && out_idx, "bmu_coarse: null pointer");
     QARIG_CHECK_ARG(N > 0 && C > 0 && H > 0 && W > 0 && pH > 0 && pW > 0 && K > 0 && pH <= H && pW <= W,
                     "bmu_coarse: bad extents");
@@ -1545,10 +1893,32 @@ extern "C" int qarig_bmu_fwd_coarse(const float* x, int N, int C, int H, int W, 
     const int64_t rows = (int64_t)N * g.gh * g.gw;
     QARIG_CHECK_ARG(rows < INT_MAX, "bmu_coarse: too many patch rows");
     g.R = (int)rows;
-    QARIG_CHECK_ARG(bmu_coarse_ok(g, K, codebook),
-                    "bmu_coarse: needs D <= 16, D %% 4 == 0, K %% 32 == 0, 32 <= K <= 1024, more than 25 rows");
+    QARIG_CHECK_ARG(bmu_coarse_ok(g, K, codebook) || (chunked && bmu_coarse_chunked_ok(g, K, codebook)),
+                    "bmu_coarse: needs D <= 16, D %% 4 == 0, K %% 32 == 0, 32 <= K <= %d, more than 25 rows",
+                    chunked ? BMU_K_MAX : 1024);
     QARIG_CHECK_ARG(!prepared || (((uintptr_t)prepared) & 15) == 0, "bmu_coarse: prepared image must be 16-B aligned");
-    return bmu_coarse_launch(g, codebook, K, out_idx, uncertified, prepared, (hipStream_t)stream);
+    if (K <= 1024) return bmu_coarse_launch(g, codebook, K, out_idx, uncertified, prepared, (hipStream_t)stream);
+    const size_t need = qarig_bmu_coarse_workspace_bytes(rows, K);
+    if (!workspace || ws_bytes < need) {
+        qarig_set_error("bmu_coarse: workspace too small (%zu < %zu)", workspace ? ws_bytes : (size_t)0, need);
+        return QARIG_ERR_WORKSPACE;
+    }
+    return bmu_coarse_chunked_launch(g, codebook, K, out_idx, uncertified, prepared, workspace, (hipStream_t)stream);
+}
+extern "C" int qarig_bmu_fwd_coarse(const float* x, int N, int C, int H, int W, int pH, int pW,
+                                    const float* codebook, int K, int D, int64_t* out_idx,
+                                    unsigned* uncertified, const void* prepared, void* stream) {
+    return bmu_coarse_entry(x, N, C, H, W, pH, pW, codebook, K, D, out_idx, uncertified, prepared, false, nullptr, 0,
+                            stream);
+}
+// ... and for any K the coarse form takes: 1024 < K <= 16384 runs the chunked form through `workspace`
+// (qarig_bmu_coarse_workspace_bytes; unused, may be NULL, for K <= 1024).
+extern "C" int qarig_bmu_fwd_coarse_ws(const float* x, int N, int C, int H, int W, int pH, int pW,
+                                       const float* codebook, int K, int D, int64_t* out_idx,
+                                       unsigned* uncertified, const void* prepared, void* workspace,
+                                       size_t ws_bytes, void* stream) {
+    return bmu_coarse_entry(x, N, C, H, W, pH, pW, codebook, K, D, out_idx, uncertified, prepared, true, workspace,
+                            ws_bytes, stream);
 }
 
 extern "C" int qarig_bmu_fwd_prepared(const float* x, int N, int C, int H, int W, int pH, int pW,
@@ -1628,6 +1998,9 @@ extern "C" int qarig_bmu_fwd_prepared(const float* x, int N, int C, int H, int W
     const int coarse_env = g_qarig_opt.bmu_coarse;
     if (bmu_coarse_ok(g, K, codebook) && coarse_env != 0 && (coarse_env == 1 || g.R >= 24576))
         return bmu_coarse_launch(g, codebook, K, out_idx, nullptr, prepared, st);
+    // K > 1024: the chunked form, where the option forces it (auto: see BMU_CHUNKED_AUTO_ROWS)
+    if (bmu_coarse_chunked_ok(g, K, codebook) && coarse_env != 0 && (coarse_env == 1 || g.R >= BMU_CHUNKED_AUTO_ROWS))
+        return bmu_coarse_chunked_launch(g, codebook, K, out_idx, nullptr, prepared, workspace, st);
     if (D <= 16) {
         const int ks = D <= 4 ? 2 : (D <= 8 ? 4 : 8);
         const int bpc = (2 * ks + 1) * 4;                         // LDS bytes per code

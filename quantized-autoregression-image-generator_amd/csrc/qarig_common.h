@@ -40,7 +40,7 @@ struct QarigOptions {
     int gemm_pair = -1;    // paired (two-team) GEMM kernel: -1 auto (<= 256 workgroups), 0 never, 1 wherever eligible
     int bmu_cs = 0;        // resident BMU kernel, waves sharing a row tile: 0 auto, else 1 / 2 / 4
     int bmu_groups = -1;   // resident BMU kernel, group-minimum scan: -1 auto, 0 / 1
-    int bmu_coarse = -1;   // coarse-pass BMU kernel: -1 auto (>= 24,576 rows), 0 never, 1 wherever it applies
+    int bmu_coarse = -1;   // coarse-pass BMU kernel: -1 auto (K <= 1024: >= 24,576 rows; beyond: never), 0 never, 1 wherever it applies
     int attn_qw = 0;       // attention forward, waves per head: 0 auto, else 1 / 2 / 4
     int attn_bw = 0;       // attention backward, waves per head: 0 auto, else 1 / 2 / 4
     int lp_big = -1;       // reduced precision, 256 x 256 tiles: -1 auto (>= 224 tiles), 0 / 1

@@ -30,6 +30,8 @@ SIGNATURES = {
     "qarig_bmu_fwd": (I, [P, I, I, I, I, I, I, P, I, I, P, P, Z, P]),
     "qarig_bmu_fwd_prepared": (I, [P, I, I, I, I, I, I, P, I, I, P, P, Z, P, P]),
     "qarig_bmu_fwd_coarse": (I, [P, I, I, I, I, I, I, P, I, I, P, P, P, P]),
+    "qarig_bmu_coarse_workspace_bytes": (Z, [L, I]),
+    "qarig_bmu_fwd_coarse_ws": (I, [P, I, I, I, I, I, I, P, I, I, P, P, P, P, Z, P]),
     "qarig_bmu_prepare_bytes": (Z, [I, I]),
     "qarig_bmu_prepare": (I, [P, I, I, P, P]),
     "qarig_gemm_workspace_bytes": (Z, [I, I, I]),
@@ -148,6 +150,7 @@ def load():
         v = os.environ.get("QARIG_" + name.upper())
         if v is not None:
             lib.qarig_set_option(name.encode(), int(v))
+            _option_values[name] = int(v)
     return lib
 
 
@@ -158,6 +161,9 @@ OPTIONS = ("gemm_dma", "gemm_pair", "bmu_cs", "bmu_groups", "bmu_coarse", "attn_
 OPTION_EPOCH = 0     # bumped by set_option: cached artefacts whose layout depends on the kernel family carry it in their key
 
 
+_option_values = {}  # options set through this module (set_option, QARIG_<OPTION>): name -> current value
+
+
 def set_option(name, value):
     """Kernel-selection option (include/qarig.h qarig_set_option); returns the previous value."""
     global OPTION_EPOCH
@@ -165,7 +171,13 @@ def set_option(name, value):
     old = load().qarig_set_option(name.encode(), int(value))
     if old == -2 ** 31:
         raise KeyError(f"{name}: {last_error()}")
+    _option_values[name] = int(value)
     return old
+
+
+def option_value(name):
+    """Current value of an option that was set through set_option / the environment; None = the library's default."""
+    return _option_values.get(name)
 
 
 def last_error():

@@ -23,6 +23,10 @@ def act_id(name):
 _bmu_images = {}
 _bmu_seen = {}               # id(codebook) -> state key of the last search (bmu_image only_if_stable)
 BMU_IMAGE_MIN_ROWS = 24576   # the dispatch takes the coarse-pass kernel (the image's consumer) from here up
+# K > 1024 (the chunked coarse pass): the row count from which the dispatch takes it by itself -- nowhere so far
+# (csrc/bmu.hip BMU_CHUNKED_AUTO_ROWS, profiles/r08_bmu_large_k.log); under option bmu_coarse = 1 it runs at every
+# row count, and the image is built for it there.
+BMU_IMAGE_MIN_ROWS_LARGE_K = 2 ** 31 - 1
 
 
 def bmu_invalidate():
@@ -94,7 +98,11 @@ def bmu(x, codebook, patch_dim):
     # Only for an nn.Parameter: its identity is stable, torch's version counter sees every in-place update
     # through torch, FlatAdam's step count (p._qarig_owner) those made through the flat buffer.
     img = None
-    if rows >= BMU_IMAGE_MIN_ROWS and cb is codebook and isinstance(codebook, torch.nn.Parameter) and \
+    if K <= 1024:
+        wants_image = rows >= BMU_IMAGE_MIN_ROWS
+    else:
+        wants_image = rows >= BMU_IMAGE_MIN_ROWS_LARGE_K or _lib.option_value("bmu_coarse") == 1
+    if wants_image and cb is codebook and isinstance(codebook, torch.nn.Parameter) and \
             not torch.cuda.is_current_stream_capturing():
         img = bmu_image(cb, only_if_stable=True)
     nb = lib.qarig_bmu_workspace_bytes(rows, K)
@@ -106,8 +114,9 @@ def bmu(x, codebook, patch_dim):
 
 def bmu_coarse(x, codebook, patch_dim, prepared=False):
     """(indices, rows that needed the exact re-scan): the coarse-pass form of `bmu` forced
-    (include/qarig.h qarig_bmu_fwd_coarse); raises where it does not apply.  prepared: through the
-    cached codebook image (bmu_image) instead of staging the codebook in every workgroup."""
+    (include/qarig.h qarig_bmu_fwd_coarse; beyond 1,024 codes its chunked form, qarig_bmu_fwd_coarse_ws); raises
+    where it does not apply.  prepared: through the cached codebook image (bmu_image) instead of staging the
+    codebook in every workgroup."""
     require_cuda(x, codebook)
     x = f32c(x)
     codebook = f32c(codebook)
@@ -117,8 +126,14 @@ def bmu_coarse(x, codebook, patch_dim, prepared=False):
     out = torch.empty(N * (H // pH) * (W // pW), dtype=torch.int64, device=x.device)
     cnt = torch.zeros(8, dtype=torch.int32, device=x.device)    # [0] re-scanned rows, [1..4] phase clocks
     img = bmu_image(codebook) if prepared else None
-    check(_lib.load().qarig_bmu_fwd_coarse(ptr(x), N, C, H, W, pH, pW, ptr(codebook), K, D, ptr(out), ptr(cnt),
-                                           ptr(img), stream()), "qarig_bmu_fwd_coarse")
+    lib = _lib.load()
+    if K > 1024:
+        ws = workspace(lib.qarig_bmu_coarse_workspace_bytes(out.numel(), K), x.device)
+        check(lib.qarig_bmu_fwd_coarse_ws(ptr(x), N, C, H, W, pH, pW, ptr(codebook), K, D, ptr(out), ptr(cnt),
+                                          ptr(img), ptr(ws), ws.numel(), stream()), "qarig_bmu_fwd_coarse_ws")
+    else:
+        check(lib.qarig_bmu_fwd_coarse(ptr(x), N, C, H, W, pH, pW, ptr(codebook), K, D, ptr(out), ptr(cnt),
+                                       ptr(img), stream()), "qarig_bmu_fwd_coarse")
     return out, cnt[:1] if not BMU_COARSE_PHASES else cnt
 
 
