@@ -20,8 +20,9 @@
 // non-decreasing, so argmin-first over d equals argmin-first over t unless another candidate
 // maps to the same d as the minimum (the add's rounding, the clamp or sqrt collapsing
 // neighbouring floats: ~1 row in 65k).  Exactly those rows -- f(second) == f(min) -- are
-// re-scanned by the whole block with the literal definition above, so the result is
-// bit-identical to it on every input.
+// re-scanned with the literal definition above, so the result is bit-identical to it on every
+// input.  Every search form below (MFMA tiles, resident, coarse, their finalize kernels) ends in
+// the same routines: bmu_merge of its partial states, bmu_commit_row, bmu_rescan.
 #include <limits.h>
 #include <type_traits>
 
@@ -133,75 +134,196 @@ __device__ __forceinline__ int bmu_needs_exact(const BmuState& s, float x2) {
     return s.sec < INFINITY && bmu_dist(s.sec, x2) == bmu_dist(s.d2, x2);
 }
 
-// Literal re-scan of the flagged rows of a 128-row block, all 256 threads per row:
-// thread t takes codes t, t+256, ... (ascending), the block reduces (d, index) with the
-// first-index rule.  Same fp32 chains as the MFMA path and the oracle.
-__device__ __forceinline__ void bmu_exact_rows(const PatchGeom& g, const float* __restrict__ w, int K, int p0,
-                               const int* flags, float* lds, int64_t* __restrict__ out) {
-    float* rs = lds;                                  // [256]
-    int* ri = reinterpret_cast<int*>(lds + 256);      // [256]
-    const int tid = threadIdx.x;
-    // flags[128] holds the two 64-bit ballots of the block's rows (block-uniform reads)
-    const unsigned long long* masks = reinterpret_cast<const unsigned long long*>(flags);
+// ---- The cold end every search form shares: commit a row's merged state, re-scan the rows it cannot decide.
+// Partial states of a search whose codes are split over grid.y: [split][R] each, |x|^2 [R].  (The kernels take the four
+// pointers as __restrict__ arguments of their own and pass them on as this struct: as one struct argument they moved
+// the hot kernels' kernel-argument loads and waits.)
+struct BmuPartials {
+    float* d;
+    int* idx;
+    float* sec;
+    float* x2;
+};
+
+// Row commit: merges a row's n states (sd / si / ss, `stride` apart, ascending code ranges).  Single launch (out): writes
+// the index and returns whether `undecided(state, x2)` wants the row re-scanned.  Split launch: writes the partial
+// state (split 0 the row's |x|^2 too) for the finalize kernel, which commits it.  An undecided row's index is written
+// all the same and overwritten by its re-scan, which runs in the same workgroup behind a barrier (stores of one CU to
+// one address stay ordered).  `part` is read only when `out` is null: the finalize kernels pass an empty one.
+template <class Undecided>
+__device__ __forceinline__ int bmu_commit_row(int row, int R, const float* sd, const int* si, const float* ss, int n,
+                                              int64_t stride, float x2, Undecided undecided, const BmuPartials& part,
+                                              int64_t* __restrict__ out) {
+    BmuState st{sd[0], si[0], ss[0]};
+    for (int q = 1; q < n; ++q) st = bmu_merge(st, BmuState{sd[q * stride], si[q * stride], ss[q * stride]});
+    if (out) {
+        out[row] = st.idx == INT_MAX ? 0 : (int64_t)st.idx;
+        return undecided(st, x2);
+    }
+    const int64_t o = (int64_t)blockIdx.y * R + row;
+    part.d[o] = st.d2;
+    part.idx[o] = st.idx;
+    part.sec[o] = st.sec;
+    if (blockIdx.y == 0) part.x2[row] = x2;
+    return 0;
+}
+// The flags of a block's 128 rows (threads 0..127, one row each) as two 64-bit ballots, and their walk (block-uniform).
+__device__ __forceinline__ void bmu_put_flags(int flag, unsigned long long* masks) {
+    const unsigned long long m = __ballot(flag);
+    if ((threadIdx.x & 63) == 0) masks[threadIdx.x >> 6] = m;
+}
+template <class F>
+__device__ __forceinline__ void bmu_each_flagged(const unsigned long long* masks, F&& f) {
     for (int half = 0; half < 2; ++half)
-    for (unsigned long long m = masks[half]; m; m &= m - 1) {
-        const int r = half * 64 + __ffsll((long long)m) - 1;
-        const int row = p0 + r;
-        const int64_t base = patch_row_base(g, row);
-        float x2 = 0.0f;
+        for (unsigned long long m = masks[half]; m; m &= m - 1) f(half * 64 + __ffsll((long long)m) - 1);
+}
+
+// (d, index) under the first-index rule, its reduction over a wave and over the 4-wave block (through red[8]; the
+// block's result is thread 0's).  Which thread scanned which code does not matter to a minimum in that order.
+struct BmuPick {
+    float d;
+    int idx;
+};
+__device__ __forceinline__ BmuPick bmu_pick_min(BmuPick a, BmuPick b) {
+    return (b.d < a.d || (b.d == a.d && b.idx < a.idx)) ? b : a;
+}
+__device__ __forceinline__ BmuPick bmu_pick_wave(BmuPick p) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) p = bmu_pick_min(p, BmuPick{__shfl_xor(p.d, o), __shfl_xor(p.idx, o)});
+    return p;
+}
+__device__ __forceinline__ BmuPick bmu_pick_block(BmuPick p, float* red) {
+    int* ri = reinterpret_cast<int*>(red + 4);
+    const int tid = threadIdx.x;
+    p = bmu_pick_wave(p);
+    __syncthreads();   // thread 0 has read the previous row's slots
+    if ((tid & 63) == 0) { red[tid >> 6] = p.d; ri[tid >> 6] = p.idx; }
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+        for (int q = 1; q < 4; ++q) p = bmu_pick_min(p, BmuPick{red[q], ri[q]});
+    }
+    return p;
+}
+__device__ __forceinline__ int64_t bmu_pick_index(BmuPick p) { return p.idx == INT_MAX ? 0 : (int64_t)p.idx; }
+
+// The literal re-scan: the definition at the head of this file, written once.  Codes first, first + stride, ... < K
+// (ascending, strict <: the first minimum) against one patch row; returns this thread's (d, index).
+//   Row:   each(f) calls f(e, x[e]) for the row's elements, e ascending.
+//   Codes: at(k) returns code k as {m2(e) = -2 w[k][e], w2 = |w[k]|^2 by its chain}; UNROLL codes in flight per thread
+//          (2 where they come from memory one wave per row, so that the loads of two codes overlap).
+// Rows and codes held in registers are zero past D: fmaf(-0, 0, acc) = acc, the chains are the definition's.
+template <class Row, class Codes>
+__device__ __forceinline__ BmuPick bmu_rescan(const Row& row, const Codes& codes, int first, int stride, int K) {
+    float x2 = 0.0f;
+    row.each([&](int, float xe) { x2 = fmaf(xe, xe, x2); });
+    BmuPick best{INFINITY, INT_MAX};
+#pragma unroll Codes::UNROLL
+    for (int k = first; k < K; k += stride) {
+        const auto c = codes.at(k);
+        float acc = 0.0f;
+        row.each([&](int e, float xe) { acc = fmaf(c.m2(e), xe, acc); });
+        const float d = sqrtf(fmaxf((acc + c.w2) + x2, 0.0f));
+        if (d < best.d) best = BmuPick{d, k};
+    }
+    return best;
+}
+// Rows: NE elements in registers (NE >= D, zero past D), of which the chains take the first n (D <= n <= NE: the
+// coarse forms stop at D, since a one-wave re-scan of thousands of codes is a chain of these chains) / any patch,
+// gathered from the latent as it is walked.
+template <int NE>
+struct BmuRowRegs {
+    float x[NE];
+    int n;
+    template <class F>
+    __device__ __forceinline__ void each(F&& f) const {
+#pragma unroll
+        for (int e = 0; e < NE; ++e)
+            if (e < n) f(e, x[e]);
+    }
+};
+struct BmuRowGather {
+    const PatchGeom& g;
+    int64_t base;
+    template <class F>
+    __device__ __forceinline__ void each(F&& f) const {
+        int e = 0;
         for (int c = 0; c < g.C; ++c)
             for (int i = 0; i < g.pH; ++i) {
                 const float* p = g.x + base + ((int64_t)c * g.H + i) * g.W;
-                for (int j = 0; j < g.pW; ++j) x2 = fmaf(p[j], p[j], x2);
+                for (int j = 0; j < g.pW; ++j, ++e) f(e, p[j]);
             }
-        float best = INFINITY;
-        int bidx = INT_MAX;
-        for (int k = tid; k < K; k += 256) {
-            const float* wk = w + (int64_t)k * g.D;
-            float w2 = 0.0f;
-            for (int e = 0; e < g.D; ++e) w2 = fmaf(wk[e], wk[e], w2);
-            float acc = 0.0f;
-            int e = 0;
-            for (int c = 0; c < g.C; ++c)
-                for (int i = 0; i < g.pH; ++i) {
-                    const float* p = g.x + base + ((int64_t)c * g.H + i) * g.W;
-                    for (int j = 0; j < g.pW; ++j, ++e) acc = fmaf(-2.0f * wk[e], p[j], acc);
-                }
-            const float d = sqrtf(fmaxf((acc + w2) + x2, 0.0f));
-            if (d < best) { best = d; bidx = k; }
-        }
-        __syncthreads();
-        rs[tid] = best;
-        ri[tid] = bidx;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if (tid < o) {
-                const float s2 = rs[tid + o];
-                const int i2 = ri[tid + o];
-                if (s2 < rs[tid] || (s2 == rs[tid] && i2 < ri[tid])) { rs[tid] = s2; ri[tid] = i2; }
-            }
-            __syncthreads();
-        }
-        if (tid == 0) out[row] = ri[0] == INT_MAX ? 0 : (int64_t)ri[0];
     }
+};
+// Codes: a code in registers (what the LDS-image policies of the resident and coarse kernels and the D <= 16 memory
+// policy return) / the fp32 codebook in memory, any D.
+template <int NE>
+struct BmuCodeRegs {
+    float m[NE];
+    float w2;
+    __device__ __forceinline__ float m2(int e) const { return m[e]; }
+};
+struct BmuCodesMemory {
+    static constexpr int UNROLL = 1;
+    const float* __restrict__ w;
+    int D;
+    struct Code {
+        const float* wk;
+        float w2;
+        __device__ __forceinline__ float m2(int e) const { return -2.0f * wk[e]; }
+    };
+    __device__ __forceinline__ Code at(int k) const {
+        const float* wk = w + (int64_t)k * D;
+        float w2 = 0.0f;
+        for (int e = 0; e < D; ++e) w2 = fmaf(wk[e], wk[e], w2);
+        return Code{wk, w2};
+    }
+};
+struct BmuCodesMemory16 {   // D <= 16, D % 4 == 0, 16-B aligned codebook (host): a code's loads in flight together
+    static constexpr int UNROLL = 2;
+    const float* __restrict__ w;
+    int D;
+    __device__ __forceinline__ BmuCodeRegs<16> at(int k) const {
+        const float4* wk4 = reinterpret_cast<const float4*>(w + (int64_t)k * D);
+        float v[16];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float4 t = 4 * q < D ? wk4[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+            v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
+        }
+        BmuCodeRegs<16> c;
+        c.w2 = 0.0f;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            if (e < D) c.w2 = fmaf(v[e], v[e], c.w2);
+            c.m[e] = -2.0f * v[e];
+        }
+        return c;
+    }
+};
+
+// Re-scan of the flagged rows of a 128-row block against the codebook in memory, all 256 threads per row.
+__device__ __forceinline__ void bmu_exact_rows(const PatchGeom& g, const float* __restrict__ w, int K, int p0,
+                                               const unsigned long long* flags, float* red,
+                                               int64_t* __restrict__ out) {
+    bmu_each_flagged(flags, [&](int r) {
+        const int row = p0 + r;
+        const BmuPick p = bmu_pick_block(bmu_rescan(BmuRowGather{g, patch_row_base(g, row)}, BmuCodesMemory{w, g.D},
+                                                    threadIdx.x, NTHREADS, K), red);
+        if (threadIdx.x == 0) out[row] = bmu_pick_index(p);
+    });
 }
 
-// Block epilogue shared by the BMU kernels: combine the 4 holders of each patch column
-// (lane halves x waves along the code axis), write the index (or the per-split partial
-// state), then re-scan exactly the rows whose minimum shares its sqrt with another candidate.
-// `lds` needs 13*128 + 512 floats and must no longer be in use as operand tiles.
+// Block epilogue of the MFMA-tile kernels: combine the 4 holders of each patch column (lane halves x waves along
+// the code axis), commit the rows, re-scan the flagged ones.  `lds` needs 13*128 floats and must no longer be in
+// use as operand tiles.
 __device__ __forceinline__ void bmu_block_finish(const PatchGeom& g, const float* __restrict__ w,
                                                  int K, int p0, const float (&best_d2)[2],
                                                  const int (&best_i)[2], const float (&sec_d2)[2],
-                                                 float* lds, const float* x2rows,
-                                                 float* __restrict__ part_d,
-                                                 int* __restrict__ part_i,
-                                                 float* __restrict__ part_s,
-                                                 float* __restrict__ part_x2,
+                                                 float* lds, const float* x2rows, const BmuPartials& part,
                                                  int64_t* __restrict__ out) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1, cl = lane & 31;
-    // Combine the 4 holders of each patch column: lane halves (h) x waves (wm).
     float* cd = lds;                                   // [4][128] min d2
     int* ci = reinterpret_cast<int*>(lds + 4 * 128);   // [4][128] its first index
     float* cs = lds + 8 * 128;                         // [4][128] second-smallest d2
@@ -214,28 +336,13 @@ __device__ __forceinline__ void bmu_block_finish(const PatchGeom& g, const float
         cs[slot * 128 + col] = sec_d2[j];
     }
     __syncthreads();
-    int* flags = reinterpret_cast<int*>(lds + 12 * 128);   // [128] rows needing the exact scan
+    unsigned long long* flags = reinterpret_cast<unsigned long long*>(lds + 12 * 128);
     if (tid < 128) {
-        const int prow = p0 + tid;
         int flag = 0;
-        if (prow < g.R) {
-            BmuState st{cd[tid], ci[tid], cs[tid]};
-#pragma unroll
-            for (int q = 1; q < 4; ++q) st = bmu_merge(st, BmuState{cd[q * 128 + tid], ci[q * 128 + tid],
-                                                                   cs[q * 128 + tid]});
-            if (out) {
-                flag = bmu_needs_exact(st, x2rows[tid]);
-                out[prow] = st.idx == INT_MAX ? 0 : (int64_t)st.idx;
-            } else {
-                const int64_t o = (int64_t)blockIdx.y * g.R + prow;
-                part_d[o] = st.d2;
-                part_i[o] = st.idx;
-                part_s[o] = st.sec;
-                if (blockIdx.y == 0) part_x2[prow] = x2rows[tid];
-            }
-        }
-        const unsigned long long m = __ballot(flag);
-        if (lane == 0) reinterpret_cast<unsigned long long*>(flags)[wave] = m;
+        if (p0 + tid < g.R)
+            flag = bmu_commit_row(p0 + tid, g.R, cd + tid, ci + tid, cs + tid, 4, 128, x2rows[tid], bmu_needs_exact,
+                                  part, out);
+        bmu_put_flags(flag, flags);
     }
     __syncthreads();
     if (out) bmu_exact_rows(g, w, K, p0, flags, lds, out);
@@ -243,12 +350,9 @@ __device__ __forceinline__ void bmu_block_finish(const PatchGeom& g, const float
 
 __global__ __launch_bounds__(NTHREADS, 2) void bmu_mma_kernel(PatchGeom g,
                                                               const float* __restrict__ w, int K,
-                                                              int tiles_per_split,
-                                                              float* __restrict__ part_d,
-                                                              int* __restrict__ part_i,
-                                                              float* __restrict__ part_s,
-                                                              float* __restrict__ part_x2,
-                                                              int64_t* __restrict__ out) {
+                                                              int tiles_per_split, float* __restrict__ part_d,
+                                                              int* __restrict__ part_i, float* __restrict__ part_s,
+                                                              float* __restrict__ part_x2, int64_t* __restrict__ out) {
     __shared__ __attribute__((aligned(16))) float lds[GEMM_LDS_FLOATS];
     __shared__ float norms[256];   // [0,128): |w|^2 of the code tile, [128,256): |x|^2 of the rows
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -290,8 +394,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void bmu_mma_kernel(PatchGeom g,
         __syncthreads();   // norms[0..127] is rewritten by the next code tile
     }
 
-    bmu_block_finish(g, w, K, p0, best_d2, best_i, sec_d2, lds, norms + 128, part_d, part_i, part_s,
-                     part_x2, out);
+    bmu_block_finish(g, w, K, p0, best_d2, best_i, sec_d2, lds, norms + 128,
+                     BmuPartials{part_d, part_i, part_s, part_x2}, out);
 }
 
 // Small patch widths (D <= 16*NKT <= 64: every hierarchical patch size of the reference's
@@ -299,16 +403,12 @@ __global__ __launch_bounds__(NTHREADS, 2) void bmu_mma_kernel(PatchGeom g,
 // (with their |x|^2 chains); code tiles stream through a double-buffered LDS slot whose
 // next global loads are in flight under the current tile's MFMAs; the branch-free
 // (min, first index, second) scan follows each tile.  Nothing is re-read from HBM.
-template <int NKT, int KS>
+template <int NKT>
 __global__ __launch_bounds__(NTHREADS, 2) void bmu_small_kernel(PatchGeom g,
                                                                 const float* __restrict__ w, int K,
-                                                                int tiles_per_split,
-                                                                float* __restrict__ part_d,
-                                                                int* __restrict__ part_i,
-                                                                float* __restrict__ part_s,
-                                                                float* __restrict__ part_x2,
-                                                                int64_t* __restrict__ out) {
-    // KS = 2-deep MFMA steps that carry data in the last k-tile (D <= 4 -> 2 ... D > 8 -> 8)
+                                                                int tiles_per_split, float* __restrict__ part_d,
+                                                                int* __restrict__ part_i, float* __restrict__ part_s,
+                                                                float* __restrict__ part_x2, int64_t* __restrict__ out) {
     // TB[NKT] | TA[2][NKT]; the combine / exact-rescan scratch reuses TA after the loop
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ float norms[256];
@@ -382,9 +482,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void bmu_small_kernel(PatchGeom g,
         Acc acc;
         acc_zero(acc);
 #pragma unroll
-        for (int kt = 0; kt < NKT - 1; ++kt)
+        for (int kt = 0; kt < NKT; ++kt)
             mma_tile<BK / 2>(acc, ta + kt * TILE_FLOATS, TB + kt * TILE_FLOATS, wm, wn, lane);
-        mma_tile<KS>(acc, ta + (NKT - 1) * TILE_FLOATS, TB + (NKT - 1) * TILE_FLOATS, wm, wn, lane);
         if (more) {
 #pragma unroll
             for (int kt = 0; kt < NKT; ++kt) sa.store(ra[kt], na + kt * TILE_FLOATS, tid);
@@ -403,8 +502,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void bmu_small_kernel(PatchGeom g,
             }
         __syncthreads();   // norms[0..127] is rewritten by the next tile
     }
-    bmu_block_finish(g, w, K, p0, best_d2, best_i, sec_d2, TA, norms + 128, part_d, part_i, part_s,
-                     part_x2, out);
+    bmu_block_finish(g, w, K, p0, best_d2, best_i, sec_d2, TA, norms + 128,
+                     BmuPartials{part_d, part_i, part_s, part_x2}, out);
 }
 
 // ---------------------------------------------------------------------------------
@@ -527,73 +626,45 @@ __device__ __forceinline__ void res_frag(const float* AE, int c, int hi, int chu
     }
 }
 
-// Literal re-scan of the flagged rows (bmu_exact_rows) for a single-chunk launch of the
-// resident kernel: the codes are read back from their LDS image (-2w, so the product chain
-// takes them as they are; w = -0.5 * (-2w) is exact) and the patch row is fetched with all
-// its loads in flight at once -- a flagged row costs about one memory round trip instead of
-// ~50 dependent ones, which matters because the launch ends with its slowest workgroup.
-template <int KS>
-__device__ __forceinline__ void res_exact_rows(const PatchGeom& g, const PatchOffsets& po, const float* AE,
-                                            const float* W2, int chunk, int K, int p0, const int* flags,
-                                            float* lds, int64_t* __restrict__ out) {
-    float* rs = lds;                                  // [4] per-wave minima
-    int* ri = reinterpret_cast<int*>(lds + 4);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const unsigned long long* masks = reinterpret_cast<const unsigned long long*>(flags);
-    for (int half = 0; half < 2; ++half)
-    for (unsigned long long m = masks[half]; m; m &= m - 1) {
-        const int r = half * 64 + __ffsll((long long)m) - 1;
-        const int row = p0 + r;
-        const float* px = g.x + patch_row_base(g, row);
-        float xs[2 * KS];
+// Re-scan policies of the kernels that keep narrow rows (D <= NE <= 16) in registers.  The row: all its loads in
+// flight at once -- a flagged row costs about one memory round trip instead of ~50 dependent ones, which matters
+// because the launch ends with its slowest workgroup.  The codes of a single-chunk launch of the resident kernel:
+// read back from their LDS image (-2w, so the product chain takes them as they are; w = -0.5 * (-2w) is exact).
+template <int NE>
+__device__ __forceinline__ BmuRowRegs<NE> bmu_row_fetch(const PatchGeom& g, const PatchOffsets& po, int row, int n) {
+    const float* px = g.x + patch_row_base(g, row);
+    BmuRowRegs<NE> r;
+    r.n = n;
 #pragma unroll
-        for (int e = 0; e < 2 * KS; ++e) {
-            const float v = px[po.off[e]];
-            xs[e] = e < g.D ? v : 0.0f;
-        }
-        float x2 = 0.0f;
-#pragma unroll
-        for (int e = 0; e < 2 * KS; ++e) x2 = fmaf(xs[e], xs[e], x2);
-        float best = INFINITY;
-        int bidx = INT_MAX;
-        for (int k = tid; k < K; k += NTHREADS) {      // K <= chunk: one chunk
-            float ev[KS], od[KS];
-            res_frag<KS>(AE, k, 0, chunk, ev);
-            res_frag<KS>(AE, k, 1, chunk, od);
-            float acc = 0.0f;
-#pragma unroll
-            for (int q = 0; q < KS; ++q) {
-                acc = fmaf(ev[q], xs[2 * q], acc);
-                acc = fmaf(od[q], xs[2 * q + 1], acc);
-            }
-            const float d = sqrtf(fmaxf((acc + W2[k]) + x2, 0.0f));
-            if (d < best) { best = d; bidx = k; }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float s2 = __shfl_xor(best, o);
-            const int i2 = __shfl_xor(bidx, o);
-            if (s2 < best || (s2 == best && i2 < bidx)) { best = s2; bidx = i2; }
-        }
-        __syncthreads();
-        if (lane == 0) { rs[wave] = best; ri[wave] = bidx; }
-        __syncthreads();
-        if (tid == 0) {
-#pragma unroll
-            for (int q = 1; q < 4; ++q)
-                if (rs[q] < best || (rs[q] == best && ri[q] < bidx)) { best = rs[q]; bidx = ri[q]; }
-            out[row] = bidx == INT_MAX ? 0 : (int64_t)bidx;
-        }
+    for (int e = 0; e < NE; ++e) {
+        const float v = px[po.off[e]];                          // (po.off[e >= D] = po.off[0]: a valid address)
+        r.x[e] = e < g.D ? v : 0.0f;
     }
+    return r;
 }
+template <int KS>
+struct BmuCodesFrags {
+    static constexpr int UNROLL = 1;
+    const float* AE;
+    const float* W2;
+    int chunk;
+    __device__ __forceinline__ BmuCodeRegs<2 * KS> at(int k) const {
+        float ev[KS], od[KS];
+        res_frag<KS>(AE, k, 0, chunk, ev);
+        res_frag<KS>(AE, k, 1, chunk, od);
+        BmuCodeRegs<2 * KS> c;
+#pragma unroll
+        for (int q = 0; q < KS; ++q) { c.m[2 * q] = ev[q]; c.m[2 * q + 1] = od[q]; }
+        c.w2 = W2[k];
+        return c;
+    }
+};
 
 template <int KS, int CS, bool GROUPS, int NT>
 __global__ __launch_bounds__(NTHREADS, 2) void bmu_resident_kernel(PatchGeom g, PatchOffsets po,
                                                                    const float* __restrict__ w, int K,
-                                                                   int chunk,
-                                                                   float* __restrict__ part_d,
-                                                                   int* __restrict__ part_i,
-                                                                   float* __restrict__ part_s,
+                                                                   int chunk, float* __restrict__ part_d,
+                                                                   int* __restrict__ part_i, float* __restrict__ part_s,
                                                                    float* __restrict__ part_x2,
                                                                    int64_t* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -809,8 +880,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void bmu_resident_kernel(PatchGeom g, 
     int* ci = reinterpret_cast<int*>(sc + CS * RPB);
     float* cs = sc + 2 * CS * RPB;
     float* cx = sc + 3 * CS * RPB;                     // [RPB] |x|^2
-    int* flags = reinterpret_cast<int*>(sc + 3 * CS * RPB + RPB);   // 128 ints (two 64-bit ballots)
-    float* scratch = sc + 3 * CS * RPB + RPB + 128;    // 512 floats for the exact re-scan
+    unsigned long long* flags = reinterpret_cast<unsigned long long*>(sc + 3 * CS * RPB + RPB);   // 128 ints reserved
+    float* red = sc + 3 * CS * RPB + RPB + 128;        // the re-scan's reduction slots
     if (hi == 0) {
         const int col = rtile * 32 + cl;
         cd[cpart * RPB + col] = st.d2;
@@ -820,59 +891,42 @@ __global__ __launch_bounds__(NTHREADS, 2) void bmu_resident_kernel(PatchGeom g, 
     }
     __syncthreads();
     if (tid < 128) {
-        const int prow = p0 + tid;
         int flag = 0;
-        if (tid < RPB && prow < g.R) {
-            BmuState m{cd[tid], ci[tid], cs[tid]};
-#pragma unroll
-            for (int q = 1; q < CS; ++q) m = bmu_merge(m, BmuState{cd[q * RPB + tid], ci[q * RPB + tid], cs[q * RPB + tid]});
-            if (out) {
-                flag = bmu_needs_exact(m, cx[tid]);
-                out[prow] = m.idx == INT_MAX ? 0 : (int64_t)m.idx;
-            } else {
-                const int64_t o = (int64_t)blockIdx.y * g.R + prow;
-                part_d[o] = m.d2;
-                part_i[o] = m.idx;
-                part_s[o] = m.sec;
-                if (blockIdx.y == 0) part_x2[prow] = cx[tid];
-            }
-        }
-        const unsigned long long mk = __ballot(flag);
-        if (lane == 0) reinterpret_cast<unsigned long long*>(flags)[wave] = mk;
+        if (tid < RPB && p0 + tid < g.R)
+            flag = bmu_commit_row(p0 + tid, g.R, cd + tid, ci + tid, cs + tid, CS, RPB, cx[tid], bmu_needs_exact,
+                                  BmuPartials{part_d, part_i, part_s, part_x2}, out);
+        bmu_put_flags(flag, flags);
     }
     __syncthreads();
-    if (out) res_exact_rows<KS>(g, po, AE, W2, chunk, K, p0, flags, scratch, out);
+    if (out)   // one chunk: K <= chunk, every code is in LDS
+        bmu_each_flagged(flags, [&](int r) {
+            const BmuPick p = bmu_pick_block(bmu_rescan(bmu_row_fetch<2 * KS>(g, po, p0 + r, 2 * KS),
+                                                        BmuCodesFrags<KS>{AE, W2, chunk}, tid, NTHREADS, K), red);
+            if (tid == 0) out[p0 + r] = bmu_pick_index(p);
+        });
 }
 
-// Merge of the per-split partial states (splits cover ascending code ranges), then the
-// exact re-scan of flagged rows.  One block per 128 rows.
-__global__ __launch_bounds__(256) void bmu_finalize_kernel(PatchGeom g, const float* __restrict__ w,
-                                                           int K, const float* __restrict__ part_d,
+// Commit of the per-split partial states (splits cover ascending code ranges), then the exact re-scan of flagged
+// rows.  One block per 128 rows.
+__global__ __launch_bounds__(256) void bmu_finalize_kernel(PatchGeom g, const float* __restrict__ w, int K,
+                                                           const float* __restrict__ part_d,
                                                            const int* __restrict__ part_i,
                                                            const float* __restrict__ part_s,
-                                                           const float* __restrict__ part_x2,
-                                                           int nsplit, int64_t* __restrict__ out) {
-    __shared__ __attribute__((aligned(16))) float lds[512];
-    __shared__ int flags[128];
+                                                           const float* __restrict__ part_x2, int nsplit,
+                                                           int64_t* __restrict__ out) {
+    __shared__ float red[8];
+    __shared__ unsigned long long flags[2];
     const int p0 = blockIdx.x * 128;
-    const int tid = threadIdx.x;
+    const int tid = threadIdx.x, row = p0 + tid;
     if (tid < 128) {
-        const int row = p0 + tid;
         int flag = 0;
-        if (row < g.R) {
-            BmuState st{part_d[row], part_i[row], part_s[row]};
-            for (int z = 1; z < nsplit; ++z) {
-                const int64_t o = (int64_t)z * g.R + row;
-                st = bmu_merge(st, BmuState{part_d[o], part_i[o], part_s[o]});
-            }
-            flag = bmu_needs_exact(st, part_x2[row]);
-            out[row] = st.idx == INT_MAX ? 0 : (int64_t)st.idx;
-        }
-        const unsigned long long m = __ballot(flag);
-        if ((tid & 63) == 0) reinterpret_cast<unsigned long long*>(flags)[tid >> 6] = m;
+        if (row < g.R)
+            flag = bmu_commit_row(row, g.R, part_d + row, part_i + row, part_s + row, nsplit, g.R, part_x2[row],
+                                  bmu_needs_exact, BmuPartials{}, out);
+        bmu_put_flags(flag, flags);
     }
     __syncthreads();
-    bmu_exact_rows(g, w, K, p0, flags, lds, out);
+    bmu_exact_rows(g, w, K, p0, flags, red, out);
 }
 
 // torch.cdist's small-input branch (both operands <= 25 rows): direct
@@ -1294,17 +1348,78 @@ __device__ __forceinline__ void bmu_coarse_scan(const bmu_u32x4* frag, int plane
         : "vcc", "scc", "memory", BMU_SCAN_CLOBBERS);
 }
 
-// PREP: stages the image of a codebook (what every block of the search kernel builds in LDS) into
-// `image` instead: [3 planes: K x 96 B][|w|^2 in accumulator order: K x 4 B][max |w|^2, inexact flag: 8 B].  A frozen
-// codebook (tokenising a dataset, the Transformer training loop) is prepared once and its image
-// copied into LDS by every later launch (qarig_bmu_prepare).
-template <bool PREP>
+// This lane's half (elements 8h .. 8h + 7) of a patch row.  Two steps, so that the loads' latency runs under the
+// codebook staging issued between them: the loads; then masked to D and split three ways, with the row's |x|^2 for the
+// certificate's scale (both halves; not the definition's chain).  Returns whether this half's split is inexact.
+__device__ __forceinline__ void bmu_half_row_load(const PatchGeom& g, const PatchOffsets& po, int row, int h,
+                                                  float (&xv)[8]) {
+    const float* px = g.x + patch_row_base_fast(g, po, row);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) xv[q] = px[po.off[8 * h + q]];   // (po.off[e >= D] = po.off[0]: a valid address)
+}
+__device__ __forceinline__ int bmu_half_row_split(float (&xv)[8], int D, int h, bmu_u32x4& XH, bmu_u32x4& XM,
+                                                  bmu_u32x4& XL, float& x2a) {
+    int inexact = 0;
+    x2a = 0.0f;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) xv[q] = 8 * h + q < D ? xv[q] : 0.0f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        uint32_t a, b, cc;
+        if (!bmu_split3(xv[2 * q], xv[2 * q + 1], a, b, cc)) inexact = 1;
+        XH[q] = a; XM[q] = b; XL[q] = cc;
+        x2a += xv[2 * q] * xv[2 * q] + xv[2 * q + 1] * xv[2 * q + 1];
+    }
+    x2a += __shfl_xor(x2a, 32);
+    return inexact;
+}
+// Block-wide (max |w|^2, inexact) of what the threads staged, through red[8]: put before a barrier, get after it.
+__device__ __forceinline__ void bmu_w2_put(float w2max, int inexact, float* red) {
+    w2max = wave_max(w2max);
+    inexact = __any(inexact);
+    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = w2max; red[4 + (threadIdx.x >> 6)] = inexact ? 1.0f : 0.0f; }
+}
+__device__ __forceinline__ void bmu_w2_get(const float* red, float& w2max, bool& inexact) {
+    w2max = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    inexact = (red[4] + red[5] + red[6] + red[7]) != 0.0f;
+}
+// No certificate: the row is re-scanned.  x2a = NaN (a row whose split is inexact) never passes.
+__device__ __forceinline__ int bmu_coarse_undecided(const BmuState& st, float x2a, float w2max, bool inexact) {
+    const float eps = BMU_COARSE_EPS * (1.001f * x2a + 2.0f * w2max);
+    return inexact || !(st.sec - st.d2 > 3.0f * eps);
+}
+// Re-scan policy: codes rebuilt exactly from a three-plane LDS image (h + m + l), |w|^2 from its accumulator-order copy.
+struct BmuCodesImage {
+    static constexpr int UNROLL = 1;
+    const bmu_u32x4* frag;
+    int plane;
+    const float* W2;
+    __device__ __forceinline__ BmuCodeRegs<16> at(int k) const {
+        BmuCodeRegs<16> c;
+        const int T = k >> 5, cc = k & 31;
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) {
+            const int at = (T * 2 + hh) * 32 + cc;
+            const bmu_u32x4 H = frag[at], M = frag[plane + at], L = frag[2 * plane + at];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                c.m[8 * hh + 2 * q] = bmu_join3(H[q], M[q], L[q], 0);
+                c.m[8 * hh + 2 * q + 1] = bmu_join3(H[q], M[q], L[q], 1);
+            }
+        }
+        c.w2 = W2[bmu_w2_at(k)];
+        return c;
+    }
+};
+
+// The whole codebook as one LDS image, staged by every block -- or copied from `image_in`, the image that
+// qarig_bmu_prepare wrote once for a frozen codebook (tokenising a dataset, the Transformer training loop):
+// [3 planes: K x 96 B][|w|^2 in accumulator order: K x 4 B][max |w|^2, inexact flag, 8 B of padding].
 __global__ __launch_bounds__(NTHREADS, 2) void bmu_coarse_kernel(PatchGeom g, PatchOffsets po,
                                                                  const float* __restrict__ w, int K,
                                                                  int64_t* __restrict__ out,
                                                                  unsigned* __restrict__ stats,
-                                                                 const unsigned char* __restrict__ image_in,
-                                                                 unsigned char* __restrict__ image_out) {
+                                                                 const unsigned char* __restrict__ image_in) {
     // planes [hi | mid | lo] of fragments: [plane][tile][half][code] x 16 B
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     bmu_u32x4* frag = reinterpret_cast<bmu_u32x4*>(lds_raw);
@@ -1313,7 +1428,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void bmu_coarse_kernel(PatchGeom g, Pa
     // exact |w|^2 chains in the accumulator's order: [tile][lane half][register] (bmu_w2_at)
     float* W2 = reinterpret_cast<float*>(frag + 3 * plane);
     float* XS = W2 + K;                                         // [128][16] the block's patch rows, fp32
-    float* red = XS + 128 * 16;                                 // [8] reductions, [8..12) flag masks, [12] inexact
+    float* red = XS + 128 * 16;                                 // [8] reductions, [8..12) flag masks
     unsigned* flagmask = reinterpret_cast<unsigned*>(red + 8);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int h = lane >> 5, cl = lane & 31;
@@ -1321,67 +1436,32 @@ __global__ __launch_bounds__(NTHREADS, 2) void bmu_coarse_kernel(PatchGeom g, Pa
     const int D = g.D;
     const long long tc0 = stats ? clock64() : 0;      // phase clocks (tests / tools only)
 
-    // ---- this lane's patch row: 8 of its 16 elements (e = 8h .. 8h+7); the loads are issued first
-    // so that their latency runs under the codebook staging
     const int prow = p0 + wave * 32 + cl;
     const bool live = prow < g.R;
     float xv[8];
-    if constexpr (!PREP) {
-        const float* px = g.x + patch_row_base_fast(g, po, live ? prow : g.R - 1);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int off = h ? po.off[8 + q] : po.off[q];        // (po.off[e >= D] = po.off[0]: a valid address)
-            xv[q] = px[off];
-        }
-    }
-    // ---- stage the codebook: -2w split three ways, |w|^2 chain, its three pieces; two codes per
-    // pass with all eight 16-B loads in flight
+    bmu_half_row_load(g, po, live ? prow : g.R - 1, h, xv);
+    // ---- stage the codebook (or start the image's DMA), split the patch rows under it
     float w2max = 0.0f;
     int inexact = 0;
     const size_t image_bytes = (size_t)K * 100;               // planes + |w|^2 (a multiple of 16: K % 32 == 0)
-    if (!PREP && image_in) {
+    if (image_in) {
         bmu_image_to_lds(image_in, image_bytes, lds_raw);
         const float* hdr = reinterpret_cast<const float*>(image_in + image_bytes);
         w2max = hdr[0];
         inexact = hdr[1] != 0.0f;
     } else
         bmu_stage_codes(w, D, 0, K, frag, plane, W2, w2max, inexact);
-    float x2a = 0.0f;
-    bmu_u32x4 XH = {0u, 0u, 0u, 0u}, XM = XH, XL = XH;
-    if constexpr (!PREP) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) xv[q] = 8 * h + q < D ? xv[q] : 0.0f;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            uint32_t a, b, cc;
-            if (!bmu_split3(xv[2 * q], xv[2 * q + 1], a, b, cc)) inexact = 1;   // (the coarse value is then off; the
-            XH[q] = a; XM[q] = b; XL[q] = cc;                                   //  block re-scans every row exactly)
-            x2a += xv[2 * q] * xv[2 * q] + xv[2 * q + 1] * xv[2 * q + 1];
-        }
-#pragma unroll
-        for (int q = 0; q < 8; ++q) XS[(wave * 32 + cl) * 16 + 8 * h + q] = xv[q];
-        x2a += __shfl_xor(x2a, 32);
-    }
+    float x2a;
+    bmu_u32x4 XH, XM, XL;
+    inexact |= bmu_half_row_split(xv, D, h, XH, XM, XL, x2a);   // (the coarse values are then off: the block re-scans
+#pragma unroll                                                  //  every row exactly)
+    for (int q = 0; q < 8; ++q) XS[(wave * 32 + cl) * 16 + 8 * h + q] = xv[q];
     // the image's DMA has run under the split of the patch rows: landed before the barrier publishes it
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    // block-wide max |w|^2 and the inexact flag
-    w2max = wave_max(w2max);
-    inexact = __any(inexact);
-    if (lane == 0) { red[wave] = w2max; red[4 + wave] = inexact ? 1.0f : 0.0f; }
+    bmu_w2_put(w2max, inexact, red);
     __syncthreads();
-    w2max = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    const bool any_inexact = (red[4] + red[5] + red[6] + red[7]) != 0.0f;   // then every row is re-scanned
-    if constexpr (PREP) {
-        const uint4* src = reinterpret_cast<const uint4*>(lds_raw);
-        uint4* dst = reinterpret_cast<uint4*>(image_out);
-        for (int i = tid; i < (int)(image_bytes >> 4); i += NTHREADS) dst[i] = src[i];
-        if (tid == 0) {
-            float* hdr = reinterpret_cast<float*>(image_out + image_bytes);
-            hdr[0] = w2max;
-            hdr[1] = any_inexact ? 1.0f : 0.0f;
-        }
-        return;
-    }
+    bool any_inexact;                                           // then every row is re-scanned, from memory
+    bmu_w2_get(red, w2max, any_inexact);
 
     const long long tc1 = stats ? clock64() : 0;
     // ---- the coarse scan, software-pipelined over three accumulator sets in rotation: while tile T is scanned,
@@ -1392,19 +1472,16 @@ __global__ __launch_bounds__(NTHREADS, 2) void bmu_coarse_kernel(PatchGeom g, Pa
     // its registers): hipcc's scheduler did not keep this shape under any sched_group_barrier pipeline.
     // scan state: (min, second-smallest) of t~, the minimum carrying its register number in its low four bits
     // (3 vector instructions per candidate: v_and_or_b32, 2 x v_med3_f32), and the tile in which the minimum fell
-    float best = INFINITY, sec = INFINITY;
-    int tidx = -1;
-    if constexpr (!PREP) {
-        bmu_coarse_scan(frag, plane, W2, NT, h, cl, XH, XM, XL, best, sec, tidx);
-    }
+    float best, sec;
+    int tidx;
+    bmu_coarse_scan(frag, plane, W2, NT, h, cl, XH, XM, XL, best, sec, tidx);
     const int ridx = (int)(__float_as_uint(best) & 15u);
     const long long tc2 = stats ? clock64() : 0;
     // ---- merge the two lane halves of a row, certify
     const int idx = tidx < 0 ? INT_MAX : tidx * 32 + 4 * h + (ridx & 3) + 8 * (ridx >> 2);
     BmuState st = bmu_merge(BmuState{best, idx, sec},
                             BmuState{__shfl_xor(best, 32), __shfl_xor(idx, 32), __shfl_xor(sec, 32)});
-    const float eps = BMU_COARSE_EPS * (1.001f * x2a + 2.0f * w2max);
-    const bool certified = !any_inexact && (st.sec - st.d2 > 3.0f * eps);
+    const bool certified = !bmu_coarse_undecided(st, x2a, w2max, any_inexact);
     const int flag = live && h == 0 && !certified;
     if (live && h == 0 && certified) out[prow] = (int64_t)st.idx;
     const unsigned long long fm = __ballot(flag);
@@ -1414,61 +1491,21 @@ __global__ __launch_bounds__(NTHREADS, 2) void bmu_coarse_kernel(PatchGeom g, Pa
         const unsigned n = __popc(flagmask[0]) + __popc(flagmask[1]) + __popc(flagmask[2]) + __popc(flagmask[3]);
         if (n) atomicAdd(stats, n);
     }
-    // ---- literal re-scan of the rows without a certificate
-    const bool from_memory = any_inexact;
-    float* rs = red;                                   // [4] per-wave minima (red[0..3] no longer needed)
-    int* ri = reinterpret_cast<int*>(red + 4);
+    // ---- literal re-scan of the rows without a certificate: rows from their LDS copy, codes from the image -- or,
+    // when a split was inexact (the image is then not the codebook), from memory, four 16-B loads a code (the host
+    // checks D % 4 == 0 and the alignment).  tests/test_gpu_core.py test_bmu_coarse_pass_bit_exact[tiny] (denormal
+    // data: every split inexact, every row re-scanned) is the test of that branch.
     for (int wv = 0; wv < 4; ++wv)
     for (unsigned m = flagmask[wv]; m; m &= m - 1) {
         const int r = wv * 32 + __ffs((int)m) - 1;
-        float xs[16];
+        BmuRowRegs<16> xr;
+        xr.n = D;
 #pragma unroll
-        for (int e = 0; e < 16; ++e) xs[e] = XS[r * 16 + e];
-        float x2 = 0.0f;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) x2 = e < D ? fmaf(xs[e], xs[e], x2) : x2;
-        float bd = INFINITY;
-        int bi = INT_MAX;
-        for (int k = tid; k < K; k += NTHREADS) {
-            float m2[16];
-            if (from_memory) {
-                const float* wk = w + (int64_t)k * D;
-#pragma unroll
-                for (int e = 0; e < 16; ++e) m2[e] = e < D ? -2.0f * wk[e] : 0.0f;
-            } else {
-                const int T = k >> 5, c = k & 31;
-#pragma unroll
-                for (int hh = 0; hh < 2; ++hh) {
-                    const int at = (T * 2 + hh) * 32 + c;
-                    const bmu_u32x4 H = frag[at], M = frag[plane + at], L = frag[2 * plane + at];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        m2[8 * hh + 2 * q] = bmu_join3(H[q], M[q], L[q], 0);
-                        m2[8 * hh + 2 * q + 1] = bmu_join3(H[q], M[q], L[q], 1);
-                    }
-                }
-            }
-            float acc = 0.0f;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc = e < D ? fmaf(m2[e], xs[e], acc) : acc;
-            const float d = sqrtf(fmaxf((acc + W2[bmu_w2_at(k)]) + x2, 0.0f));
-            if (d < bd) { bd = d; bi = k; }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float s2 = __shfl_xor(bd, o);
-            const int i2 = __shfl_xor(bi, o);
-            if (s2 < bd || (s2 == bd && i2 < bi)) { bd = s2; bi = i2; }
-        }
-        __syncthreads();
-        if (lane == 0) { rs[wave] = bd; ri[wave] = bi; }
-        __syncthreads();
-        if (tid == 0) {
-#pragma unroll
-            for (int q = 1; q < 4; ++q)
-                if (rs[q] < bd || (rs[q] == bd && ri[q] < bi)) { bd = rs[q]; bi = ri[q]; }
-            out[p0 + r] = bi == INT_MAX ? 0 : (int64_t)bi;
-        }
+        for (int e = 0; e < 16; ++e) xr.x[e] = XS[r * 16 + e];
+        const BmuPick p = bmu_pick_block(any_inexact ? bmu_rescan(xr, BmuCodesMemory16{w, D}, tid, NTHREADS, K)
+                                                     : bmu_rescan(xr, BmuCodesImage{frag, plane, W2}, tid, NTHREADS, K),
+                                         red);                  // (red[0..8) no longer needed)
+        if (tid == 0) out[p0 + r] = bmu_pick_index(p);
     }
     if (stats && tid == 0) {
         const long long tc3 = clock64();
@@ -1519,18 +1556,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void bmu_coarse_chunk_kernel(PatchGeom
     const int D = g.D;
     const long long tc0 = stats ? clock64() : 0;
 
-    // ---- this lane's half patch row, split three ways (as bmu_coarse_kernel)
     const int prow = p0 + wave * 32 + cl;
     const bool live = prow < g.R;
     float xv[8];
-    {
-        const float* px = g.x + patch_row_base_fast(g, po, live ? prow : g.R - 1);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int off = h ? po.off[8 + q] : po.off[q];
-            xv[q] = px[off];
-        }
-    }
+    bmu_half_row_load(g, po, live ? prow : g.R - 1, h, xv);
     const int c_begin = blockIdx.y * per_group, c_end = min(nchunks, c_begin + per_group);
     BmuState run{INFINITY, INT_MAX, INFINITY};
     float x2a = 0.0f;
@@ -1554,32 +1583,17 @@ __global__ __launch_bounds__(NTHREADS, 2) void bmu_coarse_chunk_kernel(PatchGeom
         } else
             bmu_stage_codes(w, D, kbase, kn, frag, plane, W2, w2max, inexact);
         if (c == c_begin) {                                     // under the first chunk's loads
-#pragma unroll
-            for (int q = 0; q < 8; ++q) xv[q] = 8 * h + q < D ? xv[q] : 0.0f;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                uint32_t a, b, cc;
-                if (!bmu_split3(xv[2 * q], xv[2 * q + 1], a, b, cc)) x_inexact = 1;
-                XH[q] = a; XM[q] = b; XL[q] = cc;
-                x2a += xv[2 * q] * xv[2 * q] + xv[2 * q + 1] * xv[2 * q + 1];
-            }
-            x2a += __shfl_xor(x2a, 32);
+            x_inexact = bmu_half_row_split(xv, D, h, XH, XM, XL, x2a);
             x_inexact |= __shfl_xor(x_inexact, 32);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // the image's DMA has landed before the barrier publishes it
-        if (!image_in) {                                        // (uniform) the chunk's max |w|^2 and inexact flag
-            w2max = wave_max(w2max);
-            inexact = __any(inexact);
-            if (lane == 0) { red[wave] = w2max; red[4 + wave] = inexact ? 1.0f : 0.0f; }
-        }
+        if (!image_in) bmu_w2_put(w2max, inexact, red);         // (uniform) the chunk's max |w|^2 and inexact flag
         __syncthreads();
         if (blockIdx.x == 0 && tid == 0) {
-            if (!image_in) {
-                w2max = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-                inexact = (red[4] + red[5] + red[6] + red[7]) != 0.0f;
-            }
+            bool any_inexact = inexact;
+            if (!image_in) bmu_w2_get(red, w2max, any_inexact);
             chunk_hdr[2 * c] = w2max;
-            chunk_hdr[2 * c + 1] = inexact ? 1.0f : 0.0f;
+            chunk_hdr[2 * c + 1] = any_inexact ? 1.0f : 0.0f;
         }
         const long long tc2 = stats ? clock64() : 0;
         float best, sec;
@@ -1612,14 +1626,15 @@ __global__ __launch_bounds__(NTHREADS, 2) void bmu_coarse_chunk_kernel(PatchGeom
     }
 }
 
-// One block per chunk of the prepared image of a K > 1024 codebook (no reduction across blocks: the search's
-// finalize takes the maximum over the chunk headers).
+// The prepared image, one block per chunk: what a block of the search kernels stages into LDS, written out with the
+// chunk's header.  K <= 1024 is the one chunk of K codes.  (No reduction across blocks: the search's finalize takes
+// the maximum over the chunk headers.)
 __global__ __launch_bounds__(NTHREADS) void bmu_coarse_prepare_chunks_kernel(const float* __restrict__ w, int K, int D,
                                                                              int chunk,
                                                                              unsigned char* __restrict__ image_out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     bmu_u32x4* frag = reinterpret_cast<bmu_u32x4*>(lds_raw);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int kbase = blockIdx.x * chunk;
     const int kn = min(chunk, K - kbase);
     const int plane = (kn >> 5) * 64;
@@ -1628,27 +1643,27 @@ __global__ __launch_bounds__(NTHREADS) void bmu_coarse_prepare_chunks_kernel(con
     float w2max = 0.0f;
     int inexact = 0;
     bmu_stage_codes(w, D, kbase, kn, frag, plane, W2, w2max, inexact);
-    w2max = wave_max(w2max);
-    inexact = __any(inexact);
-    if (lane == 0) { red[wave] = w2max; red[4 + wave] = inexact ? 1.0f : 0.0f; }
+    bmu_w2_put(w2max, inexact, red);
     __syncthreads();
     unsigned char* img = image_out + (size_t)blockIdx.x * ((size_t)chunk * 100 + 16);
     const uint4* src = reinterpret_cast<const uint4*>(lds_raw);
     uint4* dst = reinterpret_cast<uint4*>(img);
     for (int i = tid; i < kn * 100 / 16; i += NTHREADS) dst[i] = src[i];
     if (tid == 0) {
+        bool any_inexact;
+        bmu_w2_get(red, w2max, any_inexact);
         float* hdr = reinterpret_cast<float*>(img + (size_t)kn * 100);
-        hdr[0] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-        hdr[1] = (red[4] + red[5] + red[6] + red[7]) != 0.0f ? 1.0f : 0.0f;
+        hdr[0] = w2max;
+        hdr[1] = any_inexact ? 1.0f : 0.0f;
         hdr[2] = hdr[3] = 0.0f;
     }
 }
 
 // Finalize of the chunked coarse pass, BMU_FIN_ROWS rows per workgroup.  Wave 0: a row per lane -- its partials
-// merged in group (= ascending code) order, max |w|^2 over all chunks, the unchanged certificate; certified rows are
-// written, the others listed.  Then every wave takes listed rows (wave v the v-th, v+4-th, ...: no barrier, no
-// cooperation inside the block) and re-scans them with the literal definition against the fp32 codebook in memory,
-// lane l codes l, l + 64, ... ascending, (d, index) reduced with the first-index rule.
+// committed in group (= ascending code) order under the unchanged certificate, with max |w|^2 over all chunks
+// (bmu_commit_row: every row's coarse index is written); the rows without a certificate are listed.  Then every wave
+// takes listed rows (wave v the v-th, v+4-th, ...: no barrier, no cooperation inside the block) and re-scans them
+// against the fp32 codebook in memory, lane l codes l, l + 64, ...
 __global__ __launch_bounds__(256) void bmu_coarse_finalize_kernel(PatchGeom g, PatchOffsets po,
                                                                   const float* __restrict__ w, int K,
                                                                   const float* __restrict__ part_d,
@@ -1662,7 +1677,6 @@ __global__ __launch_bounds__(256) void bmu_coarse_finalize_kernel(PatchGeom g, P
     __shared__ int list[BMU_FIN_ROWS];
     __shared__ int nlist;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int D = g.D;
     const long long tc0 = stats ? clock64() : 0;
     if (wave == 0) {
         float w2max = 0.0f;
@@ -1675,17 +1689,11 @@ __global__ __launch_bounds__(256) void bmu_coarse_finalize_kernel(PatchGeom g, P
         inexact = __any(inexact);
         const int row = blockIdx.x * BMU_FIN_ROWS + lane;
         int flag = 0;
-        if (row < g.R) {
-            BmuState st{part_d[row], part_i[row], part_s[row]};
-            for (int z = 1; z < ngroups; ++z) {
-                const int64_t o = (int64_t)z * g.R + row;
-                st = bmu_merge(st, BmuState{part_d[o], part_i[o], part_s[o]});
-            }
-            const float eps = BMU_COARSE_EPS * (1.001f * part_x2[row] + 2.0f * w2max);   // NaN: x's split was inexact
-            const bool certified = !inexact && (st.sec - st.d2 > 3.0f * eps);
-            if (certified) out[row] = (int64_t)st.idx;
-            flag = !certified;
-        }
+        if (row < g.R)
+            flag = bmu_commit_row(row, g.R, part_d + row, part_i + row, part_s + row, ngroups, g.R, part_x2[row],
+                                  [&](const BmuState& st, float x2a) {
+                                      return bmu_coarse_undecided(st, x2a, w2max, inexact);
+                                  }, BmuPartials{}, out);
         const unsigned long long m = __ballot(flag);
         if (flag) list[__popcll(m & ((1ull << lane) - 1ull))] = row;
         if (lane == 0) {
@@ -1697,42 +1705,9 @@ __global__ __launch_bounds__(256) void bmu_coarse_finalize_kernel(PatchGeom g, P
     const int n = nlist;
     for (int i = wave; i < n; i += 4) {
         const int row = list[i];
-        const float* px = g.x + patch_row_base(g, row);
-        float xs[16];
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const float v = px[po.off[e]];                      // (po.off[e >= D] = po.off[0]: a valid address)
-            xs[e] = e < D ? v : 0.0f;
-        }
-        float x2 = 0.0f;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) x2 = e < D ? fmaf(xs[e], xs[e], x2) : x2;
-        float bd = INFINITY;
-        int bi = INT_MAX;
-#pragma unroll 2
-        for (int k = lane; k < K; k += 64) {
-            const float4* wk4 = reinterpret_cast<const float4*>(w + (int64_t)k * D);   // host: D % 4 == 0, 16-B aligned
-            float v[16];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float4 t = 4 * q < D ? wk4[q] : make_float4(0.f, 0.f, 0.f, 0.f);
-                v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
-            }
-            float w2 = 0.0f, acc = 0.0f;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) w2 = e < D ? fmaf(v[e], v[e], w2) : w2;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc = e < D ? fmaf(-2.0f * v[e], xs[e], acc) : acc;
-            const float d = sqrtf(fmaxf((acc + w2) + x2, 0.0f));
-            if (d < bd) { bd = d; bi = k; }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float s2 = __shfl_xor(bd, o);
-            const int i2 = __shfl_xor(bi, o);
-            if (s2 < bd || (s2 == bd && i2 < bi)) { bd = s2; bi = i2; }
-        }
-        if (lane == 0) out[row] = bi == INT_MAX ? 0 : (int64_t)bi;
+        const BmuPick p = bmu_pick_wave(bmu_rescan(bmu_row_fetch<16>(g, po, row, g.D), BmuCodesMemory16{w, g.D},
+                                                   lane, 64, K));
+        if (lane == 0) out[row] = bmu_pick_index(p);
     }
     if (stats && tid == 0) {
         atomicAdd(stats + 5, (unsigned)(clock64() - tc0));
@@ -1763,17 +1738,42 @@ extern "C" size_t qarig_bmu_workspace_bytes(int64_t rows, int K) {
     return need > chunked ? need : chunked;
 }
 
-static bool bmu_coarse_ok(const PatchGeom& g, int K, const float* codebook) {
-    return g.D <= 16 && g.D % 4 == 0 && K % 32 == 0 && K >= 32 && K <= 1024 && g.R > 25 &&
+// The partial states of `nsplit` splits of R rows at the head of the workspace: d, idx, sec [nsplit][R], then x2 [R]
+// (the chunked coarse pass keeps its chunk headers behind x2).
+static BmuPartials bmu_partials(void* workspace, size_t nsplit, int R) {
+    BmuPartials p;
+    p.d = (float*)workspace;
+    p.idx = (int*)(p.d + nsplit * R);
+    p.sec = (float*)(p.idx + nsplit * R);
+    p.x2 = p.sec + nsplit * R;
+    return p;
+}
+
+// What every search entry point checks (`who` prefixes the messages), and the patch geometry it launches with.
+static int bmu_geom(const char* who, const float* x, int N, int C, int H, int W, int pH, int pW, const float* codebook,
+                    int K, int D, const int64_t* out_idx, const void* prepared, PatchGeom& g) {
+    QARIG_CHECK_ARG(x && codebook && out_idx, "%s: null pointer", who);
+    QARIG_CHECK_ARG(!prepared || (((uintptr_t)prepared) & 15) == 0, "%s: prepared image must be 16-B aligned", who);
+    QARIG_CHECK_ARG(N > 0 && C > 0 && H > 0 && W > 0 && pH > 0 && pW > 0 && K > 0, "%s: bad extents", who);
+    QARIG_CHECK_ARG(pH <= H && pW <= W, "%s: patch larger than the latent", who);
+    QARIG_CHECK_ARG(qarig_dims_ok({N, C, H, W}) && qarig_dims_ok({K, C, pH, pW}),
+                    "%s: extents must be positive, at most 2^24 each, product at most 2^40", who);
+    QARIG_CHECK_ARG(D == C * pH * pW, "%s: codebook width %d != C*pH*pW = %d", who, D, C * pH * pW);
+    g = PatchGeom{x, N, C, H, W, pH, pW, H / pH, W / pW, D, 0};
+    const int64_t rows = (int64_t)N * g.gh * g.gw;
+    QARIG_CHECK_ARG(rows < INT_MAX, "%s: too many patch rows", who);
+    g.R = (int)rows;
+    return QARIG_OK;
+}
+
+// The coarse pass takes this search: kmax = 1024 for the single image, BMU_K_MAX with the chunked form.
+static bool bmu_coarse_ok(const PatchGeom& g, int K, const float* codebook, int kmax) {
+    return g.D <= 16 && g.D % 4 == 0 && K % 32 == 0 && K >= 32 && K <= kmax && g.R > 25 &&
            (((uintptr_t)codebook) & 15) == 0;
 }
 
-static bool bmu_coarse_chunked_ok(const PatchGeom& g, int K, const float* codebook) {
-    return g.D <= 16 && g.D % 4 == 0 && K % 32 == 0 && K > 1024 && K <= BMU_K_MAX && g.R > 25 &&
-           (((uintptr_t)codebook) & 15) == 0;
-}
-
-static void bmu_patch_offsets(const PatchGeom& g, PatchOffsets& po) {
+static PatchOffsets bmu_patch_offsets(const PatchGeom& g) {
+    PatchOffsets po;
     for (int e = 0; e < 16; ++e) {
         const int ee = e < g.D ? e : 0;
         const int j = ee % g.pW, i = (ee / g.pW) % g.pH, c = ee / (g.pW * g.pH);
@@ -1787,26 +1787,24 @@ static void bmu_patch_offsets(const PatchGeom& g, PatchOffsets& po) {
     };
     magic(g.gh * g.gw, po.m_per, po.sh_per);
     magic(g.gw, po.m_gw, po.sh_gw);
+    return po;
 }
 
-static size_t bmu_coarse_lds(int K) { return (size_t)K * 96 + (size_t)K * 4 + 128 * 16 * 4 + 16 * 4; }
-static void bmu_coarse_attr(size_t shm) {
-    static size_t attr_shm = 0;
-    if (shm > attr_shm) {
-        (void)hipFuncSetAttribute((const void*)bmu_coarse_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        (void)hipFuncSetAttribute((const void*)bmu_coarse_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        attr_shm = shm;
+// More than 64 KB of dynamic LDS needs the opt-in, raised to the largest size a kernel has been launched with.
+static void bmu_lds_attr(const void* kernel, size_t shm, size_t& raised) {
+    if (shm > raised) {
+        (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+        raised = shm;
     }
 }
 
 static int bmu_coarse_launch(const PatchGeom& g, const float* codebook, int K, int64_t* out_idx,
                              unsigned* stats, const void* image, hipStream_t st) {
-    PatchOffsets po;
-    bmu_patch_offsets(g, po);
-    const size_t shm = bmu_coarse_lds(K);
-    bmu_coarse_attr(shm);
-    hipLaunchKernelGGL(bmu_coarse_kernel<false>, dim3((g.R + 127) / 128), dim3(NTHREADS), shm, st, g, po, codebook, K,
-                       out_idx, stats, (const unsigned char*)image, (unsigned char*)nullptr);
+    static size_t raised = 0;
+    const size_t shm = (size_t)K * 96 + (size_t)K * 4 + 128 * 16 * 4 + 16 * 4;
+    bmu_lds_attr((const void*)bmu_coarse_kernel, shm, raised);
+    hipLaunchKernelGGL(bmu_coarse_kernel, dim3((g.R + 127) / 128), dim3(NTHREADS), shm, st, g, bmu_patch_offsets(g),
+                       codebook, K, out_idx, stats, (const unsigned char*)image);
     QARIG_CHECK_LAUNCH("bmu coarse");
     return QARIG_OK;
 }
@@ -1828,29 +1826,25 @@ static BmuChunkPlan bmu_chunk_plan(int R, int K, bool image) {
 
 static int bmu_coarse_chunked_launch(const PatchGeom& g, const float* codebook, int K, int64_t* out_idx,
                                      unsigned* stats, const void* image, void* workspace, hipStream_t st) {
-    PatchOffsets po;
-    bmu_patch_offsets(g, po);
+    const PatchOffsets po = bmu_patch_offsets(g);
     const BmuChunkPlan pl = bmu_chunk_plan(g.R, K, image != nullptr);
-    float* part_d = (float*)workspace;
-    int* part_i = (int*)(part_d + (size_t)pl.ngroups * g.R);
-    float* part_s = (float*)(part_i + (size_t)pl.ngroups * g.R);
-    float* part_x2 = part_s + (size_t)pl.ngroups * g.R;
-    float* chunk_hdr = part_x2 + g.R;
+    const BmuPartials part = bmu_partials(workspace, pl.ngroups, g.R);
+    float* chunk_hdr = part.x2 + g.R;
     const size_t shm = (size_t)pl.chunk * 100 + BMU_CHUNK_PAD;
     hipLaunchKernelGGL(bmu_coarse_chunk_kernel, dim3((g.R + 127) / 128, pl.ngroups), dim3(NTHREADS), shm, st, g, po,
-                       codebook, K, pl.chunk, pl.nchunks, pl.per_group, (const unsigned char*)image, part_d, part_i,
-                       part_s, part_x2, chunk_hdr, stats);
+                       codebook, K, pl.chunk, pl.nchunks, pl.per_group, (const unsigned char*)image, part.d, part.idx,
+                       part.sec, part.x2, chunk_hdr, stats);
     QARIG_CHECK_LAUNCH("bmu coarse chunks");
     hipLaunchKernelGGL(bmu_coarse_finalize_kernel, dim3((g.R + BMU_FIN_ROWS - 1) / BMU_FIN_ROWS), dim3(256), 0, st, g,
-                       po, codebook, K, part_d, part_i, part_s, part_x2, chunk_hdr, pl.ngroups, pl.nchunks, out_idx,
+                       po, codebook, K, part.d, part.idx, part.sec, part.x2, chunk_hdr, pl.ngroups, pl.nchunks, out_idx,
                        stats);
     QARIG_CHECK_LAUNCH("bmu coarse finalize");
     return QARIG_OK;
 }
 
 // Image of a codebook for qarig_bmu_fwd_coarse / _coarse_ws / _prepared (their `prepared` argument): bytes, and the
-// kernel that writes it (one block; one block per chunk for K > 1024).  0 bytes = the coarse form does not take this
-// codebook.  K <= 1024: K x 100 B + 16; beyond: that layout per BMU_CHUNK_MAX-code chunk, chunk after chunk.
+// launch that writes it, one block per chunk.  0 bytes = the coarse form does not take this codebook.  Per chunk
+// (K <= 1024: the one chunk of K codes; beyond: BMU_CHUNK_MAX codes each, chunk after chunk): codes x 100 B + 16.
 extern "C" size_t qarig_bmu_prepare_bytes(int K, int D) {
     if (D < 1 || D > 16 || D % 4 || K < 32 || K > BMU_K_MAX || K % 32) return 0;
     if (K <= 1024) return (size_t)K * 100 + 16;
@@ -1860,19 +1854,12 @@ extern "C" int qarig_bmu_prepare(const float* codebook, int K, int D, void* imag
     QARIG_CHECK_ARG(codebook && image, "bmu_prepare: null pointer");
     QARIG_CHECK_ARG(qarig_bmu_prepare_bytes(K, D) != 0 && (((uintptr_t)codebook | (uintptr_t)image) & 15) == 0,
                     "bmu_prepare: needs D <= 16, D %% 4 == 0, K %% 32 == 0, 32 <= K <= 16384, 16-B aligned pointers");
-    if (K > 1024) {
-        hipLaunchKernelGGL(bmu_coarse_prepare_chunks_kernel, dim3((K + BMU_CHUNK_MAX - 1) / BMU_CHUNK_MAX),
-                           dim3(NTHREADS), (size_t)BMU_CHUNK_MAX * 100 + 64, (hipStream_t)stream, codebook, K, D,
-                           BMU_CHUNK_MAX, (unsigned char*)image);
-        QARIG_CHECK_LAUNCH("bmu prepare chunks");
-        return QARIG_OK;
-    }
-    PatchGeom g{nullptr, 1, 1, 1, 1, 1, 1, 1, 1, D, 1};
-    PatchOffsets po{};
-    const size_t shm = bmu_coarse_lds(K);
-    bmu_coarse_attr(shm);
-    hipLaunchKernelGGL(bmu_coarse_kernel<true>, dim3(1), dim3(NTHREADS), shm, (hipStream_t)stream, g, po, codebook, K,
-                       (int64_t*)nullptr, (unsigned*)nullptr, (const unsigned char*)nullptr, (unsigned char*)image);
+    static size_t raised = 0;
+    const int chunk = K <= 1024 ? K : BMU_CHUNK_MAX;
+    const size_t shm = (size_t)chunk * 100 + 64;
+    bmu_lds_attr((const void*)bmu_coarse_prepare_chunks_kernel, shm, raised);
+    hipLaunchKernelGGL(bmu_coarse_prepare_chunks_kernel, dim3((K + chunk - 1) / chunk), dim3(NTHREADS), shm,
+                       (hipStream_t)stream, codebook, K, D, chunk, (unsigned char*)image);
     QARIG_CHECK_LAUNCH("bmu prepare");
     return QARIG_OK;
 }
@@ -1883,22 +1870,13 @@ extern "C" int qarig_bmu_prepare(const float* codebook, int K, int D, void* imag
 static int bmu_coarse_entry(const float* x, int N, int C, int H, int W, int pH, int pW, const float* codebook, int K,
                             int D, int64_t* out_idx, unsigned* uncertified, const void* prepared, bool chunked,
                             void* workspace, size_t ws_bytes, void* stream) {
-    QARIG_CHECK_ARG(x && codebook && out_idx, "bmu_coarse: null pointer");
-    QARIG_CHECK_ARG(N > 0 && C > 0 && H > 0 && W > 0 && pH > 0 && pW > 0 && K > 0 && pH <= H && pW <= W,
-                    "bmu_coarse: bad extents");
-    QARIG_CHECK_DIMS("bmu_coarse", N, C, H, W);
-    QARIG_CHECK_DIMS("bmu_coarse", K, C, pH, pW);
-    QARIG_CHECK_ARG(D == C * pH * pW, "bmu_coarse: codebook width %d != C*pH*pW = %d", D, C * pH * pW);
-    PatchGeom g{x, N, C, H, W, pH, pW, H / pH, W / pW, D, 0};
-    const int64_t rows = (int64_t)N * g.gh * g.gw;
-    QARIG_CHECK_ARG(rows < INT_MAX, "bmu_coarse: too many patch rows");
-    g.R = (int)rows;
-    QARIG_CHECK_ARG(bmu_coarse_ok(g, K, codebook) || (chunked && bmu_coarse_chunked_ok(g, K, codebook)),
+    PatchGeom g;
+    if (const int e = bmu_geom("bmu_coarse", x, N, C, H, W, pH, pW, codebook, K, D, out_idx, prepared, g)) return e;
+    QARIG_CHECK_ARG(bmu_coarse_ok(g, K, codebook, chunked ? BMU_K_MAX : 1024),
                     "bmu_coarse: needs D <= 16, D %% 4 == 0, K %% 32 == 0, 32 <= K <= %d, more than 25 rows",
                     chunked ? BMU_K_MAX : 1024);
-    QARIG_CHECK_ARG(!prepared || (((uintptr_t)prepared) & 15) == 0, "bmu_coarse: prepared image must be 16-B aligned");
     if (K <= 1024) return bmu_coarse_launch(g, codebook, K, out_idx, uncertified, prepared, (hipStream_t)stream);
-    const size_t need = qarig_bmu_coarse_workspace_bytes(rows, K);
+    const size_t need = qarig_bmu_coarse_workspace_bytes(g.R, K);
     if (!workspace || ws_bytes < need) {
         qarig_set_error("bmu_coarse: workspace too small (%zu < %zu)", workspace ? ws_bytes : (size_t)0, need);
         return QARIG_ERR_WORKSPACE;
@@ -1921,32 +1899,13 @@ extern "C" int qarig_bmu_fwd_coarse_ws(const float* x, int N, int C, int H, int 
                             ws_bytes, stream);
 }
 
-extern "C" int qarig_bmu_fwd_prepared(const float* x, int N, int C, int H, int W, int pH, int pW,
-                                      const float* codebook, int K, int D, int64_t* out_idx,
-                                      void* workspace, size_t ws_bytes, const void* prepared, void* stream);
-extern "C" int qarig_bmu_fwd(const float* x, int N, int C, int H, int W, int pH, int pW,
-                             const float* codebook, int K, int D, int64_t* out_idx,
-                             void* workspace, size_t ws_bytes, void* stream) {
-    return qarig_bmu_fwd_prepared(x, N, C, H, W, pH, pW, codebook, K, D, out_idx, workspace, ws_bytes, nullptr, stream);
-}
-
-// qarig_bmu_fwd with the codebook's prepared image (qarig_bmu_prepare; NULL = none): where the dispatch takes the
-// coarse-pass kernel its workgroups copy the image into LDS instead of converting the codebook themselves.
+// The dispatcher, with the codebook's prepared image (qarig_bmu_prepare; NULL = none): where it takes a coarse-pass
+// kernel the workgroups copy the image into LDS instead of converting the codebook themselves.
 extern "C" int qarig_bmu_fwd_prepared(const float* x, int N, int C, int H, int W, int pH, int pW,
                                       const float* codebook, int K, int D, int64_t* out_idx,
                                       void* workspace, size_t ws_bytes, const void* prepared, void* stream) {
-    QARIG_CHECK_ARG(x && codebook && out_idx, "bmu: null pointer");
-    QARIG_CHECK_ARG(!prepared || (((uintptr_t)prepared) & 15) == 0, "bmu: prepared image must be 16-B aligned");
-    QARIG_CHECK_ARG(N > 0 && C > 0 && H > 0 && W > 0 && pH > 0 && pW > 0 && K > 0,
-                    "bmu: bad extents");
-    QARIG_CHECK_ARG(pH <= H && pW <= W, "bmu: patch larger than the latent");
-    QARIG_CHECK_DIMS("bmu", N, C, H, W);
-    QARIG_CHECK_DIMS("bmu", K, C, pH, pW);
-    QARIG_CHECK_ARG(D == C * pH * pW, "bmu: codebook width %d != C*pH*pW = %d", D, C * pH * pW);
-    PatchGeom g{x, N, C, H, W, pH, pW, H / pH, W / pW, D, 0};
-    const int64_t rows = (int64_t)N * g.gh * g.gw;
-    QARIG_CHECK_ARG(rows < INT_MAX, "bmu: too many patch rows");
-    g.R = (int)rows;
+    PatchGeom g;
+    if (const int e = bmu_geom("bmu", x, N, C, H, W, pH, pW, codebook, K, D, out_idx, prepared, g)) return e;
     hipStream_t st = (hipStream_t)stream;
 
     if (g.R <= 25 && K <= 25) {
@@ -1955,9 +1914,9 @@ extern "C" int qarig_bmu_fwd_prepared(const float* x, int N, int C, int H, int W
         QARIG_CHECK_LAUNCH("bmu direct");
         return QARIG_OK;
     }
-    if (!workspace || ws_bytes < qarig_bmu_workspace_bytes(rows, K)) {
+    if (!workspace || ws_bytes < qarig_bmu_workspace_bytes(g.R, K)) {
         qarig_set_error("bmu: workspace too small (%zu < %zu)", ws_bytes,
-                        qarig_bmu_workspace_bytes(rows, K));
+                        qarig_bmu_workspace_bytes(g.R, K));
         return QARIG_ERR_WORKSPACE;
     }
     if (g.R <= FEWROWS_MAX && D >= FEWROWS_MIN_D) {
@@ -1979,28 +1938,17 @@ extern "C" int qarig_bmu_fwd_prepared(const float* x, int N, int C, int H, int W
         QARIG_CHECK_LAUNCH("bmu fewrows argmin");
         return QARIG_OK;
     }
-    float* part_d = (float*)workspace;
-    int* part_i = (int*)(part_d + (size_t)bmu_code_tiles(K) * g.R);
-    float* part_s = (float*)(part_i + (size_t)bmu_code_tiles(K) * g.R);
-    float* part_x2 = part_s + (size_t)bmu_code_tiles(K) * g.R;
-
-    const int ptiles = (g.R + BN - 1) / BN;
-    const int ctiles = bmu_code_tiles(K);
-    int nsplit = (512 + ptiles - 1) / ptiles;
-    if (nsplit > ctiles) nsplit = ctiles;
-    if (nsplit < 1) nsplit = 1;
-    const int per = (ctiles + nsplit - 1) / nsplit;
-    nsplit = (ctiles + per - 1) / per;
-    int64_t* direct = nsplit == 1 ? out_idx : (int64_t*)nullptr;
     // coarse bf16 pass + certificate + exact re-scan where it beats the exact kernels although every
-    // workgroup stages the codebook itself (callers with a frozen codebook pass a prepared image to
-    // qarig_bmu_fwd_coarse instead: qarig.ops.bmu)
+    // workgroup stages the codebook itself (callers with a frozen codebook pass a prepared image: qarig.ops.bmu)
     const int coarse_env = g_qarig_opt.bmu_coarse;
-    if (bmu_coarse_ok(g, K, codebook) && coarse_env != 0 && (coarse_env == 1 || g.R >= 24576))
+    if (bmu_coarse_ok(g, K, codebook, 1024) && coarse_env != 0 && (coarse_env == 1 || g.R >= 24576))
         return bmu_coarse_launch(g, codebook, K, out_idx, nullptr, prepared, st);
     // K > 1024: the chunked form, where the option forces it (auto: see BMU_CHUNKED_AUTO_ROWS)
-    if (bmu_coarse_chunked_ok(g, K, codebook) && coarse_env != 0 && (coarse_env == 1 || g.R >= BMU_CHUNKED_AUTO_ROWS))
+    if (K > 1024 && bmu_coarse_ok(g, K, codebook, BMU_K_MAX) && coarse_env != 0 &&
+        (coarse_env == 1 || g.R >= BMU_CHUNKED_AUTO_ROWS))
         return bmu_coarse_chunked_launch(g, codebook, K, out_idx, nullptr, prepared, workspace, st);
+
+    const BmuPartials part = bmu_partials(workspace, bmu_code_tiles(K), g.R);
     if (D <= 16) {
         const int ks = D <= 4 ? 2 : (D <= 8 ? 4 : 8);
         const int bpc = (2 * ks + 1) * 4;                         // LDS bytes per code
@@ -2013,20 +1961,7 @@ extern "C" int qarig_bmu_fwd_prepared(const float* x, int N, int C, int H, int W
         const int unit = 64 * cs;                                 // two 32-code tiles per wave
         const int chunk = ((K + nchunks - 1) / nchunks + unit - 1) / unit * unit;
         const size_t shm = (size_t)chunk * bpc + (size_t)(3 * 128 + 128 + 128 + 512) * sizeof(float);
-        PatchOffsets po;
-        for (int e = 0; e < 16; ++e) {
-            const int ee = e < D ? e : 0;
-            const int j = ee % pW, i = (ee / pW) % pH, c = ee / (pW * pH);
-            po.off[e] = (c * H + i) * W + j;
-        }
-        auto magic = [](int d, unsigned& m, int& sh) {
-            int L = 0;
-            while ((1LL << L) < d) ++L;
-            sh = 31 + L;
-            m = (unsigned)((1ULL << sh) / (unsigned long long)d + 1ULL);
-        };
-        magic(g.gh * g.gw, po.m_per, po.sh_per);
-        magic(g.gw, po.m_gw, po.sh_gw);
+        const PatchOffsets po = bmu_patch_offsets(g);
         int64_t* direct_r = nchunks == 1 ? out_idx : (int64_t*)nullptr;
         dim3 grid((g.R + 128 / cs - 1) / (128 / cs), nchunks), block(NTHREADS);
         // group scan where a wave walks at least 4 tile pairs (its one-off re-evaluation of the winning
@@ -2039,10 +1974,10 @@ extern "C" int qarig_bmu_fwd_prepared(const float* x, int N, int C, int H, int W
         do {                                                                                       \
             if (groups)                                                                            \
                 hipLaunchKernelGGL((bmu_resident_kernel<KS_, CS_, true, 2>), grid, block, shm, st, g, po,     \
-                                   codebook, K, chunk, part_d, part_i, part_s, part_x2, direct_r); \
+                                   codebook, K, chunk, part.d, part.idx, part.sec, part.x2, direct_r); \
             else                                                                                   \
                 hipLaunchKernelGGL((bmu_resident_kernel<KS_, CS_, false, 2>), grid, block, shm, st, g, po,    \
-                                   codebook, K, chunk, part_d, part_i, part_s, part_x2, direct_r); \
+                                   codebook, K, chunk, part.d, part.idx, part.sec, part.x2, direct_r); \
         } while (0)
 #define QARIG_BMU_RES_CS(KS_)                                                                      \
         do {                                                                                       \
@@ -2058,38 +1993,45 @@ extern "C" int qarig_bmu_fwd_prepared(const float* x, int N, int C, int H, int W
         QARIG_CHECK_LAUNCH("bmu resident");
         if (nchunks > 1) {
             hipLaunchKernelGGL(bmu_finalize_kernel, dim3((g.R + 127) / 128), dim3(256), 0, st, g, codebook,
-                               K, part_d, part_i, part_s, part_x2, nchunks, out_idx);
+                               K, part.d, part.idx, part.sec, part.x2, nchunks, out_idx);
             QARIG_CHECK_LAUNCH("bmu finalize");
         }
         return QARIG_OK;
     }
-    if (D <= 64) {
-        const int nkt = D <= 32 ? 2 : 4;
-        const size_t shm = (size_t)3 * nkt * TILE_FLOATS * sizeof(float);
-        dim3 grid(ptiles, nsplit), block(NTHREADS);
-#define QARIG_BMU_SMALL(NKT_, KS_)                                                              \
-        hipLaunchKernelGGL((bmu_small_kernel<NKT_, KS_>), grid, block, shm, st, g, codebook, K, per, \
-                           part_d, part_i, part_s, part_x2, direct)
-        if (D <= 32) QARIG_BMU_SMALL(2, 8);      // (D <= 16 never gets here: the resident / coarse kernels take it)
-        else {
-            static bool attr_set = false;   // > 64 KB of dynamic LDS needs the opt-in once
-            if (!attr_set) {
-                (void)hipFuncSetAttribute((const void*)bmu_small_kernel<4, 8>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-                attr_set = true;
-            }
-            QARIG_BMU_SMALL(4, 8);
-        }
-#undef QARIG_BMU_SMALL
+    // MFMA-tile kernels: the code tiles split over grid.y until the grid has 512 workgroups
+    const int ptiles = (g.R + BN - 1) / BN;
+    const int ctiles = bmu_code_tiles(K);
+    int nsplit = (512 + ptiles - 1) / ptiles;
+    if (nsplit > ctiles) nsplit = ctiles;
+    if (nsplit < 1) nsplit = 1;
+    const int per = (ctiles + nsplit - 1) / nsplit;
+    nsplit = (ctiles + per - 1) / per;
+    int64_t* direct = nsplit == 1 ? out_idx : (int64_t*)nullptr;
+    const dim3 grid(ptiles, nsplit), block(NTHREADS);
+    if (D <= 32) {      // (D <= 16 never gets here: the resident / coarse kernels take it)
+        hipLaunchKernelGGL(bmu_small_kernel<2>, grid, block, (size_t)3 * 2 * TILE_FLOATS * sizeof(float), st, g,
+                           codebook, K, per, part.d, part.idx, part.sec, part.x2, direct);
+    } else if (D <= 64) {
+        static size_t raised = 0;
+        const size_t shm = (size_t)3 * 4 * TILE_FLOATS * sizeof(float);
+        bmu_lds_attr((const void*)bmu_small_kernel<4>, shm, raised);
+        hipLaunchKernelGGL(bmu_small_kernel<4>, grid, block, shm, st, g, codebook, K, per, part.d, part.idx, part.sec,
+                           part.x2, direct);
     } else {
-        hipLaunchKernelGGL(bmu_mma_kernel, dim3(ptiles, nsplit), dim3(NTHREADS), 0, st, g, codebook, K,
-                           per, part_d, part_i, part_s, part_x2, direct);
+        hipLaunchKernelGGL(bmu_mma_kernel, grid, block, 0, st, g, codebook, K, per, part.d, part.idx, part.sec, part.x2,
+                           direct);
     }
     QARIG_CHECK_LAUNCH("bmu mma");
     if (nsplit > 1) {
         hipLaunchKernelGGL(bmu_finalize_kernel, dim3((g.R + 127) / 128), dim3(256), 0, st, g, codebook,
-                           K, part_d, part_i, part_s, part_x2, nsplit, out_idx);
+                           K, part.d, part.idx, part.sec, part.x2, nsplit, out_idx);
         QARIG_CHECK_LAUNCH("bmu finalize");
     }
     return QARIG_OK;
+}
+
+extern "C" int qarig_bmu_fwd(const float* x, int N, int C, int H, int W, int pH, int pW,
+                             const float* codebook, int K, int D, int64_t* out_idx,
+                             void* workspace, size_t ws_bytes, void* stream) {
+    return qarig_bmu_fwd_prepared(x, N, C, H, W, pH, pW, codebook, K, D, out_idx, workspace, ws_bytes, nullptr, stream);
 }
