@@ -336,6 +336,25 @@ int qarig_decode_sample(const float* logits, int64_t ldl, int B, int V, float te
                         int inc_len, int beams, int64_t* ids, int64_t* chunk, float* comb,
                         float* probs_log, void* stream);
 
+/* qarig_decode_sample with the row filtered before the draw (a kernel of its own: a workgroup per row, the
+ * row staged once in LDS, the cuts found by a bitwise threshold search instead of a sort).  probs is computed
+ * as above; filtering only zeroes entries:
+ *   top_k (0: off): the top_k largest non-zero entries stay; equal entries at the cut stay in index order
+ *     (lower index first); top_k >= the number of non-zero entries changes nothing;
+ *   top_p (in (0, 1], 1: off), on what top_k left: with q = probs / sum(probs) in descending order (equal
+ *     entries: lower index first), an entry stays iff the q-mass strictly in front of it is < top_p; the
+ *     largest entry always stays.
+ * Kept entries keep their values -- no renormalisation: the draw scales its target by the row's total, and
+ * comb takes the probability it would take without a filter.  forced tokens are taken whether or not they
+ * were kept (comb then takes the filtered value, possibly 0); probs_log receives the filtered row.  Every
+ * sum runs in a fixed order: the same input gives the same bits.  top_k < 0, top_p outside (0, 1] or NaN,
+ * and V > 32768 (the row must fit LDS) are refused with status -1. */
+int qarig_decode_sample_filtered(const float* logits, int64_t ldl, int B, int V, float temperature,
+                                 int end_token, int generate_mode, int64_t shift, const float* uniforms,
+                                 const int64_t* forced, int* ctl, int slot, int beam_width, int max_draws,
+                                 int inc_len, int beams, int64_t* ids, int64_t* chunk, float* comb,
+                                 float* probs_log, int top_k, float top_p, void* stream);
+
 /* After a candidate chunk: per image the beam with the largest product (first on ties) replaces the
  * kept chunk unless the kept product is >= (generate_images.py:325-337); take[n] = 1 + that beam or
  * 0; comb is reset to 1, ctl: candidate + 1, draws + `draws` (the draw rows the candidate set consumed),

@@ -675,6 +675,249 @@ __global__ __launch_bounds__(64) void decode_sample_kernel(
     }
 }
 
+// ---- decode_sample_kernel's draw from a top-k / nucleus (top-p) filtered row -----------------------------------
+// A workgroup of four waves per row.  The row is staged ONCE in LDS (logits / T coalesced in, then exp, then the
+// probabilities -- one expf and one division per entry); thread t owns the contiguous entries [t per, (t + 1) per)
+// with per odd, so the 64 lanes of a wave read 64 different banks.  Every workgroup-wide sum has one shape: the
+// thread's entries in index order, a fixed butterfly over the wave (wave_sum_multi), the four wave totals in wave
+// order -- at most 129 + 6 + 4 roundings at V = 32,768 (65 + 6 + 4 at 16,385): 8e-6 of the total at worst, run-to-
+// run bit-reproducible.  Two slots per hand-over buffer, used alternately: one barrier per sum.
+constexpr int SF_THREADS = 256;
+constexpr int SF_MAX_V = 32768;       // 128 KB of the 160 KB of LDS; a larger V is refused by the entry point
+
+template <int NV>
+__device__ __forceinline__ void sf_block_sum(float (&v)[NV], float (*red)[4][4], int& phase, int lane, int w) {
+    bool own;
+    const int idx = wave_sum_multi<NV>(v, lane, own);
+    float (*r)[4] = red[phase & 1];
+    ++phase;
+    if (own) r[w][idx] = v[0];
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NV; ++j) v[j] = ((r[0][j] + r[1][j]) + r[2][j]) + r[3][j];
+}
+
+// Number of x over the threads in front of this one (thread order = index order of the entries they own).
+__device__ __forceinline__ int sf_block_rank(int x, int (*ired)[4][2], int& phase, int lane, int w) {
+    int inc = x;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int y = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += y;
+    }
+    int (*r)[2] = ired[phase & 1];
+    ++phase;
+    if (lane == 63) r[w][0] = inc;
+    __syncthreads();
+    int off = 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        if (k < w) off += r[k][0];
+    return off + inc - x;
+}
+
+// The largest T with f(T) >= want, f(T) = the number (MASS: the sum) of the entries whose bits are >= T.  The
+// entries are non-negative floats, so the order of their uint32 images is their order, and at most 1: bits 29..0
+// decide.  Two bits per round -- three candidates counted in one pass over the row, fifteen rounds, no sort.
+// f does not increase with T, in fp32 too: a candidate's sum runs over a subset of the next lower one's
+// non-negative terms in the same order.
+template <bool MASS>
+__device__ __forceinline__ uint32_t sf_threshold(const float* row, int i0, int i1, float want, float (*red)[4][4],
+                                                 int& phase, int lane, int w) {
+    uint32_t T = 0;
+    for (int sh = 28; sh >= 0; sh -= 2) {
+        const uint32_t c1 = T | (1u << sh), c2 = T | (2u << sh), c3 = T | (3u << sh);
+        float a[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll 4
+        for (int i = i0; i < i1; ++i) {
+            const float x = row[i];
+            const uint32_t u = __float_as_uint(x);
+            const float y = MASS ? x : 1.0f;
+            a[0] += u >= c1 ? y : 0.0f;
+            a[1] += u >= c2 ? y : 0.0f;
+            a[2] += u >= c3 ? y : 0.0f;
+        }
+        sf_block_sum<4>(a, red, phase, lane, w);
+        T = a[2] >= want ? c3 : (a[1] >= want ? c2 : (a[0] >= want ? c1 : T));
+    }
+    return T;
+}
+
+// qarig_decode_sample_filtered (include/qarig.h).  probs as decode_sample_kernel computes them; then only zeroing:
+//   top_k > 0: the top_k largest non-zero entries stay (the k-th largest value T by sf_threshold on counts; the
+//              entries equal to T stay in index order until top_k are kept); fewer non-zero entries: nothing to do;
+//   top_p < 1: of what is left, in descending order (equal entries: lower index first) an entry stays iff the mass
+//              strictly in front of it is < top_p * (mass left) -- T by sf_threshold on sums: the largest T with
+//              sum(entries >= T) >= top_p * total, so sum(entries > T) < top_p * total and the first entry equal to
+//              T always stays; the r-th one stays iff sum(entries > T) + r T is still below.
+// Kept entries keep their values (no renormalisation: the draw scales its target by the row's total).  From there
+// on decode_sample_kernel's statements on the filtered row: the inverse-CDF draw, the last non-zero entry when
+// rounding leaves the target at or past the total, forced tokens (taken whether or not they were kept -- comb then
+// takes the filtered value, possibly 0), the product, the train-mode <end> -> 0, the counters, the draw numbers.
+__global__ __launch_bounds__(SF_THREADS) void decode_sample_filtered_kernel(
+    const float* __restrict__ logits, int64_t ldl, int B, int V, float temperature, int end_token,
+    int generate_mode, int64_t shift, const float* __restrict__ uniforms, const int64_t* __restrict__ forced,
+    int* __restrict__ ctl, int slot, int bw, int max_draws, int inc_len, int beams, int64_t* __restrict__ ids,
+    int64_t* __restrict__ chunk, float* __restrict__ comb, float* __restrict__ probs_log, int top_k, float top_p) {
+    extern __shared__ float sf_row[];           // V floats
+    __shared__ float red[2][4][4];
+    __shared__ int ired[2][4][2];
+    __shared__ float part[SF_THREADS];
+    __shared__ float wtot[4];
+    float* row = sf_row;
+    const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
+    int phase = 0;
+    if (slot < 0) slot = min(max(ctl[CTL_TOK], 0), bw - 1);
+    const int dcol = beams > 0 ? b / beams : b, dcols = beams > 0 ? B / beams : B;
+    const int d = min(max(ctl[CTL_DRAW] + (beams > 0 ? (b - dcol * beams) * bw : 0) + slot, 0), max_draws - 1);
+    const float* z = logits + (int64_t)b * ldl;
+    float mx = -INFINITY;
+    for (int i = t; i < V; i += SF_THREADS) {
+        const float x = z[i] / temperature;
+        row[i] = x;
+        mx = fmaxf(mx, x);
+    }
+    mx = wave_max_dpp(mx);
+    {
+        float (*r)[4] = red[phase & 1];
+        ++phase;
+        if (lane == 0) r[w][0] = mx;
+        __syncthreads();                        // the staged row is whole, too
+        mx = fmaxf(fmaxf(r[0][0], r[1][0]), fmaxf(r[2][0], r[3][0]));
+    }
+    const int per = ((V + SF_THREADS - 1) / SF_THREADS) | 1;
+    const int i0 = min(V, t * per), i1 = min(V, i0 + per);
+    float s[1] = {0.0f};
+#pragma unroll 4
+    for (int i = i0; i < i1; ++i) {
+        const float e = expf(row[i] - mx);
+        row[i] = e;
+        s[0] += e;
+    }
+    sf_block_sum<1>(s, red, phase, lane, w);
+    const float S = s[0];
+    float nz[1] = {0.0f};
+#pragma unroll 4
+    for (int i = i0; i < i1; ++i) {
+        float pr = row[i] / S;
+        if (generate_mode && i == end_token) pr = 0.0f;
+        row[i] = pr;
+        nz[0] += pr > 0.0f ? 1.0f : 0.0f;
+    }
+    if (top_k > 0) {
+        sf_block_sum<1>(nz, red, phase, lane, w);         // counts are whole numbers below 2^24: exact
+        if ((float)top_k < nz[0]) {
+            const uint32_t T = sf_threshold<false>(row, i0, i1, (float)top_k, red, phase, lane, w);
+            float gt[1] = {0.0f};
+            int eq = 0;
+#pragma unroll 4
+            for (int i = i0; i < i1; ++i) {
+                const uint32_t u = __float_as_uint(row[i]);
+                gt[0] += u > T ? 1.0f : 0.0f;
+                eq += u == T ? 1 : 0;
+            }
+            sf_block_sum<1>(gt, red, phase, lane, w);
+            const int ties = top_k - (int)gt[0];
+            int rank = sf_block_rank(eq, ired, phase, lane, w);
+            for (int i = i0; i < i1; ++i) {
+                const uint32_t u = __float_as_uint(row[i]);
+                if (u < T) row[i] = 0.0f;
+                else if (u == T) {
+                    if (rank >= ties) row[i] = 0.0f;
+                    ++rank;
+                }
+            }
+        }
+    }
+    if (top_p < 1.0f) {
+        float m[1] = {0.0f};
+#pragma unroll 4
+        for (int i = i0; i < i1; ++i) m[0] += row[i];
+        sf_block_sum<1>(m, red, phase, lane, w);
+        const float want = top_p * m[0];
+        const uint32_t T = sf_threshold<true>(row, i0, i1, want, red, phase, lane, w);
+        const float tv = __uint_as_float(T);
+        float gt[1] = {0.0f};
+        int eq = 0;
+#pragma unroll 4
+        for (int i = i0; i < i1; ++i) {
+            const float x = row[i];
+            const uint32_t u = __float_as_uint(x);
+            gt[0] += u > T ? x : 0.0f;
+            eq += u == T ? 1 : 0;
+        }
+        sf_block_sum<1>(gt, red, phase, lane, w);
+        int rank = sf_block_rank(eq, ired, phase, lane, w);
+        for (int i = i0; i < i1; ++i) {
+            const uint32_t u = __float_as_uint(row[i]);
+            if (u < T) row[i] = 0.0f;
+            else if (u == T) {
+                if (rank > 0 && !(fmaf((float)rank, tv, gt[0]) < want)) row[i] = 0.0f;
+                ++rank;
+            }
+        }
+    }
+    // ---- the draw, on the filtered row
+    float ps = 0.0f;
+    int last_nz = -1;
+#pragma unroll 4
+    for (int i = i0; i < i1; ++i) {
+        const float pr = row[i];
+        ps += pr;
+        if (pr > 0.0f) last_nz = i;
+    }
+    part[t] = ps;
+    __syncthreads();                            // the filtered row is whole
+    if (probs_log) {
+        float* lg = probs_log + ((int64_t)d * dcols + dcol) * V;
+        for (int i = t; i < V; i += SF_THREADS) lg[i] = row[i];
+    }
+    float base = 0.0f, wsum = 0.0f;
+    for (int k = 0; k < 64; ++k) {
+        if (k == lane) base = wsum;
+        wsum += part[64 * w + k];
+    }
+    if (lane == 0) wtot[w] = wsum;
+    __syncthreads();
+    float off = 0.0f, total = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (k == w) off = total;
+        total += wtot[k];
+    }
+    const float target = uniforms[(int64_t)d * dcols + dcol] * total;
+    int cand = 0x7fffffff;
+    float run = off + base;
+#pragma unroll 4
+    for (int i = i0; i < i1; ++i) {
+        const float pr = row[i];
+        run += pr;
+        if (pr > 0.0f && run > target && cand == 0x7fffffff) cand = i;
+    }
+    cand = wave_min_int(cand);
+    int fallback = wave_max_int(last_nz);         // rounding left the target at or past the total
+    {
+        int (*r)[2] = ired[phase & 1];
+        ++phase;
+        if (lane == 0) { r[w][0] = cand; r[w][1] = fallback; }
+        __syncthreads();
+        cand = min(min(r[0][0], r[1][0]), min(r[2][0], r[3][0]));
+        fallback = max(max(r[0][1], r[1][1]), max(r[2][1], r[3][1]));
+    }
+    if (t == 0) {
+        int64_t nxt = cand == 0x7fffffff ? max(fallback, 0) : cand;
+        if (forced) {
+            const int64_t f = forced[(int64_t)d * dcols + dcol];
+            if (f >= 0 && f < V) nxt = f;
+        }
+        comb[b] *= row[nxt];
+        if (!generate_mode && nxt == end_token) nxt = 0;      // reference HACK: <end> -> index 0
+        ids[b] = nxt + shift;
+        chunk[(int64_t)b * bw + slot] = nxt + shift;
+        if (b == 0 && inc_len) ctl[CTL_LEN] += 1;             // no other workgroup of this launch reads it
+    }
+}
+
 // After a candidate chunk (all rows have drawn beam_width tokens): per image, the beam with the largest
 // probability product (first one on ties: torch.argmax) competes with the best chunk kept so far --
 // generate_images.py:325-337 keeps the earlier candidate unless the new product is larger -- and the
@@ -1039,6 +1282,38 @@ extern "C" int qarig_decode_sample(const float* logits, int64_t ldl, int B, int 
                        temperature, end_token, generate_mode, shift, uniforms, forced, ctl, slot, beam_width,
                        max_draws, inc_len, beams, ids, chunk, comb, probs_log);
     QARIG_CHECK_LAUNCH("decode_sample");
+    return QARIG_OK;
+}
+
+extern "C" int qarig_decode_sample_filtered(const float* logits, int64_t ldl, int B, int V, float temperature,
+                                            int end_token, int generate_mode, int64_t shift, const float* uniforms,
+                                            const int64_t* forced, int* ctl, int slot, int beam_width, int max_draws,
+                                            int inc_len, int beams, int64_t* ids, int64_t* chunk, float* comb,
+                                            float* probs_log, int top_k, float top_p, void* stream) {
+    QARIG_CHECK_ARG(logits && uniforms && ctl && ids && chunk && comb, "decode_sample_filtered: null pointer");
+    QARIG_CHECK_ARG(B > 0 && V > 0 && beam_width > 0 && max_draws > 0 && slot >= -1 && slot < beam_width,
+                    "decode_sample_filtered: bad extents");
+    QARIG_CHECK_DIMS("decode_sample_filtered", B, V);
+    QARIG_CHECK_DIMS("decode_sample_filtered", max_draws, B);
+    QARIG_CHECK_DIMS("decode_sample_filtered", B, beam_width);
+    QARIG_CHECK_ARG(ldl >= V && temperature > 0.0f, "decode_sample_filtered: ldl < V or temperature <= 0");
+    QARIG_CHECK_ARG(beams >= 0 && (beams == 0 || B % beams == 0), "decode_sample_filtered: beams must divide the rows");
+    QARIG_CHECK_ARG(!probs_log || qarig_dims_ok({max_draws, B, V}), "decode_sample_filtered: probability log too large");
+    QARIG_CHECK_ARG(top_k >= 0, "decode_sample_filtered: top_k must be >= 0 (0: off), got %d", top_k);
+    QARIG_CHECK_ARG(top_p > 0.0f && top_p <= 1.0f, "decode_sample_filtered: top_p must be in (0, 1] (1: off), got %g",
+                    (double)top_p);
+    QARIG_CHECK_ARG(V <= SF_MAX_V, "decode_sample_filtered: the row is staged in LDS, V = %d exceeds %d", V, SF_MAX_V);
+    const size_t lds = (size_t)V * sizeof(float);
+    static bool allowed = false;
+    if (!allowed && lds > 48 * 1024) {          // beyond the default dynamic allowance: V up to 16,385 needs 64 KB + 4 B
+        (void)hipFuncSetAttribute((const void*)decode_sample_filtered_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  SF_MAX_V * (int)sizeof(float));
+        allowed = true;
+    }
+    hipLaunchKernelGGL(decode_sample_filtered_kernel, dim3(B), dim3(SF_THREADS), lds, (hipStream_t)stream, logits, ldl,
+                       B, V, temperature, end_token, generate_mode, shift, uniforms, forced, ctl, slot, beam_width,
+                       max_draws, inc_len, beams, ids, chunk, comb, probs_log, top_k, top_p);
+    QARIG_CHECK_LAUNCH("decode_sample_filtered");
     return QARIG_OK;
 }
 

@@ -26,7 +26,10 @@ def parse_args():
     p.add_argument("--decoder-path", required=True, type=pathlib.Path,
                    help="File path to pre-trained decoder model.")
     p.add_argument("--num-images", type=int, default=25, help="Num of images to generate.")
-    p.add_argument("--seed", type=int, default=None, help="Seed value.")
+    p.add_argument("--seed", type=int, default=None,
+                   help="Seed value.  Reproduces a run of this program; only --sampler torch keeps the reference's "
+                        "generator stream (the default fused sampler draws the same distribution from a stream of "
+                        "its own).")
     p.add_argument("--config-path", required=True, type=pathlib.Path,
                    help="File path to load json config file.")
     p.add_argument("--out-dir", required=True, type=pathlib.Path, help="File path to output directory.")
@@ -46,6 +49,14 @@ def parse_args():
                         "graph on the GPU instead of an eager pass over the window.  Applies only to the fused "
                         "sampler, images x num_beam <= 16 and models with a cache kernel (head dim <= 64); "
                         "elsewhere it is ignored.")
+    p.add_argument("--top-k", type=int, default=None,
+                   help="(additive) sample from the top-k most probable tokens only (ties at the cut: lower index "
+                        "first); 0: off.  Overrides the config's per-stage \"top_k\" for all stages.")
+    p.add_argument("--top-p", type=float, default=None,
+                   help="(additive) nucleus sampling: of the tokens in descending probability, keep those with "
+                        "less than this share of the mass in front of them (in (0, 1]; 1: off); applied after "
+                        "--top-k.  Kept probabilities are not renormalised: best-of-num_beam still ranks chunks by "
+                        "the model's own likelihood.  Overrides the config's per-stage \"top_p\" for all stages.")
     return vars(p.parse_args())
 
 
@@ -107,6 +118,9 @@ def main():
                 lr_input = hr_input                                   # previous stage's tokens
                 hr_input = torch.full((n_local, 1), k_hr, dtype=torch.int64, device=device)
 
+            # optional per-stage keys (the reference's config files have neither: off)
+            top_k = data.get("top_k", 0) if args["top_k"] is None else args["top_k"]
+            top_p = data.get("top_p", 1.0) if args["top_p"] is None else args["top_p"]
             if n_local:
                 hr_input = sampling.generate_tokens(
                     model, hr_input, lr_input, total_Seq, data["temperature"], md["use_sliding_window"],
@@ -114,7 +128,7 @@ def main():
                     beam_width=data["beam_width"], mode="generate",
                     progress=lambda i, t: log(f"{i:,} / {t:,}"), batch_beams=args["batch_beams"],
                     use_kv_cache=not args["no_kv_cache"], sampler=args["sampler"],
-                    window_graph=args["window_graph"])
+                    window_graph=args["window_graph"], top_k=top_k, top_p=top_p)
                 hr_input = hr_input[:, 1:] - shift
             else:                                        # more ranks than images: nothing to generate here
                 hr_input = torch.zeros((0, total_Seq), dtype=torch.int64, device=device)

@@ -399,12 +399,15 @@ class DecodeCache:
     # -- device-resident chunk search ----------------------------------------------------------
     @torch.no_grad()
     def begin_search(self, first_ids, images, beams, beam_width, temperature, end_token, shift, generate_mode,
-                     max_chunks, candidates, forced=None, log_probs=False, generator=None, reference_order=False):
+                     max_chunks, candidates, forced=None, log_probs=False, generator=None, reference_order=False,
+                     top_k=0, top_p=1.0):
         """Prepares the search of generate_images.py:256-345 on `images` x `beams` cache rows (beams > 1:
         the candidate chunks of an image as rows of one batch; beams == 1: `candidates` chunks one after the
         other): evaluates the first token (window index 0), captures the step's graph, draws the uniforms of
         every draw the stage can make (ONE call of the device generator).  forced: optional (draws, columns)
         int64, entries >= 0 replace the draw (tests); log_probs: keep every probability row sampled from.
+        top_k / top_p: every draw of the search is made from the filtered row (ops.decode_sample; 0 / 1.0: off).
+        The draws are launches of their own between the replays of the step graph, so the graph does not change.
 
         reference_order (beams > 1): the candidates of a chunk are independent given the kept prefix, so they
         run as rows of one batch, but every draw keeps the number the reference's candidate-after-candidate
@@ -413,6 +416,7 @@ class DecodeCache:
         beams == 1 with `candidates` = beams, at the cost of the batched search."""
         N, NB, bw = int(images), int(beams), int(beam_width)
         B, D, dev = self.batch, self.dim, self.kv.device
+        top_k, top_p = ops.check_sample_filter(top_k, top_p)
         if N * NB != B or self.dim % 4:
             raise ValueError("begin_search: images * beams must equal the cache's batch (and the width be 4-aligned)")
         if self.model.use_pos_cond and self._table is None:
@@ -460,6 +464,7 @@ class DecodeCache:
         s.ids.copy_(first.repeat_interleave(NB))
         self.ctl.zero_()
         s.gen, s.T, s.end, s.shift = bool(generate_mode), float(temperature), int(end_token), int(shift)
+        s.top_k, s.top_p = top_k, top_p
         if s.g_step is None:
             # A capture records launches without running them, and the first launch of a kernel in a process (code
             # object load) or a workspace that has to grow cannot happen inside one: the first step of a given
@@ -486,7 +491,7 @@ class DecodeCache:
     def _draw(self, slot, src, inc):
         s = self._search
         ops.decode_sample(src, s.T, s.end, s.gen, s.shift, s.uniforms, self.ctl, slot, s.bw, s.ids, s.chunk, s.comb,
-                          forced=s.forced, probs_log=s.probs, inc_len=inc, beams=s.beams)
+                          forced=s.forced, probs_log=s.probs, inc_len=inc, beams=s.beams, top_k=s.top_k, top_p=s.top_p)
 
     @torch.no_grad()
     def run_chunk(self, last=False):

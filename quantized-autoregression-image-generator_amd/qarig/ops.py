@@ -1146,10 +1146,27 @@ def decode_embed(ids, table, pe, ctl=None, length=0, proj_table=None, proj_row=N
     return x
 
 
+def check_sample_filter(top_k, top_p):
+    """(top_k, top_p) as (int, float), or ValueError: top_k an integer >= 0 (0: off), top_p in (0, 1] (1: off)."""
+    import operator
+    try:
+        k = operator.index(top_k)
+    except TypeError:
+        raise ValueError(f"top_k must be an integer >= 0 (0: off), got {top_k!r}") from None
+    p = float(top_p)
+    if k < 0:
+        raise ValueError(f"top_k must be an integer >= 0 (0: off), got {top_k!r}")
+    if not (0.0 < p <= 1.0):        # NaN fails both comparisons
+        raise ValueError(f"top_p must be in (0, 1] (1: off), got {top_p!r}")
+    return min(k, 2 ** 31 - 1), p
+
+
 def decode_sample(logits, temperature, end_token, generate_mode, shift, uniforms, ctl, slot, beam_width, ids,
-                  chunk, comb, forced=None, probs_log=None, inc_len=False, beams=0):
+                  chunk, comb, forced=None, probs_log=None, inc_len=False, beams=0, top_k=0, top_p=1.0):
     """One draw per row of logits (B, V): see include/qarig.h qarig_decode_sample.  beams > 0: candidate-major
-    draw numbering, uniforms / forced / probs_log have B // beams columns."""
+    draw numbering, uniforms / forced / probs_log have B // beams columns.  top_k > 0 or top_p < 1: the row is
+    filtered first (qarig_decode_sample_filtered); both off: the unfiltered kernel, as without the keywords."""
+    top_k, top_p = check_sample_filter(top_k, top_p)
     require_cuda(logits, uniforms, ctl, ids, chunk, comb, forced, probs_log)
     B, V = logits.shape
     max_draws = uniforms.shape[0]
@@ -1159,6 +1176,13 @@ def decode_sample(logits, temperature, end_token, generate_mode, shift, uniforms
     assert comb.shape == (B,) and comb.dtype == torch.float32 and ctl.dtype == torch.int32
     assert forced is None or (forced.shape == (max_draws, cols) and forced.dtype == torch.int64 and forced.is_contiguous())
     assert probs_log is None or (probs_log.shape == (max_draws, cols, V) and probs_log.is_contiguous())
+    if top_k > 0 or top_p < 1.0:
+        check(_lib.load().qarig_decode_sample_filtered(
+            ptr(logits), logits.stride(0), B, V, float(temperature), int(end_token), int(bool(generate_mode)),
+            int(shift), ptr(uniforms), ptr(forced), ptr(ctl), int(slot), int(beam_width), max_draws,
+            int(bool(inc_len)), int(beams), ptr(ids), ptr(chunk), ptr(comb), ptr(probs_log), top_k, top_p, stream()),
+            "qarig_decode_sample_filtered")
+        return
     check(_lib.load().qarig_decode_sample(ptr(logits), logits.stride(0), B, V, float(temperature), int(end_token),
                                           int(bool(generate_mode)), int(shift), ptr(uniforms), ptr(forced), ptr(ctl),
                                           int(slot), int(beam_width), max_draws, int(bool(inc_len)), int(beams),

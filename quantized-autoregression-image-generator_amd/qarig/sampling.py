@@ -4,9 +4,16 @@
  - plain ancestral sampling with the <end> -> 0 hack (the periodic sample inside
    train_quantized_transformer.py:581-656)                          -> mode "train".
 The encoder half runs ONCE per stage (its input is constant across decode steps; the
-reference recomputes it on every call).  Sampling uses torch.multinomial on the device
-generator exactly like the reference on --device cuda, so a given --seed reproduces the
-reference's draw sequence as long as the logits agree.
+reference recomputes it on every call).  Two samplers: the default, "fused", draws inside
+the sampling kernel by inverse CDF from uniforms of the device generator -- the reference's
+distribution, NOT its generator stream: a given --seed does not reproduce the reference's
+tokens; sampler="torch" calls torch.multinomial on the device generator exactly like the
+reference on --device cuda, so there a given --seed reproduces the reference's draw
+sequence as long as the logits agree.
+
+top_k / top_p (off by default; the reference has neither) filter the probabilities of
+every draw, on every path by the one definition of `filter_probs`: zeroing only, kept
+entries keep their values.
 
 Reference quirks kept on purpose (drop-in behaviour):
  - "generate" numbers the appended window positions cur_len + tok + 1 (position 1 is
@@ -20,11 +27,46 @@ from . import ops
 from .kvcache import DecodeCache, WindowStep
 
 
-def _sample(logits, temperature, end_token, mode, rows, comb):
+def filter_probs(probs, top_k=0, top_p=1.0):
+    """Top-k and nucleus (top-p) filtering of probability rows (..., V), non-negative entries, on any device.
+    Only zeroes entries:
+      top_k (int, 0 = off): the top_k largest non-zero entries stay, ties at the cut going to the lower index;
+        top_k >= the number of non-zero entries changes nothing;
+      top_p (float in (0, 1], 1.0 = off), on what top_k left: with q = probs / sum(probs) in descending order
+        (ties: lower index first), an entry stays iff the q-mass strictly in front of it is < top_p; at least
+        one entry stays.
+    Kept entries keep their values -- no renormalisation: torch.multinomial and the sampling kernel's
+    inverse-CDF draw normalise by the row total themselves, and the probability product of a chunk keeps the
+    model's own likelihood.  Both off: returns `probs` itself."""
+    top_k, top_p = ops.check_sample_filter(top_k, top_p)
+    if top_k == 0 and top_p == 1.0:
+        return probs
+    V = probs.shape[-1]
+    out = probs
+    if 0 < top_k < V:
+        # a stable sort keeps equal entries in index order
+        srt, idx = torch.sort(out, dim=-1, descending=True, stable=True)
+        keep = (torch.arange(V, device=probs.device) < top_k) & (srt > 0)
+        keep = torch.zeros_like(keep).scatter_(-1, idx, keep)
+        out = torch.where(keep, out, torch.zeros_like(out))
+    if top_p < 1.0:
+        srt, idx = torch.sort(out, dim=-1, descending=True, stable=True)
+        q = srt / srt.sum(dim=-1, keepdim=True)
+        before = torch.cumsum(q, dim=-1) - q
+        keep = (before < top_p) & (srt > 0)
+        keep[..., 0] = srt[..., 0] > 0
+        keep = torch.zeros_like(keep).scatter_(-1, idx, keep)
+        out = torch.where(keep, out, torch.zeros_like(out))
+    return out
+
+
+def _sample(logits, temperature, end_token, mode, rows, comb, top_k=0, top_p=1.0):
     """One sampling draw as the reference makes it; returns (next ids (B,1), comb)."""
     probs = torch.softmax(logits / temperature, dim=1)
     if mode == "generate":
         probs[:, end_token] = 0.0              # <end> removed from consideration
+    if top_k > 0 or top_p < 1.0:
+        probs = filter_probs(probs, top_k, top_p)
     nxt = torch.multinomial(probs, 1)
     comb = comb * probs[rows, nxt.squeeze(1)]
     if mode == "train":
@@ -190,7 +232,8 @@ def _window_tail(model, cache, hr_input, enc, sliding_window, beam_width, progre
                 else:
                     logits = step.evaluate()
                 ops.decode_sample(logits, s.T, s.end, s.gen, s.shift, s.uniforms, ctl, tok, bw, s.ids, s.chunk,
-                                  s.comb, forced=s.forced, probs_log=s.probs, inc_len=False, beams=s.beams)
+                                  s.comb, forced=s.forced, probs_log=s.probs, inc_len=False, beams=s.beams,
+                                  top_k=s.top_k, top_p=s.top_p)
                 step.append(s.ids)
             ops.decode_decide(ctl, N, NB, bw, s.comb, s.chunk, s.best_p, s.best_chunk, s.take, draws=s.per_set)
         ops.decode_advance(ctl, bw)
@@ -204,11 +247,12 @@ def _window_tail(model, cache, hr_input, enc, sliding_window, beam_width, progre
 
 def _generate_fused(model, hr_input, enc, total_seq, temperature, use_sliding_window,
                     sliding_window, end_token, shift, num_beam, beam_width, mode, progress,
-                    stop_len, pos_off, batch_beams):
+                    stop_len, pos_off, batch_beams, top_k=0, top_p=1.0):
     """The cached search with sampling, candidate bookkeeping and the decoder steps replayed from
     captured graphs (kvcache.DecodeCache.begin_search); nothing is read back before the stage ends.
     Returns (hr_input, pos, cache), or None when the model does not fit the fused kernels; the cache (rows of
-    the kept tokens but the last) serves the evaluations of the next chunk that come before the window slides."""
+    the kept tokens but the last) serves the evaluations of the next chunk that come before the window slides.
+    top_k / top_p go to the search state (begin_search): _fused_tail and _window_tail draw with them too."""
     device = hr_input.device
     N = hr_input.shape[0]
     # The candidate chunks of a position are independent given the kept prefix: they run as rows of one batch
@@ -238,7 +282,7 @@ def _generate_fused(model, hr_input, enc, total_seq, temperature, use_sliding_wi
     tail_chunks = max(0, -(-(stop_len - after) // beam_width))          # chunks _fused_tail draws for
     cache.begin_search(hr_input[:, 0], N, B, beam_width, temperature, end_token, shift, mode == "generate",
                        chunks + tail_chunks, 1 if B > 1 else num_beam, forced=dbg.get("forced"),
-                       log_probs=bool(dbg.get("log")), reference_order=ordered)
+                       log_probs=bool(dbg.get("log")), reference_order=ordered, top_k=top_k, top_p=top_p)
     tm.mark("capture")
     for c in range(chunks):
         cache.run_chunk(last=c == chunks - 1)
@@ -301,7 +345,8 @@ def _fused_tail(model, cache, hr_input, pos, enc, use_sliding_window, sliding_wi
                         logits = model.decode(win.contiguous(), enc_eval, wpos.long(), pos_bound=pos_bound)
                     logits = logits[:, -2 if pad else -1, :]
                 ops.decode_sample(logits, s.T, s.end, s.gen, s.shift, s.uniforms, ctl, tok, bw, s.ids, s.chunk,
-                                  s.comb, forced=s.forced, probs_log=s.probs, inc_len=False, beams=s.beams)
+                                  s.comb, forced=s.forced, probs_log=s.probs, inc_len=False, beams=s.beams,
+                                  top_k=s.top_k, top_p=s.top_p)
                 t_in = torch.cat((t_in, s.ids[:, None]), dim=1)
                 if use_sliding_window:
                     t_pos = torch.cat((t_pos, torch.full((B, 1), float(cur + tok + pos_off), device=device)), dim=1)
@@ -319,7 +364,7 @@ def _fused_tail(model, cache, hr_input, pos, enc, use_sliding_window, sliding_wi
 
 def _generate_cached(model, hr_input, enc, total_seq, temperature, use_sliding_window,
                      sliding_window, end_token, shift, num_beam, beam_width, mode, progress,
-                     stop_len, pos_off, batch_beams):
+                     stop_len, pos_off, batch_beams, top_k=0, top_p=1.0):
     """The same search as the loops below, evaluating one token per model call from a
     `DecodeCache` for as long as no evaluation of the next chunk would slide the window.
     Sampling draws are made in the reference's order (same shapes, same generator), so the
@@ -351,7 +396,7 @@ def _generate_cached(model, hr_input, enc, total_seq, temperature, use_sliding_w
             comb = torch.ones(N * B, device=device)
             logits, new = last, []
             for tok in range(beam_width):
-                nxt, comb = _sample(logits, temperature, end_token, mode, rows, comb)
+                nxt, comb = _sample(logits, temperature, end_token, mode, rows, comb, top_k, top_p)
                 new.append(nxt + shift)
                 if tok < beam_width - 1:
                     logits = cache.step(new[-1].squeeze(1), positions(cur + tok + pos_off),
@@ -393,7 +438,8 @@ def _generate_cached(model, hr_input, enc, total_seq, temperature, use_sliding_w
 @torch.no_grad()
 def generate_tokens(model, hr_input, lr_input, total_seq, temperature, use_sliding_window,
                     sliding_window, end_token, shift=0, num_beam=1, beam_width=1, mode="generate",
-                    progress=None, batch_beams=False, use_kv_cache=True, sampler=None, window_graph=False):
+                    progress=None, batch_beams=False, use_kv_cache=True, sampler=None, window_graph=False,
+                    top_k=0, top_p=1.0):
     """hr_input: (N, S0) int64 conditioning/start tokens.  Returns the extended (N, S) tensor
     (first tokens included; callers strip them and undo `shift`).  use_kv_cache: evaluate one
     token per step from a key/value cache until the window starts to slide (same logits up
@@ -401,8 +447,13 @@ def generate_tokens(model, hr_input, lr_input, total_seq, temperature, use_slidi
     sampler: "fused" / "torch" for the cached loop (DEFAULT_SAMPLER).
     window_graph (opt-in): with the fused sampler, up to DECODE_ROWS rows (images x candidates) and a model the
     window kernels take, every evaluation after the window slides is a replay of one captured graph
-    (kvcache.WindowStep) instead of an eager model.decode of the window; other cases ignore it."""
+    (kvcache.WindowStep) instead of an eager model.decode of the window; other cases ignore it.
+    top_k / top_p: every draw is made from filter_probs(probs, top_k, top_p) -- inside the sampling kernel with
+    the fused sampler, in front of torch.multinomial elsewhere; 0 / 1.0 (default): off, the code of a call
+    without them."""
     assert mode in ("generate", "train")
+    top_k, top_p = ops.check_sample_filter(top_k, top_p)
+    filtered = top_k > 0 or top_p < 1.0
     device = hr_input.device
     N = hr_input.shape[0]
     fused = (sampler or os.environ.get("QARIG_SAMPLER", DEFAULT_SAMPLER)) == "fused"
@@ -422,7 +473,7 @@ def generate_tokens(model, hr_input, lr_input, total_seq, temperature, use_slidi
             outs.append(generate_tokens(model, hr_input[sub], None if lr_input is None else lr_input[sub], total_seq,
                                         temperature, use_sliding_window, sliding_window, end_token, shift, num_beam,
                                         beam_width, mode, sub_progress, batch_beams, use_kv_cache, sampler,
-                                        window_graph=window_graph))
+                                        window_graph=window_graph, top_k=top_k, top_p=top_p))
         return torch.cat(outs, dim=0)
     enc = model.encode(lr_input) if model.use_encoder else None
     pos = torch.zeros((N, 1), device=device) if use_sliding_window else None
@@ -433,7 +484,7 @@ def generate_tokens(model, hr_input, lr_input, total_seq, temperature, use_slidi
     cache = None
     if use_kv_cache and _cacheable(model, hr_input, use_sliding_window):
         args = (model, hr_input, enc, total_seq, temperature, use_sliding_window, sliding_window, end_token,
-                shift, num_beam, beam_width, mode, progress, stop_len, pos_off, batch_beams)
+                shift, num_beam, beam_width, mode, progress, stop_len, pos_off, batch_beams, top_k, top_p)
         done = None
         if fused:
             done = _generate_fused(*args)
@@ -474,7 +525,7 @@ def generate_tokens(model, hr_input, lr_input, total_seq, temperature, use_slidi
         enc_eval = enc.repeat_interleave(num_beam, dim=0) if enc is not None else None
         out = _generate_batched(model, hr_input, last_logits, total_seq, temperature, use_sliding_window,
                                 sliding_window, end_token, shift, num_beam, beam_width, mode,
-                                progress, stop_len, pos_off, pos)
+                                progress, stop_len, pos_off, pos, top_k, top_p)
         tail.mark("windowed tail (batched beams)")
         tail.report()
         return out
@@ -492,6 +543,8 @@ def generate_tokens(model, hr_input, lr_input, total_seq, temperature, use_slidi
                 probs = torch.softmax(logits / temperature, dim=1)
                 if mode == "generate":
                     probs[:, end_token] = 0.0          # <end> removed from consideration
+                if filtered:
+                    probs = filter_probs(probs, top_k, top_p)
                 nxt = torch.multinomial(probs, 1)
                 comb = comb * probs[rows, nxt.squeeze(1)]
                 if mode == "train":
@@ -519,7 +572,7 @@ def generate_tokens(model, hr_input, lr_input, total_seq, temperature, use_slidi
 
 def _generate_batched(model, hr_input, last_logits, total_seq, temperature, use_sliding_window,
                       sliding_window, end_token, shift, num_beam, beam_width, mode, progress,
-                      stop_len, pos_off, pos):
+                      stop_len, pos_off, pos, top_k=0, top_p=1.0):
     """Same search, with the `num_beam` independent candidate chunks evaluated as ONE batch
     of N*num_beam sequences per model call (the reference runs them one after the other).
     Additive option: 1/num_beam of the model calls; the device generator is consumed in a
@@ -542,6 +595,8 @@ def _generate_batched(model, hr_input, last_logits, total_seq, temperature, use_
             probs = torch.softmax(logits / temperature, dim=1)
             if mode == "generate":
                 probs[:, end_token] = 0.0
+            if top_k > 0 or top_p < 1.0:
+                probs = filter_probs(probs, top_k, top_p)
             nxt = torch.multinomial(probs, 1)
             comb = comb * probs[rows, nxt.squeeze(1)]
             if mode == "train":

@@ -46,13 +46,16 @@ def run_cascade(args, dev, K, N, patches, prev, models=None):
                                         shift=K if base else 0, num_beam=args.num_beam,
                                         beam_width=args.beam_width, mode="generate",
                                         batch_beams=args.batch_beams,
-                                        use_kv_cache=not args.no_kv_cache, sampler=args.sampler)
+                                        use_kv_cache=not args.no_kv_cache, sampler=args.sampler,
+                                        top_k=getattr(args, "top_k", 0),          # (callers with a namespace of their own:
+                                        top_p=getattr(args, "top_p", 1.0))        # filters off)
         t_host = time.perf_counter() - t0           # until the call returned: everything enqueued, nothing awaited
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         prev = toks[:, 1:] - (K if base else 0)
         acc = N * total
-        stages.append({"stage": s, "seq": total, "seconds": round(dt, 3), "host_enqueue_seconds": round(t_host, 3),
+        stages.append({"stage": s, "seq": total, "seconds": round(dt, 3), "seconds_us": round(dt * 1e6),
+                       "host_enqueue_seconds": round(t_host, 3),
                        "accepted_tokens_per_s": round(acc / dt, 1),
                        "model_eval_tokens_per_s": round(acc * args.num_beam / dt, 1)})
         del model
@@ -72,6 +75,11 @@ def main():
     ap.add_argument("--no-kv-cache", action="store_true")
     ap.add_argument("--sampler", choices=["fused", "torch"], default=None,
                     help="cached loop: in-graph sampling kernel (default) or one torch.multinomial per token")
+    ap.add_argument("--top-k", type=int, default=0, help="top-k filter of every draw (0: off)")
+    ap.add_argument("--top-p", type=float, default=1.0, help="nucleus (top-p) filter of every draw (1: off)")
+    ap.add_argument("--filter-ab", type=int, default=0, metavar="ROUNDS",
+                    help="A/B in one process: ROUNDS times the cascade with both filters off, then with --top-k / "
+                         "--top-p, alternating; reports accepted tokens/s of every round and the medians")
     ap.add_argument("--rebuild-models", action="store_true",
                     help="new random stage models for every cascade (no decode cache is ever reused: the cost of a "
                          "generator's first call) instead of one set kept for the run")
@@ -94,12 +102,29 @@ def main():
     out = {"config": f"cascade generate, {args.stages} stages, N={N}, num_beam={args.num_beam}, "
                      f"beam_width={args.beam_width}, window 256, fp32, batch_beams={args.batch_beams}, "
                      f"candidates={'one by one' if args.one_by_one else 'rows of one batch'}, "
-                     f"kv_cache={not args.no_kv_cache}, sampler={args.sampler or sampling.DEFAULT_SAMPLER}, warm={not args.cold}"}
+                     f"kv_cache={not args.no_kv_cache}, sampler={args.sampler or sampling.DEFAULT_SAMPLER}, warm={not args.cold}, "
+                     f"top_k={args.top_k}, top_p={args.top_p}"}
     prev0 = torch.randint(0, K, (N, 1), device=dev)
     models = None if args.rebuild_models else [build_stage_model(s_, K, dev) for s_ in range(args.stages)]
     out["config"] += f", models={'rebuilt per cascade' if models is None else 'kept'}"
     if not args.cold:
         run_cascade(args, dev, K, N, patches, prev0, models)
+    if args.filter_ab > 0:
+        import copy
+        import statistics
+        off = copy.copy(args)
+        off.top_k, off.top_p = 0, 1.0
+        if not args.cold:
+            run_cascade(off, dev, K, N, patches, prev0, models)
+        rates = {"off": [], "filtered": []}
+        for _ in range(args.filter_ab):
+            for name, a in (("off", off), ("filtered", args)):
+                _, st = run_cascade(a, dev, K, N, patches, prev0, models)
+                rates[name].append(round(sum(N * x["seq"] for x in st) / sum(x["seconds_us"] * 1e-6 for x in st), 1))
+        out["filter_ab"] = {"accepted_tokens_per_s": rates,
+                            "median": {k: statistics.median(v) for k, v in rates.items()}}
+        out["filter_ab"]["filtered_over_off"] = round(out["filter_ab"]["median"]["filtered"] /
+                                                      out["filter_ab"]["median"]["off"], 4)
     prev, out["stages"] = run_cascade(args, dev, K, N, patches, prev0, models)
     tot_tokens = sum(N * st["seq"] for st in out["stages"])
     tot_time = sum(st["seconds"] for st in out["stages"])

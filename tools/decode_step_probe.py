@@ -3,7 +3,10 @@
 ms per captured-graph replay (the device chain alone), per DecodeCache.step (with the host feeds) and
 C-ABI launches per step: "table" = the per-position table of the cond projections + fused norms (what
 generation runs), "fused" = per-token cond path + fused norms, "separate" = every norm its own launch.
-    python tools/decode_step_probe.py [--rows 4] [--steps 200]"""
+    python tools/decode_step_probe.py [--rows 4] [--steps 200]
+With --top-k / --top-p also the sampling draw of a step in isolation: microseconds per launch of the draw
+kernel, unfiltered against filtered, in alternating blocks of back-to-back launches (--draw-vocab: V;
+--draw-only skips the step measurements)."""
 import argparse
 import json
 import os
@@ -18,13 +21,59 @@ from bench_generate import build_stage_model  # noqa: E402
 from qarig import kvcache, _lib  # noqa: E402
 
 
+def probe_draw(rows, V, top_k, top_p, dev, launches=400, rounds=7):
+    """us per launch of ops.decode_sample on (rows, V) logits: both filters off against (top_k, top_p), `rounds`
+    alternating blocks of `launches` back-to-back launches each, timed with device events."""
+    import statistics
+    from qarig import ops
+    g = torch.Generator().manual_seed(V)
+    logits = (torch.randn((rows, V), generator=g) * 3).to(dev)
+    uniforms = torch.rand((launches, rows), generator=g).to(dev)
+    ctl = torch.zeros(ops.DECODE_CTL_WORDS, dtype=torch.int32, device=dev)
+    ids = torch.zeros(rows, dtype=torch.int64, device=dev)
+    chunk = torch.zeros((rows, 1), dtype=torch.int64, device=dev)
+    comb = torch.ones(rows, device=dev)
+
+    def block(k, p):
+        comb.fill_(1.0)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(launches):
+            ops.decode_sample(logits, 1.0, V - 1, True, 0, uniforms, ctl, 0, 1, ids, chunk, comb, top_k=k, top_p=p)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / launches * 1e3
+
+    block(0, 1.0), block(top_k, top_p)              # code-object loads
+    t = {"off": [], "filtered": []}
+    for _ in range(rounds):
+        t["off"].append(round(block(0, 1.0), 3))
+        t["filtered"].append(round(block(top_k, top_p), 3))
+    med = {k: statistics.median(v) for k, v in t.items()}
+    return {"rows": rows, "V": V, "top_k": top_k, "top_p": top_p, "launches_per_block": launches,
+            "us_per_launch": t, "median_us": med, "min_us": {k: min(v) for k, v in t.items()},
+            "filtered_over_off": round(med["filtered"] / med["off"], 3)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=4)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--base", action="store_true", help="decoder-only base stage")
     ap.add_argument("--opt", action="append", default=[], help="name=value kernel-selection option (qarig_set_option)")
+    ap.add_argument("--top-k", type=int, default=0, help="draw probe: top-k filter (0: off)")
+    ap.add_argument("--top-p", type=float, default=1.0, help="draw probe: nucleus filter (1: off)")
+    ap.add_argument("--draw-vocab", type=int, action="append", default=[], help="draw probe: V (default 513); repeatable")
+    ap.add_argument("--draw-only", action="store_true", help="only the draw probe")
     args = ap.parse_args()
+    if args.draw_only or args.top_k > 0 or args.top_p < 1.0:
+        dev = torch.device("cuda", 0)
+        draws = [probe_draw(args.rows, V, args.top_k, args.top_p, dev) for V in (args.draw_vocab or [513])]
+        if args.draw_only:
+            print(json.dumps({"draw": draws}))
+            return
+    else:
+        draws = None
     for o in args.opt:
         k, v = o.split("=")
         _lib.load().qarig_set_option(k.encode(), int(v))
@@ -63,6 +112,8 @@ def main():
             out[name] = {"qarig_launches_per_step": launches, "step_ms": round(step_ms, 4),
                          "graph_replay_ms": round(replay_ms, 4)}
         kvcache.FUSE_NORMS = True
+    if draws is not None:
+        out["draw"] = draws
     print(json.dumps(out))
 
 
