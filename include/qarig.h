@@ -581,7 +581,11 @@ size_t qarig_conv2d_fwd_workspace_bytes(int Cin, int Cout, int k);
 /* ... plus, at few images (generate_images.py:366 decodes the 1-8 images just sampled), room for the
  * partial sums of a launch whose reduction is split 2-8 ways because its tiles alone would leave CUs
  * idle (<= 256 workgroups): given this much scratch the call splits, given only the size above it
- * does not.  The split changes the summation order (parts added in order after the k-loop). */
+ * does not.  The split changes the summation order (parts added in order after the k-loop).
+ * This and the three other *_workspace_bytes_n functions below answer from the plan that drives the launch
+ * itself (csrc/conv.hip conv_ring_plan), with padding 1 and aligned pointers assumed: slabs are counted exactly
+ * for the geometries whose launch takes the ring kernel and splits, and a geometry the launch keeps off the ring
+ * (grid rows not a multiple of 4 wide, an input of 2 GB or more, option conv_ring = 0, ...) gets the size above. */
 size_t qarig_conv2d_fwd_workspace_bytes_n(int N, int Cin, int H, int W, int Cout, int k, int stride);
 /* flags: QARIG_CONV_PACKED_VALID = the head of `workspace` still holds the re-ordered weights an earlier
  * call with the same w, geometry and workspace wrote there (inference: the weights do not change between
@@ -602,7 +606,8 @@ int qarig_conv_transpose2d_fwd(const float* x, int N, int Cin, int H, int W, con
 
 /* autograd of the conv layers (dT = dy * act'(preact), via qarig_act_bwd, first) */
 size_t qarig_conv2d_bwd_data_workspace_bytes(int Cin, int Cout, int k);
-/* ... plus room for the split slabs of a few-image launch (3x3 / stride 1; see qarig_conv2d_fwd_workspace_bytes_n) */
+/* ... plus room for the split slabs of a few-image launch (3x3 / stride 1; the stride-2 input gradient is never
+ * split; see qarig_conv2d_fwd_workspace_bytes_n) */
 size_t qarig_conv2d_bwd_data_workspace_bytes_n(int N, int Cin, int H, int W, int Cout, int k, int stride);
 int qarig_conv2d_bwd_data(const float* dT, int N, int Cout, int Ho, int Wo, const float* w, int Cin,
                           int k, int stride, int pad, int H, int W, float* dx, void* workspace,

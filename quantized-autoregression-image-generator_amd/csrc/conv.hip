@@ -155,6 +155,68 @@ struct SrcIm2colRow {
     }
 };
 
+// NCHW store epilogue of a 128 x 128 (channels x logical pixels) accumulator tile: an accumulator register row is one
+// output channel and its 32 lanes are 32 consecutive logical pixels, at physical position (oy * os + py, ox * os + px);
+// bias, saved pre-activation and activation are applied here.  GUARD: the tile may hang over Cout or P (the gather
+// kernels; the ring kernel's tiles are whole).
+template <bool GUARD>
+__device__ __forceinline__ void conv_store_tile(const Acc& acc, const ConvGeom& g, const ConvOut& o, int c0, int p0) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wm = wave >> 1, wn = wave & 1, cl = lane & 31;
+    const int per = g.Ho * g.Wo;
+    const int64_t plane = (int64_t)o.HoP * o.WoP;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int p = p0 + wn * 64 + j * 32 + cl;
+        if (GUARD && p >= g.P) continue;
+        const int n = p / per, rem = p - n * per;
+        const int oy = rem / g.Wo, ox = rem - oy * g.Wo;
+        const int64_t pix = (int64_t)(oy * o.os + o.py) * o.WoP + (ox * o.os + o.px);
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int co = c0 + wm * 64 + i * 32 + acc_row(r, lane);
+                if (GUARD && co >= o.Cout) continue;
+                float t = acc.t[i][j][r];
+                if (o.bias) t += o.bias[co];
+                const int64_t idx = ((int64_t)n * o.Cout + co) * plane + pix;
+                if (o.preact) o.preact[idx] = t;
+                o.y[idx] = act_fwd(t, o.act);
+            }
+    }
+}
+// The two column-parity classes of one row parity o.py of a stride-2 output (acc0: px = 0, acc1: px = 1): the pair
+// (2 ox, 2 ox + 1) of output columns as one 8-B value per lane, 256 contiguous bytes per 32 lanes.
+template <bool GUARD>
+__device__ __forceinline__ void conv_store_pair(const Acc& acc0, const Acc& acc1, const ConvGeom& g, const ConvOut& o,
+                                                int c0, int p0) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wm = wave >> 1, wn = wave & 1, cl = lane & 31;
+    const int per = g.Ho * g.Wo;
+    const int64_t plane = (int64_t)o.HoP * o.WoP;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int p = p0 + wn * 64 + j * 32 + cl;
+        if (GUARD && p >= g.P) continue;
+        const int n = p / per, rem = p - n * per;
+        const int oy = rem / g.Wo, ox = rem - oy * g.Wo;
+        const int64_t pix = (int64_t)(oy * 2 + o.py) * o.WoP + ox * 2;     // even: 8-B aligned
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int co = c0 + wm * 64 + i * 32 + acc_row(r, lane);
+                if (GUARD && co >= o.Cout) continue;
+                float t0 = acc0.t[i][j][r], t1 = acc1.t[i][j][r];
+                if (o.bias) { const float bv = o.bias[co]; t0 += bv; t1 += bv; }
+                const int64_t idx = ((int64_t)n * o.Cout + co) * plane + pix;
+                if (o.preact) *reinterpret_cast<float2*>(o.preact + idx) = make_float2(t0, t1);
+                *reinterpret_cast<float2*>(o.y + idx) = make_float2(act_fwd(t0, o.act), act_fwd(t1, o.act));
+            }
+    }
+}
+
 // FAST: Cout % 128 == 0, K % 16 == 0, P % 128 == 0 and vector-loadable weights: the
 // branch-free software-pipelined main loop of the GEMM (the gather keeps its own guards).
 template <class SB, bool FAST>
@@ -170,31 +232,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv_mma_kernel(SrcKContig sa, Co
     Acc acc;
     acc_zero(acc);
     contract_loop<FAST>(acc, sa, sb, c0, p0, 0, g.K, lds);
-
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wm = wave >> 1, wn = wave & 1, cl = lane & 31;
-    const int per = g.Ho * g.Wo;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int p = p0 + wn * 64 + j * 32 + cl;
-        if (p >= g.P) continue;
-        const int n = p / per, rem = p - n * per;
-        const int oy = rem / g.Wo, ox = rem - oy * g.Wo;
-        const int64_t pix = (int64_t)(oy * o.os + o.py) * o.WoP + (ox * o.os + o.px);
-        const int64_t plane = (int64_t)o.HoP * o.WoP;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int co = c0 + wm * 64 + i * 32 + acc_row(r, lane);
-                if (co >= o.Cout) continue;
-                float t = acc.t[i][j][r];
-                if (o.bias) t += o.bias[co];
-                const int64_t idx = ((int64_t)n * o.Cout + co) * plane + pix;
-                if (o.preact) o.preact[idx] = t;
-                o.y[idx] = act_fwd(t, o.act);
-            }
-    }
+    conv_store_tile<true>(acc, g, o, c0, p0);
 }
 
 // ConvTranspose2d(4,2,1) forward, both column-parity classes of one row parity in one workgroup:
@@ -226,30 +264,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void convt_pair_kernel(SrcKContig sa, 
         contract_loop<FAST>(acc[px], sw, sb, c0, p0, 0, g.K, lds);
         __syncthreads();                     // the tiles of this class are done with the LDS
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wm = wave >> 1, wn = wave & 1, cl = lane & 31;
-    const int per = g.Ho * g.Wo;
-    const int64_t plane = (int64_t)o.HoP * o.WoP;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int p = p0 + wn * 64 + j * 32 + cl;
-        if (p >= g.P) continue;
-        const int n = p / per, rem = p - n * per;
-        const int oy = rem / g.Wo, ox = rem - oy * g.Wo;
-        const int64_t pix = (int64_t)(oy * 2 + o.py) * o.WoP + ox * 2;     // even: 8-B aligned
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int co = c0 + wm * 64 + i * 32 + acc_row(r, lane);
-                if (co >= o.Cout) continue;
-                float t0 = acc[0].t[i][j][r], t1 = acc[1].t[i][j][r];
-                if (o.bias) { const float bv = o.bias[co]; t0 += bv; t1 += bv; }
-                const int64_t idx = ((int64_t)n * o.Cout + co) * plane + pix;
-                if (o.preact) *reinterpret_cast<float2*>(o.preact + idx) = make_float2(t0, t1);
-                *reinterpret_cast<float2*>(o.y + idx) = make_float2(act_fwd(t0, o.act), act_fwd(t1, o.act));
-            }
-    }
+    conv_store_pair<true>(acc[0], acc[1], g, o, c0, p0);
 }
 
 // Direct kernel for very few output channels (COUT <= 8): lane per logical pixel.
@@ -699,7 +714,7 @@ __global__ __launch_bounds__(1024) void channel_sum_kernel(const float* __restri
 //     stage's [k][128] image, which is the GEMM's tile-contiguous operand layout.
 // Results differ from conv_mma_kernel only by the summation order.
 __global__ void conv_pack_tap_kernel(const float* __restrict__ w, int M, int C, int64_t sm, int64_t sc,
-                                     int flip, float* __restrict__ packed, int ntaps = 9) {
+                                     int flip, float* __restrict__ packed, int ntaps) {
     const int64_t total = (int64_t)M * ntaps * C;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
          idx += (int64_t)gridDim.x * blockDim.x) {
@@ -899,34 +914,12 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv3x3_ring_kernel(const float* 
     const int tile = xcd_remap(blockIdx.x, gridDim.x);
     const int tc = tile / tiles_p, tp = tile - tc * tiles_p;   // pixel tile fastest
     const int c0m = tc * BM, p0 = tp * BN;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wm = wave >> 1, wn = wave & 1, cl = lane & 31;
-    const int per = S2 ? g.Ho * g.Wo : g.H * g.W, W = S2 ? g.Wo : g.W;   // the pixel grid
-    const int64_t plane = (int64_t)o.HoP * o.WoP;
     if constexpr (!PAIR) {
         Acc acc;
         acc_zero(acc);
         const int nkp = splits > 1 ? g.K / BK / splits : 0;
         conv_ring_pass<T3K, S2>(acc, lds, wp, g, c0m, p0, x_bytes, kz * nkp, nkp);
-        // epilogue: as conv_mma_kernel (32 consecutive pixels of one output channel per store instruction)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int pp = p0 + wn * 64 + j * 32 + cl;
-            const int nn = pp / per, rr = pp - nn * per;
-            const int yy = rr / W, xx = rr - yy * W;
-            const int64_t pix = (int64_t)yy * o.WoP + xx;
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int co = c0m + wm * 64 + i * 32 + acc_row(r, lane);
-                    float v = acc.t[i][j][r];
-                    if (o.bias) v += o.bias[co];
-                    const int64_t idx = ((int64_t)nn * o.Cout + co) * plane + pix;
-                    if (o.preact) o.preact[idx] = v;
-                    o.y[idx] = act_fwd(v, o.act);
-                }
-        }
+        conv_store_tile<false>(acc, g, o, c0m, p0);
     } else {
         // mode 0: ConvTranspose2d(4, 2, 1) forward, class (py, px) = 2 x 2 taps at offsets (py - th, px - tw), class
         // weights class_stride apart.  mode 1: input gradient of Conv2d(3, stride 2, padding 1), class (ry, rx) of
@@ -950,24 +943,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void conv3x3_ring_kernel(const float* 
             const int nkp = splits > 1 ? g.K / BK / splits : 0;     // (mode 0 only: equal classes)
             conv_ring_pass<false>(acc[px], lds, wp + woff, g, c0m, p0, x_bytes, kz * nkp, nkp);
         }
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int pp = p0 + wn * 64 + j * 32 + cl;
-            const int nn = pp / per, rr = pp - nn * per;
-            const int yy = rr / W, xx = rr - yy * W;
-            const int64_t pix = (int64_t)(yy * 2 + py) * o.WoP + xx * 2;     // even: 8-B aligned
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int co = c0m + wm * 64 + i * 32 + acc_row(r, lane);
-                    float t0 = acc[0].t[i][j][r], t1 = acc[1].t[i][j][r];
-                    if (o.bias) { const float bv = o.bias[co]; t0 += bv; t1 += bv; }
-                    const int64_t idx = ((int64_t)nn * o.Cout + co) * plane + pix;
-                    if (o.preact) *reinterpret_cast<float2*>(o.preact + idx) = make_float2(t0, t1);
-                    *reinterpret_cast<float2*>(o.y + idx) = make_float2(act_fwd(t0, o.act), act_fwd(t1, o.act));
-                }
-        }
+        o.py = py;
+        conv_store_pair<false>(acc[0], acc[1], g, o, c0m, p0);
     }
 }
 
@@ -1195,7 +1172,27 @@ static int launch_conv_split_reduce(const float* slabs, int splits, const ConvOu
     QARIG_CHECK_LAUNCH("conv split reduce");
     return QARIG_OK;
 }
+// Grid of a weight-packing kernel over `total` elements (256 threads, grid-stride loop).
+static int pack_grid(int64_t total) {
+    int blocks = (int)((total + 255) / 256);
+    if (blocks > 4096) blocks = 4096;
+    return blocks;
+}
 
+// The four instantiations of a gather kernel (conv_mma_kernel, convt_pair_kernel): the row-vector loader where
+// `rowvec`, the branch-free main loop where `fast`.
+#define QARIG_LAUNCH_GATHER(KERNEL, rowvec, fast, grid, st, ...)                                                  \
+    do {                                                                                                         \
+        const dim3 block_(NTHREADS);                                                                             \
+        if ((rowvec) && (fast))                                                                                  \
+            hipLaunchKernelGGL((KERNEL<SrcIm2colRow, true>), grid, block_, 0, st, __VA_ARGS__);                  \
+        else if (rowvec)                                                                                         \
+            hipLaunchKernelGGL((KERNEL<SrcIm2colRow, false>), grid, block_, 0, st, __VA_ARGS__);                 \
+        else if (fast)                                                                                           \
+            hipLaunchKernelGGL((KERNEL<SrcIm2col, true>), grid, block_, 0, st, __VA_ARGS__);                     \
+        else                                                                                                     \
+            hipLaunchKernelGGL((KERNEL<SrcIm2col, false>), grid, block_, 0, st, __VA_ARGS__);                    \
+    } while (0)
 
 static int launch_conv(const float* wmat, const ConvGeom& g, const ConvOut& o, hipStream_t st) {
     const bool fwd_taps = g.oy0 == -1 && g.ox0 == -1 && g.oys == 1 && g.oxs == 1;
@@ -1234,61 +1231,163 @@ static int launch_conv(const float* wmat, const ConvGeom& g, const ConvOut& o, h
         const int tiles_c = (o.Cout + BM - 1) / BM, tiles_p = (g.P + BN - 1) / BN;
         const bool rowvec = g.stride == 1 && g.Wo % 4 == 0 && g.K < 65536;
         const bool fast = sa.vec4 && o.Cout % BM == 0 && g.K % BK == 0 && g.P % BN == 0;
-        const dim3 grid(tiles_c * tiles_p), block(NTHREADS);
-        if (rowvec && fast)
-            hipLaunchKernelGGL((conv_mma_kernel<SrcIm2colRow, true>), grid, block, 0, st, sa, g, o, tiles_p);
-        else if (rowvec)
-            hipLaunchKernelGGL((conv_mma_kernel<SrcIm2colRow, false>), grid, block, 0, st, sa, g, o, tiles_p);
-        else if (fast)
-            hipLaunchKernelGGL((conv_mma_kernel<SrcIm2col, true>), grid, block, 0, st, sa, g, o, tiles_p);
-        else
-            hipLaunchKernelGGL((conv_mma_kernel<SrcIm2col, false>), grid, block, 0, st, sa, g, o, tiles_p);
+        QARIG_LAUNCH_GATHER(conv_mma_kernel, rowvec, fast, dim3(tiles_c * tiles_p), st, sa, g, o, tiles_p);
     }
     QARIG_CHECK_LAUNCH("conv");
     return QARIG_OK;
 }
 
-// 3x3 / stride 1 / padding 1 on the LDS-DMA ring (conv3x3_ring_kernel) where its tiles are whole:
-// M (output channels of this product) % 128, C (reduced channels) % 16, pixels % 128, W % 4, the
-// input below 2 GB (32-bit buffer offsets).  w element (m, c, tap) at w[m * sm + c * sc + tap];
-// flip: the data gradient's tap order.  `packed`: M * 9 * C floats.  QARIG_CONV_RING=0 disables.
-static bool conv3x3_ring_ok(int N, int C, int H, int W, int M, const void* x, const void* packed) {
-    const bool on = g_qarig_opt.conv_ring != 0;          // option conv_ring = 0: the gather kernels (cross-check)
-    const int64_t P = (int64_t)N * H * W, xb = P * C * 4;
-    return on && packed && C % 16 == 0 && C >= 16 && M % BM == 0 && P % BN == 0 && W % 4 == 0 && xb < (1LL << 31) &&
-           (int64_t)9 * C < (1 << 20) && (((uintptr_t)x | (uintptr_t)packed) & 15) == 0;
+// Every launch of conv3x3_ring_kernel is planned here, once: conv_ring_plan decides from the product and its
+// extents whether the ring applies, the launch geometry, the reduction parts and the scratch; run_conv_ring packs
+// the weights and launches what the plan says; the *_workspace_bytes_n functions size the scratch from the same plan.
+// N, C, H, W, M of a plan: images, reduced channels, the launch's logical pixel grid (g.Ho x g.Wo) and the
+// product's output channels.
+enum ConvRingKind {
+    RING_S1_FWD,       // Conv2d(3, 1, 1) forward: C = Cin, M = Cout; grid = input = output
+    RING_S1_DGRAD,     // its input gradient: dx[ci] = sum_{co, tap} dT[co] at offset (1 - tap) * w[co][ci][tap], a 3x3
+                       // conv over dT with C = Cout, M = Cin and the taps flipped
+    RING_S2_FWD,       // Conv2d(3, 2, 1) forward with a strided im2col (four 4-B loads per k row): grid = output,
+                       // input 2H x 2W
+    RING_CONVT_FWD,    // ConvTranspose2d(4, 2, 1) forward: the four parity classes as 2x2-tap stride-1 products, two
+                       // column parities per workgroup; grid = input, output 2H x 2W
+    RING_S2_DGRAD,     // input gradient of Conv2d(3, 2, 1): the four output-parity classes of dx as (1 + ry) x (1 + rx)-tap
+                       // stride-1 products over dT, two column parities per workgroup (8-B stores), both row parities
+                       // in one launch; C = Cout, M = Cin, grid = dT, dx 2H x 2W
+    RING_CONVT_DGRAD,  // input gradient of ConvTranspose2d(4, 2, 1) = Conv2d(4, stride 2, padding 1) over dT: 16 taps at
+                       // offsets -1 .. 2 on the strided ring; C = Cout, M = Cin, grid = dx, dT 2H x 2W
+};
+struct ConvRingPlan {
+    bool ok;                    // the ring serves this product (pointers aside: conv_ring_usable)
+    ConvRingKind kind;
+    const char* name;
+    ConvGeom g;                 // g.x is filled in by the runner
+    int M, tiles_p, grid_y;     // grid = (M / 128 * tiles_p, grid_y, parts)
+    int64_t class_stride;       // kernel arguments
+    int mode;
+    unsigned x_bytes;
+    size_t packed_bytes;        // tap-major weights at the head of the workspace, the slabs behind them
+    int64_t out_elems;          // floats of one slab = of the output
+    int splits;                 // parts of the reduction (conv_ring_splits) given room and alignment for them
+    unsigned align, align_split;   // address bits of y | preact that must be clear: to run at all, to run split
+};
+
+// Where the tiles are whole: M % 128, C % 16, pixels % 128, grid rows a multiple of 4 wide, the input below 2 GB
+// (32-bit buffer offsets).  Option conv_ring = 0 (QARIG_CONV_RING=0): the gather kernels (cross-check).
+static ConvRingPlan conv_ring_plan(ConvRingKind kind, int N, int C, int H, int W, int M) {
+    ConvRingPlan p{};
+    p.kind = kind;
+    const bool in2 = kind == RING_S2_FWD || kind == RING_CONVT_DGRAD;     // the input is read with stride 2
+    const bool pair = kind == RING_CONVT_FWD || kind == RING_S2_DGRAD;    // the output is 2H x 2W, stored as column pairs
+    const int is = in2 ? 2 : 1, os = pair ? 2 : 1;
+    const int64_t P = (int64_t)N * H * W, xb = P * C * is * is * 4;
+    p.ok = g_qarig_opt.conv_ring != 0 && C % 16 == 0 && M % BM == 0 && P % BN == 0 && W % 4 == 0 && xb < (1LL << 31);
+    if (!in2) p.ok = p.ok && C >= 16 && (int64_t)9 * C < (1 << 20);      // (the unit-stride kinds only)
+    if (!p.ok) return p;
+    // taps per side and their offsets o0 + ot * t: forward-like kinds walk -1, 0, 1 (, 2); the parity classes
+    // of a stride-2 output walk p, p - 1 (the kernel sets the parity p and, in mode 1, the class's tap counts)
+    const int nt = kind == RING_CONVT_FWD ? 2 : kind == RING_S2_DGRAD ? 1 : kind == RING_CONVT_DGRAD ? 4 : 3;
+    const int o0 = pair ? 0 : -1, ot = pair ? -1 : 1;
+    p.g = ConvGeom{nullptr, N, C, H * is, W * is, H, W, is, nt, nt, o0, ot, o0, ot, C * nt * nt, (int)P};
+    p.M = M;
+    p.tiles_p = (int)(P / BN);
+    p.grid_y = pair ? 2 : 1;                                              // row parity
+    p.class_stride = kind == RING_CONVT_FWD ? (int64_t)M * p.g.K : 0;
+    p.mode = kind == RING_S2_DGRAD;
+    p.x_bytes = (unsigned)xb;
+    p.packed_bytes = (size_t)M * C * (kind == RING_CONVT_FWD || kind == RING_CONVT_DGRAD ? 16 : 9) * sizeof(float);
+    p.out_elems = (int64_t)N * M * H * W * os * os;
+    // (the stride-2 input gradient's classes are 1, 2, 2 and 4 taps long: never split)
+    p.splits = kind == RING_S2_DGRAD ? 1 : conv_ring_splits((long)p.grid_y * (M / BM) * p.tiles_p, p.g.K / BK);
+    p.align = pair ? 7 : 0;                                               // 8-B pair stores
+    p.align_split = 15;                                                   // conv_split_reduce_kernel: 16 B per lane
+    static const char* const names[] = {"conv3x3 ring", "conv2d_bwd_data 3x3 ring", "conv3x3 stride-2 ring",
+                                        "conv_transpose2d ring", "conv2d_bwd_data stride-2 ring",
+                                        "conv_transpose2d_bwd_data ring"};
+    p.name = names[kind];
+    return p;
 }
-// `slabs` / `slab_bytes`: scratch behind the packed weights for a split launch (conv_ring_splits), else
-// the launch is not split.
-static int launch_conv3x3_ring(const float* w, int64_t sm, int64_t sc, int flip, const float* x, int N, int C,
-                               int H, int W, int M, const ConvOut& o, float* packed, hipStream_t st,
-                               float* slabs = nullptr, size_t slab_bytes = 0, bool packed_valid = false) {
+// The Conv2d product (forward, or input gradient of the layer Cin -> Cout over an H x W input) that has a ring kind.
+static ConvRingPlan conv2d_ring_plan(bool dgrad, int N, int Cin, int H, int W, int Cout, int k, int stride, int pad) {
+    if (k == 3 && pad == 1 && stride == 1)
+        return dgrad ? conv_ring_plan(RING_S1_DGRAD, N, Cout, H, W, Cin) : conv_ring_plan(RING_S1_FWD, N, Cin, H, W, Cout);
+    if (k == 3 && pad == 1 && stride == 2 && H % 2 == 0 && W % 2 == 0)
+        return dgrad ? conv_ring_plan(RING_S2_DGRAD, N, Cout, H / 2, W / 2, Cin)
+                     : conv_ring_plan(RING_S2_FWD, N, Cin, H / 2, W / 2, Cout);
+    return ConvRingPlan{};
+}
+// Scratch of a planned launch when every pointer is aligned: the packed weights (`base`) + the slabs of its parts.
+static size_t conv_ring_workspace_bytes(size_t base, const ConvRingPlan& p) {
+    return base + (p.ok && p.splits > 1 ? (size_t)p.splits * p.out_elems * sizeof(float) : 0);
+}
+static bool conv_ring_usable(const ConvRingPlan& p, const float* x, const ConvOut& o, const void* workspace,
+                             size_t ws_bytes) {
+    return p.ok && workspace && ws_bytes >= p.packed_bytes && (((uintptr_t)x | (uintptr_t)workspace) & 15) == 0 &&
+           (((uintptr_t)o.y | (uintptr_t)o.preact) & p.align) == 0;
+}
+// w: the layer's weight as stored.  packed_valid: the head of the workspace already holds its tap-major copy.
+static int run_conv_ring(const ConvRingPlan& p, const float* x, const float* w, const ConvOut& o, void* workspace,
+                         size_t ws_bytes, bool packed_valid, hipStream_t st) {
+    float* packed = (float*)workspace;
+    const int C = p.g.C, M = p.M;
     if (!packed_valid) {
-        const int64_t total = (int64_t)M * 9 * C;
-        int blocks = (int)((total + 255) / 256);
-        if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(conv_pack_tap_kernel, dim3(blocks), dim3(256), 0, st, w, M, C, sm, sc, flip, packed);
-        QARIG_CHECK_LAUNCH("conv3x3 pack");
+        const dim3 pgrid(pack_grid((int64_t)(p.packed_bytes / sizeof(float)))), pblock(256);
+        switch (p.kind) {   // conv_pack_tap_kernel: w element (m, c, tap) at w[m * sm + c * sc + tap] -> [M][taps][C]
+            case RING_S1_FWD:
+            case RING_S2_FWD:        // w (M, C, 3, 3)
+                hipLaunchKernelGGL(conv_pack_tap_kernel, pgrid, pblock, 0, st, w, M, C, (int64_t)C * 9, (int64_t)9, 0,
+                                   packed, 9);
+                break;
+            case RING_S1_DGRAD:      // w (C, M, 3, 3); the flip of the data gradient is applied here
+                hipLaunchKernelGGL(conv_pack_tap_kernel, pgrid, pblock, 0, st, w, M, C, (int64_t)9, (int64_t)M * 9, 1,
+                                   packed, 9);
+                break;
+            case RING_CONVT_DGRAD:   // w (M, C, 4, 4)
+                hipLaunchKernelGGL(conv_pack_tap_kernel, pgrid, pblock, 0, st, w, M, C, (int64_t)C * 16, (int64_t)16, 0,
+                                   packed, 16);
+                break;
+            case RING_CONVT_FWD:     // w (C, M, 4, 4)
+                hipLaunchKernelGGL(convt_pack_tap_kernel, pgrid, pblock, 0, st, w, C, M, packed);
+                break;
+            case RING_S2_DGRAD:      // w (C, M, 3, 3)
+                hipLaunchKernelGGL(conv_s2_dgrad_pack_tap_kernel, pgrid, pblock, 0, st, w, C, M, packed);
+                break;
+        }
+        QARIG_CHECK_LAUNCH(p.name);
     }
-    ConvGeom g{x, N, C, H, W, H, W, 1, 3, 3, -1, 1, -1, 1, 9 * C, N * H * W};
-    const int tiles_c = M / BM, tiles_p = g.P / BN;
-    const int64_t out_elems = (int64_t)N * M * H * W;
-    int splits = conv_ring_splits((long)tiles_c * tiles_p, g.K / BK);
-    if (splits > 1 && (!slabs || slab_bytes < (size_t)splits * out_elems * sizeof(float) ||
-                       o.os != 1 || o.HoP != H || o.WoP != W || (((uintptr_t)o.y | (uintptr_t)o.preact) & 15)))
+    // the parts need room for their slabs behind the packed weights and 16-B aligned outputs for the reduction:
+    // else the launch is not split
+    int splits = p.splits;
+    if (splits > 1 && (ws_bytes < p.packed_bytes + (size_t)splits * p.out_elems * sizeof(float) ||
+                       (((uintptr_t)o.y | (uintptr_t)o.preact) & p.align_split)))
         splits = 1;
-    if (splits > 1) {
-        ConvOut raw{slabs, nullptr, nullptr, o.Cout, o.HoP, o.WoP, o.os, o.py, o.px, ACT_NONE};
-        hipLaunchKernelGGL((conv3x3_ring_kernel<false>), dim3(tiles_c * tiles_p, 1, splits), dim3(NTHREADS), 0, st,
-                           packed, g, raw, tiles_p, (unsigned)((int64_t)N * C * H * W * 4), (int64_t)0, 0, splits,
-                           out_elems);
-        QARIG_CHECK_LAUNCH("conv3x3 ring (split)");
-        return launch_conv_split_reduce(slabs, splits, o, N, st);
+    float* slabs = (float*)((char*)workspace + p.packed_bytes);
+    ConvGeom g = p.g;
+    g.x = x;
+    const ConvOut out = splits > 1 ? ConvOut{slabs, nullptr, nullptr, o.Cout, o.HoP, o.WoP, o.os, o.py, o.px, ACT_NONE} : o;
+    const int64_t slab_stride = splits > 1 ? p.out_elems : 0;
+    const dim3 grid((M / BM) * p.tiles_p, p.grid_y, splits), block(NTHREADS);
+    switch (p.kind) {
+        case RING_S1_FWD:
+        case RING_S1_DGRAD:
+            hipLaunchKernelGGL((conv3x3_ring_kernel<false>), grid, block, 0, st, packed, g, out, p.tiles_p, p.x_bytes,
+                               p.class_stride, p.mode, splits, slab_stride);
+            break;
+        case RING_S2_FWD:
+            hipLaunchKernelGGL((conv3x3_ring_kernel<false, true>), grid, block, 0, st, packed, g, out, p.tiles_p, p.x_bytes,
+                               p.class_stride, p.mode, splits, slab_stride);
+            break;
+        case RING_CONVT_DGRAD:
+            hipLaunchKernelGGL((conv3x3_ring_kernel<false, true, false>), grid, block, 0, st, packed, g, out, p.tiles_p,
+                               p.x_bytes, p.class_stride, p.mode, splits, slab_stride);
+            break;
+        case RING_CONVT_FWD:
+        case RING_S2_DGRAD:
+            hipLaunchKernelGGL((conv3x3_ring_kernel<true>), grid, block, 0, st, packed, g, out, p.tiles_p, p.x_bytes,
+                               p.class_stride, p.mode, splits, slab_stride);
+            break;
     }
-    hipLaunchKernelGGL((conv3x3_ring_kernel<false>), dim3(tiles_c * tiles_p), dim3(NTHREADS), 0, st, packed, g, o,
-                       tiles_p, (unsigned)((int64_t)N * C * H * W * 4), (int64_t)0, 0, 1, (int64_t)0);
-    QARIG_CHECK_LAUNCH("conv3x3 ring");
-    return QARIG_OK;
+    QARIG_CHECK_LAUNCH(p.name);
+    return splits > 1 ? launch_conv_split_reduce(slabs, splits, o, p.g.N, st) : QARIG_OK;
 }
 
 // nn.Conv2d(Cin, Cout, k, stride, padding) + bias + activation, NCHW fp32.
@@ -1315,51 +1414,9 @@ static int conv2d_fwd_impl(const float* x, int N, int Cin, int H, int W, const f
                     "conv2d: too large");
     ConvGeom g{x, N, Cin, H, W, Ho, Wo, stride, k, k, -pad, 1, -pad, 1, Cin * k * k, N * Ho * Wo};
     ConvOut o{y, preact, bias, Cout, Ho, Wo, 1, 0, 0, act};
-    if (k == 3 && stride == 1 && pad == 1 && workspace &&
-        ws_bytes >= (size_t)Cout * 9 * Cin * sizeof(float) &&
-        conv3x3_ring_ok(N, Cin, H, W, Cout, x, workspace)) {
-        const size_t packed_bytes = (size_t)Cout * 9 * Cin * sizeof(float);     // a multiple of 16 B
-        return launch_conv3x3_ring(w, (int64_t)Cin * 9, 9, 0, x, N, Cin, H, W, Cout, o, (float*)workspace,
-                                   (hipStream_t)stream, (float*)((char*)workspace + packed_bytes),
-                                   ws_bytes - packed_bytes, packed_valid);
-    }
-    {   // stride 2: the same kernel with a strided im2col (four 4-B loads per k row)
-        const int64_t P = (int64_t)N * Ho * Wo, xb = (int64_t)N * Cin * H * W * 4;
-        if (g_qarig_opt.conv_ring != 0 && k == 3 && stride == 2 && pad == 1 && H == 2 * Ho && W == 2 * Wo && workspace &&
-            ws_bytes >= (size_t)Cout * 9 * Cin * sizeof(float) && Cin % 16 == 0 && Cout % BM == 0 && P % BN == 0 &&
-            Wo % 4 == 0 && xb < (1LL << 31) && (((uintptr_t)x | (uintptr_t)workspace) & 15) == 0) {
-            hipStream_t st = (hipStream_t)stream;
-            float* packed = (float*)workspace;
-            const int64_t total = (int64_t)Cout * 9 * Cin;
-            int blocks = (int)((total + 255) / 256);
-            if (blocks > 4096) blocks = 4096;
-            if (!packed_valid) {
-                hipLaunchKernelGGL(conv_pack_tap_kernel, dim3(blocks), dim3(256), 0, st, w, Cout, Cin, (int64_t)Cin * 9,
-                                   (int64_t)9, 0, packed);
-                QARIG_CHECK_LAUNCH("conv3x3 pack");
-            }
-            const int tiles_p = (int)(P / BN);
-            const size_t packed_bytes = (size_t)Cout * 9 * Cin * sizeof(float);
-            const int64_t out_elems = (int64_t)N * Cout * Ho * Wo;
-            int splits = conv_ring_splits((long)(Cout / BM) * tiles_p, 9 * Cin / BK);
-            if (splits > 1 && (ws_bytes < packed_bytes + (size_t)splits * out_elems * sizeof(float) ||
-                               (((uintptr_t)y | (uintptr_t)preact) & 15)))
-                splits = 1;
-            if (splits > 1) {
-                float* slabs = (float*)((char*)workspace + packed_bytes);
-                ConvOut raw{slabs, nullptr, nullptr, Cout, Ho, Wo, 1, 0, 0, ACT_NONE};
-                hipLaunchKernelGGL((conv3x3_ring_kernel<false, true>), dim3((Cout / BM) * tiles_p, 1, splits),
-                                   dim3(NTHREADS), 0, st, packed, g, raw, tiles_p, (unsigned)xb, (int64_t)0, 0, splits,
-                                   out_elems);
-                QARIG_CHECK_LAUNCH("conv3x3 stride-2 ring (split)");
-                return launch_conv_split_reduce(slabs, splits, o, N, st);
-            }
-            hipLaunchKernelGGL((conv3x3_ring_kernel<false, true>), dim3((Cout / BM) * tiles_p), dim3(NTHREADS), 0, st,
-                               packed, g, o, tiles_p, (unsigned)xb, (int64_t)0, 0, 1, (int64_t)0);
-            QARIG_CHECK_LAUNCH("conv3x3 stride-2 ring");
-            return QARIG_OK;
-        }
-    }
+    const ConvRingPlan p = conv2d_ring_plan(false, N, Cin, H, W, Cout, k, stride, pad);
+    if (conv_ring_usable(p, x, o, workspace, ws_bytes))
+        return run_conv_ring(p, x, w, o, workspace, ws_bytes, packed_valid, (hipStream_t)stream);
     return launch_conv(w, g, o, (hipStream_t)stream);
 }
 
@@ -1370,25 +1427,26 @@ extern "C" int qarig_conv2d_fwd(const float* x, int N, int Cin, int H, int W, co
 }
 
 // The same with a scratch buffer (Cout * Cin * k * k floats) for a re-ordered copy of the weights:
-// enables the LDS-DMA ring kernel on the 3x3 / stride 1 / padding 1 layers (conv3x3_ring_kernel).
-extern "C" size_t qarig_conv2d_fwd_workspace_bytes(int Cin, int Cout, int k) {
+// enables the LDS-DMA ring kernel on the 3x3 / padding 1 layers (conv3x3_ring_kernel).  The input gradient's
+// scratch is the same size.
+static size_t conv2d_packed_bytes(int Cin, int Cout, int k) {
     if (Cin < 1 || Cout < 1 || k < 1 || k > 4 || Cin > (1 << 20) || Cout > (1 << 20)) return 0;
     return (size_t)Cin * Cout * k * k * sizeof(float);
 }
-// ... and, at few images, room for the split launch's slabs (conv_ring_splits): the 3x3 / stride 1 / padding 1
-// layers of a <= 8-image decoder run their reduction in 2-4 parts to fill the chip.
-static size_t conv_split_slab_bytes(long wgs, int nk, int64_t out_elems) {
-    const int s = conv_ring_splits(wgs, nk);
-    return s > 1 ? (size_t)s * out_elems * sizeof(float) : 0;
-}
+extern "C" size_t qarig_conv2d_fwd_workspace_bytes(int Cin, int Cout, int k) { return conv2d_packed_bytes(Cin, Cout, k); }
+extern "C" size_t qarig_conv2d_bwd_data_workspace_bytes(int Cin, int Cout, int k) { return conv2d_packed_bytes(Cin, Cout, k); }
+// ... and, at few images, room for the split launch's slabs (conv_ring_splits): the 3x3 / padding 1 layers of a
+// <= 8-image decoder run their reduction in 2-8 parts to fill the chip.  Padding 1 is assumed.
 extern "C" size_t qarig_conv2d_fwd_workspace_bytes_n(int N, int Cin, int H, int W, int Cout, int k, int stride) {
-    const size_t base = qarig_conv2d_fwd_workspace_bytes(Cin, Cout, k);
+    const size_t base = conv2d_packed_bytes(Cin, Cout, k);
     if (!base || N < 1 || H < 1 || W < 1 || !qarig_dims_ok({N, Cout, H, W}, 1LL << 20, 1LL << 31)) return base;
-    if (k != 3 || (stride != 1 && stride != 2) || H % stride || W % stride) return base;
-    const int Ho = H / stride, Wo = W / stride;          // (padding 1: the ring geometries)
-    if (Cin % 16 || Cout % BM || ((int64_t)N * Ho * Wo) % BN) return base;
-    return base + conv_split_slab_bytes((long)(Cout / BM) * ((int64_t)N * Ho * Wo / BN), 9 * Cin / BK,
-                                        (int64_t)N * Cout * Ho * Wo);
+    return conv_ring_workspace_bytes(base, conv2d_ring_plan(false, N, Cin, H, W, Cout, k, stride, 1));
+}
+// (the same ring launch as the forward; the stride-2 input gradient is never split)
+extern "C" size_t qarig_conv2d_bwd_data_workspace_bytes_n(int N, int Cin, int H, int W, int Cout, int k, int stride) {
+    const size_t base = conv2d_packed_bytes(Cin, Cout, k);
+    if (!base || N < 1 || H < 1 || W < 1 || !qarig_dims_ok({N, Cin, H, W}, 1LL << 20, 1LL << 31)) return base;
+    return conv_ring_workspace_bytes(base, conv2d_ring_plan(true, N, Cin, H, W, Cout, k, stride, 1));
 }
 extern "C" int qarig_conv2d_fwd_ws(const float* x, int N, int Cin, int H, int W, const float* w,
                                    const float* bias, int Cout, int k, int stride, int pad, int act,
@@ -1405,9 +1463,13 @@ extern "C" size_t qarig_conv_transpose2d_workspace_bytes(int Cin, int Cout) {
 extern "C" size_t qarig_conv_transpose2d_workspace_bytes_n(int N, int Cin, int H, int W, int Cout) {
     const size_t base = qarig_conv_transpose2d_workspace_bytes(Cin, Cout);
     if (!base || N < 1 || H < 1 || W < 1 || !qarig_dims_ok({N, Cout, H, W, 4}, 1LL << 20, 1LL << 31)) return base;
-    if (Cin % 16 || Cout % BM || ((int64_t)N * H * W) % BN) return base;
-    return base + conv_split_slab_bytes(2L * (Cout / BM) * ((int64_t)N * H * W / BN), 4 * Cin / BK,
-                                        (int64_t)N * Cout * H * W * 4);
+    return conv_ring_workspace_bytes(base, conv_ring_plan(RING_CONVT_FWD, N, Cin, H, W, Cout));
+}
+// scratch of qarig_conv_transpose2d_bwd_data_ws: the tap-major weights + a few-image launch's split slabs
+extern "C" size_t qarig_conv_transpose2d_bwd_data_workspace_bytes_n(int N, int Cin, int H, int W, int Cout) {
+    const size_t base = qarig_conv_transpose2d_workspace_bytes(Cin, Cout);
+    if (!base || N < 1 || H < 1 || W < 1 || !qarig_dims_ok({N, Cin, H, W}, 1LL << 20, 1LL << 31)) return base;
+    return conv_ring_workspace_bytes(base, conv_ring_plan(RING_CONVT_DGRAD, N, Cout, H, W, Cin));
 }
 
 // nn.ConvTranspose2d(Cin, Cout, 4, stride 2, padding 1) + bias + activation.
@@ -1431,41 +1493,16 @@ extern "C" int qarig_conv_transpose2d_fwd(const float* x, int N, int Cin, int H,
     }
     hipStream_t st = (hipStream_t)stream;
     float* packed = (float*)workspace;
-    const int64_t total = (int64_t)16 * Cin * Cout;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    // the four parity classes as 2x2-tap stride-1 products on the LDS-DMA ring, two column parities per workgroup
-    if (conv3x3_ring_ok(N, Cin, H, W, Cout, x, packed) && (((uintptr_t)y | (uintptr_t)preact) & 7) == 0) {
-        if (!packed_valid) {
-            hipLaunchKernelGGL(convt_pack_tap_kernel, dim3(blocks), dim3(256), 0, st, w, Cin, Cout, packed);
-            QARIG_CHECK_LAUNCH("conv_transpose2d pack");
-        }
-        const int K = Cin * 4, P = N * H * W;
-        ConvGeom g{x, N, Cin, H, W, H, W, 1, 2, 2, 0, -1, 0, -1, K, P};
-        ConvOut o{y, preact, bias, Cout, 2 * H, 2 * W, 2, 0, 0, act};
-        const int tiles_p = P / BN;
-        const size_t packed_bytes = qarig_conv_transpose2d_workspace_bytes(Cin, Cout);
-        const int64_t out_elems = (int64_t)N * Cout * H * W * 4;
-        int splits = conv_ring_splits(2L * (Cout / BM) * tiles_p, K / BK);
-        if (splits > 1 && (ws_bytes < packed_bytes + (size_t)splits * out_elems * sizeof(float) ||
-                           (((uintptr_t)y | (uintptr_t)preact) & 15) || W % 2))
-            splits = 1;
-        if (splits > 1) {
-            float* slabs = (float*)((char*)workspace + packed_bytes);
-            ConvOut raw{slabs, nullptr, nullptr, Cout, 2 * H, 2 * W, 2, 0, 0, ACT_NONE};
-            hipLaunchKernelGGL((conv3x3_ring_kernel<true>), dim3((Cout / BM) * tiles_p, 2, splits), dim3(NTHREADS), 0,
-                               st, packed, g, raw, tiles_p, (unsigned)((int64_t)N * Cin * H * W * 4),
-                               (int64_t)Cout * K, 0, splits, out_elems);
-            QARIG_CHECK_LAUNCH("conv_transpose2d ring (split)");
-            return launch_conv_split_reduce(slabs, splits, o, N, st);
-        }
-        hipLaunchKernelGGL((conv3x3_ring_kernel<true>), dim3((Cout / BM) * tiles_p, 2), dim3(NTHREADS), 0, st, packed, g,
-                           o, tiles_p, (unsigned)((int64_t)N * Cin * H * W * 4), (int64_t)Cout * K, 0, 1, (int64_t)0);
-        QARIG_CHECK_LAUNCH("conv_transpose2d ring");
-        return QARIG_OK;
-    }
+    const int K = Cin * 4, P = N * H * W;
+    // class (py, px): taps at input offsets (py - th, px - tw); the ring and pair kernels set the parities themselves
+    const ConvGeom g{x, N, Cin, H, W, H, W, 1, 2, 2, 0, -1, 0, -1, K, P};
+    const ConvOut o{y, preact, bias, Cout, 2 * H, 2 * W, 2, 0, 0, act};
+    const ConvRingPlan p = conv_ring_plan(RING_CONVT_FWD, N, Cin, H, W, Cout);
+    if (conv_ring_usable(p, x, o, workspace, ws_bytes))
+        return run_conv_ring(p, x, w, o, workspace, ws_bytes, packed_valid, st);
     if (!packed_valid) {
-        hipLaunchKernelGGL(convt_pack_kernel, dim3(blocks), dim3(256), 0, st, w, Cin, Cout, packed);
+        hipLaunchKernelGGL(convt_pack_kernel, dim3(pack_grid((int64_t)16 * Cin * Cout)), dim3(256), 0, st, w, Cin, Cout,
+                           packed);
         QARIG_CHECK_LAUNCH("conv_transpose2d pack");
     }
     // both column parities per launch (8-B stores) where the MFMA kernel applies and y / preact
@@ -1474,57 +1511,33 @@ extern "C" int qarig_conv_transpose2d_fwd(const float* x, int N, int Cin, int H,
     // ... and where one class per launch would leave the chip half empty (< 512 workgroups per class:
     // the 512 -> 256 layer at 16 images ran 61.7 TF that way, 88.4 TF paired; at 32 images one class
     // per launch is the faster form, 94.6 against 90.9 TF for the whole decoder)
-    const long class_wgs = (long)((Cout + BM - 1) / BM) * (((long)N * H * W + BN - 1) / BN);
+    const int tiles_c = (Cout + BM - 1) / BM, tiles_p = (P + BN - 1) / BN;
+    const long class_wgs = (long)tiles_c * tiles_p;
     const bool pair = pair_on && Cout > 8 && class_wgs < 512 && (((uintptr_t)y | (uintptr_t)preact) & 7) == 0;
     if (pair) {
-        const int K = Cin * 4, P = N * H * W;
-        const int tiles_c = (Cout + BM - 1) / BM, tiles_p = (P + BN - 1) / BN;
-        const dim3 grid(tiles_c * tiles_p, 2), block(NTHREADS);      // y = row parity
-        {
-            ConvGeom g{x, N, Cin, H, W, H, W, 1, 2, 2, 0, -1, 0, -1, K, P};
-            ConvOut o{y, preact, bias, Cout, 2 * H, 2 * W, 2, 0, 0, act};
-            const float* wmat = packed;
-            SrcKContig sa{wmat, (int64_t)K, Cout, K, 1.0f, (((uintptr_t)wmat & 15) == 0) && K % 4 == 0};
-            const bool rowvec = W % 4 == 0 && K < 65536;
-            const bool fast = sa.vec4 && Cout % BM == 0 && K % BK == 0 && P % BN == 0;
-            const int64_t cs = (int64_t)Cout * K;
-            if (rowvec && fast)
-                hipLaunchKernelGGL((convt_pair_kernel<SrcIm2colRow, true>), grid, block, 0, st, sa, g, o, tiles_p, cs);
-            else if (rowvec)
-                hipLaunchKernelGGL((convt_pair_kernel<SrcIm2colRow, false>), grid, block, 0, st, sa, g, o, tiles_p, cs);
-            else if (fast)
-                hipLaunchKernelGGL((convt_pair_kernel<SrcIm2col, true>), grid, block, 0, st, sa, g, o, tiles_p, cs);
-            else
-                hipLaunchKernelGGL((convt_pair_kernel<SrcIm2col, false>), grid, block, 0, st, sa, g, o, tiles_p, cs);
-            QARIG_CHECK_LAUNCH("conv_transpose2d pair");
-        }
+        SrcKContig sa{packed, (int64_t)K, Cout, K, 1.0f, (((uintptr_t)packed & 15) == 0) && K % 4 == 0};
+        const bool rowvec = W % 4 == 0 && K < 65536;
+        const bool fast = sa.vec4 && Cout % BM == 0 && K % BK == 0 && P % BN == 0;
+        QARIG_LAUNCH_GATHER(convt_pair_kernel, rowvec, fast, dim3(tiles_c * tiles_p, 2), st, sa, g, o, tiles_p,
+                            (int64_t)Cout * K);                           // grid.y = row parity
+        QARIG_CHECK_LAUNCH("conv_transpose2d pair");
         return QARIG_OK;
     }
     for (int cls = 0; cls < 4; ++cls) {
         const int py = cls >> 1, px = cls & 1;
         // oy = 2a+py: tap th uses kh = 1-py+2th and input row a + (py + 1 - kh)/2 = a + py - th
-        ConvGeom g{x, N, Cin, H, W, H, W, 1, 2, 2, py, -1, px, -1, Cin * 4, N * H * W};
-        ConvOut o{y, preact, bias, Cout, 2 * H, 2 * W, 2, py, px, act};
-        if (int e = launch_conv(packed + (int64_t)cls * Cout * Cin * 4, g, o, st)) return e;
+        ConvGeom gc = g;
+        gc.oy0 = py;
+        gc.ox0 = px;
+        ConvOut oc = o;
+        oc.py = py;
+        oc.px = px;
+        if (int e = launch_conv(packed + (int64_t)cls * Cout * K, gc, oc, st)) return e;
     }
     return QARIG_OK;
 }
 
 // ------------------------------------------------------------------ backward entry points
-
-extern "C" size_t qarig_conv2d_bwd_data_workspace_bytes(int Cin, int Cout, int k) {
-    if (Cin < 1 || Cout < 1 || k < 1 || k > 4 || Cin > (1 << 20) || Cout > (1 << 20)) return 0;
-    return (size_t)Cin * Cout * k * k * sizeof(float);
-}
-
-// ... plus room for a few-image launch's split slabs (3x3 / stride 1: the same ring launch as the forward)
-extern "C" size_t qarig_conv2d_bwd_data_workspace_bytes_n(int N, int Cin, int H, int W, int Cout, int k, int stride) {
-    const size_t base = qarig_conv2d_bwd_data_workspace_bytes(Cin, Cout, k);
-    if (!base || N < 1 || H < 1 || W < 1 || !qarig_dims_ok({N, Cin, H, W}, 1LL << 20, 1LL << 31)) return base;
-    if (k != 3 || stride != 1 || Cout % 16 || Cin % BM || ((int64_t)N * H * W) % BN) return base;
-    return base + conv_split_slab_bytes((long)(Cin / BM) * ((int64_t)N * H * W / BN), 9 * Cout / BK,
-                                        (int64_t)N * Cin * H * W);
-}
 
 // d(input) of Conv2d: dT (N,Cout,Ho,Wo) -> dx (N,Cin,H,W).  One stride-1 implicit-GEMM
 // launch per output-parity class of dx (1 class for stride 1, 4 for stride 2), each with
@@ -1546,31 +1559,11 @@ extern "C" int qarig_conv2d_bwd_data(const float* dT, int N, int Cout, int Ho, i
     hipStream_t st = (hipStream_t)stream;
     float* packed = (float*)workspace;
     const int s = stride;
-    if (k == 3 && s == 1 && pad == 1 && Ho == H && Wo == W && conv3x3_ring_ok(N, Cout, H, W, Cin, dT, packed)) {
-        // dx[ci] = sum_{co, tap} dT[co] at offset (1 - tap) * w[co][ci][tap]: a 3x3 conv over dT with M = Cin,
-        // C = Cout and the taps flipped
-        ConvOut o{dx, nullptr, nullptr, Cin, H, W, 1, 0, 0, ACT_NONE};
-        const size_t packed_bytes = qarig_conv2d_bwd_data_workspace_bytes(Cin, Cout, k);
-        return launch_conv3x3_ring(w, 9, (int64_t)Cin * 9, 1, dT, N, Cout, H, W, Cin, o, packed, st,
-                                   (float*)((char*)workspace + packed_bytes), ws_bytes - packed_bytes);
-    }
-    if (k == 3 && s == 2 && pad == 1 && H == 2 * Ho && W == 2 * Wo && conv3x3_ring_ok(N, Cout, Ho, Wo, Cin, dT, packed) &&
-        ((uintptr_t)dx & 7) == 0) {
-        // the four output-parity classes of dx as (1 + ry) x (1 + rx)-tap stride-1 products over dT on the ring,
-        // two column parities per workgroup (8-B stores), both row parities in one launch
-        const int64_t total = (int64_t)9 * Cin * Cout;
-        int blocks = (int)((total + 255) / 256);
-        if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(conv_s2_dgrad_pack_tap_kernel, dim3(blocks), dim3(256), 0, st, w, Cout, Cin, packed);
-        QARIG_CHECK_LAUNCH("conv2d_bwd_data pack");
-        const int P = N * Ho * Wo;
-        ConvGeom g{dT, N, Cout, Ho, Wo, Ho, Wo, 1, 1, 1, 0, -1, 0, -1, Cout, P};
-        ConvOut o{dx, nullptr, nullptr, Cin, H, W, 2, 0, 0, ACT_NONE};
-        const int tiles_p = P / BN;
-        hipLaunchKernelGGL((conv3x3_ring_kernel<true>), dim3((Cin / BM) * tiles_p, 2), dim3(NTHREADS), 0, st, packed, g,
-                           o, tiles_p, (unsigned)((int64_t)N * Cout * Ho * Wo * 4), (int64_t)0, 1, 1, (int64_t)0);
-        QARIG_CHECK_LAUNCH("conv2d_bwd_data ring");
-        return QARIG_OK;
+    {   // 3x3 / padding 1 with whole tiles: one ring launch, for stride 1 and for all four classes of stride 2
+        const ConvOut o{dx, nullptr, nullptr, Cin, H, W, s, 0, 0, ACT_NONE};
+        const ConvRingPlan p = conv2d_ring_plan(true, N, Cin, H, W, Cout, k, s, pad);
+        if (H == s * Ho && W == s * Wo && conv_ring_usable(p, dT, o, workspace, ws_bytes))
+            return run_conv_ring(p, dT, w, o, workspace, ws_bytes, false, st);
     }
     for (int ry = 0; ry < s; ++ry)
         for (int rx = 0; rx < s; ++rx) {
@@ -1583,40 +1576,17 @@ extern "C" int qarig_conv2d_bwd_data(const float* dT, int N, int Cout, int Ho, i
                        (rx + pad - kx0) / s, -1, Cout * nty * ntx, N * gh * gw};
             ConvOut o{dx, nullptr, nullptr, Cin, H, W, s, ry, rx, ACT_NONE};
             if (nty == 0 || ntx == 0) return QARIG_ERR_ARG;  // cannot happen for pad < k
-            const int64_t total = (int64_t)Cin * Cout * nty * ntx;
-            int blocks = (int)((total + 255) / 256);
-            if (blocks > 4096) blocks = 4096;
-            hipLaunchKernelGGL(conv_bwd_pack_kernel, dim3(blocks), dim3(256), 0, st, w, Cout, Cin, k,
-                               s, ky0, kx0, nty, ntx, packed);
+            hipLaunchKernelGGL(conv_bwd_pack_kernel, dim3(pack_grid((int64_t)Cin * Cout * nty * ntx)), dim3(256), 0, st, w,
+                               Cout, Cin, k, s, ky0, kx0, nty, ntx, packed);
             QARIG_CHECK_LAUNCH("conv2d_bwd_data pack");
             if (int e = launch_conv(packed, g, o, st)) return e;
         }
     return QARIG_OK;
 }
 
-// scratch of qarig_conv_transpose2d_bwd_data_ws: the tap-major weights + a few-image launch's split slabs
-extern "C" size_t qarig_conv_transpose2d_bwd_data_workspace_bytes_n(int N, int Cin, int H, int W, int Cout) {
-    const size_t base = qarig_conv_transpose2d_workspace_bytes(Cin, Cout);
-    if (!base || N < 1 || H < 1 || W < 1 || !qarig_dims_ok({N, Cin, H, W}, 1LL << 20, 1LL << 31)) return base;
-    if (Cout % 16 || Cin % BM || ((int64_t)N * H * W) % BN) return base;
-    return base + conv_split_slab_bytes((long)(Cin / BM) * ((int64_t)N * H * W / BN), Cout, (int64_t)N * Cin * H * W);
-}
-
 // d(input) of ConvTranspose2d(4,2,1): dT (N,Cout,2H,2W) -> dx (N,Cin,H,W) is a
 // Conv2d(k=4, stride 2, pad 1) over dT whose weight matrix [Cin][Cout*16] is the
 // ConvTranspose weight exactly as stored.
-static int convt_bwd_data_impl(const float* dT, int N, int Cout, int H, int W, const float* w, int Cin, float* dx,
-                               void* workspace, size_t ws_bytes, void* stream);
-extern "C" int qarig_conv_transpose2d_bwd_data(const float* dT, int N, int Cout, int H, int W,
-                                               const float* w, int Cin, float* dx, void* stream) {
-    return convt_bwd_data_impl(dT, N, Cout, H, W, w, Cin, dx, nullptr, 0, stream);
-}
-// The same with a scratch buffer (16 * Cin * Cout floats) for a tap-major copy of the weights: the strided
-// ring kernel then serves the layers whose tiles are whole (Cout % 16, Cin % 128, N*H*W % 128, W % 4 == 0).
-extern "C" int qarig_conv_transpose2d_bwd_data_ws(const float* dT, int N, int Cout, int H, int W, const float* w,
-                                                  int Cin, float* dx, void* workspace, size_t ws_bytes, void* stream) {
-    return convt_bwd_data_impl(dT, N, Cout, H, W, w, Cin, dx, workspace, ws_bytes, stream);
-}
 static int convt_bwd_data_impl(const float* dT, int N, int Cout, int H, int W, const float* w, int Cin, float* dx,
                                void* workspace, size_t ws_bytes, void* stream) {
     QARIG_CHECK_ARG(dT && w && dx, "conv_transpose2d_bwd_data: null pointer");
@@ -1626,43 +1596,20 @@ static int convt_bwd_data_impl(const float* dT, int N, int Cout, int H, int W, c
 
     ConvGeom g{dT, N, Cout, 2 * H, 2 * W, H, W, 2, 4, 4, -1, 1, -1, 1, Cout * 16, N * H * W};
     ConvOut o{dx, nullptr, nullptr, Cin, H, W, 1, 0, 0, ACT_NONE};
-    {   // Conv2d(4, stride 2, padding 1) over dT on the strided ring: 16 taps at offsets -1 .. 2
-        const int64_t P = (int64_t)N * H * W, xb = (int64_t)N * Cout * 4 * H * W * 4;
-        if (g_qarig_opt.conv_ring != 0 && workspace && ws_bytes >= (size_t)16 * Cin * Cout * sizeof(float) &&
-            Cout % 16 == 0 && Cin % BM == 0 && P % BN == 0 && W % 4 == 0 && xb < (1LL << 31) &&
-            (((uintptr_t)dT | (uintptr_t)workspace) & 15) == 0) {
-            hipStream_t st = (hipStream_t)stream;
-            float* packed = (float*)workspace;
-            const int64_t total = (int64_t)Cin * 16 * Cout;
-            int blocks = (int)((total + 255) / 256);
-            if (blocks > 4096) blocks = 4096;
-            // w (Cin, Cout, 4, 4): element (m = ci, c = co, tap) at ci * Cout * 16 + co * 16 + tap
-            hipLaunchKernelGGL(conv_pack_tap_kernel, dim3(blocks), dim3(256), 0, st, w, Cin, Cout, (int64_t)Cout * 16,
-                               (int64_t)16, 0, packed, 16);
-            QARIG_CHECK_LAUNCH("conv_transpose2d_bwd_data pack");
-            const int tiles_p = (int)(P / BN);
-            const size_t packed_bytes = (size_t)16 * Cin * Cout * sizeof(float);
-            const int64_t out_elems = (int64_t)N * Cin * H * W;
-            int splits = conv_ring_splits((long)(Cin / BM) * tiles_p, Cout);         // 16 * Cout / 16 k-tiles
-            if (splits > 1 && (ws_bytes < packed_bytes + (size_t)splits * out_elems * sizeof(float) ||
-                               ((uintptr_t)dx & 15)))
-                splits = 1;
-            if (splits > 1) {
-                float* slabs = (float*)((char*)workspace + packed_bytes);
-                ConvOut raw{slabs, nullptr, nullptr, Cin, H, W, 1, 0, 0, ACT_NONE};
-                hipLaunchKernelGGL((conv3x3_ring_kernel<false, true, false>), dim3((Cin / BM) * tiles_p, 1, splits),
-                                   dim3(NTHREADS), 0, st, packed, g, raw, tiles_p, (unsigned)xb, (int64_t)0, 0, splits,
-                                   out_elems);
-                QARIG_CHECK_LAUNCH("conv_transpose2d_bwd_data ring (split)");
-                return launch_conv_split_reduce(slabs, splits, o, N, st);
-            }
-            hipLaunchKernelGGL((conv3x3_ring_kernel<false, true, false>), dim3((Cin / BM) * tiles_p), dim3(NTHREADS), 0,
-                               st, packed, g, o, tiles_p, (unsigned)xb, (int64_t)0, 0, 1, (int64_t)0);
-            QARIG_CHECK_LAUNCH("conv_transpose2d_bwd_data ring");
-            return QARIG_OK;
-        }
-    }
+    const ConvRingPlan p = conv_ring_plan(RING_CONVT_DGRAD, N, Cout, H, W, Cin);
+    if (conv_ring_usable(p, dT, o, workspace, ws_bytes))
+        return run_conv_ring(p, dT, w, o, workspace, ws_bytes, false, (hipStream_t)stream);
     return launch_conv(w, g, o, (hipStream_t)stream);
+}
+extern "C" int qarig_conv_transpose2d_bwd_data(const float* dT, int N, int Cout, int H, int W,
+                                               const float* w, int Cin, float* dx, void* stream) {
+    return convt_bwd_data_impl(dT, N, Cout, H, W, w, Cin, dx, nullptr, 0, stream);
+}
+// The same with a scratch buffer (16 * Cin * Cout floats) for a tap-major copy of the weights: the strided
+// ring kernel then serves the layers whose tiles are whole (Cout % 16, Cin % 128, N*H*W % 128, W % 4 == 0).
+extern "C" int qarig_conv_transpose2d_bwd_data_ws(const float* dT, int N, int Cout, int H, int W, const float* w,
+                                                  int Cin, float* dx, void* workspace, size_t ws_bytes, void* stream) {
+    return convt_bwd_data_impl(dT, N, Cout, H, W, w, Cin, dx, workspace, ws_bytes, stream);
 }
 
 namespace qarig {

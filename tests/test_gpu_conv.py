@@ -419,7 +419,10 @@ def test_conv_transpose2d_input_gradient_ring_vs_fp64(N, Cin, H, W, Cout):
     ("convt", 4, 256, 16, 16, 128),     # 16 workgroups x 2 column parities, 4 parts of 16 k-tiles
     ("convt", 1, 512, 32, 32, 256),     # the README upsampling layer at one image: 8 parts
     ("direct", 4, 256, 64, 64, 3),      # the decoder's last layer: channels split over 8 waves
-    ("direct", 1, 64, 16, 16, 4)])
+    ("direct", 1, 64, 16, 16, 4),
+    ("s2", 2, 128, 32, 32, 256),        # the other ring products fall back through the same code (run_conv_ring):
+    ("dgrad", 1, 128, 16, 16, 128),     # stride-2 forward, 3x3 input gradient, ConvTranspose input gradient
+    ("convt_dgrad", 2, 128, 16, 16, 128)])
 def test_few_image_launches_split_the_reduction(kind, N, Cin, H, W, Cout):
     """At few images (generate_images.py:366 decodes the handful just sampled) the ring launches have too
     few tiles to fill the chip: the reduction is split over blockIdx.z into slabs that
@@ -433,6 +436,45 @@ def test_few_image_launches_split_the_reduction(kind, N, Cin, H, W, Cout):
     g = torch.Generator().manual_seed(N * 3 + Cin + Cout)
     x = torch.randn((N, Cin, H, W), generator=g)
     b = torch.randn(Cout, generator=g)
+    if kind in ("s2", "dgrad", "convt_dgrad"):
+        # the entry point itself, once with the scratch its _n function asks for and once with the packed weights' only
+        F = torch.nn.functional
+        if kind == "s2":
+            w = torch.randn((Cout, Cin, 3, 3), generator=g) / (3 * Cin ** 0.5)
+            ref = F.silu(F.conv2d(x.double(), w.double(), b.double(), stride=2, padding=1))
+            small, big = (lib.qarig_conv2d_fwd_workspace_bytes(Cin, Cout, 3),
+                          lib.qarig_conv2d_fwd_workspace_bytes_n(N, Cin, H, W, Cout, 3, 2))
+            src, bc = x.cuda(), b.cuda()
+            call = lambda out, ws, n: lib.qarig_conv2d_fwd_ws(ptr(src), N, Cin, H, W, ptr(wc), ptr(bc), Cout, 3, 2, 1, 1,
+                                                              ptr(out), None, ptr(ws), n, 0, _lib.stream())
+        elif kind == "dgrad":
+            w = torch.randn((Cout, Cin, 3, 3), generator=g) / (3 * Cin ** 0.5)
+            dT = torch.randn((N, Cout, H, W), generator=g)
+            ref = F.conv_transpose2d(dT.double(), w.double(), stride=1, padding=1)
+            small, big = (lib.qarig_conv2d_bwd_data_workspace_bytes(Cin, Cout, 3),
+                          lib.qarig_conv2d_bwd_data_workspace_bytes_n(N, Cin, H, W, Cout, 3, 1))
+            src = dT.cuda()
+            call = lambda out, ws, n: lib.qarig_conv2d_bwd_data(ptr(src), N, Cout, H, W, ptr(wc), Cin, 3, 1, 1, H, W,
+                                                                ptr(out), ptr(ws), n, _lib.stream())
+        else:
+            w = torch.randn((Cin, Cout, 4, 4), generator=g) / (4 * Cin ** 0.5)
+            dT = torch.randn((N, Cout, 2 * H, 2 * W), generator=g)
+            ref = F.conv2d(dT.double(), w.double(), stride=2, padding=1)
+            small, big = (lib.qarig_conv_transpose2d_workspace_bytes(Cin, Cout),
+                          lib.qarig_conv_transpose2d_bwd_data_workspace_bytes_n(N, Cin, H, W, Cout))
+            src = dT.cuda()
+            call = lambda out, ws, n: lib.qarig_conv_transpose2d_bwd_data_ws(ptr(src), N, Cout, H, W, ptr(wc), Cin,
+                                                                             ptr(out), ptr(ws), n, _lib.stream())
+        assert big > small
+        wc = w.cuda()
+        ws = torch.empty(big, dtype=torch.uint8, device="cuda")
+        y, y1 = (torch.empty(ref.shape, dtype=torch.float32, device="cuda") for _ in range(2))
+        rc, rc1 = call(y, ws, big), call(y1, ws, small)
+        torch.cuda.synchronize()
+        assert rc == 0 and rc1 == 0
+        assert rel_err(y, ref) < 4e-6
+        assert rel_err(y1, y) < 5e-6 and not torch.equal(y1, y)
+        return
     if kind == "convt":
         w = torch.randn((Cin, Cout, 4, 4), generator=g) / (4 * Cin ** 0.5)
         ref = torch.nn.functional.conv_transpose2d(x.double(), w.double(), b.double(), stride=2, padding=1)
