@@ -289,6 +289,20 @@ int qarig_decode_linear_f32(const float* X, int64_t ldx, int64_t x_gs, float eps
                             int64_t ldr, const float* mul, int64_t ldmul, float* C, int64_t ldc,
                             int64_t c_gs, int groups, int M, int N, int K, int act, void* stream);
 
+/* The same launch with the weights streamed as bf16: W is a row-major (N, K) bf16 image of the fp32 weight
+ * (qarig_cast_bf16: rounded once, to nearest even), ldw and w_gs in bf16 elements -- half the bytes per token
+ * of the Linear layers generate_images.py:283-286 evaluates per sampled token (models/layers.py:60-98).
+ * Only the weights are reduced: X, LN, the fp32 accumulation, bias / residual / act / mul and C are as in
+ * qarig_decode_linear_f32, and bf16 -> fp32 is exact, so the result is that entry's on the rounded weights
+ * (same fixed summation order per shape, no atomics).  Same shapes (qarig_decode_linear_supported) and
+ * checks, plus ldw % 8 == 0, w_gs % 8 == 0 and W 16-B aligned.  Weight-only: not the fp32 parity mode. */
+int qarig_decode_linear_bf16w(const float* X, int64_t ldx, int64_t x_gs, float eps,
+                              const float* gamma, const float* beta, const float* scale,
+                              const float* shift, int64_t ldmod, const void* W, int64_t ldw,
+                              int64_t w_gs, const float* bias, int64_t bias_gs, const float* residual,
+                              int64_t ldr, const float* mul, int64_t ldmul, float* C, int64_t ldc,
+                              int64_t c_gs, int groups, int M, int N, int K, int act, void* stream);
+
 /* ---- Device-resident sampling loop (generate_images.py:256-345) ------------------------------
  * The reference samples a token, appends it on the host and re-runs the decoder.  Here the loop's
  * state stays on the device and the host only enqueues launches, never reading a token back: `ctl` is an int32 array

@@ -42,6 +42,49 @@ __device__ __forceinline__ float4 ld4_nt(const float* p) {
 #endif
 }
 
+// Weight element types of the streaming kernels.  A lane's weight load carries E consecutive weights of a row and
+// meets E activations (E / 4 float4): fp32, 16 B = 4 weights; bf16 (row-major (N, K) images as qarig_cast_bf16 writes
+// them), 16 B = 8 weights, or 8 B = 4 weights for K = 256, where 64 lanes cover a row as they do in fp32.  bf16 -> fp32
+// is exact -- a shift for the low half of a dword, a mask for the high half: no rounding mode, subnormals pass.
+struct bf16w { uint16_t bits; };
+__device__ __forceinline__ float bf16_lo(uint32_t d) { return __uint_as_float(d << 16); }
+__device__ __forceinline__ float bf16_hi(uint32_t d) { return __uint_as_float(d & 0xffff0000u); }
+template <typename WT, int E> struct WLoad;
+template <> struct WLoad<float, 4> {
+    float4 r;
+    __device__ __forceinline__ void issue(const float* p) { r = ld4_nt(p); }
+    __device__ __forceinline__ void get(float4 (&w)[1]) const { w[0] = r; }
+};
+template <> struct WLoad<bf16w, 8> {
+    typedef uint32_t v4 __attribute__((ext_vector_type(4)));
+    v4 r;
+    __device__ __forceinline__ void issue(const bf16w* p) {
+#ifdef QARIG_DECODE_NO_NT
+        r = *reinterpret_cast<const v4*>(p);
+#else
+        r = __builtin_nontemporal_load(reinterpret_cast<const v4*>(p));
+#endif
+    }
+    __device__ __forceinline__ void get(float4 (&w)[2]) const {
+        w[0] = make_float4(bf16_lo(r.x), bf16_hi(r.x), bf16_lo(r.y), bf16_hi(r.y));
+        w[1] = make_float4(bf16_lo(r.z), bf16_hi(r.z), bf16_lo(r.w), bf16_hi(r.w));
+    }
+};
+template <> struct WLoad<bf16w, 4> {
+    typedef uint32_t v2 __attribute__((ext_vector_type(2)));
+    v2 r;
+    __device__ __forceinline__ void issue(const bf16w* p) {
+#ifdef QARIG_DECODE_NO_NT
+        r = *reinterpret_cast<const v2*>(p);
+#else
+        r = __builtin_nontemporal_load(reinterpret_cast<const v2*>(p));
+#endif
+    }
+    __device__ __forceinline__ void get(float4 (&w)[1]) const {
+        w[0] = make_float4(bf16_lo(r.x), bf16_hi(r.x), bf16_lo(r.y), bf16_hi(r.y));
+    }
+};
+
 template <int CTRL>
 __device__ __forceinline__ float dpp_lane(float x) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, true));
@@ -99,24 +142,27 @@ __device__ __forceinline__ int wave_sum_multi(float (&v)[V], int lane, bool& own
 
 // MR: activation rows held (M padded up); LN: 0 none, 1 gamma/beta, 2 scale/shift rows, 3 one scale/shift
 // row for every activation row (all rows of a decode step sit at the same window position);
-// J: 16-B weight loads per thread; KS: 1-K chunks of a weight row per thread (K = 1024 KS floats
-// when KS > 1).  256 threads.  K/4 = kq float4 per row:
+// WT, E: the weight element type and the weights per load (WLoad); a "unit" below is E consecutive k;
+// J: weight loads per thread; KS: 1-K chunks of a weight row per thread (K = 256 E KS when KS > 1).
+// 256 threads.  K/E = kq units per row:
 //   KS == 1: kq in {64, 128, 256}; the workgroup's load pass j covers 256/kq whole rows,
-//            thread t sits in row group t / kq at float4 t % kq; a column is summed over kq/64 waves;
+//            thread t sits in row group t / kq at unit t % kq; a column is summed over kq/64 waves;
 //   KS  > 1: kq = 256 KS; passes j = c KS + s cover chunk s of row c; a column is summed over all 4 waves.
-template <int MR, int LN, int J, int KS>
-__global__ __launch_bounds__(256) void decode_linear_kernel(const float* __restrict__ Xb, const float* __restrict__ Wb,
+template <typename WT, int E, int MR, int LN, int J, int KS>
+__global__ __launch_bounds__(256) void decode_linear_kernel(const float* __restrict__ Xb, const WT* __restrict__ Wb,
                                                             int64_t ldx, int64_t ldw, int M, int N, int K, int act,
                                                             int64_t x_gs, int64_t w_gs, DecLin p) {
-    static_assert(J % KS == 0 && (LN == 0 || KS == 1) && LN >= 0 && LN <= 3, "");
+    static_assert(J % KS == 0 && (LN == 0 || KS == 1) && LN >= 0 && LN <= 3 && (E == 4 || E == 8), "");
+    constexpr int Q = E / 4;            // float4 of activations per unit
+    constexpr int ES = E == 4 ? 2 : 3;  // log2 E
     constexpr int NC = J / KS;          // distinct columns per thread
     constexpr int V = NC * MR;          // partial sums per thread
     __shared__ float red[4][V];
     __shared__ float stat[4][MR];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     const int g = blockIdx.y;
-    // kq = K/4 is a power of two (host-checked): shifts instead of integer divisions
-    const int kqs = KS == 1 ? 31 - __builtin_clz(K >> 2) : 8;     // log2 kq (KS > 1: of the 256-float4 chunk)
+    // kq = K/E is a power of two (host-checked): shifts instead of integer divisions
+    const int kqs = KS == 1 ? 31 - __builtin_clz(K >> ES) : 8;    // log2 kq (KS > 1: of the 256-unit chunk)
     const int cgs = KS == 1 ? 8 - kqs : 0;                          // log2 CG, CG = 256 / kq row groups per pass
     const int WS = 4 >> cgs;                                        // waves that share a column
     const int cg = KS == 1 ? t >> kqs : 0;                          // wave-uniform
@@ -125,30 +171,38 @@ __global__ __launch_bounds__(256) void decode_linear_kernel(const float* __restr
     const int cws = ncs + cgs;                                      // log2 CW, CW = NC * CG columns of this workgroup
     const int n0 = blockIdx.x << cws;
     const float* X = Xb + (int64_t)g * x_gs;
-    const float* W = Wb + (int64_t)g * w_gs;
+    const WT* W = Wb + (int64_t)g * w_gs;
 
     // ---- every load of the launch, oldest first in the order they are needed.  No load sits behind a
     //      branch (the compiler waits for a conditional load where its value meets the alternative):
     //      rows / columns past the end re-read the last one, absent operands read X; what they produce
     //      is never stored.
     const int Ml = M - 1, Nl = N - 1;
-    float4 xv[KS][MR];
+    float4 xv[KS][MR][Q];
 #pragma unroll
     for (int s = 0; s < KS; ++s)
 #pragma unroll
         for (int m = 0; m < MR; ++m)
-            xv[s][m] = ld4(X + (int64_t)min(m, Ml) * ldx + 4 * (kc + 256 * s));
-    float4 lg, lb, ls[LN == 2 ? MR : 1], lh[LN == 2 ? MR : 1];
+#pragma unroll
+            for (int q = 0; q < Q; ++q)
+                xv[s][m][q] = ld4(X + (int64_t)min(m, Ml) * ldx + E * (kc + 256 * s) + 4 * q);
+    float4 lg[Q], lb[Q], ls[LN == 2 ? MR : 1][Q], lh[LN == 2 ? MR : 1][Q];
     if (LN == 1 || LN == 3) {
-        lg = ld4((LN == 1 ? p.gamma : p.scale) + 4 * kc);
-        lb = ld4((LN == 1 ? p.beta : p.shift) + 4 * kc);
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            lg[q] = ld4((LN == 1 ? p.gamma : p.scale) + E * kc + 4 * q);
+            lb[q] = ld4((LN == 1 ? p.beta : p.shift) + E * kc + 4 * q);
+        }
     }
     if (LN == 2) {
 #pragma unroll
         for (int m = 0; m < MR; ++m) {
-            const int64_t mo = (int64_t)min(m, Ml) * p.ldmod + 4 * kc;
-            ls[m] = ld4(p.scale + mo);
-            lh[m] = ld4(p.shift + mo);
+            const int64_t mo = (int64_t)min(m, Ml) * p.ldmod + E * kc;
+#pragma unroll
+            for (int q = 0; q < Q; ++q) {
+                ls[m][q] = ld4(p.scale + mo + 4 * q);
+                lh[m][q] = ld4(p.shift + mo + 4 * q);
+            }
         }
     }
     // the output this thread will finish: row t / CW, column t % CW
@@ -159,11 +213,11 @@ __global__ __launch_bounds__(256) void decode_linear_kernel(const float* __restr
     const float eb = *(p.bias ? p.bias + (int64_t)g * p.bias_gs + onc : X);
     const float er = *(p.residual ? p.residual + (int64_t)omc * p.ldr + onc : X);
     const float em = *(p.mul ? p.mul + (int64_t)omc * p.ldmul + onc : X);
-    float4 wv[J];
+    WLoad<WT, E> wv[J];
 #pragma unroll
     for (int j = 0; j < J; ++j) {
         const int c = j / KS, s = j % KS;
-        wv[j] = ld4_nt(W + (int64_t)min(n0 + (c << cgs) + cg, Nl) * ldw + 4 * (kc + 256 * s));
+        wv[j].issue(W + (int64_t)min(n0 + (c << cgs) + cg, Nl) * ldw + E * (kc + 256 * s));
     }
     __builtin_amdgcn_sched_barrier(0);      // nothing that waits for a load moves in front of the last issue
 
@@ -173,7 +227,11 @@ __global__ __launch_bounds__(256) void decode_linear_kernel(const float* __restr
         const float invK = 1.0f / (float)K;       // K is a power of two here: exact
         float s1[MR];
 #pragma unroll
-        for (int m = 0; m < MR; ++m) s1[m] = (xv[0][m].x + xv[0][m].y) + (xv[0][m].z + xv[0][m].w);
+        for (int m = 0; m < MR; ++m) {
+            s1[m] = (xv[0][m][0].x + xv[0][m][0].y) + (xv[0][m][0].z + xv[0][m][0].w);
+#pragma unroll
+            for (int q = 1; q < Q; ++q) s1[m] += (xv[0][m][q].x + xv[0][m][q].y) + (xv[0][m][q].z + xv[0][m][q].w);
+        }
         bool own;
         int idx = wave_sum_multi<MR>(s1, lane, own);
         if (own) stat[w][idx] = s1[0];
@@ -190,11 +248,14 @@ __global__ __launch_bounds__(256) void decode_linear_kernel(const float* __restr
         float s2[MR];
 #pragma unroll
         for (int m = 0; m < MR; ++m) {
-            float4& x = xv[0][m];
-            x.x -= mean[m]; x.y -= mean[m]; x.z -= mean[m]; x.w -= mean[m];
-            float q = x.x * x.x;
-            q = fmaf(x.y, x.y, q); q = fmaf(x.z, x.z, q); q = fmaf(x.w, x.w, q);
-            s2[m] = q;
+#pragma unroll
+            for (int q = 0; q < Q; ++q) {
+                float4& x = xv[0][m][q];
+                x.x -= mean[m]; x.y -= mean[m]; x.z -= mean[m]; x.w -= mean[m];
+                float sq = q == 0 ? x.x * x.x : fmaf(x.x, x.x, s2[m]);
+                sq = fmaf(x.y, x.y, sq); sq = fmaf(x.z, x.z, sq); sq = fmaf(x.w, x.w, sq);
+                s2[m] = sq;
+            }
         }
         idx = wave_sum_multi<MR>(s2, lane, own);
         if (own) stat[w][idx] = s2[0];
@@ -207,11 +268,14 @@ __global__ __launch_bounds__(256) void decode_linear_kernel(const float* __restr
             // v_rsq_f32: 1 ulp of 1 / sqrt() -- 6e-8 relative on the row, far inside the 2e-6 of the parity tests
             // (every vector instruction of this single-wave-per-SIMD kernel is on the launch's critical path)
             const float rstd = __builtin_amdgcn_rsqf(a * invK + p.eps);
-            float4& x = xv[0][m];
-            const float4 gg = LN == 2 ? ls[LN == 2 ? m : 0] : lg;
-            const float4 hh = LN == 2 ? lh[LN == 2 ? m : 0] : lb;
-            x.x = fmaf(x.x * rstd, gg.x, hh.x); x.y = fmaf(x.y * rstd, gg.y, hh.y);
-            x.z = fmaf(x.z * rstd, gg.z, hh.z); x.w = fmaf(x.w * rstd, gg.w, hh.w);
+#pragma unroll
+            for (int q = 0; q < Q; ++q) {
+                float4& x = xv[0][m][q];
+                const float4 gg = LN == 2 ? ls[LN == 2 ? m : 0][q] : lg[q];
+                const float4 hh = LN == 2 ? lh[LN == 2 ? m : 0][q] : lb[q];
+                x.x = fmaf(x.x * rstd, gg.x, hh.x); x.y = fmaf(x.y * rstd, gg.y, hh.y);
+                x.z = fmaf(x.z * rstd, gg.z, hh.z); x.w = fmaf(x.w * rstd, gg.w, hh.w);
+            }
         }
     }
 
@@ -222,11 +286,16 @@ __global__ __launch_bounds__(256) void decode_linear_kernel(const float* __restr
 #pragma unroll
     for (int j = 0; j < J; ++j) {
         const int c = j / KS, s = j % KS;
+        float4 wq[Q];
+        wv[j].get(wq);
 #pragma unroll
         for (int m = 0; m < MR; ++m) {
             float a = acc[c * MR + m];
-            a = fmaf(wv[j].x, xv[s][m].x, a); a = fmaf(wv[j].y, xv[s][m].y, a);
-            a = fmaf(wv[j].z, xv[s][m].z, a); a = fmaf(wv[j].w, xv[s][m].w, a);
+#pragma unroll
+            for (int q = 0; q < Q; ++q) {
+                a = fmaf(wq[q].x, xv[s][m][q].x, a); a = fmaf(wq[q].y, xv[s][m][q].y, a);
+                a = fmaf(wq[q].z, xv[s][m][q].z, a); a = fmaf(wq[q].w, xv[s][m][q].w, a);
+            }
             acc[c * MR + m] = a;
         }
     }
@@ -273,44 +342,52 @@ __device__ __forceinline__ int wave_sum_multi_index(int lane, bool& owner) {
 // rows in every lane (decode_linear_kernel<16, ...>: 2,057 instructions in its LayerNorm form, every one of them on
 // the critical path of a single-wave-per-SIMD launch) a lane now carries 4 rows: a quarter of the LayerNorm and
 // statistics arithmetic, sums that stay inside the wave (no LDS hand-over, no workgroup barrier at all), the same
-// fma count.  KW: 256-float chunks of a weight row per lane (K = 256 KW); a lane's loads j = c KW + s cover chunk
-// s of column c.
-template <int LN, int CW, int KW>
-__global__ __launch_bounds__(256) void decode_linear_rows_kernel(const float* __restrict__ Xb, const float* __restrict__ Wb,
+// fma count.  WT, E as in decode_linear_kernel; KW: 64-unit chunks of a weight row per lane (K = 64 E KW); a lane's
+// loads j = c KW + s cover chunk s of column c.
+template <typename WT, int E, int LN, int CW, int KW>
+__global__ __launch_bounds__(256) void decode_linear_rows_kernel(const float* __restrict__ Xb, const WT* __restrict__ Wb,
                                                                  int64_t ldx, int64_t ldw, int M, int N, int K, int act,
                                                                  int64_t x_gs, int64_t w_gs, DecLin p) {
-    static_assert(LN >= 0 && LN <= 3 && CW * 4 <= 64, "");
+    static_assert(LN >= 0 && LN <= 3 && CW * 4 <= 64 && (E == 4 || E == 8), "");
+    constexpr int Q = E / 4;
     constexpr int V = CW * 4;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if (4 * w >= M) return;                 // a whole wave without rows (no barrier below)
     const int g = blockIdx.y;
     const int n0 = blockIdx.x * CW;
     const float* X = Xb + (int64_t)g * x_gs;
-    const float* W = Wb + (int64_t)g * w_gs;
+    const WT* W = Wb + (int64_t)g * w_gs;
     const int Ml = M - 1, Nl = N - 1;
-    float4 xv[KW][4];
+    float4 xv[KW][4][Q];
 #pragma unroll
     for (int s = 0; s < KW; ++s)
 #pragma unroll
         for (int m = 0; m < 4; ++m)
-            xv[s][m] = ld4(X + (int64_t)min(4 * w + m, Ml) * ldx + 4 * (lane + 64 * s));
-    float4 lg[(LN == 1 || LN == 3) ? KW : 1], lb[(LN == 1 || LN == 3) ? KW : 1];
-    float4 ls[LN == 2 ? KW : 1][4], lh[LN == 2 ? KW : 1][4];
+#pragma unroll
+            for (int q = 0; q < Q; ++q)
+                xv[s][m][q] = ld4(X + (int64_t)min(4 * w + m, Ml) * ldx + E * (lane + 64 * s) + 4 * q);
+    float4 lg[(LN == 1 || LN == 3) ? KW : 1][Q], lb[(LN == 1 || LN == 3) ? KW : 1][Q];
+    float4 ls[LN == 2 ? KW : 1][4][Q], lh[LN == 2 ? KW : 1][4][Q];
     if (LN == 1 || LN == 3) {
 #pragma unroll
-        for (int s = 0; s < KW; ++s) {
-            lg[s] = ld4((LN == 1 ? p.gamma : p.scale) + 4 * (lane + 64 * s));
-            lb[s] = ld4((LN == 1 ? p.beta : p.shift) + 4 * (lane + 64 * s));
-        }
+        for (int s = 0; s < KW; ++s)
+#pragma unroll
+            for (int q = 0; q < Q; ++q) {
+                lg[s][q] = ld4((LN == 1 ? p.gamma : p.scale) + E * (lane + 64 * s) + 4 * q);
+                lb[s][q] = ld4((LN == 1 ? p.beta : p.shift) + E * (lane + 64 * s) + 4 * q);
+            }
     }
     if (LN == 2) {
 #pragma unroll
         for (int s = 0; s < KW; ++s)
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
-                const int64_t mo = (int64_t)min(4 * w + m, Ml) * p.ldmod + 4 * (lane + 64 * s);
-                ls[s][m] = ld4(p.scale + mo);
-                lh[s][m] = ld4(p.shift + mo);
+                const int64_t mo = (int64_t)min(4 * w + m, Ml) * p.ldmod + E * (lane + 64 * s);
+#pragma unroll
+                for (int q = 0; q < Q; ++q) {
+                    ls[s][m][q] = ld4(p.scale + mo + 4 * q);
+                    lh[s][m][q] = ld4(p.shift + mo + 4 * q);
+                }
             }
     }
     bool own;
@@ -321,12 +398,12 @@ __global__ __launch_bounds__(256) void decode_linear_rows_kernel(const float* __
     const float eb = *(p.bias ? p.bias + (int64_t)g * p.bias_gs + onc : X);
     const float er = *(p.residual ? p.residual + (int64_t)omc * p.ldr + onc : X);
     const float em = *(p.mul ? p.mul + (int64_t)omc * p.ldmul + onc : X);
-    float4 wv[CW * KW];
+    WLoad<WT, E> wv[CW * KW];
 #pragma unroll
     for (int c = 0; c < CW; ++c)
 #pragma unroll
         for (int s = 0; s < KW; ++s)
-            wv[c * KW + s] = ld4_nt(W + (int64_t)min(n0 + c, Nl) * ldw + 4 * (lane + 64 * s));
+            wv[c * KW + s].issue(W + (int64_t)min(n0 + c, Nl) * ldw + E * (lane + 64 * s));
     __builtin_amdgcn_sched_barrier(0);
 
     if (LN) {
@@ -336,7 +413,10 @@ __global__ __launch_bounds__(256) void decode_linear_rows_kernel(const float* __
         for (int m = 0; m < 4; ++m) {
             float a = 0.0f;
 #pragma unroll
-            for (int s = 0; s < KW; ++s) a += (xv[s][m].x + xv[s][m].y) + (xv[s][m].z + xv[s][m].w);
+            for (int s = 0; s < KW; ++s)
+#pragma unroll
+                for (int q = 0; q < Q; ++q)
+                    a += (xv[s][m][q].x + xv[s][m][q].y) + (xv[s][m][q].z + xv[s][m][q].w);
             s1[m] = a;
         }
         bool o4;
@@ -347,27 +427,31 @@ __global__ __launch_bounds__(256) void decode_linear_rows_kernel(const float* __
         float s2[4];
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
-            float q = 0.0f;
+            float sq = 0.0f;
 #pragma unroll
-            for (int s = 0; s < KW; ++s) {
-                float4& x = xv[s][m];
-                x.x -= mean[m]; x.y -= mean[m]; x.z -= mean[m]; x.w -= mean[m];
-                q = fmaf(x.x, x.x, q); q = fmaf(x.y, x.y, q); q = fmaf(x.z, x.z, q); q = fmaf(x.w, x.w, q);
-            }
-            s2[m] = q;
+            for (int s = 0; s < KW; ++s)
+#pragma unroll
+                for (int q = 0; q < Q; ++q) {
+                    float4& x = xv[s][m][q];
+                    x.x -= mean[m]; x.y -= mean[m]; x.z -= mean[m]; x.w -= mean[m];
+                    sq = fmaf(x.x, x.x, sq); sq = fmaf(x.y, x.y, sq); sq = fmaf(x.z, x.z, sq); sq = fmaf(x.w, x.w, sq);
+                }
+            s2[m] = sq;
         }
         wave_sum_multi<4>(s2, lane, o4);
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
             const float rstd = __builtin_amdgcn_rsqf(__shfl(s2[0], 4 * m, 64) * invK + p.eps);
 #pragma unroll
-            for (int s = 0; s < KW; ++s) {
-                float4& x = xv[s][m];
-                const float4 gg = LN == 2 ? ls[LN == 2 ? s : 0][m] : lg[LN == 2 ? 0 : s];
-                const float4 hh = LN == 2 ? lh[LN == 2 ? s : 0][m] : lb[LN == 2 ? 0 : s];
-                x.x = fmaf(x.x * rstd, gg.x, hh.x); x.y = fmaf(x.y * rstd, gg.y, hh.y);
-                x.z = fmaf(x.z * rstd, gg.z, hh.z); x.w = fmaf(x.w * rstd, gg.w, hh.w);
-            }
+            for (int s = 0; s < KW; ++s)
+#pragma unroll
+                for (int q = 0; q < Q; ++q) {
+                    float4& x = xv[s][m][q];
+                    const float4 gg = LN == 2 ? ls[LN == 2 ? s : 0][m][q] : lg[LN == 2 ? 0 : s][q];
+                    const float4 hh = LN == 2 ? lh[LN == 2 ? s : 0][m][q] : lb[LN == 2 ? 0 : s][q];
+                    x.x = fmaf(x.x * rstd, gg.x, hh.x); x.y = fmaf(x.y * rstd, gg.y, hh.y);
+                    x.z = fmaf(x.z * rstd, gg.z, hh.z); x.w = fmaf(x.w * rstd, gg.w, hh.w);
+                }
         }
     }
 
@@ -377,15 +461,20 @@ __global__ __launch_bounds__(256) void decode_linear_rows_kernel(const float* __
 #pragma unroll
     for (int c = 0; c < CW; ++c)
 #pragma unroll
-        for (int s = 0; s < KW; ++s)
+        for (int s = 0; s < KW; ++s) {
+            float4 wq[Q];
+            wv[c * KW + s].get(wq);
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
-                const float4 wq = wv[c * KW + s];
                 float a = acc[c * 4 + m];
-                a = fmaf(wq.x, xv[s][m].x, a); a = fmaf(wq.y, xv[s][m].y, a);
-                a = fmaf(wq.z, xv[s][m].z, a); a = fmaf(wq.w, xv[s][m].w, a);
+#pragma unroll
+                for (int q = 0; q < Q; ++q) {
+                    a = fmaf(wq[q].x, xv[s][m][q].x, a); a = fmaf(wq[q].y, xv[s][m][q].y, a);
+                    a = fmaf(wq[q].z, xv[s][m][q].z, a); a = fmaf(wq[q].w, xv[s][m][q].w, a);
+                }
                 acc[c * 4 + m] = a;
             }
+        }
     bool own2;
     wave_sum_multi<V>(acc, lane, own2);        // lands where wave_sum_multi_index said
     if (oval) {
@@ -1085,30 +1174,34 @@ extern "C" int qarig_decode_linear_supported(int M, int N, int K, int ln) {
     return (K == 2048 || K == 4096) && !ln;
 }
 
-struct DecLinHead { const float* X; const float* W; int64_t ldx, ldw; int M, N, K, act; int64_t x_gs, w_gs; };
+template <typename WT>
+struct DecLinHead { const float* X; const WT* W; int64_t ldx, ldw; int M, N, K, act; int64_t x_gs, w_gs; };
 
-template <int MR, int LN>
-static void launch_decode_linear(const DecLinHead& h, const DecLin& p, int groups, hipStream_t st) {
-    const int kq = h.K / 4;
+// E weights per load: kq = K/E units per row.  bf16 images take E = 8 (16-B loads) except at K = 256, where 8-B loads
+// keep 64 lanes on a row (E = 4: the fp32 mapping of K = 256); E = 4 is instantiated for that K alone.
+template <typename WT, int E, int MR, int LN>
+static void launch_decode_linear(const DecLinHead<WT>& h, const DecLin& p, int groups, hipStream_t st) {
+    constexpr bool f32 = sizeof(WT) == 4;
+    const int kq = h.K / E;
     auto grid = [&](int cw) { return dim3((h.N + cw - 1) / cw, groups); };
     auto wgs = [&](int cw) { return (int64_t)((h.N + cw - 1) / cw) * groups; };
-#define QARIG_DL(J, KS, CW)                                                                                     \
-    hipLaunchKernelGGL((decode_linear_kernel<MR, LN, J, KS>), grid(CW), dim3(256), 0, st, h.X, h.W, h.ldx, h.ldw, \
+#define QARIG_DL(J, KS, CW)                                                                                         \
+    hipLaunchKernelGGL((decode_linear_kernel<WT, E, MR, LN, J, KS>), grid(CW), dim3(256), 0, st, h.X, h.W, h.ldx, h.ldw, \
                        h.M, h.N, h.K, h.act, h.x_gs, h.w_gs, p)
     if (kq <= 256) {
         const int CG = 256 / kq;
-        // 16 KB of weights per workgroup while that leaves >= 256 workgroups, else fewer bytes each
+        // 16 KB of weights (fp32; 4 load passes) per workgroup while that leaves >= 256 workgroups, else fewer
         // (16 rows of per-row AdaLN operands leave no registers for four loads)
         if constexpr (!(MR == 16 && LN == 2)) {
             if (wgs(4 * CG) >= 256) { QARIG_DL(4, 1, 4 * CG); return; }
         }
         if (wgs(2 * CG) >= 256) QARIG_DL(2, 1, 2 * CG);
         else QARIG_DL(1, 1, CG);
-    } else if constexpr (LN == 0) {
+    } else if constexpr (LN == 0 && (f32 || E == 8)) {
         if (kq == 512) {
             if (wgs(2) >= 256) QARIG_DL(4, 2, 2);
             else QARIG_DL(2, 2, 1);
-        } else {
+        } else if constexpr (f32) {
             QARIG_DL(4, 4, 1);
         }
     }
@@ -1116,40 +1209,74 @@ static void launch_decode_linear(const DecLinHead& h, const DecLin& p, int group
 }
 
 /* C-ABI: see include/qarig.h */
-// 5 ... 16 rows, K <= 2048: the row-split kernel.  CW columns per workgroup: 16 KB of weights while that leaves
+// 5 ... 16 rows, K <= 512 E: the row-split kernel.  CW columns per workgroup: 16 load passes while that leaves
 // >= 256 workgroups, else a quarter of it.
-template <int LN>
-static bool launch_decode_linear_rows(const DecLinHead& h, const DecLin& p, int groups, hipStream_t st) {
-    const int kw = h.K / 256;
+template <typename WT, int E, int LN>
+static bool launch_decode_linear_rows(const DecLinHead<WT>& h, const DecLin& p, int groups, hipStream_t st) {
+    constexpr bool f32 = sizeof(WT) == 4;
+    const int kw = h.K / (64 * E);
     // one wave per 4 rows; <= 4 rows: single-wave workgroups, so four times the workgroups for the bytes per CU
     const int threads = 64 * ((h.M + 3) / 4);
     const int64_t want = h.M <= 4 ? 1024 : 256;
     auto wgs = [&](int cw) { return (int64_t)((h.N + cw - 1) / cw) * groups; };
-#define QARIG_DR(CW, KW)                                                                                                  \
-    hipLaunchKernelGGL((decode_linear_rows_kernel<LN, CW, KW>), dim3((h.N + CW - 1) / CW, groups), dim3(threads), 0, st, \
-                       h.X, h.W, h.ldx, h.ldw, h.M, h.N, h.K, h.act, h.x_gs, h.w_gs, p)
-    switch (kw) {
-        case 1: if (wgs(16) >= want) QARIG_DR(16, 1); else QARIG_DR(4, 1); return true;
-        case 2: if (wgs(8) >= want) QARIG_DR(8, 2); else QARIG_DR(2, 2); return true;
-        case 4: if (wgs(4) >= want) QARIG_DR(4, 4); else QARIG_DR(1, 4); return true;
-        case 8:
-            if constexpr (LN == 0) {
-                if (wgs(2) >= want) QARIG_DR(2, 8); else QARIG_DR(1, 8);
-                return true;
-            }
-            return false;
-        default: return false;
+#define QARIG_DR(CW, KW)                                                                                      \
+    hipLaunchKernelGGL((decode_linear_rows_kernel<WT, E, LN, CW, KW>), dim3((h.N + CW - 1) / CW, groups), dim3(threads), \
+                       0, st, h.X, h.W, h.ldx, h.ldw, h.M, h.N, h.K, h.act, h.x_gs, h.w_gs, p)
+    if (kw == 1) {
+        if (wgs(16) >= want) QARIG_DR(16, 1); else QARIG_DR(4, 1);
+        return true;
     }
+    if constexpr (f32 || E == 8) {
+        switch (kw) {
+            case 2: if (wgs(8) >= want) QARIG_DR(8, 2); else QARIG_DR(2, 2); return true;
+            case 4:         // a bf16 row of 4 chunks is K = 2048: no LayerNorm form (qarig_decode_linear_supported)
+                if constexpr (f32 || LN == 0) {
+                    if (wgs(4) >= want) QARIG_DR(4, 4); else QARIG_DR(1, 4);
+                    return true;
+                }
+                return false;
+            case 8:
+                if constexpr (LN == 0) {
+                    if (wgs(2) >= want) QARIG_DR(2, 8); else QARIG_DR(1, 8);
+                    return true;
+                }
+                return false;
+            default: return false;
+        }
+    }
+    return false;
 #undef QARIG_DR
 }
 
-extern "C" int qarig_decode_linear_f32(const float* X, int64_t ldx, int64_t x_gs, float eps,
-                                       const float* gamma, const float* beta, const float* scale,
-                                       const float* shift, int64_t ldmod, const float* W, int64_t ldw,
-                                       int64_t w_gs, const float* bias, int64_t bias_gs,
-                                       const float* residual, int64_t ldr, const float* mul,
-                                       int64_t ldmul, float* C, int64_t ldc, int64_t c_gs, int groups,
-                                       int M, int N, int K, int act, void* stream) {
+template <typename WT, int E, int MR>
+static void launch_decode_linear_ln(int ln, const DecLinHead<WT>& h, const DecLin& p, int groups, hipStream_t st) {
+    switch (ln) {
+        case 0: launch_decode_linear<WT, E, MR, 0>(h, p, groups, st); break;
+        case 1: launch_decode_linear<WT, E, MR, 1>(h, p, groups, st); break;
+        case 2: launch_decode_linear<WT, E, MR, 2>(h, p, groups, st); break;
+        default: launch_decode_linear<WT, E, MR, 3>(h, p, groups, st); break;
+    }
+}
+
+template <typename WT, int E>
+static bool launch_decode_linear_rows_ln(int ln, const DecLinHead<WT>& h, const DecLin& p, int groups, hipStream_t st) {
+    switch (ln) {
+        case 0: return launch_decode_linear_rows<WT, E, 0>(h, p, groups, st);
+        case 1: return launch_decode_linear_rows<WT, E, 1>(h, p, groups, st);
+        case 2: return launch_decode_linear_rows<WT, E, 2>(h, p, groups, st);
+        default: return launch_decode_linear_rows<WT, E, 3>(h, p, groups, st);
+    }
+}
+
+// The two entry points below: WA = weight elements per 16 B (strides and the group stride are multiples of it).
+template <typename WT>
+static int decode_linear_entry(const float* X, int64_t ldx, int64_t x_gs, float eps, const float* gamma,
+                               const float* beta, const float* scale, const float* shift, int64_t ldmod, const WT* W,
+                               int64_t ldw, int64_t w_gs, const float* bias, int64_t bias_gs, const float* residual,
+                               int64_t ldr, const float* mul, int64_t ldmul, float* C, int64_t ldc, int64_t c_gs,
+                               int groups, int M, int N, int K, int act, void* stream) {
+    constexpr bool f32 = sizeof(WT) == 4;
+    constexpr int WA = 16 / (int)sizeof(WT);
     QARIG_CHECK_ARG(X && W && C, "decode_linear: null operand");
     QARIG_CHECK_ARG(groups >= 1 && groups <= 65535, "decode_linear: bad group count %d", groups);
     QARIG_CHECK_ARG((gamma == nullptr) == (beta == nullptr), "decode_linear: gamma/beta pair");
@@ -1163,36 +1290,64 @@ extern "C" int qarig_decode_linear_f32(const float* X, int64_t ldx, int64_t x_gs
     QARIG_CHECK_ARG(act >= 0 && act <= 3, "decode_linear: bad activation id");
     QARIG_CHECK_ARG(!ln || eps > 0.0f, "decode_linear: eps must be positive");
     auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
-    QARIG_CHECK_ARG(al16(X) && al16(W) && ldx % 4 == 0 && ldw % 4 == 0 && x_gs % 4 == 0 && w_gs % 4 == 0 &&
+    QARIG_CHECK_ARG(al16(X) && al16(W) && ldx % 4 == 0 && ldw % WA == 0 && x_gs % 4 == 0 && w_gs % WA == 0 &&
                         al16(gamma) && al16(beta) && al16(scale) && al16(shift) && ldmod % 4 == 0,
                     "decode_linear: operands must be 16-B aligned");
     QARIG_CHECK_ARG(ldx >= K && ldw >= K && ldc >= N && (!residual || ldr >= N) && (!mul || ldmul == 0 || ldmul >= N) &&
                         (!scale || ldmod == 0 || ldmod >= K),
                     "decode_linear: a row stride is shorter than its row");
-    const DecLinHead h{X, W, ldx, ldw, M, N, K, act, x_gs, w_gs};
+    const DecLinHead<WT> h{X, W, ldx, ldw, M, N, K, act, x_gs, w_gs};
     const DecLin p{bias, bias_gs, C, ldc, c_gs, residual, ldr, mul, ldmul, gamma, beta, scale, shift, ldmod, eps};
     hipStream_t st = (hipStream_t)stream;
-#define QARIG_DL_LN(MR)                                                     \
-    switch (ln) {                                                           \
-        case 0: launch_decode_linear<MR, 0>(h, p, groups, st); break;          \
-        case 1: launch_decode_linear<MR, 1>(h, p, groups, st); break;          \
-        case 2: launch_decode_linear<MR, 2>(h, p, groups, st); break;          \
-        default: launch_decode_linear<MR, 3>(h, p, groups, st); break;         \
-    }
-    bool done = false;
-    if ((M > 4 && g_qarig_opt.decode_rows != 0) || g_qarig_opt.decode_rows == 2) {
-        switch (ln) {
-            case 0: done = launch_decode_linear_rows<0>(h, p, groups, st); break;
-            case 1: done = launch_decode_linear_rows<1>(h, p, groups, st); break;
-            case 2: done = launch_decode_linear_rows<2>(h, p, groups, st); break;
-            default: done = launch_decode_linear_rows<3>(h, p, groups, st); break;
+    if constexpr (f32) {
+        bool done = false;
+        if ((M > 4 && g_qarig_opt.decode_rows != 0) || g_qarig_opt.decode_rows == 2)
+            done = launch_decode_linear_rows_ln<WT, 4>(ln, h, p, groups, st);
+        if (done) {
+        } else if (M <= 4) {
+            launch_decode_linear_ln<WT, 4, 4>(ln, h, p, groups, st);
+        } else {
+            launch_decode_linear_ln<WT, 4, 16>(ln, h, p, groups, st);
         }
+    } else {
+        // the row-split kernel takes every K of a bf16 image (K = 4096 is 8 chunks of 512), so 5 ... 16 rows always
+        // run on it: the all-rows kernel exists for <= 4 rows only (the decode_rows = 0 ablation is an fp32 one)
+        const bool rows = M > 4 || g_qarig_opt.decode_rows == 2;
+        bool done = true;
+        if (K == 256) {
+            if (rows) done = launch_decode_linear_rows_ln<WT, 4>(ln, h, p, groups, st);
+            else launch_decode_linear_ln<WT, 4, 4>(ln, h, p, groups, st);
+        } else {
+            if (rows) done = launch_decode_linear_rows_ln<WT, 8>(ln, h, p, groups, st);
+            else launch_decode_linear_ln<WT, 8, 4>(ln, h, p, groups, st);
+        }
+        QARIG_CHECK_ARG(done, "decode_linear: no bf16-weight kernel for M=%d K=%d ln=%d", M, K, ln);
     }
-    if (done) {
-    } else if (M <= 4) { QARIG_DL_LN(4) } else { QARIG_DL_LN(16) }
-#undef QARIG_DL_LN
     QARIG_CHECK_LAUNCH("decode_linear");
     return QARIG_OK;
+}
+
+extern "C" int qarig_decode_linear_f32(const float* X, int64_t ldx, int64_t x_gs, float eps,
+                                       const float* gamma, const float* beta, const float* scale,
+                                       const float* shift, int64_t ldmod, const float* W, int64_t ldw,
+                                       int64_t w_gs, const float* bias, int64_t bias_gs,
+                                       const float* residual, int64_t ldr, const float* mul,
+                                       int64_t ldmul, float* C, int64_t ldc, int64_t c_gs, int groups,
+                                       int M, int N, int K, int act, void* stream) {
+    return decode_linear_entry<float>(X, ldx, x_gs, eps, gamma, beta, scale, shift, ldmod, W, ldw, w_gs, bias, bias_gs,
+                                      residual, ldr, mul, ldmul, C, ldc, c_gs, groups, M, N, K, act, stream);
+}
+
+extern "C" int qarig_decode_linear_bf16w(const float* X, int64_t ldx, int64_t x_gs, float eps,
+                                         const float* gamma, const float* beta, const float* scale,
+                                         const float* shift, int64_t ldmod, const void* W, int64_t ldw,
+                                         int64_t w_gs, const float* bias, int64_t bias_gs,
+                                         const float* residual, int64_t ldr, const float* mul,
+                                         int64_t ldmul, float* C, int64_t ldc, int64_t c_gs, int groups,
+                                         int M, int N, int K, int act, void* stream) {
+    return decode_linear_entry<bf16w>(X, ldx, x_gs, eps, gamma, beta, scale, shift, ldmod, (const bf16w*)W, ldw, w_gs,
+                                      bias, bias_gs, residual, ldr, mul, ldmul, C, ldc, c_gs, groups, M, N, K, act,
+                                      stream);
 }
 
 

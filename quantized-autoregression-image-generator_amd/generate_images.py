@@ -57,6 +57,12 @@ def parse_args():
                         "less than this share of the mass in front of them (in (0, 1]; 1: off); applied after "
                         "--top-k.  Kept probabilities are not renormalised: best-of-num_beam still ranks chunks by "
                         "the model's own likelihood.  Overrides the config's per-stage \"top_p\" for all stages.")
+    p.add_argument("--decode-weights", choices=["f32", "bf16"], default="f32",
+                   help="(additive) weights of the cached single-token decode steps: 'bf16' streams every Linear weight "
+                        "of a step as a bf16 image (rounded once, to nearest even; half the bytes per token) when "
+                        "images x num_beam <= 16 and the model fits the streaming kernel.  Weight-only: activations, "
+                        "accumulation, LayerNorm, attention, the key/value cache and sampling stay fp32.  Not the "
+                        "fp32 parity mode.")
     return vars(p.parse_args())
 
 
@@ -128,7 +134,8 @@ def main():
                     beam_width=data["beam_width"], mode="generate",
                     progress=lambda i, t: log(f"{i:,} / {t:,}"), batch_beams=args["batch_beams"],
                     use_kv_cache=not args["no_kv_cache"], sampler=args["sampler"],
-                    window_graph=args["window_graph"], top_k=top_k, top_p=top_p)
+                    window_graph=args["window_graph"], top_k=top_k, top_p=top_p,
+                    decode_weights=args["decode_weights"])
                 hr_input = hr_input[:, 1:] - shift
             else:                                        # more ranks than images: nothing to generate here
                 hr_input = torch.zeros((0, total_Seq), dtype=torch.int64, device=device)

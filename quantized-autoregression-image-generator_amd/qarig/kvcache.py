@@ -39,6 +39,7 @@ import torch
 
 from models.layers import _lin_params, _mlp2_forward, _norm_forward
 from . import functional as QF
+from . import functional_lp as QL
 from . import ops
 
 # LayerNorm (affine or AdaLN form) inside the launch of the Linear that reads it, the feed-forward
@@ -48,6 +49,29 @@ FUSE_NORMS = True
 
 _WARM_SHAPES = set()        # step shapes that have run eagerly once in this process (begin_search)
 
+# Weight-only bf16 for the <= 16-row Linear layers of a step (`weights="bf16"`): each weight is streamed as its bf16
+# image (rounded once, to nearest even: ops.cast_bf16) by qarig_decode_linear_bf16w, half the bytes per token.
+# Activations, accumulation, LayerNorm, attention, the key/value cache, the conditioning path and sampling stay
+# fp32 -- it is neither the fp32 parity path nor ops.PRECISION's bf16 mode (which rounds activations too).
+DECODE_WEIGHTS = ("f32", "bf16")
+_WEIGHTS_WARNED = False
+
+
+def check_decode_weights(weights):
+    if weights not in DECODE_WEIGHTS:
+        raise ValueError(f"decode weights {weights!r}: expected one of {DECODE_WEIGHTS}")
+    return weights
+
+
+def _warn_weights_fallback(what):
+    """Once per process: a bf16 request the streaming kernel cannot serve keeps the fp32 path."""
+    global _WEIGHTS_WARNED
+    if not _WEIGHTS_WARNED:
+        import warnings
+        warnings.warn(f'{what}: weights="bf16" needs every per-token Linear on the weight-streaming kernel '
+                      "(<= 16 rows, K in {256, 512, 1024}, or 2048 / 4096 without LayerNorm); keeping fp32 weights")
+        _WEIGHTS_WARNED = True
+
 
 def _rows(t, B):
     """A (D,) row of the per-position table as the (B, D) operand the general kernels take."""
@@ -55,10 +79,13 @@ def _rows(t, B):
 
 
 class DecodeCache:
-    def __init__(self, model, enc, batch, max_len, graph=None, positions=None):
+    def __init__(self, model, enc, batch, max_len, graph=None, positions=None, weights="f32"):
         """positions: optional sequence of max_len floats, the `pos_cond` value of the token at each
         window index (known before the loop: generate_images.py:306-322 numbers them cur + tok + 1);
-        given, the conditioning path is evaluated once per position here and `step` ignores `pos`."""
+        given, the conditioning path is evaluated once per position here and `step` ignores `pos`.
+        weights: "f32", or "bf16" -- every Linear the step evaluates per token streams the bf16 image of its
+        weight (DECODE_WEIGHTS above); a model the streaming kernel does not take keeps fp32 and warns once."""
+        self.weights = check_decode_weights(weights)
         if not all(layer.self_attn_block.self_attn.use_masked_attn for layer in model.decoder_layers):
             raise ValueError("a KV cache needs causal decoder self-attention")
         self.model = model
@@ -82,6 +109,9 @@ class DecodeCache:
         self.cross = self._cross_kv(enc)
         self._enc_shape = None if enc is None else tuple(enc.shape)
         self._stack_weights()
+        self._img = None            # bf16 mode: id(weight) -> bf16 image, all built here (none inside a capture)
+        if weights == "bf16":
+            self._build_images()
         self._table = None
         if positions is not None and model.use_pos_cond and self._proj_lin and self.dim % 4 == 0:
             self._build_table(positions)
@@ -218,6 +248,48 @@ class DecodeCache:
                     blocks[0][0]._act, blocks[0][1]._act))
             self._qkv = packed
 
+    def _step_linears(self):
+        """The Linear layers a step evaluates per token besides the stacked q/k/v MLPs: the two-layer MLPs that sit
+        behind a LayerNorm, the residual layers, the classifier."""
+        mlps, res = [], []
+        for layer in self.model.decoder_layers:
+            res.append(layer.self_attn_block.self_attn_res)
+            if layer.use_cross_attn:
+                mlps.append(layer.cross_attn_block.cross_attn.q_block)
+                res.append(layer.cross_attn_block.cross_attn_res)
+            mlps.append(layer.feedforward_block.feedforward)
+            res.append(layer.feedforward_block.feedforward_res)
+        return mlps, res, self.model.classifier
+
+    @torch.no_grad()
+    def _build_images(self):
+        """bf16 mode: the image of every weight `_forward` streams -- the stacked q/k/v weights cast here, single
+        weights through functional_lp._shadow (the optimiser's own bf16 copy, or a cast cached until the weights
+        change) -- or, when some Linear of the step does not fit the streaming kernel, none and the fp32 path."""
+        B, D = self.batch, self.dim
+        fits = lambda w, ln: ops.decode_linear_supported(B, w.shape[-2], w.shape[-1], ln)
+        mlps, res, classifier = self._step_linears()
+        ok = self._stacked and FUSE_NORMS and B <= 16 and D % 4 == 0
+        singles = []
+        for seq, ln in [(q, True) for q in mlps] + [(classifier, False)]:
+            (w1, b1), (w2, b2) = _lin_params(seq[0]), _lin_params(seq[1])
+            ok = ok and b1 is not None and b2 is not None and w1.shape[1] == D and fits(w1, ln) and fits(w2, False)
+            singles += [w1, w2]
+        for r in res:
+            w = _lin_params(r.linear)[0]
+            ok = ok and isinstance(r.skip_linear, torch.nn.Identity) and w.shape[1] == D and fits(w, False)
+            singles.append(w)
+        ok = ok and all(fits(q[0], True) and fits(q[2], False) for q in self._qkv)
+        if not ok:
+            _warn_weights_fallback("DecodeCache")
+            return
+        self._img = {id(w): QL._shadow(w) for w in singles}
+        self._qkv_lp = [(ops.cast_bf16(w1), b1, ops.cast_bf16(w2), b2, a1, a2) for w1, b1, w2, b2, a1, a2 in self._qkv]
+
+    def _w(self, w):
+        """The operand a step's Linear streams for weight `w`: its bf16 image in bf16 mode, `w` itself otherwise."""
+        return w if self._img is None else self._img[id(w)]
+
     @torch.no_grad()
     def _build_table(self, positions):
         """(max_len, P * D): row L holds every projection of cond(positions[L]); the views of `_proj_row`
@@ -289,6 +361,8 @@ class DecodeCache:
         x2 = x.reshape(B, D)
         H = w1.shape[-2]
         if B <= 16 and ops.decode_linear_supported(B, H, D, True) and ops.decode_linear_supported(B, D, H, False):
+            if stacked is None:
+                w1, w2 = self._w(w1), self._w(w2)
             if use_adaln0:
                 scale, shift = proj[key]
                 hid = ops.decode_linear(x2, w1, b1, act1, scale=scale, shift=shift, eps=norm.norm.eps)
@@ -311,6 +385,10 @@ class DecodeCache:
         if res.use_scale_layer and not scaled:
             x = QF.mul(x, _rows(proj[key], self.batch).reshape(x.shape))
         w, b = _lin_params(res.linear)
+        if self._img is not None:       # bf16 mode: straight to the streaming kernel (skip_linear is the identity)
+            B = self.batch
+            y = ops.decode_linear(x.reshape(B, -1), self._w(w), b, res._act, residual=x_skip.reshape(B, -1))
+            return y.reshape(B, 1, -1)
         return QF.linear_act(x, w, b, residual=res.skip_linear(x_skip), act=res._act)
 
     def _forward(self, ids, pos, length, len_dev, out=None):
@@ -339,7 +417,8 @@ class DecodeCache:
             sab = layer.self_attn_block
             at = sab.self_attn
             qkv = self._ln_mlp(sab.self_attn_norm, x, proj, "self_norm", sab.use_adaln0, None,
-                               stacked=self._qkv[li]) if self._stacked and FUSE_NORMS else None
+                               stacked=self._qkv[li] if self._img is None else self._qkv_lp[li]) \
+                if self._stacked and FUSE_NORMS else None
             if qkv is not None:
                 q, k, v = qkv
             else:
@@ -380,6 +459,9 @@ class DecodeCache:
                 h = _mlp2_forward(fb.feedforward, h)
                 x = self._residual(fb.feedforward_res, h, x, proj, "ffn_scale")
         (w1, b1), (w2, b2) = _lin_params(model.classifier[0]), _lin_params(model.classifier[1])
+        if self._img is not None:
+            hid = ops.decode_linear(x.reshape(B, D), self._w(w1), b1, model.classifier[0]._act)
+            return ops.decode_linear(hid, self._w(w2), b2, model.classifier[1]._act, out=out)
         if out is not None and B <= 16 and b1 is not None and b2 is not None and \
                 ops.decode_linear_supported(B, w1.shape[0], D, False) and \
                 ops.decode_linear_supported(B, w2.shape[0], w2.shape[1], False):
@@ -471,7 +553,7 @@ class DecodeCache:
             # shape in this process runs eagerly once; later stages of that shape go straight to the capture and
             # evaluate their first token by replaying it.
             sig = (B, D, V, self.heads, len(self.model.decoder_layers), tuple(c is not None for c in self.cross),
-                   self._table is not None, self._stacked, FUSE_NORMS,
+                   self._table is not None, self._stacked, FUSE_NORMS, self._img is not None,
                    tuple(k.shape[2] for c in self.cross if c is not None for k in c[:1]))
             if sig not in _WARM_SHAPES:
                 self._forward(s.ids, None, 0, self.ctl, out=s.logits)
@@ -524,13 +606,24 @@ class DecodeCache:
         return s.tokens[:, :1 + s.chunks * s.bw].clone()
 
 
-def _mlp2_rows(seq, x, out=None):
+def _mlp2_fits(seq, R):
+    (w1, b1), (w2, b2) = _lin_params(seq[0]), _lin_params(seq[1])
+    return b1 is not None and b2 is not None and ops.decode_linear_supported(R, w1.shape[0], w1.shape[1], False) and \
+        ops.decode_linear_supported(R, w2.shape[0], w2.shape[1], False)
+
+
+def _mlp2_rows(seq, x, out=None, weights="f32", images=None):
     """The two-layer MLP `seq` on R <= 16 rows x (R, K): the weight-streaming decode kernel when the shapes
-    fit it, the general kernels otherwise.  Returns (R, N) (written into `out` when given)."""
+    fit it, the general kernels otherwise.  Returns (R, N) (written into `out` when given).
+    weights "bf16": the streaming kernel reads the weights' bf16 images (DECODE_WEIGHTS) -- from `images`
+    (id(weight) -> image; a caller that captures a graph builds them first) or functional_lp._shadow; shapes the
+    kernel does not take run in fp32 as before."""
+    check_decode_weights(weights)
     (w1, b1), (w2, b2) = _lin_params(seq[0]), _lin_params(seq[1])
     R, K = x.shape
-    if b1 is not None and b2 is not None and ops.decode_linear_supported(R, w1.shape[0], K, False) and \
-            ops.decode_linear_supported(R, w2.shape[0], w2.shape[1], False):
+    if _mlp2_fits(seq, R) and w1.shape[1] == K:
+        if weights == "bf16":
+            w1, w2 = ((images[id(w)] if images is not None and id(w) in images else QL._shadow(w)) for w in (w1, w2))
         hid = ops.decode_linear(x, w1, b1, seq[0]._act)
         return ops.decode_linear(hid, w2, b2, seq[1]._act, out=out)
     y = _mlp2_forward(seq, x.reshape(R, 1, K)).reshape(R, -1)
@@ -556,7 +649,10 @@ class WindowStep:
     for every layer (`rebind` recomputes them for another stage's encoder output).
     pos_off: the loop's position numbering (1: generate_images.py:306-322, cur + tok + 1; 0: training's)."""
 
-    def __init__(self, model, enc, rows, window, capacity, pos_bound, pos_off, graph=True):
+    def __init__(self, model, enc, rows, window, capacity, pos_bound, pos_off, graph=True, weights="f32"):
+        """weights "bf16": the two <= 16-row MLPs of the evaluation (last layer's q, classifier) stream bf16
+        images of their weights (DECODE_WEIGHTS); everything on all rows of the window stays as it is."""
+        self.weights = check_decode_weights(weights)
         table = model.dec_embedding.weight
         self.model, self.rows, self.window = model, int(rows), int(window)
         self.dim, dev = table.shape[1], table.device
@@ -586,6 +682,14 @@ class WindowStep:
             self.cross = [None] * len(model.decoder_layers)
             self._enc_shape = None if enc is None else tuple(enc.shape)
             self._cross_kv(enc)
+            self._img = None        # bf16 mode: the images exist before the capture
+            if weights == "bf16":
+                seqs = (model.decoder_layers[-1].self_attn_block.self_attn.q_block, model.classifier)
+                if all(_mlp2_fits(seq, self.rows) for seq in seqs):
+                    self._img = {id(w): QL._shadow(w) for seq in seqs for w in (_lin_params(seq[0])[0],
+                                                                                 _lin_params(seq[1])[0])}
+                else:
+                    _warn_weights_fallback("WindowStep")
         self._graph = None
         if graph:
             self._capture()
@@ -686,11 +790,12 @@ class WindowStep:
         h, _ = _norm_forward(sab.self_attn_norm, x, cond, sab.use_adaln0)
         k = _mlp2_forward(at.k_block, h)
         v = _mlp2_forward(at.v_block, h)
-        q = _mlp2_rows(at.q_block, h[:, last].contiguous())
+        lp = dict(weights="bf16", images=self._img) if self._img is not None else {}
+        q = _mlp2_rows(at.q_block, h[:, last].contiguous(), **lp)
         o = ops.window_attention(q, k, v, self.W1, at.heads)
         # from here on only the last real token of each sequence is read (logits[:, -1])
         x = sab.self_attn_res(x=o.reshape(R, 1, D), x_skip=x[:, last:last + 1].contiguous(), cond=self.cond_last)
         if layer.use_cross_attn:
             x = layer.cross_attn_block(x, cross_cond=None, cond=self.cond_last, kv=self.cross[-1])
         x = layer.feedforward_block(x, cond=self.cond_last)
-        _mlp2_rows(model.classifier, x.reshape(R, D), out=self.logits)
+        _mlp2_rows(model.classifier, x.reshape(R, D), out=self.logits, **lp)

@@ -613,7 +613,9 @@ def decode_linear(x, W, bias=None, act=0, gamma=None, beta=None, scale=None, shi
     step on the weight-streaming kernel (csrc/decode.hip; M <= 16 rows).  x: (M, K) shared by the
     groups, or (G, M, K); W: (G, N, K) or (N, K); bias like W without K.  LN: gamma/beta (K,), or
     scale/shift (M, K) rows or ONE (K,) row for every activation row.  residual (M, N) (one group);
-    mul (M, N) or (N,).  Returns (G, M, N), or (M, N) for a 2-D W."""
+    mul (M, N) or (N,).  Returns (G, M, N), or (M, N) for a 2-D W.
+    W fp32, or torch.bfloat16 -- a bf16 image of the weight (cast_bf16), streamed at half the bytes and widened
+    exactly in the kernel (qarig_decode_linear_bf16w): everything else stays fp32."""
     require_cuda(x, W, bias, gamma, beta, scale, shift, residual, mul)
     single = W.dim() == 2
     G, (N, K) = (1 if single else W.shape[0]), W.shape[-2:]
@@ -622,7 +624,9 @@ def decode_linear(x, W, bias=None, act=0, gamma=None, beta=None, scale=None, shi
         M, x_gs = x.shape[1], x.shape[1] * K
     else:
         M, x_gs = x.shape[0], 0
-    assert x.shape[-1] == K and x.is_contiguous() and W.is_contiguous() and x.dtype == W.dtype == torch.float32
+    assert x.shape[-1] == K and x.is_contiguous() and W.is_contiguous() and x.dtype == torch.float32
+    assert W.dtype in (torch.float32, torch.bfloat16)
+    lp = W.dtype == torch.bfloat16
     if bias is not None:
         assert bias.numel() == G * N and bias.is_contiguous()
     for t in (gamma, beta):
@@ -640,10 +644,10 @@ def decode_linear(x, W, bias=None, act=0, gamma=None, beta=None, scale=None, shi
         ldmul = N if mul.dim() == 2 else 0
     C = out if out is not None else torch.empty((G, M, N), dtype=torch.float32, device=x.device)
     assert C.numel() == G * M * N and C.is_contiguous() and C.dtype == torch.float32
-    check(_lib.load().qarig_decode_linear_f32(
+    entry = "qarig_decode_linear_bf16w" if lp else "qarig_decode_linear_f32"
+    check(getattr(_lib.load(), entry)(
         ptr(x), K, x_gs, float(eps), ptr(gamma), ptr(beta), ptr(scale), ptr(shift), ldmod, ptr(W), K, N * K,
-        ptr(bias), N, ptr(residual), N, ptr(mul), ldmul, ptr(C), N, M * N, G, M, N, K, act, stream()),
-        "qarig_decode_linear_f32")
+        ptr(bias), N, ptr(residual), N, ptr(mul), ldmul, ptr(C), N, M * N, G, M, N, K, act, stream()), entry)
     return C.view(M, N) if single else C.view(G, M, N)
 
 

@@ -24,7 +24,7 @@ import os
 import torch
 
 from . import ops
-from .kvcache import DecodeCache, WindowStep
+from .kvcache import DecodeCache, WindowStep, check_decode_weights
 
 
 def filter_probs(probs, top_k=0, top_p=1.0):
@@ -150,17 +150,17 @@ def _weights_key(model):
     return tuple(key)
 
 
-def decode_cache(model, enc, batch, limit, positions):
-    """A DecodeCache(model, enc, batch, limit, positions=positions) -- a kept one re-bound to `enc` when the
-    model's weights have not changed since it was built, a new one otherwise."""
+def decode_cache(model, enc, batch, limit, positions, weights="f32"):
+    """A DecodeCache(model, enc, batch, limit, positions=positions, weights=weights) -- a kept one re-bound to
+    `enc` when the model's weights have not changed since it was built, a new one otherwise."""
     import weakref
     slot = (id(model), batch, limit, None if positions is None else tuple(positions),
-            None if enc is None else tuple(enc.shape))
+            None if enc is None else tuple(enc.shape), weights)
     wkey = _weights_key(model)
     hit = _DECODE_CACHES.get(slot)
     if hit is not None and hit[0]() is model and hit[1] == wkey and hit[2].rebind(enc):
         return hit[2]
-    cache = DecodeCache(model, enc, batch, limit, graph=False, positions=positions)
+    cache = DecodeCache(model, enc, batch, limit, graph=False, positions=positions, weights=weights)
     if len(_DECODE_CACHES) >= DECODE_CACHE_SLOTS:
         _DECODE_CACHES.pop(next(iter(_DECODE_CACHES)))
     _DECODE_CACHES[slot] = (weakref.ref(model), wkey, cache)
@@ -175,18 +175,18 @@ _WINDOW_STEPS = {}
 WINDOW_STEP_SLOTS = 4
 
 
-def window_step(model, enc, rows, window, capacity, pos_bound, pos_off):
+def window_step(model, enc, rows, window, capacity, pos_bound, pos_off, weights="f32"):
     """A WindowStep for these shapes -- a kept one re-bound to `enc` when the weights have not changed since it
     was built, a new one otherwise."""
     import weakref
-    slot = (id(model), rows, window, capacity, pos_bound, pos_off, None if enc is None else tuple(enc.shape))
+    slot = (id(model), rows, window, capacity, pos_bound, pos_off, None if enc is None else tuple(enc.shape), weights)
     wkey = (_weights_key(model), ops.LP_EPOCH)
     hit = _WINDOW_STEPS.pop(slot, None)
     if hit is not None and hit[0]() is model and hit[1] == wkey and hit[2].rebind(enc):
         step = hit[2]
     else:
         hit = None
-        step = WindowStep(model, enc, rows, window, capacity, pos_bound, pos_off)
+        step = WindowStep(model, enc, rows, window, capacity, pos_bound, pos_off, weights=weights)
     if len(_WINDOW_STEPS) >= WINDOW_STEP_SLOTS:
         _WINDOW_STEPS.pop(next(iter(_WINDOW_STEPS)))
     _WINDOW_STEPS[slot] = (weakref.ref(model), wkey, step)
@@ -216,7 +216,8 @@ def _window_tail(model, cache, hr_input, enc, sliding_window, beam_width, progre
     s = cache._search
     N, NB, bw, ctl = s.N, s.NB, s.bw, cache.ctl
     enc_eval = enc.repeat_interleave(NB, dim=0) if (enc is not None and NB > 1) else enc
-    step = window_step(model, enc_eval, N * NB, sliding_window, stop_len + bw, pos_bound, pos_off)
+    step = window_step(model, enc_eval, N * NB, sliding_window, stop_len + bw, pos_bound, pos_off,
+                       weights=cache.weights)
     step.load(hr_input.repeat_interleave(NB, dim=0) if NB > 1 else hr_input)
     cur = hr_input.shape[1]
     while cur < stop_len:
@@ -247,12 +248,13 @@ def _window_tail(model, cache, hr_input, enc, sliding_window, beam_width, progre
 
 def _generate_fused(model, hr_input, enc, total_seq, temperature, use_sliding_window,
                     sliding_window, end_token, shift, num_beam, beam_width, mode, progress,
-                    stop_len, pos_off, batch_beams, top_k=0, top_p=1.0):
+                    stop_len, pos_off, batch_beams, top_k=0, top_p=1.0, decode_weights="f32"):
     """The cached search with sampling, candidate bookkeeping and the decoder steps replayed from
     captured graphs (kvcache.DecodeCache.begin_search); nothing is read back before the stage ends.
     Returns (hr_input, pos, cache), or None when the model does not fit the fused kernels; the cache (rows of
     the kept tokens but the last) serves the evaluations of the next chunk that come before the window slides.
-    top_k / top_p go to the search state (begin_search): _fused_tail and _window_tail draw with them too."""
+    top_k / top_p go to the search state (begin_search): _fused_tail and _window_tail draw with them too.
+    decode_weights: the cache's `weights` mode (kvcache.DECODE_WEIGHTS)."""
     device = hr_input.device
     N = hr_input.shape[0]
     # The candidate chunks of a position are independent given the kept prefix: they run as rows of one batch
@@ -273,7 +275,7 @@ def _generate_fused(model, hr_input, enc, total_seq, temperature, use_sliding_wi
     positions = [0.0] + [float(L + pos_off) for L in range(1, limit)] if use_sliding_window else None
     enc_b = enc.repeat_interleave(B, dim=0) if (enc is not None and B > 1) else enc
     tm = _Timer()
-    cache = decode_cache(model, enc_b, N * B, limit, positions)
+    cache = decode_cache(model, enc_b, N * B, limit, positions, decode_weights)
     if cache.dim % 4 or (model.use_pos_cond and cache._table is None):
         return None
     tm.mark("cache")
@@ -364,7 +366,7 @@ def _fused_tail(model, cache, hr_input, pos, enc, use_sliding_window, sliding_wi
 
 def _generate_cached(model, hr_input, enc, total_seq, temperature, use_sliding_window,
                      sliding_window, end_token, shift, num_beam, beam_width, mode, progress,
-                     stop_len, pos_off, batch_beams, top_k=0, top_p=1.0):
+                     stop_len, pos_off, batch_beams, top_k=0, top_p=1.0, decode_weights="f32"):
     """The same search as the loops below, evaluating one token per model call from a
     `DecodeCache` for as long as no evaluation of the next chunk would slide the window.
     Sampling draws are made in the reference's order (same shapes, same generator), so the
@@ -383,7 +385,7 @@ def _generate_cached(model, hr_input, enc, total_seq, temperature, use_sliding_w
     if cur + beam_width > limit:
         return hr_input, pos
     enc_b = enc.repeat_interleave(B, dim=0) if (enc is not None and B > 1) else enc
-    cache = DecodeCache(model, enc_b, N * B, limit)
+    cache = DecodeCache(model, enc_b, N * B, limit, weights=decode_weights)
     rows = torch.arange(N * B, device=device)
 
     def positions(value):
@@ -439,7 +441,7 @@ def _generate_cached(model, hr_input, enc, total_seq, temperature, use_sliding_w
 def generate_tokens(model, hr_input, lr_input, total_seq, temperature, use_sliding_window,
                     sliding_window, end_token, shift=0, num_beam=1, beam_width=1, mode="generate",
                     progress=None, batch_beams=False, use_kv_cache=True, sampler=None, window_graph=False,
-                    top_k=0, top_p=1.0):
+                    top_k=0, top_p=1.0, decode_weights="f32"):
     """hr_input: (N, S0) int64 conditioning/start tokens.  Returns the extended (N, S) tensor
     (first tokens included; callers strip them and undo `shift`).  use_kv_cache: evaluate one
     token per step from a key/value cache until the window starts to slide (same logits up
@@ -450,8 +452,12 @@ def generate_tokens(model, hr_input, lr_input, total_seq, temperature, use_slidi
     (kvcache.WindowStep) instead of an eager model.decode of the window; other cases ignore it.
     top_k / top_p: every draw is made from filter_probs(probs, top_k, top_p) -- inside the sampling kernel with
     the fused sampler, in front of torch.multinomial elsewhere; 0 / 1.0 (default): off, the code of a call
-    without them."""
+    without them.
+    decode_weights: "f32" (default), or "bf16": the cached single-token steps stream bf16 images of their Linear
+    weights (kvcache.DECODE_WEIGHTS: weight-only, everything else fp32; the full-window evaluations are not
+    affected)."""
     assert mode in ("generate", "train")
+    check_decode_weights(decode_weights)
     top_k, top_p = ops.check_sample_filter(top_k, top_p)
     filtered = top_k > 0 or top_p < 1.0
     device = hr_input.device
@@ -473,7 +479,8 @@ def generate_tokens(model, hr_input, lr_input, total_seq, temperature, use_slidi
             outs.append(generate_tokens(model, hr_input[sub], None if lr_input is None else lr_input[sub], total_seq,
                                         temperature, use_sliding_window, sliding_window, end_token, shift, num_beam,
                                         beam_width, mode, sub_progress, batch_beams, use_kv_cache, sampler,
-                                        window_graph=window_graph, top_k=top_k, top_p=top_p))
+                                        window_graph=window_graph, top_k=top_k, top_p=top_p,
+                                        decode_weights=decode_weights))
         return torch.cat(outs, dim=0)
     enc = model.encode(lr_input) if model.use_encoder else None
     pos = torch.zeros((N, 1), device=device) if use_sliding_window else None
@@ -484,7 +491,8 @@ def generate_tokens(model, hr_input, lr_input, total_seq, temperature, use_slidi
     cache = None
     if use_kv_cache and _cacheable(model, hr_input, use_sliding_window):
         args = (model, hr_input, enc, total_seq, temperature, use_sliding_window, sliding_window, end_token,
-                shift, num_beam, beam_width, mode, progress, stop_len, pos_off, batch_beams, top_k, top_p)
+                shift, num_beam, beam_width, mode, progress, stop_len, pos_off, batch_beams, top_k, top_p,
+                decode_weights)
         done = None
         if fused:
             done = _generate_fused(*args)

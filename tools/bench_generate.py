@@ -48,7 +48,8 @@ def run_cascade(args, dev, K, N, patches, prev, models=None):
                                         batch_beams=args.batch_beams,
                                         use_kv_cache=not args.no_kv_cache, sampler=args.sampler,
                                         top_k=getattr(args, "top_k", 0),          # (callers with a namespace of their own:
-                                        top_p=getattr(args, "top_p", 1.0))        # filters off)
+                                        top_p=getattr(args, "top_p", 1.0),        # filters off, fp32 weights)
+                                        decode_weights=getattr(args, "decode_weights", "f32"))
         t_host = time.perf_counter() - t0           # until the call returned: everything enqueued, nothing awaited
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
@@ -80,6 +81,11 @@ def main():
     ap.add_argument("--filter-ab", type=int, default=0, metavar="ROUNDS",
                     help="A/B in one process: ROUNDS times the cascade with both filters off, then with --top-k / "
                          "--top-p, alternating; reports accepted tokens/s of every round and the medians")
+    ap.add_argument("--decode-weights", choices=["f32", "bf16"], default="f32",
+                    help="weights of the cached decode steps (bf16: weight-only images, everything else fp32)")
+    ap.add_argument("--weights-ab", type=int, default=0, metavar="ROUNDS",
+                    help="A/B in one process: ROUNDS times the cascade with --decode-weights f32, then bf16, "
+                         "alternating; reports accepted tokens/s of every round and the medians")
     ap.add_argument("--rebuild-models", action="store_true",
                     help="new random stage models for every cascade (no decode cache is ever reused: the cost of a "
                          "generator's first call) instead of one set kept for the run")
@@ -103,7 +109,7 @@ def main():
                      f"beam_width={args.beam_width}, window 256, fp32, batch_beams={args.batch_beams}, "
                      f"candidates={'one by one' if args.one_by_one else 'rows of one batch'}, "
                      f"kv_cache={not args.no_kv_cache}, sampler={args.sampler or sampling.DEFAULT_SAMPLER}, warm={not args.cold}, "
-                     f"top_k={args.top_k}, top_p={args.top_p}"}
+                     f"top_k={args.top_k}, top_p={args.top_p}, decode_weights={args.decode_weights}"}
     prev0 = torch.randint(0, K, (N, 1), device=dev)
     models = None if args.rebuild_models else [build_stage_model(s_, K, dev) for s_ in range(args.stages)]
     out["config"] += f", models={'rebuilt per cascade' if models is None else 'kept'}"
@@ -125,6 +131,24 @@ def main():
                             "median": {k: statistics.median(v) for k, v in rates.items()}}
         out["filter_ab"]["filtered_over_off"] = round(out["filter_ab"]["median"]["filtered"] /
                                                       out["filter_ab"]["median"]["off"], 4)
+    if args.weights_ab > 0:
+        import copy
+        import statistics
+        legs = {}
+        for w in ("f32", "bf16"):
+            legs[w] = copy.copy(args)
+            legs[w].decode_weights = w
+            if not args.cold:                   # each mode's caches and graphs exist before the timed rounds
+                run_cascade(legs[w], dev, K, N, patches, prev0, models)
+        rates = {w: [] for w in legs}
+        for _ in range(args.weights_ab):
+            for w, a in legs.items():
+                _, st = run_cascade(a, dev, K, N, patches, prev0, models)
+                rates[w].append(round(sum(N * x["seq"] for x in st) / sum(x["seconds_us"] * 1e-6 for x in st), 1))
+        med = {w: statistics.median(v) for w, v in rates.items()}
+        out["weights_ab"] = {"accepted_tokens_per_s": rates, "median": med,
+                             "min": {w: min(v) for w, v in rates.items()}, "max": {w: max(v) for w, v in rates.items()},
+                             "bf16_over_f32": round(med["bf16"] / med["f32"], 4)}
     prev, out["stages"] = run_cascade(args, dev, K, N, patches, prev0, models)
     tot_tokens = sum(N * st["seq"] for st in out["stages"])
     tot_time = sum(st["seconds"] for st in out["stages"])

@@ -6,7 +6,11 @@ generation runs), "fused" = per-token cond path + fused norms, "separate" = ever
     python tools/decode_step_probe.py [--rows 4] [--steps 200]
 With --top-k / --top-p also the sampling draw of a step in isolation: microseconds per launch of the draw
 kernel, unfiltered against filtered, in alternating blocks of back-to-back launches (--draw-vocab: V;
---draw-only skips the step measurements)."""
+--draw-only skips the step measurements).
+--decode-weights bf16 runs the step measurements with the weight-only bf16 step (kvcache.DECODE_WEIGHTS);
+--weights-ab instead times the "table" step's graph replay with fp32 and bf16 weights alternating in one process
+(7 rounds of --steps replays each: median, min, max) and reports the weight bytes a step streams in each mode,
+counted from the shapes of its Linear layers."""
 import argparse
 import json
 import os
@@ -55,6 +59,48 @@ def probe_draw(rows, V, top_k, top_p, dev, launches=400, rounds=7):
             "filtered_over_off": round(med["filtered"] / med["off"], 3)}
 
 
+def streamed_weight_elements(cache):
+    """Weight elements one step of `cache` streams: every Linear it evaluates per token (stacked q/k/v MLPs, the
+    other two-layer MLPs, residual layers, classifier), from their shapes."""
+    from models.layers import _lin_params
+    mlps, res, classifier = cache._step_linears()
+    n = sum(_lin_params(lin)[0].numel() for seq in mlps + [classifier] for lin in (seq[0], seq[1]))
+    n += sum(_lin_params(r.linear)[0].numel() for r in res)
+    for layer in cache.model.decoder_layers:
+        at = layer.self_attn_block.self_attn
+        n += sum(_lin_params(lin)[0].numel() for blk in (at.q_block, at.k_block, at.v_block) for lin in (blk[0], blk[1]))
+    return n
+
+
+def weights_ab(model, enc, B, S, positions, steps, rounds=7):
+    """ms per graph replay of the "table" step, fp32 weights against bf16 weights: both caches captured first, then
+    `rounds` alternating blocks of `steps` replays each."""
+    import statistics
+    caches = {w: kvcache.DecodeCache(model, enc, B, S, graph=True, positions=positions, weights=w)
+              for w in kvcache.DECODE_WEIGHTS}
+    ids = torch.zeros(B, dtype=torch.int64, device=caches["f32"].kv.device)
+    for c in caches.values():
+        for t in range(8):
+            c.step(ids, None, t)
+        c.ctl[0:1].fill_(S - 1)
+    t = {w: [] for w in caches}
+    for _ in range(rounds):
+        for w, c in caches.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                c._graph.replay()
+            torch.cuda.synchronize()
+            t[w].append(round((time.perf_counter() - t0) / steps * 1e3, 4))
+    n = streamed_weight_elements(caches["f32"])
+    lp = caches["bf16"]._img is not None
+    med = {w: statistics.median(v) for w, v in t.items()}
+    return {"graph_replay_ms": t, "median_ms": med, "min_ms": {w: min(v) for w, v in t.items()},
+            "max_ms": {w: max(v) for w, v in t.items()}, "bf16_over_f32": round(med["bf16"] / med["f32"], 4),
+            "bf16_images_in_use": lp,
+            "streamed_weight_bytes_per_step": {"f32": 4 * n, "bf16": (2 if lp else 4) * n}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=4)
@@ -65,6 +111,10 @@ def main():
     ap.add_argument("--top-p", type=float, default=1.0, help="draw probe: nucleus filter (1: off)")
     ap.add_argument("--draw-vocab", type=int, action="append", default=[], help="draw probe: V (default 513); repeatable")
     ap.add_argument("--draw-only", action="store_true", help="only the draw probe")
+    ap.add_argument("--decode-weights", choices=list(kvcache.DECODE_WEIGHTS), default="f32",
+                    help="weights the step streams (bf16: weight-only, everything else fp32)")
+    ap.add_argument("--weights-ab", action="store_true",
+                    help="only the fp32 / bf16 weights A/B of the table step's graph replay")
     args = ap.parse_args()
     if args.draw_only or args.top_k > 0 or args.top_p < 1.0:
         dev = torch.device("cuda", 0)
@@ -81,19 +131,27 @@ def main():
     torch.manual_seed(1)
     K, B, S = 512, args.rows, 256
     model = build_stage_model(0 if args.base else 2, K, dev)
-    out = {"rows": B, "window": S, "options": args.opt, "stage": "base" if args.base else "encoder-decoder", "steps": args.steps}
+    out = {"rows": B, "window": S, "options": args.opt, "stage": "base" if args.base else "encoder-decoder", "steps": args.steps,
+           "decode_weights": args.decode_weights}
     with torch.no_grad():
         enc = None if args.base else model.encode(torch.randint(0, K, (B, 64), device=dev))
         ids = torch.randint(0, K, (B,), device=dev)
         pos = torch.rand(B, device=dev) * 100
         positions = [0.0] + [float(i + 1) for i in range(1, S)]
+        if args.weights_ab:
+            del out["decode_weights"]
+            out["weights_ab"] = weights_ab(model, enc, B, S, positions, args.steps)
+            print(json.dumps(out))
+            return
         for name, fused, table in (("table", True, True), ("fused", True, False), ("separate", False, False)):
             kvcache.FUSE_NORMS = fused
-            eager = kvcache.DecodeCache(model, enc, B, S, graph=False, positions=positions if table else None)
+            eager = kvcache.DecodeCache(model, enc, B, S, graph=False, positions=positions if table else None,
+                                        weights=args.decode_weights)
             n0 = _lib.N_CALLS
             eager.step(ids, pos, 0)
             launches = _lib.N_CALLS - n0
-            cache = kvcache.DecodeCache(model, enc, B, S, graph=True, positions=positions if table else None)
+            cache = kvcache.DecodeCache(model, enc, B, S, graph=True, positions=positions if table else None,
+                                        weights=args.decode_weights)
             for t in range(8):
                 cache.step(ids, pos, t)
             torch.cuda.synchronize()
