@@ -327,7 +327,7 @@ int qarig_decode_embed(const int64_t* ids, int B, int D, int V, const float* tab
  * n * batch_stride + h * head_stride + j * row_stride: row-major (head_stride = d, row_stride = H * d) or
  * head-major (row_stride = d, head_stride >= max_len * d: a head's keys contiguous, what the kernel's
  * lane-per-key loads coalesce on) -- and the o_mul factor at row stride ldmul (0: one row for every
- * sequence). */
+ * sequence).  The same contract on the cache's contents and on an out-of-range len_dev. */
 int qarig_decode_attention(const float* q, const float* k_new, const float* v_new, float* kcache,
                            float* vcache, int B, int H, int d, int len, const int* len_dev,
                            int max_len, int64_t batch_stride, int64_t head_stride, int64_t row_stride,
@@ -546,7 +546,12 @@ int qarig_attention_lp_bwd(const float* q, const float* k, const float* v, const
  * (B,H*d); cache row j of sequence n at n*batch_stride + j*H*d.  k_new/v_new non-NULL:
  * stored at row len and attended as the last key; NULL: read-only cache (cross-attention).
  * len_dev (device int, optional) overrides len for graph replay.  o_mul (B,H*d), optional:
- * multiplies the output (ResidualLinearLayer's x * scale(cond), models/layers.py:293-295). */
+ * multiplies the output (ResidualLinearLayer's x * scale(cond), models/layers.py:293-295).
+ * Cache rows at or beyond the attended length are never used, whatever they hold (NaN included),
+ * the stale row `len` of an append among them: a cache need not be cleared between uses.  A host
+ * len outside the cache is refused; *len_dev is clamped instead, to [0, max_len - 1] when appending
+ * (the new row goes to the clamped row) and to [0, max_len] when read-only, and nothing outside the
+ * max_len rows is read or written.  A read-only *len_dev <= 0 attends no key: o is not defined. */
 int qarig_attention_decode(const float* q, const float* k_new, const float* v_new, float* kcache,
                            float* vcache, int B, int H, int d, int len, const int* len_dev,
                            int max_len, int64_t batch_stride, float sqrt_d, const float* o_mul,

@@ -549,9 +549,17 @@ __device__ __forceinline__ float wave_max_dpp(float x) {
 
 // One query row per sequence against its cached keys / values: a wave per (sequence, head), the four
 // waves of a workgroup on four adjacent heads (they read the same 128-B lines at head dim 8), a lane
-// per key.  Rows are loaded without waiting for the length word (rows past it hold finite data -- the
-// cache is zero-initialised -- and are masked afterwards); the running softmax of a lane's keys is
-// combined over the wave with one DPP maximum and one multi-value sum.
+// per key.  Rows are loaded without waiting for the length word and masked afterwards; the running
+// softmax of a lane's keys is combined over the wave with one DPP maximum and one multi-value sum.
+// Contract (tests/test_gpu_decode_attention.py):
+//   - with L the attended length, cache rows at or beyond it never reach the result, whatever they hold
+//     (NaN included: what is computed from them is selected away, never multiplied by zero) -- that covers
+//     the stale slot L of an append, whose key and value come from k_new / v_new (`fresh`), and every load
+//     stays inside the max_len rows of the cache;
+//   - the length word is clamped, to [0, max_len - 1] when appending (the new row is written to row L of
+//     every head and nothing else is) and to [0, max_len] when read-only (nothing is written);
+//   - a read-only call whose clamped length is 0 attends no key and its output is not defined (0 / 0); the
+//     host-side length is refused in that case.
 template <int HD>
 __global__ __launch_bounds__(256) void decode_attention_kernel(
     const float* __restrict__ q, const float* __restrict__ k_new, const float* __restrict__ v_new,

@@ -34,6 +34,8 @@ def test_attention_decode_matches_full_attention():
         k = torch.randn(B, L + 1, D, device="cuda")
         v = torch.randn(B, L + 1, D, device="cuda")
         want = ops.attention_fwd(q, k, v, heads, False)[0][:, 0]
+        qh, kh, vh = (x.double().view(B, -1, heads, d).transpose(1, 2) for x in (q, k, v))
+        want64 = (torch.softmax(qh @ kh.transpose(-1, -2) / d ** 0.5, -1) @ vh).transpose(1, 2).reshape(B, D)
         kc = torch.zeros(B, Lmax, D, device="cuda")
         vc = torch.zeros(B, Lmax, D, device="cuda")
         kc[:, :L] = k[:, :L]
@@ -41,11 +43,12 @@ def test_attention_decode_matches_full_attention():
         got = ops.attention_decode(q[:, 0].contiguous(), k[:, L].contiguous(), v[:, L].contiguous(),
                                    kc, vc, L, heads)
         assert rel_err(got, want) < 1e-5
+        assert rel_err(got, want64) < 1e-5                  # and an independent reference: fp64 torch
         assert torch.equal(kc[:, L], k[:, L]) and torch.equal(vc[:, L], v[:, L])   # appended
         assert not kc[:, L + 1:].any()
         # read-only form (cross-attention) on a strided batch view, and device-side length
         got2 = ops.attention_decode(q[:, 0].contiguous(), None, None, kc, vc, L + 1, heads)
-        assert rel_err(got2, want) < 1e-5
+        assert rel_err(got2, want) < 1e-5 and rel_err(got2, want64) < 1e-5
         ln = torch.tensor([L + 1], dtype=torch.int32, device="cuda")
         got3 = ops.attention_decode(q[::2, 0].contiguous(), None, None, kc[::2], vc[::2], 0, heads,
                                     len_dev=ln)
@@ -64,7 +67,7 @@ def test_attention_decode_matches_full_attention():
         assert rel_err(got6, want * mul) < 1e-5
         assert torch.equal(kh, hm(kc)) and torch.equal(vh, hm(vc))      # the new row landed in every head's run
         got7 = ops.attention_decode(q[:, 0].contiguous(), None, None, kh, vh, 0, heads, len_dev=ln)
-        assert rel_err(got7, want) < 1e-5
+        assert rel_err(got7, want) < 1e-5 and rel_err(got7, want64) < 1e-5
 
 
 def test_grouped_skinny_gemm():
