@@ -313,6 +313,12 @@ int qarig_decode_linear_bf16w(const float* X, int64_t ldx, int64_t x_gs, float e
  * window step's token ring (qarig_window_*). */
 #define QARIG_DECODE_CTL_WORDS 8
 
+/* Keys a wave of qarig_decode_attention / qarig_window_attention covers per pass of its loop at head dim d
+ * (the constant the launch uses: 256 / 128 / 64 for d = 4 ... 16 / 32 / 64, the grouped kernel's own for the
+ * other multiples of 4 up to 128), or 0 when d is not supported.  Lengths around its multiples are the
+ * kernel's edge cases. */
+int qarig_decode_attention_keys_per_pass(int d);
+
 /* First launch of a step: x[b] = table[ids[b]] + pe[len] (models/Transformer.py:154-167; pe may be
  * NULL), len = ctl[0] (ctl NULL: the `len` argument), and the copy of row `len` of proj_table
  * (max_len rows of proj_row_floats floats: every ScaleLayer / ShiftLayer projection of `cond` --
@@ -327,7 +333,10 @@ int qarig_decode_embed(const int64_t* ids, int B, int D, int V, const float* tab
  * n * batch_stride + h * head_stride + j * row_stride: row-major (head_stride = d, row_stride = H * d) or
  * head-major (row_stride = d, head_stride >= max_len * d: a head's keys contiguous, what the kernel's
  * lane-per-key loads coalesce on) -- and the o_mul factor at row stride ldmul (0: one row for every
- * sequence).  The same contract on the cache's contents and on an out-of-range len_dev. */
+ * sequence).  The same contract on the cache's contents and on an out-of-range len_dev.
+ * d: a multiple of 4 from 4 to 128.  4, 8, 16, 32 and 64 run a lane-per-key kernel; every other one a kernel
+ * whose keys are shared by groups of 2 or 4 lanes (rows stay compact: channels at or beyond d are never
+ * loaded).  Any other d is refused. */
 int qarig_decode_attention(const float* q, const float* k_new, const float* v_new, float* kcache,
                            float* vcache, int B, int H, int d, int len, const int* len_dev,
                            int max_len, int64_t batch_stride, int64_t head_stride, int64_t row_stride,
@@ -396,7 +405,7 @@ int qarig_decode_advance(int* ctl, int beam_width, void* stream);
  * the last token's logits.  These entry points keep that evaluation a replay of one captured graph. */
 
 /* 1 when R sequences (1..16), a window of `window` tokens, model width D (a multiple of 4) and H
- * self-attention heads (head dim 4, 8, 16, 32 or 64) fit the window step, else 0. */
+ * self-attention heads (head dim D / H a multiple of 4 from 4 to 128) fit the window step, else 0. */
 int qarig_window_step_supported(int R, int window, int D, int H);
 
 /* The window in front of ring length n = ctl[5]: start = n - W1; x[r][s] = table[ring[r][start + s]] +
@@ -413,7 +422,7 @@ int qarig_window_assemble(const int64_t* ring, int64_t ldr, const int* ctl, int 
 /* Masked self-attention of the window's last real token (models/layers.py:433-474, the last row of the
  * causal softmax(q k^T / sqrt(d)) v): q (R, H * d), k / v token-major rows of H * d floats, `rows` per
  * sequence at batch_stride, the first n_keys of them attended (a pad row behind them is ignored);
- * o = result (* o_mul at row stride ldmul, 0: one row for all). */
+ * o = result (* o_mul at row stride ldmul, 0: one row for all).  d as for qarig_decode_attention. */
 int qarig_window_attention(const float* q, const float* k, const float* v, int R, int H, int d, int n_keys,
                            int rows, int64_t batch_stride, const float* o_mul, int64_t ldmul, float* o,
                            void* stream);

@@ -684,6 +684,209 @@ __global__ __launch_bounds__(256) void decode_attention_kernel(
     }
 }
 
+// The head dims decode_attention_kernel is not instantiated for (every other multiple of 4 up to 128): a key's
+// channels are shared by G adjacent lanes.  Lane s of a group holds the 16-B chunks s, s + G, s + 2 G, ... of q,
+// of the group's keys and values and of the output (the group reads a row as consecutive 16-B pieces); C4 chunks
+// per lane bound the head dim at 4 G C4, the head dim itself arrives at run time.  Rows are compact: what follows
+// channel d - 1 is the next head's data (or the next row's, or nothing at all), so chunks at or beyond d are not
+// loaded and their registers stay 0.  A key's partial dots are summed inside the group by an xor butterfly (every
+// lane of the group ends with the same bits), the softmax state is replicated in it.
+template <int G, int C4> struct GroupedAttn {
+    static constexpr int NG = 64 / G;            // keys a wave covers per load
+    static constexpr int U = 16 / C4;            // keys per lane and pass (128 registers of rows, as above)
+    static constexpr int KEYS = NG * U;          // keys per wave and pass
+    static constexpr int V = 4 * C4;             // output channels per lane
+    static constexpr int NF = V * G >= 64 ? V * G / 64 : 1;   // of which it holds the wave totals of NF at the end
+};
+constexpr int grouped_keys_per_pass(int d) {
+    return d < 16 ? GroupedAttn<2, 2>::KEYS : d < 32 ? GroupedAttn<2, 4>::KEYS
+         : d < 64 ? GroupedAttn<4, 4>::KEYS : GroupedAttn<4, 8>::KEYS;
+}
+
+// Sums V per-lane values over the lanes that hold the same slice of a row (lane bits G ... 32), halving the values a
+// lane carries at every step like wave_sum_multi.  Afterwards v[0 .. NF) are the totals of the values number
+// group_sum_index<V, G>() ... + NF.  Fixed order: bit-reproducible.
+template <int V, int G>
+__device__ __forceinline__ void group_sum_multi(float (&v)[V], int lane) {
+    static_assert(V >= 1 && V <= 64 && (V & (V - 1)) == 0 && (G == 2 || G == 4), "");
+#define QARIG_GROUP_STEP(MASK, N0)                                              \
+    if constexpr ((MASK) >= G) {                                                \
+        if constexpr ((N0) > 1) {                                               \
+            constexpr int n = (N0) / 2;                                         \
+            const bool up = (lane & (MASK)) != 0;                               \
+            float got[n];                                                       \
+            _Pragma("unroll") for (int i = 0; i < n; ++i) {                     \
+                const float lo = v[i], hi = v[i + n];       /* values, not a choice between two addresses */ \
+                got[i] = __shfl_xor(up ? lo : hi, MASK, 64);                    \
+                v[i] = up ? hi : lo;                                            \
+            }                                                                   \
+            _Pragma("unroll") for (int i = 0; i < n; ++i) v[i] += got[i];       \
+        } else {                                                                \
+            v[0] += __shfl_xor(v[0], MASK, 64);                                 \
+        }                                                                       \
+    }
+    constexpr int N1 = V, N2 = N1 > 1 ? N1 / 2 : 1, N3 = N2 > 1 ? N2 / 2 : 1, N4 = N3 > 1 ? N3 / 2 : 1,
+                  N5 = N4 > 1 ? N4 / 2 : 1;
+    QARIG_GROUP_STEP(32, N1)
+    QARIG_GROUP_STEP(16, N2)
+    QARIG_GROUP_STEP(8, N3)
+    QARIG_GROUP_STEP(4, N4)
+    QARIG_GROUP_STEP(2, N5)
+#undef QARIG_GROUP_STEP
+}
+// The number of the first value whose total group_sum_multi<V, G> leaves on `lane`; `owner` is true on exactly
+// one lane per value and slice.
+template <int V, int G>
+__device__ __forceinline__ int group_sum_index(int lane, bool& owner) {
+    int idx = 0, dup = 0, n = V;
+#pragma unroll
+    for (int mask = 32; mask >= G; mask >>= 1) {
+        if (n > 1) {
+            n >>= 1;
+            if (lane & mask) idx += n;
+        } else {
+            dup |= mask;
+        }
+    }
+    owner = (lane & dup) == 0;
+    return idx;
+}
+
+// decode_attention_kernel's contract, word for word, for 4 <= d <= 4 G C4, d % 4 == 0.
+template <int G, int C4>
+__global__ __launch_bounds__(256) void decode_attention_grouped_kernel(
+    const float* __restrict__ q, const float* __restrict__ k_new, const float* __restrict__ v_new,
+    float* __restrict__ kc, float* __restrict__ vc, int64_t bstride, int64_t hstride, int64_t rstride, int H, int d,
+    int len_arg, const int* __restrict__ ctl, int max_len, float c2, const float* __restrict__ o_mul,
+    int64_t ldmul, float* __restrict__ o) {
+    using T = GroupedAttn<G, C4>;
+    constexpr int NG = T::NG, U = T::U, V = T::V, NF = T::NF;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int hq = (H + 3) >> 2;
+    const int n = blockIdx.x / hq, h = (blockIdx.x - n * hq) * 4 + w;
+    if (h >= H) return;                      // whole wave; no workgroup barrier below
+    const int s = lane & (G - 1), g = lane / G;
+    const bool app = k_new != nullptr;
+    const int64_t row = (int64_t)n * H * d + h * d;
+    float* kb = kc + (int64_t)n * bstride + (int64_t)h * hstride;
+    float* vb = vc + (int64_t)n * bstride + (int64_t)h * hstride;
+    // chunks s, s + G, ... below d / 4 are this lane's: the first nch of its C4
+    const int nch = (d / 4 - s + G - 1) / G;
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 qv[C4], kn[C4], vn[C4];
+#pragma unroll
+    for (int i = 0; i < C4; ++i) {
+        qv[i] = kn[i] = vn[i] = zero4;
+        if (i < nch) {
+            const int c = 4 * (s + G * i);
+            qv[i] = ld4(q + row + c);
+            kn[i] = ld4((app ? k_new : q) + row + c);
+            vn[i] = ld4((app ? v_new : q) + row + c);
+        }
+    }
+    float4 kk[U][C4], vv[U][C4];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int j = min(g + NG * u, max_len - 1);
+#pragma unroll
+        for (int i = 0; i < C4; ++i) {
+            kk[u][i] = vv[u][i] = zero4;
+            if (i < nch) {
+                kk[u][i] = ld4(kb + (int64_t)j * rstride + 4 * (s + G * i));
+                vv[u][i] = ld4(vb + (int64_t)j * rstride + 4 * (s + G * i));
+            }
+        }
+    }
+    // the NF output channels whose wave totals end on this lane, and their o_mul
+    bool own;
+    const int idx = group_sum_index<V, G>(lane, own);
+    int och[NF];
+    float mq[NF];
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+        const int li = idx + f;
+        och[f] = 4 * (s + G * (li >> 2)) + (li & 3);
+        if (!own || och[f] >= d) och[f] = -1;
+        mq[f] = (o_mul && och[f] >= 0) ? o_mul[(int64_t)n * ldmul + h * d + och[f]] : 1.0f;
+    }
+    int L = ctl ? ctl[CTL_LEN] : len_arg;
+    L = min(max(L, 0), app ? max_len - 1 : max_len);
+    const int Sk = L + (app ? 1 : 0);
+    if (app) {                               // the new row joins the cache (off the critical path)
+        for (int c = lane; c < d; c += 64) {
+            kb[(int64_t)L * rstride + c] = k_new[row + c];
+            vb[(int64_t)L * rstride + c] = v_new[row + c];
+        }
+    }
+    float m = -INFINITY, l = 0.0f;
+    float4 ov[C4];
+#pragma unroll
+    for (int i = 0; i < C4; ++i) ov[i] = zero4;
+    for (int j0 = 0; j0 < Sk; j0 += T::KEYS) {
+        if (j0 > 0) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = min(j0 + g + NG * u, max_len - 1);
+#pragma unroll
+                for (int i = 0; i < C4; ++i) {
+                    if (i < nch) {
+                        kk[u][i] = ld4(kb + (int64_t)j * rstride + 4 * (s + G * i));
+                        vv[u][i] = ld4(vb + (int64_t)j * rstride + 4 * (s + G * i));
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = j0 + g + NG * u;
+            const bool fresh = app && j == L;      // the new row comes from its source, not from the cache
+            float dot = 0.0f;
+#pragma unroll
+            for (int i = 0; i < C4; ++i) {         // chunks at or beyond d: 0 * 0, never loaded
+                dot = fmaf(qv[i].x, fresh ? kn[i].x : kk[u][i].x, dot);
+                dot = fmaf(qv[i].y, fresh ? kn[i].y : kk[u][i].y, dot);
+                dot = fmaf(qv[i].z, fresh ? kn[i].z : kk[u][i].z, dot);
+                dot = fmaf(qv[i].w, fresh ? kn[i].w : kk[u][i].w, dot);
+            }
+            dot += dpp_lane<0xB1>(dot);            // quad_perm [1,0,3,2]: the group's other lane(s)
+            if constexpr (G == 4) dot += dpp_lane<0x4E>(dot);      // quad_perm [2,3,0,1]
+            if (j < Sk) {
+                const float t = dot * c2;
+                const float mn = fmaxf(m, t);
+                const float alpha = exp2_fast(m - mn);
+                const float pr = exp2_fast(t - mn);
+                l = l * alpha + pr;
+#pragma unroll
+                for (int i = 0; i < C4; ++i) {
+                    ov[i].x = fmaf(pr, fresh ? vn[i].x : vv[u][i].x, ov[i].x * alpha);
+                    ov[i].y = fmaf(pr, fresh ? vn[i].y : vv[u][i].y, ov[i].y * alpha);
+                    ov[i].z = fmaf(pr, fresh ? vn[i].z : vv[u][i].z, ov[i].z * alpha);
+                    ov[i].w = fmaf(pr, fresh ? vn[i].w : vv[u][i].w, ov[i].w * alpha);
+                }
+                m = mn;
+            }
+        }
+    }
+    const float Mx = wave_max_dpp(m);
+    const float sc = m == -INFINITY ? 0.0f : exp2_fast(m - Mx);
+    float lt = l * sc;                       // replicated in a group: summed over the groups only
+#pragma unroll
+    for (int mask = 32; mask >= G; mask >>= 1) lt += __shfl_xor(lt, mask, 64);
+    float r[V];
+#pragma unroll
+    for (int i = 0; i < C4; ++i) {
+        r[4 * i] = ov[i].x * sc; r[4 * i + 1] = ov[i].y * sc; r[4 * i + 2] = ov[i].z * sc; r[4 * i + 3] = ov[i].w * sc;
+    }
+    group_sum_multi<V, G>(r, lane);
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+        if (och[f] >= 0) {
+            const float t = r[f] / lt;
+            o[row + och[f]] = o_mul ? t * mq[f] : t;
+        }
+    }
+}
+
 __device__ __forceinline__ int wave_min_int(int x) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) x = min(x, __shfl_xor(x, o, 64));
@@ -1384,6 +1587,16 @@ extern "C" int qarig_decode_embed(const int64_t* ids, int B, int D, int V, const
     return QARIG_OK;
 }
 
+static bool decode_head_dim_instantiated(int d) { return d == 4 || d == 8 || d == 16 || d == 32 || d == 64; }
+
+// Keys a wave covers per pass of its loop at head dim d (0: unsupported): 64 lanes x decode_attention_kernel's U
+// for the instantiated dims, the grouped kernel's own constant for every other multiple of 4 up to 128.
+extern "C" int qarig_decode_attention_keys_per_pass(int d) {
+    if (d < 4 || d > 128 || d % 4) return 0;
+    if (decode_head_dim_instantiated(d)) return d <= 16 ? 256 : (d <= 32 ? 128 : 64);
+    return grouped_keys_per_pass(d);
+}
+
 extern "C" int qarig_decode_attention(const float* q, const float* k_new, const float* v_new, float* kcache,
                                       float* vcache, int B, int H, int d, int len, const int* len_dev,
                                       int max_len, int64_t batch_stride, int64_t head_stride, int64_t row_stride,
@@ -1392,8 +1605,8 @@ extern "C" int qarig_decode_attention(const float* q, const float* k_new, const 
     QARIG_CHECK_ARG((k_new == nullptr) == (v_new == nullptr), "decode_attention: k_new and v_new go together");
     QARIG_CHECK_ARG(B > 0 && H > 0 && d > 0 && max_len > 0 && sqrt_d > 0.0f, "decode_attention: bad extents");
     QARIG_CHECK_DIMS("decode_attention", B, H, max_len);
-    QARIG_CHECK_ARG(d == 4 || d == 8 || d == 16 || d == 32 || d == 64,
-                    "decode_attention: head dim %d unsupported (4,8,16,32,64)", d);
+    QARIG_CHECK_ARG(qarig_decode_attention_keys_per_pass(d) > 0,
+                    "decode_attention: head dim %d unsupported (multiples of 4 from 4 to 128)", d);
     QARIG_CHECK_ARG((long long)B * H < (1LL << 31), "decode_attention: bad extents");
     const bool row_major = head_stride == d && row_stride == (int64_t)H * d && batch_stride >= (int64_t)max_len * H * d;
     const bool head_major = row_stride == d && head_stride >= (int64_t)max_len * d && head_stride <= (1LL << 40) &&
@@ -1415,6 +1628,22 @@ extern "C" int qarig_decode_attention(const float* q, const float* k_new, const 
 #define QARIG_DA(HD)                                                                                          \
     hipLaunchKernelGGL((decode_attention_kernel<HD>), grid, block, 0, st, q, k_new, v_new, kcache, vcache,    \
                        batch_stride, head_stride, row_stride, H, len, len_dev, max_len, c2, o_mul, ldmul, o)
+#define QARIG_DAG(G, C4)                                                                                      \
+    static_assert(GroupedAttn<G, C4>::KEYS == grouped_keys_per_pass(4 * G * C4 - 4), "");                     \
+    hipLaunchKernelGGL((decode_attention_grouped_kernel<G, C4>), grid, block, 0, st, q, k_new, v_new, kcache, \
+                       vcache, batch_stride, head_stride, row_stride, H, d, len, len_dev, max_len, c2, o_mul, \
+                       ldmul, o)
+    if (!decode_head_dim_instantiated(d)) {     // every other multiple of 4 up to 128: the bucket that holds it
+        if (d < 16) {
+            QARIG_DAG(2, 2);
+        } else if (d < 32) {
+            QARIG_DAG(2, 4);
+        } else if (d < 64) {
+            QARIG_DAG(4, 4);
+        } else {
+            QARIG_DAG(4, 8);
+        }
+    } else
     switch (d) {
         case 4: QARIG_DA(4); break;
         case 8: QARIG_DA(8); break;
@@ -1422,6 +1651,7 @@ extern "C" int qarig_decode_attention(const float* q, const float* k_new, const 
         case 32: QARIG_DA(32); break;
         default: QARIG_DA(64); break;
     }
+#undef QARIG_DAG
 #undef QARIG_DA
     QARIG_CHECK_LAUNCH("decode_attention");
     return QARIG_OK;
@@ -1532,8 +1762,7 @@ extern "C" int qarig_decode_advance(int* ctl, int beam_width, void* stream) {
 
 extern "C" int qarig_window_step_supported(int R, int window, int D, int H) {
     if (R < 1 || R > 16 || window < 2 || window > 65536 || D < 4 || D % 4 || H < 1 || D % H) return 0;
-    const int d = D / H;
-    return d == 4 || d == 8 || d == 16 || d == 32 || d == 64;
+    return qarig_decode_attention_keys_per_pass(D / H) > 0;
 }
 
 extern "C" int qarig_window_assemble(const int64_t* ring, int64_t ldr, const int* ctl, int R, int W1, int Wp, int D,
@@ -1563,8 +1792,8 @@ extern "C" int qarig_window_attention(const float* q, const float* k, const floa
                                       int n_keys, int rows, int64_t batch_stride, const float* o_mul, int64_t ldmul,
                                       float* o, void* stream) {
     QARIG_CHECK_ARG(q && k && v && o, "window_attention: null pointer");
-    QARIG_CHECK_ARG(d == 4 || d == 8 || d == 16 || d == 32 || d == 64,
-                    "window_attention: head dim %d unsupported (4,8,16,32,64)", d);
+    QARIG_CHECK_ARG(qarig_decode_attention_keys_per_pass(d) > 0,
+                    "window_attention: head dim %d unsupported (multiples of 4 from 4 to 128)", d);
     QARIG_CHECK_ARG(R > 0 && H > 0 && n_keys > 0 && rows >= n_keys, "window_attention: bad extents (0 < n_keys <= rows)");
     QARIG_CHECK_DIMS("window_attention", R, H, rows);
     QARIG_CHECK_ARG(batch_stride >= (int64_t)rows * H * d && batch_stride % 4 == 0 && batch_stride <= (1LL << 40),

@@ -47,8 +47,14 @@ def parse_args():
     p.add_argument("--window-graph", action="store_true",
                    help="(additive) once the sliding window slides, evaluate each token as one replay of a captured "
                         "graph on the GPU instead of an eager pass over the window.  Applies only to the fused "
-                        "sampler, images x num_beam <= 16 and models with a cache kernel (head dim <= 64); "
+                        "sampler, images x num_beam <= 16 and models that generate from the key/value cache "
+                        "(head dim 4 ... 64 or 128; the other multiples of 4 up to 124 with --cache-padded-heads); "
                         "elsewhere it is ignored.")
+    p.add_argument("--cache-padded-heads", action="store_true",
+                   help="(additive) generate from the key/value cache also when a head dim (width / heads) is a "
+                        "multiple of 4 up to 124 other than 4, 8, 16, 32, 64 -- the head dims that train zero-padded; "
+                        "without it such a model re-runs the whole window for every token.  Head dims that are no "
+                        "multiple of 4 (the cache's 16-byte row loads and row copies need it) keep that loop either way.")
     p.add_argument("--top-k", type=int, default=None,
                    help="(additive) sample from the top-k most probable tokens only (ties at the cut: lower index "
                         "first); 0: off.  Overrides the config's per-stage \"top_k\" for all stages.")
@@ -135,7 +141,8 @@ def main():
                     progress=lambda i, t: log(f"{i:,} / {t:,}"), batch_beams=args["batch_beams"],
                     use_kv_cache=not args["no_kv_cache"], sampler=args["sampler"],
                     window_graph=args["window_graph"], top_k=top_k, top_p=top_p,
-                    decode_weights=args["decode_weights"])
+                    decode_weights=args["decode_weights"],
+                    cache_padded_heads=args["cache_padded_heads"] or None)
                 hr_input = hr_input[:, 1:] - shift
             else:                                        # more ranks than images: nothing to generate here
                 hr_input = torch.zeros((0, total_Seq), dtype=torch.int64, device=device)

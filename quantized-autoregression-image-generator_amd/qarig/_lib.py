@@ -91,6 +91,7 @@ SIGNATURES = {
     "qarig_decode_linear_bf16w": (I, [P, L, L, F, P, P, P, P, L, P, L, L, P, L, P, L, P, L, P, L, L, I, I, I, I, I,
                                       P]),
     "qarig_decode_embed": (I, [P, I, I, I, P, P, P, I, I, P, L, P, P, P, P]),
+    "qarig_decode_attention_keys_per_pass": (ctypes.c_uint, [I]),      # a count (0 ... 256), not a status
     "qarig_decode_attention": (I, [P, P, P, P, P, I, I, I, I, P, I, L, L, L, F, P, L, P, P]),
     "qarig_decode_sample": (I, [P, L, I, I, F, I, I, L, P, P, P, I, I, I, I, I, P, P, P, P, P]),
     "qarig_decode_sample_filtered": (I, [P, L, I, I, F, I, I, L, P, P, P, I, I, I, I, I, P, P, P, P, I, F, P]),

@@ -659,7 +659,7 @@ class WindowStep:
         heads = model.decoder_layers[-1].self_attn_block.self_attn.heads
         if not ops.window_step_supported(self.rows, self.window, self.dim, heads):
             raise ValueError(f"WindowStep: {rows} rows, window {window}, width {self.dim}, {heads} heads do not fit "
-                             "the window kernels (<= 16 rows, head dim 4 ... 64)")
+                             "the window kernels (<= 16 rows, head dim a multiple of 4 from 4 to 128)")
         if not all(l.self_attn_block.self_attn.use_masked_attn for l in model.decoder_layers):
             raise ValueError("WindowStep: needs causal decoder self-attention")
         R, D = self.rows, self.dim

@@ -1070,7 +1070,11 @@ def mul_rows_bwd(dy, a, tab, idx):
 
 
 ATTENTION_HEAD_DIMS = (4, 8, 16, 32, 64, 128)   # csrc/attention.hip instantiations; 128: csrc/attention_wide.hip
-DECODE_HEAD_DIMS = (4, 8, 16, 32, 64)           # csrc/decode.hip decode_attention_kernel (key/value cache)
+# Head dims cached generation takes by default: decode_attention_kernel's instantiations and 128 (the grouped kernel's
+# full bucket).  The other multiples of 4 up to 124 run on the grouped kernel too, opt-in (DECODE_PADDED_HEAD_DIMS:
+# the dims the training path zero-pads; sampling.CACHE_PADDED_HEADS).
+DECODE_HEAD_DIMS = (4, 8, 16, 32, 64, 128)
+DECODE_PADDED_HEAD_DIMS = tuple(d for d in range(4, 128, 4) if d not in DECODE_HEAD_DIMS)
 
 
 def attention_head_dim(d):
@@ -1097,10 +1101,11 @@ def attention_fwd(q, k, v, heads, causal, scale_dim=None):
     return o, lse
 
 
-def attention_decode(q, k_new, v_new, kcache, vcache, length, heads, len_dev=None, o_mul=None):
+def attention_decode(q, k_new, v_new, kcache, vcache, length, heads, len_dev=None, o_mul=None, out=None):
     """One decode step: q (B,D) against cache rows [0,length) (+ the appended new row).
     kcache/vcache: row-major (B, max_len, D) views with unit row stride D (batch stride free), or
-    head-major (B, H, max_len, d) -- DecodeCache's layout.  o_mul: (B, D), or one (D,) row for every sequence."""
+    head-major (B, H, max_len, d) -- DecodeCache's layout.  o_mul: (B, D), or one (D,) row for every sequence.
+    out: optional contiguous (B, D) buffer for the result."""
     B, D = q.shape
     d = D // heads
     assert kcache.shape == vcache.shape and kcache.shape[0] == B and vcache.stride() == kcache.stride()
@@ -1111,7 +1116,8 @@ def attention_decode(q, k_new, v_new, kcache, vcache, length, heads, len_dev=Non
         assert kcache.shape[2] == D and kcache.stride(2) == 1 and kcache.stride(1) == D
         max_len, hstride, rstride = kcache.shape[1], d, D
     assert q.is_contiguous()
-    o = torch.empty_like(q)
+    o = out if out is not None else torch.empty_like(q)
+    assert o.shape == q.shape and o.is_contiguous() and o.dtype == q.dtype
     ldmul = 0
     if o_mul is not None:
         assert o_mul.shape in (q.shape, (D,)) and o_mul.is_contiguous()
@@ -1123,6 +1129,11 @@ def attention_decode(q, k_new, v_new, kcache, vcache, length, heads, len_dev=Non
         kcache.stride(0), hstride, rstride, float(d ** 0.5), ptr(o_mul), ldmul, ptr(o), stream()),
         "qarig_decode_attention")
     return o
+
+
+def decode_attention_keys_per_pass(d):
+    """Keys a wave of the cache attention kernel covers per pass of its loop at head dim d; 0: d unsupported."""
+    return int(_lib.load().qarig_decode_attention_keys_per_pass(int(d)))
 
 
 DECODE_CTL_WORDS = 8          # include/qarig.h QARIG_DECODE_CTL_WORDS: [0] len, [1] chunk start, [2] draws, [3] candidate

@@ -11,6 +11,11 @@ tokens; sampler="torch" calls torch.multinomial on the device generator exactly 
 reference on --device cuda, so there a given --seed reproduces the reference's draw
 sequence as long as the logits agree.
 
+Which models generate from the key/value cache (`_cacheable`): those whose head dims all have a cache
+kernel -- 4, 8, 16, 32, 64 and 128 by default; the other multiples of 4 up to 124 (the head dims the
+training path zero-pads) with `cache_padded_heads` (opt-in); any other head dim re-evaluates the
+window for every token like the reference.
+
 top_k / top_p (off by default; the reference has neither) filter the probabilities of
 every draw, on every path by the one definition of `filter_probs`: zeroing only, kept
 entries keep their values.
@@ -74,15 +79,25 @@ def _sample(logits, temperature, end_token, mode, rows, comb, top_k=0, top_p=1.0
     return nxt, comb
 
 
-def _cacheable(model, hr_input, use_sliding_window):
+# Head dims the training path zero-pads (the multiples of 4 up to 124 other than 4 ... 64: ops.DECODE_PADDED_HEAD_DIMS)
+# have a cache kernel too, but keep the full-window loop unless asked for: generate_tokens(cache_padded_heads=True),
+# generate_images.py --cache-padded-heads, or this module default.
+CACHE_PADDED_HEADS = False
+
+
+def _cacheable(model, hr_input, use_sliding_window, cache_padded_heads=None):
     if not (hr_input.shape[1] == 1 and hasattr(model, "decoder_layers")
             and bool(model.use_pos_cond) == bool(use_sliding_window)
             and all(l.self_attn_block.self_attn.use_masked_attn for l in model.decoder_layers)):
         return False
-    # head dims that run zero-padded (QF.attention) keep the full-window loop: the cache kernel takes the
-    # instantiated head dims only
-    from . import ops
-    return all(m.head_dim in ops.DECODE_HEAD_DIMS for m in model.modules() if hasattr(m, "head_dim"))
+    # every attention of the model, cross-attention included, needs a cache kernel: ops.DECODE_HEAD_DIMS by default
+    # (4 ... 64 and 128); the head dims that run zero-padded in QF.attention (the other multiples of 4 up to 124) only
+    # with cache_padded_heads; anything else (d % 4 != 0: decode_rows and the kernels' 16-B row loads need the multiple
+    # of 4; d > 128) keeps the full-window loop
+    if cache_padded_heads is None:
+        cache_padded_heads = CACHE_PADDED_HEADS
+    dims = ops.DECODE_HEAD_DIMS + (ops.DECODE_PADDED_HEAD_DIMS if cache_padded_heads else ())
+    return all(m.head_dim in dims for m in model.modules() if hasattr(m, "head_dim"))
 
 
 # Which sampler the cached loop uses: "fused" (default) draws inside the captured graphs
@@ -441,7 +456,7 @@ def _generate_cached(model, hr_input, enc, total_seq, temperature, use_sliding_w
 def generate_tokens(model, hr_input, lr_input, total_seq, temperature, use_sliding_window,
                     sliding_window, end_token, shift=0, num_beam=1, beam_width=1, mode="generate",
                     progress=None, batch_beams=False, use_kv_cache=True, sampler=None, window_graph=False,
-                    top_k=0, top_p=1.0, decode_weights="f32"):
+                    top_k=0, top_p=1.0, decode_weights="f32", cache_padded_heads=None):
     """hr_input: (N, S0) int64 conditioning/start tokens.  Returns the extended (N, S) tensor
     (first tokens included; callers strip them and undo `shift`).  use_kv_cache: evaluate one
     token per step from a key/value cache until the window starts to slide (same logits up
@@ -455,7 +470,11 @@ def generate_tokens(model, hr_input, lr_input, total_seq, temperature, use_slidi
     without them.
     decode_weights: "f32" (default), or "bf16": the cached single-token steps stream bf16 images of their Linear
     weights (kvcache.DECODE_WEIGHTS: weight-only, everything else fp32; the full-window evaluations are not
-    affected)."""
+    affected).
+    cache_padded_heads: True lets a model whose head dims are multiples of 4 up to 124 other than 4 ... 64 (the ones
+    the training path zero-pads) generate from the key/value cache like the others, window_graph included; False
+    keeps the full-window loop for them; None (default): CACHE_PADDED_HEADS, which is False.  Head dims that are no
+    multiple of 4 keep the full-window loop either way."""
     assert mode in ("generate", "train")
     check_decode_weights(decode_weights)
     top_k, top_p = ops.check_sample_filter(top_k, top_p)
@@ -471,7 +490,7 @@ def generate_tokens(model, hr_input, lr_input, total_seq, temperature, use_slidi
     group = max(1, DECODE_ROWS // max(1, num_beam))
     rows_all = N * max(1, num_beam)
     if fused and GROUP_IMAGES and use_kv_cache and N > group and DECODE_ROWS < rows_all < GROUP_BELOW_ROWS and \
-            _cacheable(model, hr_input, use_sliding_window):
+            _cacheable(model, hr_input, use_sliding_window, cache_padded_heads):
         outs = []
         for g0 in range(0, N, group):
             sub = slice(g0, min(N, g0 + group))
@@ -480,7 +499,7 @@ def generate_tokens(model, hr_input, lr_input, total_seq, temperature, use_slidi
                                         temperature, use_sliding_window, sliding_window, end_token, shift, num_beam,
                                         beam_width, mode, sub_progress, batch_beams, use_kv_cache, sampler,
                                         window_graph=window_graph, top_k=top_k, top_p=top_p,
-                                        decode_weights=decode_weights))
+                                        decode_weights=decode_weights, cache_padded_heads=cache_padded_heads))
         return torch.cat(outs, dim=0)
     enc = model.encode(lr_input) if model.use_encoder else None
     pos = torch.zeros((N, 1), device=device) if use_sliding_window else None
@@ -489,7 +508,7 @@ def generate_tokens(model, hr_input, lr_input, total_seq, temperature, use_slidi
     stop_len = total_seq if mode == "generate" else hr_input.shape[1] + total_seq
     pos_off = 1 if mode == "generate" else 0
     cache = None
-    if use_kv_cache and _cacheable(model, hr_input, use_sliding_window):
+    if use_kv_cache and _cacheable(model, hr_input, use_sliding_window, cache_padded_heads):
         args = (model, hr_input, enc, total_seq, temperature, use_sliding_window, sliding_window, end_token,
                 shift, num_beam, beam_width, mode, progress, stop_len, pos_off, batch_beams, top_k, top_p,
                 decode_weights)

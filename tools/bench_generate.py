@@ -18,14 +18,16 @@ from models.Transformer import Transformer  # noqa: E402
 from qarig import sampling  # noqa: E402
 
 
-def build_stage_model(s, K, dev):
+def build_stage_model(s, K, dev, width=512, heads=64):
+    """width / heads: the README stage is 512 wide with 64 heads (head dim 8); 512 / 4 is head dim 128, 768 / 8 head
+    dim 96 (one of the head dims that train zero-padded: cached only with cache_padded_heads)."""
     base = s == 0
     return Transformer(use_encoder=not base, use_pos_cond=True,
                        num_enc_layers=None if base else 5, num_dec_layers=7,
                        num_enc_embedding=None if base else K,
-                       num_dec_embedding=2 * K if base else K + 1, self_attn_heads=64,
-                       cross_attn_heads=None if base else 64, transformer_in_dim=512,
-                       transformer_out_dim=K + 1, transformer_hidden_dim=2048).to(dev).eval()
+                       num_dec_embedding=2 * K if base else K + 1, self_attn_heads=heads,
+                       cross_attn_heads=None if base else heads, transformer_in_dim=width,
+                       transformer_out_dim=K + 1, transformer_hidden_dim=4 * width).to(dev).eval()
 
 
 def run_cascade(args, dev, K, N, patches, prev, models=None):
@@ -36,7 +38,8 @@ def run_cascade(args, dev, K, N, patches, prev, models=None):
     stages = []
     for s in range(args.stages):
         base = s == 0
-        model = models[s] if models is not None else build_stage_model(s, K, dev)
+        model = models[s] if models is not None else build_stage_model(s, K, dev, getattr(args, "width", 512),
+                                                                       getattr(args, "heads", 64))
         total = (32 // patches[s + 1]) ** 2
         first = prev if base else torch.full((N, 1), K, dtype=torch.int64, device=dev)
         lr_in = None if base else prev
@@ -49,7 +52,8 @@ def run_cascade(args, dev, K, N, patches, prev, models=None):
                                         use_kv_cache=not args.no_kv_cache, sampler=args.sampler,
                                         top_k=getattr(args, "top_k", 0),          # (callers with a namespace of their own:
                                         top_p=getattr(args, "top_p", 1.0),        # filters off, fp32 weights)
-                                        decode_weights=getattr(args, "decode_weights", "f32"))
+                                        decode_weights=getattr(args, "decode_weights", "f32"),
+                                        cache_padded_heads=getattr(args, "cache_padded_heads", False) or None)
         t_host = time.perf_counter() - t0           # until the call returned: everything enqueued, nothing awaited
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
@@ -86,6 +90,15 @@ def main():
     ap.add_argument("--weights-ab", type=int, default=0, metavar="ROUNDS",
                     help="A/B in one process: ROUNDS times the cascade with --decode-weights f32, then bf16, "
                          "alternating; reports accepted tokens/s of every round and the medians")
+    ap.add_argument("--width", type=int, default=512, help="model width of every stage (README: 512)")
+    ap.add_argument("--heads", type=int, default=64,
+                    help="attention heads of every stage (README: 64, head dim 8); --width 512 --heads 4: head dim 128")
+    ap.add_argument("--cache-padded-heads", action="store_true",
+                    help="generate from the key/value cache at the head dims that train zero-padded (multiples of 4 up "
+                         "to 124 other than 4 ... 64), e.g. --width 768 --heads 8")
+    ap.add_argument("--cache-ab", type=int, default=0, metavar="ROUNDS",
+                    help="A/B in one process: ROUNDS times the cascade from the key/value cache, then with "
+                         "--no-kv-cache, alternating; reports accepted tokens/s of every round and the medians")
     ap.add_argument("--rebuild-models", action="store_true",
                     help="new random stage models for every cascade (no decode cache is ever reused: the cost of a "
                          "generator's first call) instead of one set kept for the run")
@@ -111,7 +124,11 @@ def main():
                      f"kv_cache={not args.no_kv_cache}, sampler={args.sampler or sampling.DEFAULT_SAMPLER}, warm={not args.cold}, "
                      f"top_k={args.top_k}, top_p={args.top_p}, decode_weights={args.decode_weights}"}
     prev0 = torch.randint(0, K, (N, 1), device=dev)
-    models = None if args.rebuild_models else [build_stage_model(s_, K, dev) for s_ in range(args.stages)]
+    models = None if args.rebuild_models else [build_stage_model(s_, K, dev, args.width, args.heads)
+                                               for s_ in range(args.stages)]
+    out["config"] += f", width={args.width}, heads={args.heads}, cache_padded_heads={args.cache_padded_heads}"
+    if models is not None:
+        out["cacheable"] = bool(sampling._cacheable(models[0], prev0, True, args.cache_padded_heads or None))
     out["config"] += f", models={'rebuilt per cascade' if models is None else 'kept'}"
     if not args.cold:
         run_cascade(args, dev, K, N, patches, prev0, models)
@@ -149,6 +166,24 @@ def main():
         out["weights_ab"] = {"accepted_tokens_per_s": rates, "median": med,
                              "min": {w: min(v) for w, v in rates.items()}, "max": {w: max(v) for w, v in rates.items()},
                              "bf16_over_f32": round(med["bf16"] / med["f32"], 4)}
+    if args.cache_ab > 0:
+        import copy
+        import statistics
+        legs = {"cached": copy.copy(args), "no_kv_cache": copy.copy(args)}
+        legs["cached"].no_kv_cache, legs["no_kv_cache"].no_kv_cache = False, True
+        if not args.cold:                       # the warm-up above ran one of the two
+            run_cascade(legs["no_kv_cache" if not args.no_kv_cache else "cached"], dev, K, N, patches, prev0, models)
+        rates = {w: [] for w in legs}
+        for r in range(args.cache_ab):
+            for w, a in legs.items():
+                _, st = run_cascade(a, dev, K, N, patches, prev0, models)
+                rates[w].append(round(sum(N * x["seq"] for x in st) / sum(x["seconds_us"] * 1e-6 for x in st), 1))
+            print(f"[cache-ab] round {r + 1}: " + ", ".join(f"{w} {v[-1]}" for w, v in rates.items()), file=sys.stderr,
+                  flush=True)
+        med = {w: statistics.median(v) for w, v in rates.items()}
+        out["cache_ab"] = {"accepted_tokens_per_s": rates, "median": med,
+                           "min": {w: min(v) for w, v in rates.items()}, "max": {w: max(v) for w, v in rates.items()},
+                           "cached_over_no_kv_cache": round(med["cached"] / med["no_kv_cache"], 2)}
     prev, out["stages"] = run_cascade(args, dev, K, N, patches, prev0, models)
     tot_tokens = sum(N * st["seq"] for st in out["stages"])
     tot_time = sum(st["seconds"] for st in out["stages"])

@@ -10,7 +10,11 @@ kernel, unfiltered against filtered, in alternating blocks of back-to-back launc
 --decode-weights bf16 runs the step measurements with the weight-only bf16 step (kvcache.DECODE_WEIGHTS);
 --weights-ab instead times the "table" step's graph replay with fp32 and bf16 weights alternating in one process
 (7 rounds of --steps replays each: median, min, max) and reports the weight bytes a step streams in each mode,
-counted from the shapes of its Linear layers."""
+counted from the shapes of its Linear layers.
+--width / --heads choose the stage's shape (512 / 64, head dim 8, by default; 512 / 4 is head dim 128, 768 / 8 head
+dim 96); --heads-ab H times the "table" step's graph replay at --heads against H heads of the same width, alternating
+in one process (7 rounds of --steps replays each): the weight bytes of a step are the same, the attention launch
+differs."""
 import argparse
 import json
 import os
@@ -101,6 +105,31 @@ def weights_ab(model, enc, B, S, positions, steps, rounds=7):
             "streamed_weight_bytes_per_step": {"f32": 4 * n, "bf16": (2 if lp else 4) * n}}
 
 
+def heads_ab(models, encs, B, S, positions, steps, weights, rounds=7):
+    """ms per graph replay of the "table" step for each of `models` (name -> model): all captured first, then
+    `rounds` alternating blocks of `steps` replays each, the cache full (the longest attention)."""
+    import statistics
+    caches = {n: kvcache.DecodeCache(m, encs[n], B, S, graph=True, positions=positions, weights=weights)
+              for n, m in models.items()}
+    for c in caches.values():
+        ids = torch.zeros(B, dtype=torch.int64, device=c.kv.device)
+        for t in range(8):
+            c.step(ids, None, t)
+        c.ctl[0:1].fill_(S - 1)
+    t = {n: [] for n in caches}
+    for _ in range(rounds):
+        for n, c in caches.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                c._graph.replay()
+            torch.cuda.synchronize()
+            t[n].append(round((time.perf_counter() - t0) / steps * 1e3, 4))
+    med = {n: statistics.median(v) for n, v in t.items()}
+    return {"graph_replay_ms": t, "median_ms": med, "min_ms": {n: min(v) for n, v in t.items()},
+            "max_ms": {n: max(v) for n, v in t.items()}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=4)
@@ -115,6 +144,10 @@ def main():
                     help="weights the step streams (bf16: weight-only, everything else fp32)")
     ap.add_argument("--weights-ab", action="store_true",
                     help="only the fp32 / bf16 weights A/B of the table step's graph replay")
+    ap.add_argument("--width", type=int, default=512, help="model width (README: 512)")
+    ap.add_argument("--heads", type=int, default=64, help="attention heads (README: 64, head dim 8)")
+    ap.add_argument("--heads-ab", type=int, default=0, metavar="H",
+                    help="only the A/B of the table step's graph replay at --heads against H heads, same width")
     args = ap.parse_args()
     if args.draw_only or args.top_k > 0 or args.top_p < 1.0:
         dev = torch.device("cuda", 0)
@@ -130,14 +163,23 @@ def main():
     dev = torch.device("cuda", 0)
     torch.manual_seed(1)
     K, B, S = 512, args.rows, 256
-    model = build_stage_model(0 if args.base else 2, K, dev)
-    out = {"rows": B, "window": S, "options": args.opt, "stage": "base" if args.base else "encoder-decoder", "steps": args.steps,
+    model = build_stage_model(0 if args.base else 2, K, dev, args.width, args.heads)
+    out = {"width": args.width, "heads": args.heads, "head_dim": args.width // args.heads, "rows": B, "window": S, "options": args.opt, "stage": "base" if args.base else "encoder-decoder", "steps": args.steps,
            "decode_weights": args.decode_weights}
     with torch.no_grad():
         enc = None if args.base else model.encode(torch.randint(0, K, (B, 64), device=dev))
         ids = torch.randint(0, K, (B,), device=dev)
         pos = torch.rand(B, device=dev) * 100
         positions = [0.0] + [float(i + 1) for i in range(1, S)]
+        if args.heads_ab:
+            other = build_stage_model(0 if args.base else 2, K, dev, args.width, args.heads_ab)
+            names = {f"heads_{args.heads}_d{args.width // args.heads}": model,
+                     f"heads_{args.heads_ab}_d{args.width // args.heads_ab}": other}
+            lr = torch.randint(0, K, (B, 64), device=dev)
+            encs = {n: None if args.base else m.encode(lr) for n, m in names.items()}
+            out["heads_ab"] = heads_ab(names, encs, B, S, positions, args.steps, args.decode_weights)
+            print(json.dumps(out))
+            return
         if args.weights_ab:
             del out["decode_weights"]
             out["weights_ab"] = weights_ab(model, enc, B, S, positions, args.steps)
