@@ -33,7 +33,10 @@
 // exponentiated with v_exp_f32 (2^x).  Against exp((q.k)/sqrt(d) - m) this perturbs each
 // probability by <= ~1e-7 absolute (the product rounding is |x| * 2^-24 in the exponent
 // and terms with large |x| are themselves tiny), two orders inside the 1e-5 tolerance
-// stated for attention tensors; the saved LSE is kept in base-2 units (internal).
+// stated for attention tensors; the saved LSE is kept in base-2 units (internal).  The backward
+// passes recompute p = exp2(s * c - L) from that fp32 L, whose rounding (|L| * 2^-24) sits in the
+// exponent: their probabilities carry a relative error proportional to |lse| * 2^-24, about
+// 0.5 |L| 2^-24 ln 2, which only scores far from zero (|L| in the hundreds) make visible.
 #include <stdlib.h>
 
 #include "qarig_common.h"
@@ -160,6 +163,12 @@ __device__ __forceinline__ Vals<LP> make_vals(float a, float b, float c, float d
     else { r.v[0] = a; r.v[1] = b; r.v[2] = c; r.v[3] = d; }
     return r;
 }
+// Sum of the lane's four bf16 values as the matrix pipe reads them: the PV product against a column of ones
+// (every row of the 4x4 result holds it), off the vector ALU that bounds the forward pass.
+__device__ __forceinline__ float sum4_bf16(s16x4 b) {
+    const s16x4 ones = {0x3f80, 0x3f80, 0x3f80, 0x3f80};
+    return __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(ones, b, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0)[0];
+}
 // o[i] += sum over the 4 staged rows r of T[column 4g + i][r] * vals[r]   (r ascending)
 template <bool LP, typename T>
 __device__ __forceinline__ void acc_cols(f32x4& o, const T* trp, const Vals<LP>& x) {
@@ -220,6 +229,11 @@ __global__ __launch_bounds__(MAXT) void attn_fwd_kernel(const float* __restrict_
 #pragma unroll
     for (int g = 0; g < G; ++g) ov[g] = f32x4{0.f, 0.f, 0.f, 0.f};
     float m = -INFINITY, l = 0.0f;
+    // LP: the output is normalised by the sum of the probabilities AS ROUNDED for the PV product, so it is a convex
+    // combination of the V rows whatever the rounding took (and whatever residual the fma below leaves on the
+    // largest score: exp2(fma(s, c2, -fl(s c2))) is 1 + O(|s c2| 2^-24), which the bf16 rounding turns into 1 in
+    // the numerator only); the saved LSE keeps the unrounded sum
+    float lr = 0.0f;
 
     const float* kb = k + (int64_t)n * a.Sk * D + hg * HPB * HD;
     const float* vb = v + (int64_t)n * a.Sk * D + hg * HPB * HD;
@@ -264,6 +278,7 @@ __global__ __launch_bounds__(MAXT) void attn_fwd_kernel(const float* __restrict_
             const float msafe = mn == -INFINITY ? 0.0f : mn;     // fully masked so far: p = 0
             const float alpha = exp2_fast(m - msafe);
             l *= alpha;
+            if constexpr (LP) lr *= alpha;
 #pragma unroll
             for (int g = 0; g < G; ++g) ov[g] *= alpha;
             float p[KS];
@@ -284,6 +299,7 @@ __global__ __launch_bounds__(MAXT) void attn_fwd_kernel(const float* __restrict_
 #pragma unroll
             for (int u = 0; u < NQ; ++u) {
                 const Vals<LP> pv = make_vals<LP>(p[4 * u], p[4 * u + 1], p[4 * u + 2], p[4 * u + 3]);
+                if constexpr (LP) lr += sum4_bf16(pv.b);
 #pragma unroll
                 for (int g = 0; g < G; ++g) acc_cols<LP>(ov[g], Vc + (4 * g + li) * TS + jj + 4 * u, pv);
             }
@@ -296,7 +312,7 @@ __global__ __launch_bounds__(MAXT) void attn_fwd_kernel(const float* __restrict_
     }
     if (active) {
         float* op = o + ((int64_t)n * a.Sq + i) * D + h * HD;
-        const float inv = 1.0f / l;
+        const float inv = 1.0f / (LP ? lr : l);
 #pragma unroll
         for (int g = 0; g < G; ++g)
             *reinterpret_cast<float4*>(op + 4 * g) =
