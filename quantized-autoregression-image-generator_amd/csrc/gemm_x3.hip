@@ -11,8 +11,12 @@
 // once, so this chain rounds K / 16 x 6 times where the fp32 fma chain rounds K times: max|err| / max|ref| against
 // fp64 8.3e-7 (rms 9.0e-8) at K = 512 where the fp32 chain has 5.1e-7 (1.1e-7); 2.1e-6 (4.0e-7) against 2.3e-6
 // (4.5e-7) at K = 8192 -- inside the 2e-6 sqrt(K / 512) the parity tests ask of the fp32 kernels, which
-// tests/test_gpu_switches.py runs under this option.  Non-finite operands give NaN where the fp32 chain gives +-inf
-// (inf - inf in the split).
+// tests/test_gpu_switches.py runs under this option.  Per element, on one-hot / few-term operands with exact answers
+// (tests/test_gpu_gemm_selectors.py: every kernel of this file x layout x split; bit-exact on power-of-two columns and
+// under power-of-two row / column scales): a full x full product within 2.8 u = 2.8 x 2^-24 of itself, four terms
+// across the reduction within 8.1 u of their absolute sum (profiles/r15_gemm_selectors.txt).  Operand magnitudes
+// below about 2^-100 lose their l piece (a bf16 subnormal).  Non-finite operands give NaN where the fp32 chain gives
+// +-inf (inf - inf in the split); they stay in their row and column.
 //
 // 128 x 128 tile, 256 threads = 4 waves in a 2 x 2 arrangement of 64 x 64 (2 x 2 accumulators of 32 x 32), k-tiles
 // of 32.  Threads 0-127 stage A, 128-255 stage B: 8 float4 loads per thread and k-tile (a row's 32 k for a
