@@ -391,6 +391,15 @@ int qarig_decode_decide(int* ctl, int N, int NB, int beam_width, int draws, floa
 int qarig_decode_rows(const int* ctl, float* kv, float* staged, const int* take, int layers2, int N,
                       int NB, int H, int R, int d, int max_len, int restore, void* stream);
 
+/* Prefix prefill: token-major k / v (images, P1, H * d), row stride ld and image stride batch_stride in
+ * floats (a column sub-view of a wider buffer is fine), into rows [0, P1) of ONE layer of the head-major
+ * cache, kv (2, images * beams, H, max_len, d): keys into half 0, values into half 1, the same rows into
+ * every one of the `beams` candidate rows of an image.  Nothing else of kv is written.  16-B loads and
+ * stores: d % 4 == 0, ld % 4 == 0, batch_stride % 4 == 0, 16-B aligned operands.  P1 > max_len, a row
+ * stride shorter than H * d, null or misaligned pointers and non-positive extents are refused (-1). */
+int qarig_decode_cache_fill(const float* k, const float* v, int64_t ld, int64_t batch_stride, float* kv,
+                            int images, int beams, int H, int d, int P1, int max_len, void* stream);
+
 /* tokens[n][ctl[1] + j] = best_chunk[n][j]; ids of every beam = the chunk's last token;
  * ctl[0] = ctl[1] + beam_width - 1 (the step that follows produces the next chunk's first logits). */
 int qarig_decode_commit(int* ctl, int N, int NB, int beam_width, const int64_t* best_chunk,

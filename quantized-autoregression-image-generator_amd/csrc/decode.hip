@@ -1288,6 +1288,33 @@ __global__ __launch_bounds__(256) void decode_rows_kernel(const int* __restrict_
     }
 }
 
+// Prefix prefill: the keys and values a batched pass over the prefix produced, token-major k / v
+// (images, P1, H * d) with row stride ld and image stride bs (floats), into rows [0, P1) of one layer of the
+// head-major cache kv (2, images * NB, H, max_len, d) -- every candidate row of an image gets the same rows.
+// One 16-B load per item, NB 16-B stores; consecutive lanes walk a head's rows, so the stores of a wave are one run.
+__global__ __launch_bounds__(256) void decode_cache_fill_kernel(const float* __restrict__ k,
+                                                                const float* __restrict__ v, int64_t ld, int64_t bs,
+                                                                float* __restrict__ kv, int images, int NB, int H,
+                                                                int d, int P1, int max_len) {
+    const int64_t dq = d / 4;
+    const int64_t per = (int64_t)H * P1 * dq;
+    const int64_t total = 2 * (int64_t)images * per;
+    const int64_t half = (int64_t)images * NB * H * max_len * d;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        int64_t r_ = i;
+        const int c = (int)(r_ % dq); r_ /= dq;
+        const int t = (int)(r_ % P1); r_ /= P1;
+        const int h = (int)(r_ % H); r_ /= H;
+        const int n = (int)(r_ % images);
+        const int hv = (int)(r_ / images);
+        const float* src = (hv ? v : k) + (int64_t)n * bs + (int64_t)t * ld + (int64_t)h * d + 4 * c;
+        const float4 val = ld4(src);
+        float* dst = kv + hv * half + ((((int64_t)n * NB) * H + h) * max_len + t) * d + 4 * c;
+        for (int b = 0; b < NB; ++b)
+            *reinterpret_cast<float4*>(dst + (int64_t)b * H * max_len * d) = val;
+    }
+}
+
 // The kept chunk becomes part of the sequence: tokens[n][cur + j] = best_chunk[n][j]; its last token is
 // the input of the step that produces the next chunk's first logits, at window index cur + bw - 1.
 __global__ __launch_bounds__(64) void decode_commit_kernel(int* __restrict__ ctl, int N, int NB, int bw,
@@ -1738,6 +1765,31 @@ extern "C" int qarig_decode_rows(const int* ctl, float* kv, float* staged, const
     hipLaunchKernelGGL(decode_rows_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, ctl, kv, staged, take,
                        layers2, N, NB, H, R, d, max_len, restore);
     QARIG_CHECK_LAUNCH("decode_rows");
+    return QARIG_OK;
+}
+
+extern "C" int qarig_decode_cache_fill(const float* k, const float* v, int64_t ld, int64_t batch_stride, float* kv,
+                                       int images, int beams, int H, int d, int P1, int max_len, void* stream) {
+    QARIG_CHECK_ARG(k && v && kv, "decode_cache_fill: null pointer");
+    QARIG_CHECK_ARG(images > 0 && beams > 0 && H > 0 && d > 0 && d % 4 == 0 && P1 > 0 && max_len > 0,
+                    "decode_cache_fill: bad extents (d %% 4 == 0)");
+    QARIG_CHECK_ARG(P1 <= max_len, "decode_cache_fill: %d prefix rows for a cache of %d", P1, max_len);
+    QARIG_CHECK_DIMS("decode_cache_fill", images, beams, H, max_len);
+    QARIG_CHECK_DIMS("decode_cache_fill", max_len, H, d);
+    QARIG_CHECK_ARG(qarig_dims_ok({2, (long long)images * beams, (long long)max_len * H * d}, 1LL << 40, 1LL << 44),
+                    "decode_cache_fill: cache too large");
+    QARIG_CHECK_ARG(ld >= (int64_t)H * d && ld % 4 == 0 && ld <= (1LL << 32),
+                    "decode_cache_fill: row stride shorter than H * d, or no multiple of 4");
+    QARIG_CHECK_ARG(batch_stride >= 0 && batch_stride % 4 == 0 && batch_stride <= (1LL << 40) &&
+                    (images == 1 || batch_stride >= (int64_t)(P1 - 1) * ld + (int64_t)H * d),
+                    "decode_cache_fill: image stride shorter than the rows of an image, or no multiple of 4");
+    QARIG_CHECK_ARG((((uintptr_t)k | (uintptr_t)v | (uintptr_t)kv) & 15) == 0,
+                    "decode_cache_fill: operands must be 16-B aligned");
+    const int64_t total = 2 * (int64_t)images * H * P1 * (d / 4);
+    const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+    hipLaunchKernelGGL(decode_cache_fill_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, k, v, ld,
+                       batch_stride, kv, images, beams, H, d, P1, max_len);
+    QARIG_CHECK_LAUNCH("decode_cache_fill");
     return QARIG_OK;
 }
 

@@ -19,7 +19,7 @@ from utils.image_utils import save_images
 from utils.model_utils import load_model
 
 
-def parse_args():
+def parse_args(argv=None):
     p = argparse.ArgumentParser(description="Generate Images.")
     p.add_argument("--device", choices=["cpu", "cuda"], type=str, default="cpu",
                    help="Which hardware device will model run on.")
@@ -69,7 +69,17 @@ def parse_args():
                         "images x num_beam <= 16 and the model fits the streaming kernel.  Weight-only: activations, "
                         "accumulation, LayerNorm, attention, the key/value cache and sampling stay fp32.  Not the "
                         "fp32 parity mode.")
-    return vars(p.parse_args())
+    p.add_argument("--prompt-fmaps", type=pathlib.Path, default=None,
+                   help="(additive) image completion: a feature-map dataset index (generate_fmap_dataset.py's JSON); "
+                        "its first --num-images latents are the prompts.  Every stage tokenises them with its own "
+                        "codebooks, keeps the top rows of its token grid (--prompt-fraction) and generates the rest; "
+                        "stage 0 takes its condition token from the latent's LR code instead of a random one.  The "
+                        "decode of the real tokens is saved as prompt_model_{index}.jpg.  Needs --prompt-fraction.")
+    p.add_argument("--prompt-fraction", type=float, default=None,
+                   help="(additive) share of the token rows each stage keeps from the prompt, inside (0, 1): "
+                        "floor(fraction x rows) rows.  The kept token count must be a multiple of the stage's "
+                        "beam_width and, for a stage with a sliding window, stay below the window.")
+    return vars(p.parse_args(argv))
 
 
 def main():
@@ -85,6 +95,8 @@ def main():
     config = cc.read_config(args["config_path"])
     decoder_model, _ = cc.load_decoder(args["decoder_path"], device)
     decoder_model.eval()
+    prompted = cc.check_prompt_args(args["prompt_fmaps"], args["prompt_fraction"])
+    prompt_z = cc.load_prompt_latents(args["prompt_fmaps"], lo, hi, device) if prompted else None
 
     hr_input = None
     for index, data in config.items():          # stages "0", "1", "2" in file order
@@ -120,7 +132,14 @@ def main():
                 # base stage: a random LR-codebook token is the image-level condition
                 k_lr = lr_d["num_embeddings"]
                 lr_input = None
-                hr_input = torch.randint(low=0, high=k_lr, size=(n_local, 1), device=device)
+                if prompted:    # the image-level condition of the real latent: its LR code (as training assembles it)
+                    hr_input = torch.zeros((n_local, 1), dtype=torch.int64, device=device)
+                    if n_local:
+                        hr_input = lr_codebook.get_patches_bmu(prompt_z, reshape=True)
+                        if hr_input.shape[1] != 1:
+                            raise Exception("Invalid LR codebook for a prompt: the base stage takes one LR token!")
+                else:
+                    hr_input = torch.randint(low=0, high=k_lr, size=(n_local, 1), device=device)
                 all_cond = parallel.gather_rows(hr_input, num_images)
                 if rank == 0:
                     cond = decoder_model(lr_codebook.get_quantized_image(indices=all_cond, unpatchify_input=True))
@@ -133,6 +152,21 @@ def main():
             # optional per-stage keys (the reference's config files have neither: off)
             top_k = data.get("top_k", 0) if args["top_k"] is None else args["top_k"]
             top_p = data.get("top_p", 1.0) if args["top_p"] is None else args["top_p"]
+            kept = 0
+            if prompted:
+                # the stage's own tokens of the real latents (train_quantized_transformer.py tokenises the same
+                # way); the top rows of the grid, in the numbering the loop appends (+ shift), follow the start token
+                kept = cc.prompt_tokens(args["prompt_fraction"], hr_d["image_dim"], hr_d["patch_dim"],
+                                        data["beam_width"], md["sliding_window"] if md["use_sliding_window"] else None)
+                real = torch.zeros((0, total_Seq), dtype=torch.int64, device=device)
+                if n_local:
+                    real = hr_codebook.get_patches_bmu(prompt_z, reshape=True)
+                    hr_input = torch.cat((hr_input, real[:, :kept] + shift), dim=1)
+                all_real = parallel.gather_rows(real, num_images)
+                if rank == 0:
+                    truth = decoder_model(hr_codebook.get_quantized_image(indices=all_real, unpatchify_input=True))
+                    save_images(images=truth, file_name=f"prompt_model_{index}", dest_path=out_dir, logging=print)
+                log(f"Prompt: {kept:,} / {total_Seq:,} tokens kept")
             if n_local:
                 hr_input = sampling.generate_tokens(
                     model, hr_input, lr_input, total_Seq, data["temperature"], md["use_sliding_window"],
@@ -144,10 +178,16 @@ def main():
                     decode_weights=args["decode_weights"],
                     cache_padded_heads=args["cache_padded_heads"] or None)
                 hr_input = hr_input[:, 1:] - shift
-            else:                                        # more ranks than images: nothing to generate here
+                if prompted and not torch.equal(hr_input[:, :kept], real[:, :kept]):
+                    raise Exception("The completion does not keep the prompt's tokens!")
+            else:                                       # more ranks than images: nothing to generate here
                 hr_input = torch.zeros((0, total_Seq), dtype=torch.int64, device=device)
             ops.check_index_flag(device, f"stage {index} tokens")
             all_tokens = parallel.gather_rows(hr_input, num_images)
+            if prompted and rank == 0:
+                same = torch.equal(all_tokens[:, :kept], all_real[:, :kept])
+                log(f"Prompt: completions {'keep' if same else 'DO NOT keep'} the {kept:,} prompt tokens of "
+                    f"{num_images:,} images")
             if rank == 0:
                 recon = decoder_model(hr_codebook.get_quantized_image(indices=all_tokens, unpatchify_input=True))
                 ops.check_index_flag(device, f"stage {index} tokens")

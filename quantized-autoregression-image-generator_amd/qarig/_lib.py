@@ -97,6 +97,7 @@ SIGNATURES = {
     "qarig_decode_sample_filtered": (I, [P, L, I, I, F, I, I, L, P, P, P, I, I, I, I, I, P, P, P, P, I, F, P]),
     "qarig_decode_decide": (I, [P, I, I, I, I, P, P, P, P, P, P]),
     "qarig_decode_rows": (I, [P, P, P, P, I, I, I, I, I, I, I, I, P]),
+    "qarig_decode_cache_fill": (I, [P, P, L, L, P, I, I, I, I, I, I, P]),
     "qarig_decode_commit": (I, [P, I, I, I, P, P, L, P, P]),
     "qarig_decode_advance": (I, [P, I, P]),
     "qarig_window_step_supported": (I, [I, I, I, I]),

@@ -102,6 +102,44 @@ class ShardedLoader:
             yield torch.utils.data.default_collate([self.dataset[i] for i in idx])
 
 
+def check_prompt_args(prompt_fmaps, prompt_fraction):
+    """generate_images.py --prompt-fmaps / --prompt-fraction: both or neither, the fraction inside (0, 1).
+    Returns whether the run is prompted."""
+    if prompt_fmaps is None and prompt_fraction is None:
+        return False
+    if prompt_fmaps is None or prompt_fraction is None:
+        raise SystemExit("--prompt-fmaps and --prompt-fraction go together")
+    if not 0.0 < float(prompt_fraction) < 1.0:       # NaN fails both comparisons
+        raise SystemExit(f"--prompt-fraction must be inside (0, 1), got {prompt_fraction!r}")
+    return True
+
+
+def prompt_tokens(fraction, image_dim, patch_dim, beam_width, sliding_window=None):
+    """Tokens of a stage's own token grid that a prompted run keeps: the top floor(fraction x patch_rows) rows.
+    The generation loop appends whole chunks, so a kept count that is no multiple of `beam_width` is refused
+    like a beam_width that does not divide the sequence; sliding_window (a stage that slides): the start token
+    and the kept tokens must leave the window room (a prefix at or past the window is out of scope)."""
+    rows, cols = image_dim[0] // patch_dim[0], image_dim[1] // patch_dim[1]
+    kept = int(float(fraction) * rows + 1e-9) * cols      # (0.29 x 100 is 28.999...6 in binary: still 29 rows)
+    if kept % beam_width != 0:
+        raise Exception("Invalid value for beam_width!")
+    if sliding_window is not None and 1 + kept >= sliding_window:
+        raise Exception(f"Invalid value for prompt-fraction: {kept} prompt tokens reach the sliding window "
+                        f"({sliding_window})!")
+    return kept
+
+
+def load_prompt_latents(path, lo, hi, device):
+    """Latents lo .. hi-1 of a feature-map dataset index (generate_fmap_dataset.py's output) as one batch."""
+    from dataset_loader.feature_map_dataset import FeatureMapDataset
+    data = FeatureMapDataset(dataset_path=path)
+    if len(data) < hi:
+        raise Exception(f"--prompt-fmaps holds {len(data)} latents, {hi} images asked for!")
+    if hi <= lo:
+        return None
+    return torch.stack([data[i] for i in range(lo, hi)]).to(device)
+
+
 def halve_lr(optim):
     for g in optim.param_groups:
         g["lr"] = g["lr"] * 0.5

@@ -57,6 +57,19 @@ DECODE_WEIGHTS = ("f32", "bf16")
 _WEIGHTS_WARNED = False
 
 
+# Generation from a token prefix (`DecodeCache.prefill`): the cache rows of the prefix but its last token come from
+# ONE batched pass over all of them (the model's full-window kernels, one row per image and not per candidate,
+# qarig_decode_cache_fill writing each layer's keys / values into every candidate row) when the prefix has at least
+# this many such rows; shorter ones replay the step graph once per token.
+# Measured (profiles/r16_prefill_ab.json: tools/bench_generate.py --prefill-ab 7 at config 3's three stages, 4 and 16
+# cache rows): the batched pass is ~150 eager launches on a few rows, 1.8 - 2.9 ms whether it covers 4 tokens or 128;
+# a replay is 0.21 - 0.44 ms per token.  At 4 rows 8 tokens are a tie (batched / replays 0.93 - 1.07), at 16 rows
+# the batched pass wins there in two stages (0.72 - 0.78; the third cell's batched arm was noisy: 1.19); from 12
+# tokens up it wins in every cell (0.48 - 0.79 at 12, 0.07 at 128 tokens); at 4 tokens the replays win everywhere
+# (1.4 - 2.0).  The batched arm is host-bound (eager launches) and scatters more than the replayed graph.
+PREFILL_MIN_TOKENS = 12
+
+
 def check_decode_weights(weights):
     if weights not in DECODE_WEIGHTS:
         raise ValueError(f"decode weights {weights!r}: expected one of {DECODE_WEIGHTS}")
@@ -113,6 +126,7 @@ class DecodeCache:
         if weights == "bf16":
             self._build_images()
         self._table = None
+        self._cross_tm = self._prefill_cond = None      # prefill's operands, built by the first batched prefill
         if positions is not None and model.use_pos_cond and self._proj_lin and self.dim % 4 == 0:
             self._build_table(positions)
         self._graph = None
@@ -148,6 +162,7 @@ class DecodeCache:
             if old is not None:
                 old[0].copy_(new[0])
                 old[1].copy_(new[1])
+        self._cross_tm = None
         self.ctl.zero_()
         return True
 
@@ -478,6 +493,93 @@ class DecodeCache:
         """View of cache rows [lo, hi) of every layer: (layer, 2, B, H, hi-lo, d)."""
         return self.kv[:, :, :, :, lo:hi]
 
+    # -- generation from a token prefix ---------------------------------------------------------
+    def prefill_batched(self, P1):
+        """Whether `prefill` evaluates P1 prefix rows as one batched pass (else: P1 replays of the step).
+        The replays serve bf16 step weights (every Linear of the cache then keeps that mode's rounded weights),
+        a position-conditioned model whose cache has no per-position table, a model width that is no multiple
+        of 4 (the fill kernel's 16-B rows), and prefixes below PREFILL_MIN_TOKENS."""
+        return P1 >= max(1, PREFILL_MIN_TOKENS) and self.weights == "f32" and self.dim % 4 == 0 and \
+            (self.dim // self.heads) % 4 == 0 and not (self.model.use_pos_cond and self._table is None)
+
+    @torch.no_grad()
+    def prefill(self, tokens, pos=None):
+        """Cache rows [0, P1) of every layer from `tokens` (images, P1) int64 -- a prefix without its last token,
+        one row per image: every candidate row of an image (batch = images x beams, beams of an image adjacent)
+        receives the image's keys and values.  The logits of these tokens are not evaluated; the caller runs the
+        prefix's last token through `step` (or the search's graph) like any other.  A run that continues from here
+        is a from-scratch run interrupted at this point, up to fp32 summation order.
+        pos: the `pos_cond` value of each of the P1 window indices, needed only by a cache built without
+        `positions` for a position-conditioned model (the step replays then take it)."""
+        tokens = tokens.to(torch.int64)
+        images, P1 = tokens.shape
+        if images < 1 or self.batch % images:
+            raise ValueError(f"prefill: {images} images do not divide the cache's {self.batch} rows")
+        if P1 > self.max_len:
+            raise IndexError(f"prefill: {P1} prefix rows for a cache of {self.max_len}")
+        if P1 == 0:
+            return
+        beams = self.batch // images
+        if not self.prefill_batched(P1):
+            B, dev = self.batch, self.kv.device
+            for t in range(P1):
+                p = None
+                if self.model.use_pos_cond and self._table is None:
+                    p = torch.full((B,), float(pos[t]), device=dev)
+                self.step(tokens[:, t].repeat_interleave(beams) if beams > 1 else tokens[:, t], p, t)
+            return
+        self._prefill_forward(tokens.contiguous(), beams)
+
+    def _prefill_operands(self, images, P1):
+        """(cond, cross): the CondTable that reads the cache's own per-position projections at window indices
+        0 .. P1-1 of every image (None without position conditioning), and per layer the encoder memory's
+        token-major (k, v) of one row per image (None without cross-attention).  Both are built from what the
+        cache holds: the projections per Linear once per cache, the k / v once per encoder memory."""
+        dev, D, L = self.kv.device, self.dim, self.max_len
+        cond = None
+        if self._table is not None:
+            if self._prefill_cond is None:
+                P = len(self._proj_lin)
+                self._prefill_cond = self._table.view(L, P, D).permute(1, 0, 2).contiguous()       # (P, L, D)
+            tabs = self._prefill_cond
+            idx = torch.arange(P1, dtype=torch.int32, device=dev).repeat(images)
+            cond = QF.CondTable(tabs[0], idx, (images, P1))
+            for j, lin in enumerate(self._proj_lin):
+                cond._proj[id(lin)] = tabs[j]
+        if self._cross_tm is None or self._cross_tm[0] != images:
+            beams = self.batch // images
+            tm = lambda t: t[::beams].permute(0, 2, 1, 3).reshape(images, t.shape[2], -1).contiguous()
+            self._cross_tm = (images, [None if c is None else (tm(c[0]), tm(c[1])) for c in self.cross])
+        return cond, self._cross_tm[1]
+
+    def _prefill_forward(self, tokens, beams):
+        """The batched pass: window assembly as QF.embedding_pos does it, then per layer what WindowStep._forward
+        spells out for its last layer, on all rows -- norm, q / k / v MLPs, causal attention, residual,
+        cross-attention block on the cache's cross k / v, feed-forward -- with the layer's k and v written into
+        the cache by one qarig_decode_cache_fill launch.  The last layer stops behind its k / v: nothing reads
+        the rows' outputs (the logits are discarded)."""
+        model = self.model
+        images, P1 = tokens.shape
+        cond, cross = self._prefill_operands(images, P1)
+        x = QF.embedding_pos(tokens, model.dec_embedding.weight, self.pe[:P1])
+        layers = model.decoder_layers
+        for li, layer in enumerate(layers):
+            sab = layer.self_attn_block
+            at = sab.self_attn
+            h, _ = _norm_forward(sab.self_attn_norm, x, cond, sab.use_adaln0)
+            final = li == len(layers) - 1
+            k = _mlp2_forward(at.k_block, h)
+            v = _mlp2_forward(at.v_block, h)
+            ops.decode_cache_fill(k, v, self.kv[li], beams)
+            if final:
+                break
+            q = _mlp2_forward(at.q_block, h)
+            o = QF.attention(q, k, v, at.heads, True)
+            x = sab.self_attn_res(x=o, x_skip=x, cond=cond)
+            if layer.use_cross_attn:
+                x = layer.cross_attn_block(x, cross_cond=None, cond=cond, kv=cross[li])
+            x = layer.feedforward_block(x, cond=cond)
+
     # -- device-resident chunk search ----------------------------------------------------------
     @torch.no_grad()
     def begin_search(self, first_ids, images, beams, beam_width, temperature, end_token, shift, generate_mode,
@@ -486,7 +588,9 @@ class DecodeCache:
         """Prepares the search of generate_images.py:256-345 on `images` x `beams` cache rows (beams > 1:
         the candidate chunks of an image as rows of one batch; beams == 1: `candidates` chunks one after the
         other): evaluates the first token (window index 0), captures the step's graph, draws the uniforms of
-        every draw the stage can make (ONE call of the device generator).  forced: optional (draws, columns)
+        every draw the stage can make (ONE call of the device generator).  first_ids: (N,) or (N, 1) ids, or an
+        (N, P) prefix: its first P - 1 tokens are prefilled (`prefill`), the step is replayed for token P - 1 and
+        the chunk search starts at window index P.  forced: optional (draws, columns)
         int64, entries >= 0 replace the draw (tests); log_probs: keep every probability row sampled from.
         top_k / top_p: every draw of the search is made from the filtered row (ops.decode_sample; 0 / 1.0: off).
         The draws are launches of their own between the replays of the step graph, so the graph does not change.
@@ -541,9 +645,14 @@ class DecodeCache:
             f = torch.as_tensor(forced, dtype=torch.int64, device=dev).reshape(-1, cols)[:draws]
             s.forced[:f.shape[0]] = f
         s.probs = torch.zeros((draws, cols, V), dtype=torch.float32, device=dev) if log_probs else None
-        first = first_ids.reshape(N).to(torch.int64)
-        s.tokens[:, 0] = first
-        s.ids.copy_(first.repeat_interleave(NB))
+        first = first_ids.to(torch.int64)
+        prefix = first.reshape(N, 1) if first.dim() < 2 else first.reshape(N, -1)
+        P = prefix.shape[1]
+        if not 1 <= P <= self.max_len:
+            raise ValueError(f"begin_search: a prefix of {P} tokens for a cache of {self.max_len} rows")
+        s.P = P
+        s.tokens[:, :P] = prefix
+        s.ids.copy_(prefix[:, 0].repeat_interleave(NB))
         self.ctl.zero_()
         s.gen, s.T, s.end, s.shift = bool(generate_mode), float(temperature), int(end_token), int(shift)
         s.top_k, s.top_p = top_k, top_p
@@ -562,12 +671,18 @@ class DecodeCache:
             s.g_step = torch.cuda.CUDAGraph()
             with torch.cuda.graph(s.g_step):
                 self._forward(s.ids, None, 0, self.ctl, out=s.logits)
-        s.g_step.replay()                      # the first token, window index 0
-        s.last.copy_(s.logits)
-        # chunk search starts behind the first token: window index 1
-        self.ctl.zero_()
-        self.ctl[0:2].fill_(1)
         self._search = s
+        if P > 1:
+            # the prefix but its last token fills cache rows [0, P - 1); the last one goes through the captured
+            # step like every token after it, so s.last comes from the same kernels as always
+            self.prefill(prefix[:, :P - 1])
+            s.ids.copy_(prefix[:, P - 1].repeat_interleave(NB))
+            self.ctl[0:1].fill_(P - 1)
+        s.g_step.replay()                      # the prefix's last token, window index P - 1 (from scratch: 0)
+        s.last.copy_(s.logits)
+        # chunk search starts behind the prefix: window index P (from scratch: 1)
+        self.ctl.zero_()
+        self.ctl[0:2].fill_(P)
         return s
 
     def _draw(self, slot, src, inc):
@@ -601,9 +716,10 @@ class DecodeCache:
         s.chunks += 1
 
     def finish_search(self):
-        """(N, 1 + chunks * beam_width) tokens of the sequences, first token included."""
+        """(N, P + chunks * beam_width) tokens of the sequences, the P tokens of the prefix (from scratch: the
+        first token) included."""
         s = self._search
-        return s.tokens[:, :1 + s.chunks * s.bw].clone()
+        return s.tokens[:, :s.P + s.chunks * s.bw].clone()
 
 
 def _mlp2_fits(seq, R):

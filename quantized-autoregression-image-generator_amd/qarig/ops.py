@@ -1226,6 +1226,23 @@ def decode_rows(ctl, kv, staged, take, N, NB, restore):
                                         max_len, int(bool(restore)), stream()), "qarig_decode_rows")
 
 
+def decode_cache_fill(k, v, kv_layer, beams):
+    """Rows [0, P1) of one layer of the head-major cache, kv_layer (2, images * beams, H, max_len, d), from
+    token-major k / v (images, P1, H * d) with a row and an image stride of their own (unit channel stride):
+    every candidate row of an image gets the image's rows.  One launch for both halves."""
+    require_cuda(k, v, kv_layer)
+    two, B, H, max_len, d = kv_layer.shape
+    images, P1, D = k.shape
+    beams = int(beams)
+    assert two == 2 and B == images * beams and D == H * d and kv_layer.is_contiguous()
+    assert k.dtype == v.dtype == kv_layer.dtype == torch.float32
+    assert v.shape == k.shape and v.stride() == k.stride() and k.stride(2) == 1
+    if P1 > max_len:
+        raise IndexError(f"decode_cache_fill: {P1} prefix rows for a cache of {max_len}")
+    check(_lib.load().qarig_decode_cache_fill(ptr(k), ptr(v), k.stride(1), k.stride(0), ptr(kv_layer), images, beams,
+                                              H, d, P1, max_len, stream()), "qarig_decode_cache_fill")
+
+
 def decode_commit(ctl, N, NB, beam_width, best_chunk, tokens, ids):
     require_cuda(ctl, best_chunk, tokens, ids)
     assert tokens.dtype == torch.int64 and tokens.dim() == 2 and tokens.shape[0] == N and tokens.stride(1) == 1

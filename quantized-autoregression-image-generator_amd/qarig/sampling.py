@@ -85,8 +85,30 @@ def _sample(logits, temperature, end_token, mode, rows, comb, top_k=0, top_p=1.0
 CACHE_PADDED_HEADS = False
 
 
-def _cacheable(model, hr_input, use_sliding_window, cache_padded_heads=None):
-    if not (hr_input.shape[1] == 1 and hasattr(model, "decoder_layers")
+def _prefix_pos(N, S0, pos_off, device):
+    """`pos_cond` values (N, S0) of a prefix as the loop would have numbered them had it produced the tokens
+    itself: index 0 gets 0, index L >= 1 gets L + pos_off (the `positions` _generate_fused builds)."""
+    if S0 == 1:
+        return torch.zeros((N, 1), device=device)
+    vals = torch.tensor([0.0] + [float(L + pos_off) for L in range(1, S0)], device=device)
+    return vals[None].expand(N, -1).contiguous()
+
+
+def _cache_limit(hr_input, total_seq, use_sliding_window, sliding_window, beam_width, mode):
+    """Rows of the decode cache of a stage (_generate_fused / _generate_cached: the tokens the loop reaches,
+    overshoot included, or the window)."""
+    stop_len = total_seq if mode == "generate" else hr_input.shape[1] + total_seq
+    cap = stop_len + beam_width
+    return min(cap, sliding_window) if use_sliding_window else cap
+
+
+def _cacheable(model, hr_input, use_sliding_window, cache_padded_heads=None, beam_width=None, limit=None):
+    """limit, beam_width: the cache's rows and the chunk length -- a prefix of S0 > 1 tokens generates from the
+    cache when at least one cached chunk fits behind it (S0 + beam_width <= limit); without them only S0 == 1."""
+    S0 = hr_input.shape[1]
+    if S0 > 1 and (limit is None or beam_width is None or S0 + beam_width > limit):
+        return False
+    if not (S0 >= 1 and hasattr(model, "decoder_layers")
             and bool(model.use_pos_cond) == bool(use_sliding_window)
             and all(l.self_attn_block.self_attn.use_masked_attn for l in model.decoder_layers)):
         return False
@@ -280,8 +302,8 @@ def _generate_fused(model, hr_input, enc, total_seq, temperature, use_sliding_wi
     B = num_beam if (batch_beams or ordered) and num_beam > 1 else 1
     cap = stop_len + beam_width
     limit = min(cap, sliding_window) if use_sliding_window else cap
-    pos = torch.zeros((N, 1), device=device) if use_sliding_window else None
     cur = hr_input.shape[1]
+    pos = _prefix_pos(N, cur, pos_off, device) if use_sliding_window else None
     chunks = 0
     while cur + chunks * beam_width < stop_len and cur + (chunks + 1) * beam_width <= limit:
         chunks += 1
@@ -297,7 +319,8 @@ def _generate_fused(model, hr_input, enc, total_seq, temperature, use_sliding_wi
     dbg = FUSED_DEBUG or {}
     after = cur + chunks * beam_width                      # tokens (first included) once the cached chunks are in
     tail_chunks = max(0, -(-(stop_len - after) // beam_width))          # chunks _fused_tail draws for
-    cache.begin_search(hr_input[:, 0], N, B, beam_width, temperature, end_token, shift, mode == "generate",
+    # a prefix of cur > 1 tokens: its first cur - 1 rows are prefilled, the search starts at window index cur
+    cache.begin_search(hr_input[:, 0] if cur == 1 else hr_input, N, B, beam_width, temperature, end_token, shift, mode == "generate",
                        chunks + tail_chunks, 1 if B > 1 else num_beam, forced=dbg.get("forced"),
                        log_probs=bool(dbg.get("log")), reference_order=ordered, top_k=top_k, top_p=top_p)
     tm.mark("capture")
@@ -395,8 +418,8 @@ def _generate_cached(model, hr_input, enc, total_seq, temperature, use_sliding_w
     # the full-window loop (whose ragged row counts run the guarded GEMM kernels: 14 % of a 3-stage cascade)
     cap = stop_len + beam_width
     limit = min(cap, sliding_window) if use_sliding_window else cap
-    pos = torch.zeros((N, 1), device=device) if use_sliding_window else None
     cur = hr_input.shape[1]
+    pos = _prefix_pos(N, cur, pos_off, device) if use_sliding_window else None
     if cur + beam_width > limit:
         return hr_input, pos
     enc_b = enc.repeat_interleave(B, dim=0) if (enc is not None and B > 1) else enc
@@ -406,7 +429,11 @@ def _generate_cached(model, hr_input, enc, total_seq, temperature, use_sliding_w
     def positions(value):
         return torch.full((N * B,), float(value), device=device) if use_sliding_window else None
 
-    last = cache.step(hr_input[:, 0].repeat_interleave(B), positions(0.0), 0)
+    # a prefix: rows [0, cur - 1) are prefilled, its last token is the first step (from scratch: token 0 at index 0)
+    pvals = [0.0] + [float(L + pos_off) for L in range(1, cur)]
+    if cur > 1:
+        cache.prefill(hr_input[:, :cur - 1], pos=pvals)
+    last = cache.step(hr_input[:, cur - 1].repeat_interleave(B), positions(pvals[cur - 1]), cur - 1)
     while cur < stop_len and cur + beam_width <= limit:
         best_chunk = best_p = best_rows = None
         for _ in range(1 if B > 1 else num_beam):
@@ -457,8 +484,16 @@ def generate_tokens(model, hr_input, lr_input, total_seq, temperature, use_slidi
                     sliding_window, end_token, shift=0, num_beam=1, beam_width=1, mode="generate",
                     progress=None, batch_beams=False, use_kv_cache=True, sampler=None, window_graph=False,
                     top_k=0, top_p=1.0, decode_weights="f32", cache_padded_heads=None):
-    """hr_input: (N, S0) int64 conditioning/start tokens.  Returns the extended (N, S) tensor
-    (first tokens included; callers strip them and undo `shift`).  use_kv_cache: evaluate one
+    """hr_input: (N, S0) int64 conditioning/start tokens, S0 >= 1.  Returns the extended (N, S) tensor
+    (first tokens included; callers strip them and undo `shift`).
+    S0 > 1 is a prefix (the start token and S0 - 1 tokens already in the `shift`ed numbering the loop appends):
+    the run behaves as a from-scratch run interrupted behind it -- the token at index L >= 1 has position
+    L + pos_off (1 in "generate", 0 in "train"), index 0 has position 0.  It generates from the key/value cache
+    when one cached chunk fits behind it (S0 + beam_width <= the cache's rows: kvcache.DecodeCache.prefill
+    fills the prefix's rows); a longer prefix keeps the full-window loop.  A prefix at or past the sliding
+    window (S0 >= sliding_window with use_sliding_window) is out of scope: the loop slides by one token per
+    draw and would evaluate a window longer than the model was trained on.
+    use_kv_cache: evaluate one
     token per step from a key/value cache until the window starts to slide (same logits up
     to fp32 summation order); False re-runs the window for every token like the reference.
     sampler: "fused" / "torch" for the cached loop (DEFAULT_SAMPLER).
@@ -489,8 +524,9 @@ def generate_tokens(model, hr_input, lr_input, total_seq, temperature, use_slidi
     # (generate_images.py:256-345 loops over them only through the batch dimension).
     group = max(1, DECODE_ROWS // max(1, num_beam))
     rows_all = N * max(1, num_beam)
+    limit = _cache_limit(hr_input, total_seq, use_sliding_window, sliding_window, beam_width, mode)
     if fused and GROUP_IMAGES and use_kv_cache and N > group and DECODE_ROWS < rows_all < GROUP_BELOW_ROWS and \
-            _cacheable(model, hr_input, use_sliding_window, cache_padded_heads):
+            _cacheable(model, hr_input, use_sliding_window, cache_padded_heads, beam_width, limit):
         outs = []
         for g0 in range(0, N, group):
             sub = slice(g0, min(N, g0 + group))
@@ -502,13 +538,13 @@ def generate_tokens(model, hr_input, lr_input, total_seq, temperature, use_slidi
                                         decode_weights=decode_weights, cache_padded_heads=cache_padded_heads))
         return torch.cat(outs, dim=0)
     enc = model.encode(lr_input) if model.use_encoder else None
-    pos = torch.zeros((N, 1), device=device) if use_sliding_window else None
+    pos_off = 1 if mode == "generate" else 0
+    pos = _prefix_pos(N, hr_input.shape[1], pos_off, device) if use_sliding_window else None
     start = 0
     rows = torch.arange(N, device=device)
     stop_len = total_seq if mode == "generate" else hr_input.shape[1] + total_seq
-    pos_off = 1 if mode == "generate" else 0
     cache = None
-    if use_kv_cache and _cacheable(model, hr_input, use_sliding_window, cache_padded_heads):
+    if use_kv_cache and _cacheable(model, hr_input, use_sliding_window, cache_padded_heads, beam_width, limit):
         args = (model, hr_input, enc, total_seq, temperature, use_sliding_window, sliding_window, end_token,
                 shift, num_beam, beam_width, mode, progress, stop_len, pos_off, batch_beams, top_k, top_p,
                 decode_weights)

@@ -67,6 +67,56 @@ def run_cascade(args, dev, K, N, patches, prev, models=None):
     return prev, stages
 
 
+def prefill_ab(args, dev, K, N, patches, models):
+    """--prefill-ab: DecodeCache.prefill of the first P - 1 tokens of a P-token prefix as one batched pass against
+    P - 1 replays of the step graph, alternating in one process, on the search cache of every stage whose cache holds
+    the prefix (config 3: 20 / 68 / 256 rows).  Wall time of the call, synchronised, in ms; ROUNDS per arm."""
+    import statistics
+    from qarig import kvcache
+    NB = args.num_beam
+    records = []
+    for s in range(args.stages):
+        base = s == 0
+        model = models[s]
+        total = (32 // patches[s + 1]) ** 2
+        limit = min(total + args.beam_width, 256)
+        g = torch.Generator().manual_seed(100 + s)
+        with torch.no_grad():
+            enc = None
+            if not base:
+                lr_in = torch.randint(0, K, (N, (32 // patches[s]) ** 2), generator=g).to(dev)
+                enc = model.encode(lr_in).repeat_interleave(NB, dim=0)
+            positions = [0.0] + [float(L + 1) for L in range(1, limit)]
+            cache = sampling.decode_cache(model, enc, N * NB, limit, positions)
+            first = torch.randint(0, K, (N,), generator=g).to(dev)
+            cache.begin_search(first, N, NB, args.beam_width, 1.0, K, K if base else 0, True, 1, 1)   # the step graph
+        for P in args.prefix:
+            if P > limit or P < 2:
+                continue
+            lo = K if base else 0
+            toks = torch.randint(lo, lo + K, (N, P - 1), generator=g).to(dev)
+            arms = {"batched": 0, "replays": 1 << 30}
+            ms = {a: [] for a in arms}
+            for r in range(args.prefill_ab + 1):            # round 0: untimed (code objects, workspaces, operands)
+                for a, floor in arms.items():
+                    kvcache.PREFILL_MIN_TOKENS = floor
+                    assert cache.prefill_batched(P - 1) == (a == "batched")
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    cache.prefill(toks)
+                    torch.cuda.synchronize()
+                    if r:
+                        ms[a].append(round((time.perf_counter() - t0) * 1e3, 3))
+            med = {a: statistics.median(v) for a, v in ms.items()}
+            rec = {"stage": s, "cache_rows": N * NB, "images": N, "cache_len": limit, "prefill_tokens": P - 1,
+                   "ms": ms, "median_ms": med, "replay_ms_per_token": round(med["replays"] / (P - 1), 4),
+                   "batched_over_replays": round(med["batched"] / med["replays"], 3)}
+            records.append(rec)
+            print(f"[prefill-ab] stage {s} rows {N * NB} P-1 {P - 1}: batched {med['batched']} ms, replays "
+                  f"{med['replays']} ms", file=sys.stderr, flush=True)
+    return records
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=4)
@@ -99,6 +149,12 @@ def main():
     ap.add_argument("--cache-ab", type=int, default=0, metavar="ROUNDS",
                     help="A/B in one process: ROUNDS times the cascade from the key/value cache, then with "
                          "--no-kv-cache, alternating; reports accepted tokens/s of every round and the medians")
+    ap.add_argument("--prefix", type=int, nargs="+", default=[17], metavar="P",
+                    help="--prefill-ab: prefix lengths (tokens, start token included); P - 1 rows are prefilled")
+    ap.add_argument("--prefill-ab", type=int, default=0, metavar="ROUNDS",
+                    help="A/B in one process: ROUNDS times DecodeCache.prefill of a P-token prefix as one batched pass, "
+                         "then as P - 1 step replays, alternating, per stage; reports every round's ms and the "
+                         "medians, then exits (no cascade).  Cache rows: --images x --num-beam")
     ap.add_argument("--rebuild-models", action="store_true",
                     help="new random stage models for every cascade (no decode cache is ever reused: the cost of a "
                          "generator's first call) instead of one set kept for the run")
@@ -130,6 +186,12 @@ def main():
     if models is not None:
         out["cacheable"] = bool(sampling._cacheable(models[0], prev0, True, args.cache_padded_heads or None))
     out["config"] += f", models={'rebuilt per cascade' if models is None else 'kept'}"
+    if args.prefill_ab > 0:
+        if models is None:
+            raise SystemExit("--prefill-ab keeps one set of models (drop --rebuild-models)")
+        out["prefill_ab"] = prefill_ab(args, dev, K, N, patches, models)
+        print(json.dumps(out))
+        return
     if not args.cold:
         run_cascade(args, dev, K, N, patches, prev0, models)
     if args.filter_ab > 0:
