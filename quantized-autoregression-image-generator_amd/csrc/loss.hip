@@ -21,17 +21,19 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ 
     float s = 0.0f;
     for (int c = lane; c < C; c += 64) s += expf(x[c] - mx);
     s = wave_sum(s);
-    const float lse = mx + logf(s);
+    // log s - (x[t] - mx) and exp((x - mx) - log s): every rounding happens at the magnitude of the loss, not of
+    // the logits (mx + log s first costs ulp(|mx|) -- 6e-5 at logits near 1000)
+    const float logs = logf(s);
     const int64_t t = target[row];
     const bool ok = t >= 0 && t < C;
     if (lane == 0) {
         if (!ok) atomicExch(bad, 1);
-        row_loss[row] = ok ? lse - x[t] : 0.0f;
+        row_loss[row] = ok ? logs - (x[t] - mx) : 0.0f;
     }
     if (dlogits) {
         float* d = dlogits + (int64_t)row * C;
         for (int c = lane; c < C; c += 64) {
-            const float p = expf(x[c] - lse);
+            const float p = expf((x[c] - mx) - logs);
             d[c] = (p - ((int64_t)c == t ? 1.0f : 0.0f)) * inv_m;
         }
     }
@@ -52,17 +54,22 @@ __global__ __launch_bounds__(256) void mean_kernel(const float* __restrict__ v, 
     if (threadIdx.x == 0) out[0] = red[0] * inv_m;
 }
 
-// F.mse_loss(pred, target) (mean) and d/dpred = 2 (pred - target) / n, fixed-order sum.
+// F.mse_loss(pred, target) (mean) and d/dpred = 2 (pred - target) / n, fixed-order sum.  The gradient is the
+// product with inv_n = 1 / n corrected by one Newton step (nf = (float)n): the quotient to within one rounding, so
+// two roundings (a - b, the quotient) and 2 u of the exact value; the bare product would add the rounding of 1 / n.
 __global__ __launch_bounds__(256) void mse_partial_kernel(const float* __restrict__ a,
                                                           const float* __restrict__ b, int64_t n,
-                                                          float inv_n, float* __restrict__ part,
+                                                          float inv_n, float nf, float* __restrict__ part,
                                                           float* __restrict__ da) {
     __shared__ float red[256];
     float s = 0.0f;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const float d = a[i] - b[i];
         s = fmaf(d, d, s);
-        if (da) da[i] = 2.0f * d * inv_n;
+        if (da) {
+            const float t = 2.0f * d, q = t * inv_n;
+            da[i] = fmaf(fmaf(-q, nf, t), inv_n, q);
+        }
     }
     red[threadIdx.x] = s;
     __syncthreads();
@@ -89,7 +96,7 @@ extern "C" int qarig_mse_fwd(const float* pred, const float* target, int64_t n, 
     hipStream_t st = (hipStream_t)stream;
     const float inv_n = 1.0f / (float)n;
     hipLaunchKernelGGL(mse_partial_kernel, dim3(MSE_BLOCKS), dim3(256), 0, st, pred, target, n,
-                       inv_n, part_ws, dpred);
+                       inv_n, (float)n, part_ws, dpred);
     QARIG_CHECK_LAUNCH("mse partial");
     hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, st, part_ws, MSE_BLOCKS, inv_n, loss);
     QARIG_CHECK_LAUNCH("mse mean");
