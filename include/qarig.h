@@ -593,6 +593,20 @@ int qarig_adam_step(float* p, const float* g, float* m, float* v, int64_t n, flo
                     float beta2, float eps, float step_size, float bc2_sqrt, float grad_scale,
                     const float* dev_step, void* shadow_bf16, void* stream);
 
+/* The same step, with an exponential moving average of the parameters kept by the same launch (additive: the
+ * reference has none): ema (n floats, in place) <- lerp(ema, p_new, ema_w) in the two-branch form of exp_avg,
+ * so ema_w = 1 copies p_new, ema_w = 0 leaves ema alone and ema == p_new stays, all exactly.  dev_step
+ * (optional) is a device float[3] here, {step_size, bc2_sqrt, ema_w}.  p, m, v and shadow_bf16 come out
+ * bit-identical to qarig_adam_step on the same inputs. */
+int qarig_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float beta1,
+                        float beta2, float eps, float step_size, float bc2_sqrt, float ema_w,
+                        float grad_scale, const float* dev_step, void* shadow_bf16, void* stream);
+
+/* Exchanges two fp32 buffers of n elements in place, bit for bit (NaN payloads included): 16-byte accesses
+ * where both buffers are 16-byte aligned, with a scalar tail; scalar throughout otherwise.  The buffers must
+ * not overlap; null pointers, n <= 0 and overlapping ranges are refused (-1) without a launch. */
+int qarig_swap_f32(float* a, float* b, int64_t n, void* stream);
+
 /* elementwise helpers (ResidualLinearLayer gate, models/layers.py:293-295) */
 int qarig_mul_fwd(const float* a, const float* b, float* y, int64_t n, void* stream);
 int qarig_mul_bwd(const float* dy, const float* a, const float* b, float* da, float* db, int64_t n,

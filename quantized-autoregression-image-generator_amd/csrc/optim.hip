@@ -7,14 +7,19 @@
 
 namespace qarig {
 
+// EMA: the same pass also moves an exponential moving average of the parameters, e <- lerp(e, pn, ema_w),
+// one more read and one more write stream on the launch (7 -> 9), no further launch.  p, m, v and the shadow
+// are computed by the very expressions of the plain instantiation.
+template <bool EMA>
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
-                            float* __restrict__ m, float* __restrict__ v, int64_t n, float beta1,
-                            float beta2, float eps, float step_size, float bc2_sqrt,
-                            float grad_scale, const float* __restrict__ dev_step,
-                            unsigned short* __restrict__ shadow) {
+                            float* __restrict__ m, float* __restrict__ v, float* __restrict__ ema,
+                            int64_t n, float beta1, float beta2, float eps, float step_size,
+                            float bc2_sqrt, float ema_w, float grad_scale,
+                            const float* __restrict__ dev_step, unsigned short* __restrict__ shadow) {
     if (dev_step) {     // captured-graph replay: the per-step scalars live in device memory
         step_size = dev_step[0];
         bc2_sqrt = dev_step[1];
+        if (EMA) ema_w = dev_step[2];
     }
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * blockDim.x) {
@@ -30,12 +35,36 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
         p[i] = pn;
         m[i] = mn;
         v[i] = vn;
+        if (EMA) {
+            // the two-branch lerp again: ema_w = 1 yields pn, ema_w = 0 keeps e, and e == pn stays, all exactly
+            const float ei = ema[i];
+            ema[i] = ema_w < 0.5f ? ei + ema_w * (pn - ei) : pn - (pn - ei) * (1.0f - ema_w);
+        }
         if (shadow) {       // reduced-precision mode: the bf16 copy the GEMMs read, from the same pass
             typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
             typedef float f32x2_t __attribute__((ext_vector_type(2)));
             const f32x2_t f = {pn, 0.0f};
             shadow[i] = (unsigned short)(__builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2_t)) & 0xffffu);
         }
+    }
+}
+
+// Exchanges two fp32 buffers in place, as bit patterns (no arithmetic touches the values): 16-byte body where
+// both buffers are 16-byte aligned, scalar tail behind it.
+__global__ void swap_f32_kernel(unsigned* __restrict__ a, unsigned* __restrict__ b, int64_t nvec, int64_t n) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    uint4* a4 = (uint4*)a;
+    uint4* b4 = (uint4*)b;
+    for (int64_t i = t; i < nvec; i += stride) {
+        const uint4 x = a4[i], y = b4[i];
+        a4[i] = y;
+        b4[i] = x;
+    }
+    for (int64_t i = nvec * 4 + t; i < n; i += stride) {
+        const unsigned x = a[i], y = b[i];
+        a[i] = y;
+        b[i] = x;
     }
 }
 
@@ -56,8 +85,42 @@ extern "C" int qarig_adam_step(float* p, const float* g, float* m, float* v, int
     QARIG_CHECK_ARG(p && g && m && v && n > 0 && n <= (1LL << 40), "adam: bad arguments");
     int64_t b = (n + 255) / 256;
     if (b > 8192) b = 8192;
-    hipLaunchKernelGGL(adam_kernel, dim3((int)b), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
-                       beta1, beta2, eps, step_size, bc2_sqrt, grad_scale, dev_step, (unsigned short*)shadow_bf16);
+    hipLaunchKernelGGL(adam_kernel<false>, dim3((int)b), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+                       (float*)nullptr, n, beta1, beta2, eps, step_size, bc2_sqrt, 0.0f, grad_scale, dev_step,
+                       (unsigned short*)shadow_bf16);
     QARIG_CHECK_LAUNCH("adam");
+    return QARIG_OK;
+}
+
+// The same step with an exponential moving average of the parameters kept from the same pass:
+// ema <- lerp(ema, p_new, ema_w), n floats, updated in place.  dev_step here holds 3 floats,
+// {step_size, bc2_sqrt, ema_w}.  p, m, v and shadow_bf16 come out as qarig_adam_step leaves them.
+extern "C" int qarig_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, int64_t n,
+                                   float beta1, float beta2, float eps, float step_size, float bc2_sqrt,
+                                   float ema_w, float grad_scale, const float* dev_step, void* shadow_bf16,
+                                   void* stream) {
+    QARIG_CHECK_ARG(p && g && m && v && ema && n > 0 && n <= (1LL << 40), "adam_ema: bad arguments");
+    int64_t b = (n + 255) / 256;
+    if (b > 8192) b = 8192;
+    hipLaunchKernelGGL(adam_kernel<true>, dim3((int)b), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n,
+                       beta1, beta2, eps, step_size, bc2_sqrt, ema_w, grad_scale, dev_step,
+                       (unsigned short*)shadow_bf16);
+    QARIG_CHECK_LAUNCH("adam_ema");
+    return QARIG_OK;
+}
+
+// a <-> b, n floats each, bit-exact.  The buffers must not overlap (refused).
+extern "C" int qarig_swap_f32(float* a, float* b, int64_t n, void* stream) {
+    QARIG_CHECK_ARG(a && b && n > 0 && n <= (1LL << 40), "swap_f32: bad arguments");
+    const uintptr_t ua = (uintptr_t)a, ub = (uintptr_t)b;
+    QARIG_CHECK_ARG(ua % 4 == 0 && ub % 4 == 0, "swap_f32: buffers must be 4-byte aligned");
+    QARIG_CHECK_ARG(ua + 4 * (uint64_t)n <= ub || ub + 4 * (uint64_t)n <= ua, "swap_f32: buffers overlap");
+    const int64_t nvec = (ua % 16 == 0 && ub % 16 == 0) ? n / 4 : 0;
+    const int64_t work = nvec > n - 4 * nvec ? nvec : n - 4 * nvec;
+    int64_t blocks = (work + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(swap_f32_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, (unsigned*)a,
+                       (unsigned*)b, nvec, n);
+    QARIG_CHECK_LAUNCH("swap_f32");
     return QARIG_OK;
 }

@@ -79,6 +79,11 @@ def parse_args(argv=None):
                    help="(additive) share of the token rows each stage keeps from the prompt, inside (0, 1): "
                         "floor(fraction x rows) rows.  The kept token count must be a multiple of the stage's "
                         "beam_width and, for a stage with a sliding window, stay below the window.")
+    # (absent from the parsed arguments unless given: a run without the flag parses to what it always did)
+    p.add_argument("--use-ema", action="store_true", default=argparse.SUPPRESS,
+                   help="(additive) every Transformer stage loads the exponential moving average of its weights "
+                        "(the checkpoint's 'model_ema', written by train_quantized_transformer.py --ema-decay) "
+                        "instead of the last-step weights; a stage file without one is an error.")
     return vars(p.parse_args(argv))
 
 
@@ -123,7 +128,10 @@ def main():
             transformer_in_dim=md["transformer_in_dim"], transformer_out_dim=md["transformer_out_dim"],
             transformer_hidden_dim=md["transformer_hidden_dim"],
             hidden_activation=md["hidden_activation"])
-        model.custom_load_state_dict(md["model"])
+        use_ema = args.get("use_ema", False)
+        if use_ema and "model_ema" not in md:
+            raise Exception(f"--use-ema: {data['model_path']} holds no 'model_ema' (train with --ema-decay)!")
+        model.custom_load_state_dict(md["model_ema" if use_ema else "model"])
         model = model.to(device).eval()
 
         with torch.no_grad():

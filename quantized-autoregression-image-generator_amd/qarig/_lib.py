@@ -109,6 +109,8 @@ SIGNATURES = {
     "qarig_mse_workspace_bytes": (Z, []),
     "qarig_mse_fwd": (I, [P, P, L, P, P, P, P]),
     "qarig_adam_step": (I, [P, P, P, P, L, F, F, F, F, F, F, P, P, P]),
+    "qarig_adam_ema_step": (I, [P, P, P, P, P, L, F, F, F, F, F, F, F, P, P, P]),
+    "qarig_swap_f32": (I, [P, P, L, P]),
     "qarig_mul_fwd": (I, [P, P, P, L, P]),
     "qarig_mul_bwd": (I, [P, P, P, P, P, L, P]),
     "qarig_act_fwd": (I, [P, P, L, I, P]),

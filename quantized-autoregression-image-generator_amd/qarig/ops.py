@@ -1345,6 +1345,28 @@ def adam_step(p, g, m, v, beta1, beta2, eps, step_size, bc2_sqrt, grad_scale=1.0
           "qarig_adam_step")
 
 
+def adam_ema_step(p, g, m, v, ema, beta1, beta2, eps, step_size, bc2_sqrt, ema_w, grad_scale=1.0, dev_step=None,
+                  shadow=None):
+    """adam_step that also moves `ema` (fp32, p's numel) towards the updated parameters by weight ema_w.
+    dev_step, when given, holds three floats: {step_size, bc2_sqrt, ema_w}."""
+    assert shadow is None or (shadow.dtype == torch.bfloat16 and shadow.numel() == p.numel())
+    assert ema.dtype == torch.float32 and ema.numel() == p.numel() and ema.is_contiguous()
+    assert dev_step is None or dev_step.numel() >= 3
+    check(_lib.load().qarig_adam_ema_step(ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), p.numel(), beta1, beta2, eps,
+                                          step_size, bc2_sqrt, ema_w, grad_scale, ptr(dev_step), ptr(shadow),
+                                          stream()),
+          "qarig_adam_ema_step")
+
+
+def swap_(a, b):
+    """Exchanges the contents of two fp32 tensors of equal size in place, bit for bit.  They must not overlap."""
+    require_cuda(a, b)
+    if a.dtype != torch.float32 or b.dtype != torch.float32 or a.numel() != b.numel() \
+            or not (a.is_contiguous() and b.is_contiguous()):
+        raise ValueError("swap_: two contiguous fp32 tensors of the same size")
+    check(_lib.load().qarig_swap_f32(ptr(a), ptr(b), a.numel(), stream()), "qarig_swap_f32")
+
+
 def mul_fwd(a, b):
     y = torch.empty_like(a)
     check(_lib.load().qarig_mul_fwd(ptr(a), ptr(b), ptr(y), a.numel(), stream()), "qarig_mul_fwd")

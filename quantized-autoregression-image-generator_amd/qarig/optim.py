@@ -8,7 +8,9 @@ torch.optim.Adam as the reference uses it (betas=(0.5, 0.999), eps 1e-8, no weig
 decay; train_quantized_transformer.py:317-334), so "model_optimizer" entries of
 reference checkpoints load and save unchanged.
 """
+import contextlib
 import math
+import struct
 
 import torch
 import torch.distributed as dist
@@ -18,6 +20,17 @@ from . import ops
 # Gradient buckets for the overlapped data-parallel all-reduce: 16 Mi floats = 64 MiB keeps
 # each xGMI link busy with few, large messages (ring collectives are per-link bound).
 BUCKET_ELEMS = 16 * 1024 * 1024
+
+
+def ema_weight(count, decay, warmup=True):
+    """Weight of the new parameters in EMA update number `count` (0-based): 1 - decay, or with warm-up
+    1 - min(decay, (1 + count) / (10 + count)), so that an average started from the initial weights forgets
+    them within tens of steps instead of 1 / (1 - decay).  Computed in double, rounded to fp32 once (the
+    value the kernel receives)."""
+    d = float(decay)
+    if warmup:
+        d = min(d, (1.0 + count) / (10.0 + count))
+    return struct.unpack("f", struct.pack("f", 1.0 - d))[0]
 
 
 class FlatAdam:
@@ -46,6 +59,8 @@ class FlatAdam:
         self._overlap = False
         self._works = []
         self._capture_cut = None    # set by pipeline._SegmentedCapture while it records a step
+        self.flat_ema = None        # enable_ema
+        self._ema_swapped = False   # inside ema_weights()
         with torch.no_grad():
             for p, o, s in zip(self.params, offs, sizes):
                 view = self.flat_param[o:o + s].view(p.shape)
@@ -181,14 +196,31 @@ class FlatAdam:
             v = self._shadow_views[i] = self.flat_shadow[o:o + p.numel()].view(p.shape)
         return v
 
+    def _adam(self, b1, b2, eps, step_size, bc2_sqrt, ema_w, grad_scale, dev_step, shadow):
+        if self.flat_ema is None:
+            ops.adam_step(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, b1, b2,
+                          eps, step_size, bc2_sqrt, grad_scale, dev_step=dev_step, shadow=shadow)
+        else:
+            ops.adam_ema_step(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, self.flat_ema,
+                              b1, b2, eps, step_size, bc2_sqrt, ema_w, grad_scale, dev_step=dev_step,
+                              shadow=shadow)
+
+    def _refuse_swapped(self):
+        if self._ema_swapped:
+            raise RuntimeError("FlatAdam: no optimizer step inside ema_weights() (the parameters hold the EMA)")
+
     def step(self, grad_scale=1.0):
+        self._refuse_swapped()
         self.step_count += 1
         g = self.param_groups[0]
         b1, b2 = g["betas"]
         step_size, bc2_sqrt = self._step_scalars(self.step_count)
         shadow = self._shadow_buffer()
-        ops.adam_step(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, b1, b2,
-                      g["eps"], step_size, bc2_sqrt, grad_scale, shadow=shadow)
+        ema_w = 0.0
+        if self.flat_ema is not None:
+            ema_w = ema_weight(self.ema_count, self.ema_decay, self.ema_warmup)
+            self.ema_count += 1
+        self._adam(b1, b2, g["eps"], step_size, bc2_sqrt, ema_w, grad_scale, None, shadow)
         ops.lp_invalidate()      # cached bf16 / e4m3 copies made from the old weights are stale now
         if shadow is not None:
             self._shadow_written()
@@ -198,18 +230,20 @@ class FlatAdam:
     # -- graph replay (qarig.pipeline.GraphedTrainStep) -----------------------------------
     def _dev_step_buffer(self):
         if not hasattr(self, "_dev_step"):
-            self._dev_step = torch.zeros(2, dtype=torch.float32, device=self.flat_param.device)
+            # {step_size, bc2_sqrt} and, with the EMA on, its weight
+            self._dev_step = torch.zeros(2 if self.flat_ema is None else 3, dtype=torch.float32,
+                                         device=self.flat_param.device)
         return self._dev_step
 
     def step_captured(self, grad_scale=1.0):
         """The Adam launch as it is recorded into a captured training-step graph: step size and
         bias correction are read from a device buffer that `advance_captured` refreshes on the
         host before every replay (learning-rate changes included)."""
+        self._refuse_swapped()
         g = self.param_groups[0]
         b1, b2 = g["betas"]
         shadow = self._shadow_buffer()
-        ops.adam_step(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, b1, b2,
-                      g["eps"], 0.0, 1.0, grad_scale, dev_step=self._dev_step_buffer(), shadow=shadow)
+        self._adam(b1, b2, g["eps"], 0.0, 1.0, 0.0, grad_scale, self._dev_step_buffer(), shadow)
         ops.lp_invalidate()
         if shadow is not None:
             self._shadow_written()
@@ -221,13 +255,110 @@ class FlatAdam:
         parameters without touching torch's version counters, so the reduced-precision weight
         shadows an eager forward may have cached (per-checkpoint sampling between replays) are stale
         from here on."""
+        self._refuse_swapped()
         self.step_count += 1
-        step_size, bc2_sqrt = self._step_scalars(self.step_count)
+        scalars = list(self._step_scalars(self.step_count))
+        if self.flat_ema is not None:
+            scalars.append(ema_weight(self.ema_count, self.ema_decay, self.ema_warmup))
+            self.ema_count += 1
         if not hasattr(self, "_dev_step_feed"):
             from .pipeline import PinnedFeed
             self._dev_step_feed = PinnedFeed(self._dev_step_buffer())
-        self._dev_step_feed.push(torch.tensor([step_size, bc2_sqrt], dtype=torch.float32))
+        self._dev_step_feed.push(torch.tensor(scalars, dtype=torch.float32))
         ops.lp_invalidate()
+
+    # -- exponential moving average of the parameters (additive: the reference keeps none) ----------------
+    def enable_ema(self, decay, warmup=True):
+        """Keeps flat_ema, an EMA of flat_param, from here on: the Adam launch of every step moves it by
+        ema_weight(ema_count, decay, warmup) towards the parameters it has just computed.  Starts as a copy of
+        the present parameters.  Must be called before a step is captured: the captured launch reads its three
+        scalars from a device buffer that has to exist, at its final size, before the capture."""
+        if not (0.0 < float(decay) < 1.0):       # (NaN fails both comparisons)
+            raise ValueError(f"EMA decay must lie in (0, 1), got {decay}")
+        if hasattr(self, "_dev_step"):
+            raise RuntimeError("FlatAdam.enable_ema: a captured step was already recorded (its launch reads a "
+                               "two-float scalar buffer and has no EMA); enable the EMA before the first "
+                               "captured step")
+        if self._ema_swapped:
+            raise RuntimeError("FlatAdam.enable_ema inside ema_weights()")
+        self.ema_decay, self.ema_warmup = float(decay), bool(warmup)
+        self.flat_ema = self.flat_param.clone()
+        self.ema_count = 0
+
+    def _need_ema(self):
+        if self.flat_ema is None:
+            raise RuntimeError("FlatAdam: no EMA (call enable_ema first)")
+
+    def ema_views(self):
+        """Per-parameter views of flat_ema, in parameter order."""
+        self._need_ema()
+        return [self.flat_ema[o:o + p.numel()].view(p.shape) for p, o in zip(self.params, self.offsets)]
+
+    def _ema_index(self, model):
+        index = {id(p): i for i, p in enumerate(self.params)}
+        return [(name, index[id(p)]) for name, p in model.named_parameters(remove_duplicate=False)
+                if id(p) in index]
+
+    def ema_meta(self):
+        """Plain numbers and a bool (loads under the weights-only unpickler)."""
+        self._need_ema()
+        return {"decay": self.ema_decay, "count": int(self.ema_count), "warmup": self.ema_warmup}
+
+    @torch.no_grad()
+    def ema_state_dict(self, model):
+        """model.state_dict() with every parameter this optimizer owns replaced by a clone of its EMA; buffers
+        (and parameters it does not own) as the model holds them."""
+        self._need_ema()
+        if self._ema_swapped:
+            raise RuntimeError("FlatAdam.ema_state_dict inside ema_weights()")
+        sd = model.state_dict()
+        views = self.ema_views()
+        for name, i in self._ema_index(model):
+            if name in sd:
+                sd[name] = views[i].clone()
+        return sd
+
+    @torch.no_grad()
+    def load_ema(self, state_dict_like, model, count):
+        """Resume: the EMA from the entries of `state_dict_like` (keys as model.state_dict()), its update
+        count from `count`."""
+        self._need_ema()
+        if self._ema_swapped:
+            raise RuntimeError("FlatAdam.load_ema inside ema_weights()")
+        views = self.ema_views()
+        for name, i in self._ema_index(model):
+            if name not in state_dict_like:
+                raise KeyError(f"EMA state has no entry {name!r}")
+            views[i].copy_(state_dict_like[name].reshape(views[i].shape))
+        self.ema_count = int(count)
+
+    def _exchange_with_ema(self):
+        ops.swap_(self.flat_param, self.flat_ema)
+        # the swap writes the flat buffer behind torch's version counters and the step count: every copy derived
+        # from the old contents is declared stale here
+        ops.lp_invalidate()
+        ops.bmu_invalidate()
+        self._shadow_versions = None
+        from . import sampling
+        sampling.decode_cache_clear()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the context the model's parameters hold the EMA (sampling, evaluation); on exit they hold the
+        raw weights again, bit for bit.  Contents are exchanged, never pointers: a captured step holds the
+        addresses.  Not re-entrant; no optimizer step inside."""
+        self._need_ema()
+        if self._ema_swapped:
+            raise RuntimeError("FlatAdam.ema_weights is not re-entrant")
+        if self._works or (self._overlap and (self._done or self._launched)):
+            raise RuntimeError("FlatAdam.ema_weights: an overlapped gradient all-reduce is pending")
+        self._exchange_with_ema()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._exchange_with_ema()
+            self._ema_swapped = False
 
     def state_dict(self):
         state = {}

@@ -96,13 +96,16 @@ def gather_rows(t, n):
 
 
 def broadcast_params(optim, src=0):
-    """Rank `src`'s parameters to every rank.  optim: the FlatAdam that owns them (or its flat parameter
-    buffer).  The broadcast writes the flat buffer behind torch's per-parameter version counters, so every
+    """Rank `src`'s parameters to every rank -- and the EMA of them, when the optimizer keeps one.  optim: the
+    FlatAdam that owns them (or its flat parameter buffer).  The broadcast writes the flat buffer behind torch's per-parameter version counters, so every
     copy derived from the old values -- the bf16 image of the reduced-precision mode, cached bf16 / e4m3 /
     re-ordered conv weights -- is declared stale here rather than left to a key that did not change."""
     flat = getattr(optim, "flat_param", optim)
+    ema = getattr(optim, "flat_ema", None)       # FlatAdam.enable_ema: the average travels with the parameters
     if world_size() > 1:
         dist.broadcast(flat, src=src)
+        if ema is not None:
+            dist.broadcast(ema, src=src)
     from . import ops
     ops.lp_invalidate()
     ops.bmu_invalidate()

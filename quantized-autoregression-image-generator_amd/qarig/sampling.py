@@ -168,8 +168,9 @@ class _Timer:
 # weights: a server, a CLI run over several batches): what a cache holds beyond the sequence itself -- the
 # per-position table of the conditioning projections, the stacked weights, the captured step graph, the search's
 # buffers -- depends on the weights, the batch and the window only.  Keyed by the model object and the state of
-# every parameter (data pointer, torch's version counter, the owning FlatAdam's step count); a write into the
-# weights that none of those sees (p.data arithmetic) needs decode_cache_clear().
+# every parameter (data pointer, torch's version counter, the owning FlatAdam's step count) plus ops.LP_EPOCH,
+# which every write into a flat parameter buffer bumps; a write into the weights that none of those sees
+# (p.data arithmetic) needs decode_cache_clear().
 _DECODE_CACHES = {}
 DECODE_CACHE_SLOTS = 8
 
@@ -180,7 +181,9 @@ def decode_cache_clear():
 
 
 def _weights_key(model):
-    key = []
+    # ops.LP_EPOCH: every write into a flat parameter buffer that none of the per-parameter entries sees
+    # (parallel.broadcast_params, FlatAdam.ema_weights' swap) bumps it
+    key = [ops.LP_EPOCH]
     for p in model.parameters():
         owner = getattr(p, "_qarig_owner", None)
         key.append((p.data_ptr(), p._version, owner.step_count if owner is not None else -1))

@@ -75,6 +75,12 @@ def parse_args():
                         "one file per item; same items, same order")
     p.add_argument("--max-steps", type=int, default=None,
                    help="(additive) stop after this many optimiser steps.")
+    p.add_argument("--ema-decay", type=float, default=0.0,
+                   help="(additive; the reference keeps no such average) keep an exponential moving average of "
+                        "the weights with this decay (0 < D < 1, e.g. 0.999; 0 = off), updated by the optimiser's "
+                        "own launch with the usual warm-up min(D, (1 + n) / (10 + n)).  Checkpoints then also "
+                        "carry 'model_ema' / 'model_ema_meta' (generate_images.py --use-ema samples from it) and "
+                        "every checkpoint writes a second sample grid, high_res_recon_ema_<steps>")
     return vars(p.parse_args())
 
 
@@ -133,6 +139,14 @@ def main():
             for g in optim.param_groups:
                 g["lr"] = model_lr
     parallel.broadcast_params(optim)
+    ema_decay = args["ema_decay"]
+    if ema_decay:
+        # after the broadcast and the optimizer state: the average starts from the parameters every rank holds
+        resumed = args["model_path"] is not None and args["load_optim"] and "model_ema" in saved
+        meta = saved.get("model_ema_meta", {}) if resumed else {}
+        optim.enable_ema(ema_decay, warmup=meta.get("warmup", True))
+        if resumed:
+            optim.load_ema(saved["model_ema"], model, meta.get("count", 0))
     optim.enable_allreduce_overlap()     # no-op at world 1
 
     dataset = FeatureMapDataset(dataset_path=args["dataset_path"], load_image=False,
@@ -186,6 +200,8 @@ def main():
     info(f"Batch Size: {args['batch_size']:,}" + (f" x {world} GPUs" if world > 1 else ""))
     info(f"Model LR Update size: {args['lr_step']:,}")
     info(f"Model Checkpoint step: {args['checkpoint_step']:,}")
+    if ema_decay:
+        info(f"EMA decay: {ema_decay}")
     info("#" * 100)
     info("Sampling Parameters.")
     info(f"Temperature: {temperature:,}")
@@ -203,6 +219,9 @@ def main():
                       "hidden_activation": hp["hidden_activation"],
                       "model": {k: v.detach().clone() for k, v in model.state_dict().items()},
                       "model_optimizer": optim.state_dict()}
+        if ema_decay:
+            model_dict["model_ema"] = optim.ema_state_dict(model)
+            model_dict["model_ema_meta"] = optim.ema_meta()
         ok = save_model(model_dict=model_dict, dest_path=out_dir, file_name=f"model_{global_steps}.pt",
                         logging=info)
         info("Successfully saved model." if ok else "Error occured saving model.")
@@ -222,18 +241,25 @@ def main():
             else:
                 first = torch.full((n, 1), hr_num_embeddings, dtype=torch.int64, device=device)
                 lr_in, shift = lr_idx, 0
-            toks = sampling.generate_tokens(
-                model, first, lr_in, total_hr_Seq, temperature, use_sliding_window, sliding_window,
-                end_token=hr_num_embeddings, shift=shift, mode="train",
-                progress=lambda i, t: print(f"{i:,} / {t:,}"))
-            toks = toks[:, first.shape[1]:] if train_base_model else toks[:, 1:]
-            if train_base_model:
-                toks = toks - lr_num_embeddings
-                toks[toks == hr_num_embeddings] = lr_num_embeddings
-            else:
-                toks[toks == hr_num_embeddings] = 0
-            save_images(decoder_model(hr_codebook.get_quantized_image(toks, unpatchify_input=True)),
-                        f"high_res_recon_{global_steps}", out_dir, logging=info)
+
+            def sample_grid(name):
+                toks = sampling.generate_tokens(
+                    model, first, lr_in, total_hr_Seq, temperature, use_sliding_window, sliding_window,
+                    end_token=hr_num_embeddings, shift=shift, mode="train",
+                    progress=lambda i, t: print(f"{i:,} / {t:,}"))
+                toks = toks[:, first.shape[1]:] if train_base_model else toks[:, 1:]
+                if train_base_model:
+                    toks = toks - lr_num_embeddings
+                    toks[toks == hr_num_embeddings] = lr_num_embeddings
+                else:
+                    toks[toks == hr_num_embeddings] = 0
+                save_images(decoder_model(hr_codebook.get_quantized_image(toks, unpatchify_input=True)),
+                            f"{name}_{global_steps}", out_dir, logging=info)
+
+            sample_grid("high_res_recon")
+            if ema_decay:
+                with optim.ema_weights():       # the same conditioning, from the averaged weights
+                    sample_grid("high_res_recon_ema")
         model.train()
         torch.cuda.empty_cache()
 
