@@ -446,6 +446,13 @@ size_t qarig_colsum_workspace_bytes(int M, int N);
 int qarig_colsum_f32(const float* X, int64_t ldx, int M, int N, float* out, int accumulate,
                      void* workspace, size_t ws_bytes, void* stream);
 
+/* The reductions qarig_gemm_f32 launches behind a split-K product, as an entry of their own:
+ * out[M][N] (ld ldc) (+)= sum_z slabs[z][M][N], z ascending from 0.0f, and, where rs_part / rs_out
+ * are given, rs_out[M] (+)= sum_z rs_part[z][M] in the same launch.  16-B accesses when N % 4 == 0,
+ * ldc % 4 == 0 and slabs / out are 16-B aligned, scalar otherwise: the same bits either way. */
+int qarig_slab_reduce_rowsum_f32(const float* slabs, float* out, int64_t ldc, int M, int N, int nslab,
+                                 int accumulate, const float* rs_part, float* rs_out, void* stream);
+
 /* ---- Codebook (continued) ------------------------------------------------------ */
 
 /* patchify / unpatchify -- models/layers.py:8-34 / :37-71.  image (N,C,H,W) <->
@@ -536,6 +543,18 @@ int qarig_mul_rows_fwd(const float* a, const float* tab, const int* idx, float* 
                        void* stream);
 int qarig_mul_rows_bwd(const float* dy, const float* a, const float* tab, const int* idx, float* da,
                        float* db_tok, int M, int D, void* stream);
+/* The two backward passes above with the table sums inside: one workgroup per table position walks
+ * the position's tokens (offsets / rows of qarig_rowmap_build), writes the per-token gradient and adds
+ * the table contribution in registers, in qarig_segment_sum's order -- dx / da and the (P,D) tables
+ * are bit-identical to qarig_layernorm_bwd (mod_idx, dy_xhat) / qarig_mul_rows_bwd followed by
+ * qarig_segment_sum, without the (M,D) intermediate and its launches.  Positions without tokens get
+ * zeros.  D = 256, 512 or 1024, 16-B aligned; dx_add optional. */
+int qarig_layernorm_bwd_table(const float* dy, const float* x, const float* mean, const float* rstd,
+                              const float* scale_tab, const int* offsets, const int* rows, int M, int P,
+                              int D, float* dx, const float* dx_add, float* dscale, float* dshift,
+                              void* stream);
+int qarig_mul_rows_bwd_table(const float* dy, const float* a, const float* tab, const int* offsets,
+                             const int* rows, int M, int P, int D, float* da, float* dg, void* stream);
 
 /* AttentionLayer core -- models/layers.py:433-474.  q (N,Sq,H*d); k,v (N,Sk,H*d);
  * o (N,Sq,H*d); lse (N,H,Sq); sqrt_d = float(d ** 0.5). */

@@ -150,6 +150,191 @@ __global__ void mul_rows_bwd_kernel(const float* __restrict__ dy, const float* _
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Backward kernels with the table sums inside.  One workgroup of 8 waves per table position p
+// walks the position's tokens rows[offsets[p] .. offsets[p+1]), one wave per token row, writes the
+// per-token gradient and keeps the per-token table contribution in registers instead of writing
+// an (M,D) tensor for segment_sum_kernel to read back.  The sums are formed in
+// segment_sum_kernel's order, so the tables are bit-identical to the two-step path: wave w takes
+// the entries beg + (w & 3) + 4 * (w >> 2) + 8 j, i.e. waves 0..3 hold accumulator a0 of
+// sub-groups 0..3 and waves 4..7 their a1; the sub-group total is a0 + a1 and the totals are added
+// in sub-group order.  D == NV * 256, so that one wave holds a whole row (float4 i of a lane covers
+// columns (i * 64 + lane) * 4 ...).  The next row's loads are issued before the current row is
+// worked on, and its row index one visit earlier still: two rows per wave are in flight.
+constexpr int TB_WAVES = 2 * SEG_GROUPS;
+
+__device__ __forceinline__ void f4_acc(float4& a, const float4 v) {
+    a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+}
+
+// part[q][w][c] holds, on entry, nothing; acc[q][i] are this wave's sums.  Adds a0 + a1 per
+// sub-group, then the sub-group totals in order, and writes out_q[p][:] for q < NQ.
+template <int NV, int NQ>
+__device__ __forceinline__ void table_sums_store(float4 (&part)[NQ][SEG_GROUPS][NV * 64],
+                                                 const float4 (&acc)[NQ][NV], int p, int D,
+                                                 float* const (&out)[NQ]) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (w >= SEG_GROUPS) {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+#pragma unroll
+            for (int i = 0; i < NV; ++i) part[q][w - SEG_GROUPS][i * 64 + lane] = acc[q][i];
+    }
+    __syncthreads();
+    if (w < SEG_GROUPS) {   // the slot's only reader is the thread that overwrites it
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const float4 a1 = part[q][w][i * 64 + lane], a0 = acc[q][i];
+                part[q][w][i * 64 + lane] = make_float4(a0.x + a1.x, a0.y + a1.y, a0.z + a1.z, a0.w + a1.w);
+            }
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < NQ * NV * 64; t += TB_WAVES * 64) {
+        const int q = t / (NV * 64), c = t - q * (NV * 64);
+        float4 r = part[q][0][c];
+#pragma unroll
+        for (int g = 1; g < SEG_GROUPS; ++g) f4_acc(r, part[q][g][c]);
+        *reinterpret_cast<float4*>(out[q] + (int64_t)p * D + c * 4) = r;
+    }
+}
+
+// AdaLN backward, scale-table form: per token exactly layernorm_bwd_kernel<NV>'s arithmetic (dx, with
+// dx_add where given); per position dscale[p] = sum dy * xhat and dshift[p] = sum dy.
+template <int NV>
+__global__ __launch_bounds__(TB_WAVES * 64) void layernorm_bwd_table_kernel(
+    const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ mean_in,
+    const float* __restrict__ rstd_in, const float* __restrict__ scale_tab,
+    const int* __restrict__ offsets, const int* __restrict__ rows, int D, float* __restrict__ dx,
+    const float* __restrict__ dx_add, float* __restrict__ dscale, float* __restrict__ dshift) {
+    __shared__ float4 part[2][SEG_GROUPS][NV * 64];
+    const int p = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int beg = offsets[p], end = offsets[p + 1];
+    float4 acc[2][NV];    // [0]: dy * xhat, [1]: dy
+    float4 m[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        acc[0][i] = acc[1][i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        m[i] = *reinterpret_cast<const float4*>(scale_tab + (int64_t)p * D + (i * 64 + lane) * 4);
+    }
+    struct Row {
+        float4 xv[NV], d[NV], a[NV];
+        float mean, rstd;
+    };
+    auto load = [&](Row& t, int row) {
+        const int64_t off = (int64_t)row * D;
+        t.mean = mean_in[row];
+        t.rstd = rstd_in[row];
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int c = (i * 64 + lane) * 4;
+            t.xv[i] = *reinterpret_cast<const float4*>(x + off + c);
+            t.d[i] = *reinterpret_cast<const float4*>(dy + off + c);
+            if (dx_add) t.a[i] = *reinterpret_cast<const float4*>(dx_add + off + c);
+        }
+    };
+    int e = beg + (w & (SEG_GROUPS - 1)) + SEG_GROUPS * (w / SEG_GROUPS);
+    int r_cur = e < end ? rows[e] : 0;
+    int r_nxt = e + TB_WAVES < end ? rows[e + TB_WAVES] : 0;
+    Row cur = {};
+    if (e < end) load(cur, r_cur);
+    for (; e < end; e += TB_WAVES) {
+        Row nxt = cur;
+        const int r_nn = e + 2 * TB_WAVES < end ? rows[e + 2 * TB_WAVES] : 0;
+        if (e + TB_WAVES < end) load(nxt, r_nxt);
+        const int64_t off = (int64_t)r_cur * D;
+        const float mean = cur.mean, rstd = cur.rstd;
+        float4 h[NV], g[NV];
+        float s1 = 0.0f, s2 = 0.0f;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const float4 xv = cur.xv[i], d = cur.d[i];
+            h[i] = make_float4((xv.x - mean) * rstd, (xv.y - mean) * rstd, (xv.z - mean) * rstd,
+                               (xv.w - mean) * rstd);
+            g[i] = make_float4(d.x * m[i].x, d.y * m[i].y, d.z * m[i].z, d.w * m[i].w);
+            s1 += (g[i].x + g[i].y) + (g[i].z + g[i].w);
+            s2 = fmaf(g[i].x, h[i].x, s2); s2 = fmaf(g[i].y, h[i].y, s2);
+            s2 = fmaf(g[i].z, h[i].z, s2); s2 = fmaf(g[i].w, h[i].w, s2);
+        }
+        s1 = wave_sum(s1) / (float)D;
+        s2 = wave_sum(s2) / (float)D;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int c = (i * 64 + lane) * 4;
+            const float4 d = cur.d[i];
+            float4 r = make_float4(rstd * ((g[i].x - s1) - h[i].x * s2), rstd * ((g[i].y - s1) - h[i].y * s2),
+                                   rstd * ((g[i].z - s1) - h[i].z * s2), rstd * ((g[i].w - s1) - h[i].w * s2));
+            if (dx_add) {
+                const float4 a = cur.a[i];
+                r = make_float4(a.x + r.x, a.y + r.y, a.z + r.z, a.w + r.w);
+            }
+            *reinterpret_cast<float4*>(dx + off + c) = r;
+            f4_acc(acc[0][i], make_float4(d.x * h[i].x, d.y * h[i].y, d.z * h[i].z, d.w * h[i].w));
+            f4_acc(acc[1][i], d);
+        }
+        cur = nxt;
+        r_cur = r_nxt;
+        r_nxt = r_nn;
+    }
+    float* const out[2] = {dscale, dshift};
+    table_sums_store<NV, 2>(part, acc, p, D, out);
+}
+
+// Gate backward: da[r] = dy[r] * tab[p] per token, dg[p] = sum dy[r] * a[r] per position.
+template <int NV>
+__global__ __launch_bounds__(TB_WAVES * 64) void mul_rows_bwd_table_kernel(
+    const float* __restrict__ dy, const float* __restrict__ a, const float* __restrict__ tab,
+    const int* __restrict__ offsets, const int* __restrict__ rows, int D, float* __restrict__ da,
+    float* __restrict__ dg) {
+    __shared__ float4 part[1][SEG_GROUPS][NV * 64];
+    const int p = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int beg = offsets[p], end = offsets[p + 1];
+    float4 acc[1][NV];
+    float4 b[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        acc[0][i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        b[i] = *reinterpret_cast<const float4*>(tab + (int64_t)p * D + (i * 64 + lane) * 4);
+    }
+    struct Row {
+        float4 d[NV], av[NV];
+    };
+    auto load = [&](Row& t, int row) {
+        const int64_t off = (int64_t)row * D;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int c = (i * 64 + lane) * 4;
+            t.d[i] = *reinterpret_cast<const float4*>(dy + off + c);
+            t.av[i] = *reinterpret_cast<const float4*>(a + off + c);
+        }
+    };
+    int e = beg + (w & (SEG_GROUPS - 1)) + SEG_GROUPS * (w / SEG_GROUPS);
+    int r_cur = e < end ? rows[e] : 0;
+    int r_nxt = e + TB_WAVES < end ? rows[e + TB_WAVES] : 0;
+    Row cur = {};
+    if (e < end) load(cur, r_cur);
+    for (; e < end; e += TB_WAVES) {
+        Row nxt = cur;
+        const int r_nn = e + 2 * TB_WAVES < end ? rows[e + 2 * TB_WAVES] : 0;
+        if (e + TB_WAVES < end) load(nxt, r_nxt);
+        const int64_t off = (int64_t)r_cur * D;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int c = (i * 64 + lane) * 4;
+            const float4 d = cur.d[i], av = cur.av[i];
+            *reinterpret_cast<float4*>(da + off + c) =
+                make_float4(d.x * b[i].x, d.y * b[i].y, d.z * b[i].z, d.w * b[i].w);
+            f4_acc(acc[0][i], make_float4(d.x * av.x, d.y * av.y, d.z * av.z, d.w * av.w));
+        }
+        cur = nxt;
+        r_cur = r_nxt;
+        r_nxt = r_nn;
+    }
+    float* const out[1] = {dg};
+    table_sums_store<NV, 1>(part, acc, p, D, out);
+}
+
 }  // namespace qarig
 
 using namespace qarig;
@@ -216,5 +401,58 @@ extern "C" int qarig_mul_rows_bwd(const float* dy, const float* a, const float* 
     hipLaunchKernelGGL(mul_rows_bwd_kernel, ct_grid((int64_t)M * (D / 4)), dim3(256), 0,
                        (hipStream_t)stream, dy, a, tab, idx, da, db_tok, M, D / 4);
     QARIG_CHECK_LAUNCH("mul_rows_bwd");
+    return QARIG_OK;
+}
+
+// AdaLN backward (scale-table form) with the table gradients inside: dx (M,D) as qarig_layernorm_bwd with
+// mod_idx writes it, dscale / dshift (P,D) as qarig_segment_sum of dy * xhat and of dy would -- bit-identical,
+// without the (M,D) dy * xhat tensor.  offsets / rows: the row map of the index vector (qarig_rowmap_build);
+// tokens no position lists (indices outside [0,P): the bad-index flag is up) get no dx.  D = 256, 512 or
+// 1024, 16-B aligned.
+extern "C" int qarig_layernorm_bwd_table(const float* dy, const float* x, const float* mean, const float* rstd,
+                                         const float* scale_tab, const int* offsets, const int* rows, int M, int P,
+                                         int D, float* dx, const float* dx_add, float* dscale, float* dshift,
+                                         void* stream) {
+    QARIG_CHECK_ARG(dy && x && mean && rstd && scale_tab && offsets && rows && dx && dscale && dshift && M > 0 &&
+                        P > 0 && (D == 256 || D == 512 || D == 1024) &&
+                        ((((uintptr_t)dy | (uintptr_t)x | (uintptr_t)scale_tab | (uintptr_t)dx | (uintptr_t)dx_add |
+                           (uintptr_t)dscale | (uintptr_t)dshift)) & 15) == 0,
+                    "layernorm_bwd_table: bad arguments (D = 256, 512 or 1024, 16-B aligned)");
+    QARIG_CHECK_DIMS("layernorm_bwd_table", M, D);
+    QARIG_CHECK_DIMS("layernorm_bwd_table", P, D);
+#define QARIG_LNT_LAUNCH(NV)                                                                                  \
+    hipLaunchKernelGGL((layernorm_bwd_table_kernel<NV>), dim3(P), dim3(TB_WAVES * 64), 0, (hipStream_t)stream, \
+                       dy, x, mean, rstd, scale_tab, offsets, rows, D, dx, dx_add, dscale, dshift)
+    switch (D / 256) {
+        case 1: QARIG_LNT_LAUNCH(1); break;
+        case 2: QARIG_LNT_LAUNCH(2); break;
+        default: QARIG_LNT_LAUNCH(4); break;
+    }
+#undef QARIG_LNT_LAUNCH
+    QARIG_CHECK_LAUNCH("layernorm_bwd_table");
+    return QARIG_OK;
+}
+
+// Gate backward with the table gradient inside: da (M,D) as qarig_mul_rows_bwd writes it, dg (P,D) as
+// qarig_segment_sum of dy * a would -- bit-identical, without the (M,D) product tensor.  Row map, D and
+// alignment as for qarig_layernorm_bwd_table.
+extern "C" int qarig_mul_rows_bwd_table(const float* dy, const float* a, const float* tab, const int* offsets,
+                                        const int* rows, int M, int P, int D, float* da, float* dg, void* stream) {
+    QARIG_CHECK_ARG(dy && a && tab && offsets && rows && da && dg && M > 0 && P > 0 &&
+                        (D == 256 || D == 512 || D == 1024) &&
+                        ((((uintptr_t)dy | (uintptr_t)a | (uintptr_t)tab | (uintptr_t)da | (uintptr_t)dg)) & 15) == 0,
+                    "mul_rows_bwd_table: bad arguments (D = 256, 512 or 1024, 16-B aligned)");
+    QARIG_CHECK_DIMS("mul_rows_bwd_table", M, D);
+    QARIG_CHECK_DIMS("mul_rows_bwd_table", P, D);
+#define QARIG_MRT_LAUNCH(NV)                                                                                 \
+    hipLaunchKernelGGL((mul_rows_bwd_table_kernel<NV>), dim3(P), dim3(TB_WAVES * 64), 0, (hipStream_t)stream, \
+                       dy, a, tab, offsets, rows, D, da, dg)
+    switch (D / 256) {
+        case 1: QARIG_MRT_LAUNCH(1); break;
+        case 2: QARIG_MRT_LAUNCH(2); break;
+        default: QARIG_MRT_LAUNCH(4); break;
+    }
+#undef QARIG_MRT_LAUNCH
+    QARIG_CHECK_LAUNCH("mul_rows_bwd_table");
     return QARIG_OK;
 }

@@ -531,6 +531,90 @@ __global__ void slab_reduce_rowsum_kernel(const float* __restrict__ slabs, float
     }
 }
 
+// The two kernels above on 16-B accesses: N % 4 == 0, ldc % 4 == 0, slabs and out 16-B aligned.  A thread owns
+// groups of four columns; all loads of a group's (up to 8) slabs are issued before the first add, the sum still
+// runs z ascending from 0.0f and the accumulate add comes last, so the result is bit-identical to the scalar
+// kernels'.  Row and column of a group advance by the grid stride's quotient and remainder: one 64-bit
+// division per thread, none per element.  Blocks [nb, gridDim.x) are the row-sum blocks, as above (rs_part
+// may be null with nb == gridDim.x).
+constexpr int SLAB_UNROLL = 8;
+__global__ __launch_bounds__(256) void slab_reduce_vec_kernel(const float* __restrict__ slabs, float* __restrict__ out,
+                                                              int64_t ldc, int M, int N4, int nslab, int accumulate,
+                                                              int nb, const float* __restrict__ rs_part,
+                                                              float* __restrict__ rs_out) {
+    if ((int)blockIdx.x >= nb) {
+        // a few blocks with one dependent chain per thread: up to 32 splits' loads in flight at once, or these
+        // blocks outlast the slab blocks in front of them
+        const int m = ((int)blockIdx.x - nb) * 256 + threadIdx.x;
+        if (m < M) {
+            float s = 0.0f;
+            for (int z0 = 0; z0 < nslab; z0 += 4 * SLAB_UNROLL) {
+                float v[4 * SLAB_UNROLL];
+#pragma unroll
+                for (int j = 0; j < 4 * SLAB_UNROLL; ++j)
+                    if (z0 + j < nslab) v[j] = rs_part[(int64_t)(z0 + j) * M + m];
+#pragma unroll
+                for (int j = 0; j < 4 * SLAB_UNROLL; ++j)
+                    if (z0 + j < nslab) s += v[j];
+            }
+            rs_out[m] = accumulate ? rs_out[m] + s : s;
+        }
+        return;
+    }
+    const int64_t total4 = (int64_t)M * N4;
+    const float4* __restrict__ src = reinterpret_cast<const float4*>(slabs);
+    const int64_t stride = (int64_t)nb * 256;
+    const int64_t srow = stride / N4;
+    const int scol = (int)(stride - srow * N4);
+    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    int64_t row = i / N4;
+    int col = (int)(i - row * N4);
+    for (; i < total4; i += stride) {
+        float4* dst = reinterpret_cast<float4*>(out + row * ldc) + col;
+        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int z0 = 0; z0 < nslab; z0 += SLAB_UNROLL) {
+            float4 v[SLAB_UNROLL];
+#pragma unroll
+            for (int j = 0; j < SLAB_UNROLL; ++j)
+                if (z0 + j < nslab) v[j] = src[(int64_t)(z0 + j) * total4 + i];
+#pragma unroll
+            for (int j = 0; j < SLAB_UNROLL; ++j)
+                if (z0 + j < nslab) { s.x += v[j].x; s.y += v[j].y; s.z += v[j].z; s.w += v[j].w; }
+        }
+        if (accumulate) {
+            const float4 o = *dst;
+            s = make_float4(o.x + s.x, o.y + s.y, o.z + s.z, o.w + s.w);
+        }
+        *dst = s;
+        row += srow;
+        col += scol;
+        if (col >= N4) { col -= N4; ++row; }
+    }
+}
+
+// out (ld ldc) (+)= sum_z slabs[z][M][N] and, with rs_part, rs_out[M] (+)= sum_z rs_part[z][M], in one launch:
+// the 16-B kernel where the shape allows it, else the scalar ones.
+static void launch_slab_reduce(hipStream_t st, const float* slabs, float* out, int64_t ldc, int M, int N, int nslab,
+                               int accumulate, const float* rs_part, float* rs_out) {
+    const int64_t total = (int64_t)M * N;
+    const int rs_blocks = rs_part ? (M + 255) / 256 : 0;
+    if (N % 4 == 0 && ldc % 4 == 0 && ((((uintptr_t)slabs | (uintptr_t)out)) & 15) == 0) {
+        int blocks = (int)((total / 4 + 255) / 256);
+        if (blocks > 2048) blocks = 2048;
+        hipLaunchKernelGGL(slab_reduce_vec_kernel, dim3(blocks + rs_blocks), dim3(256), 0, st, slabs, out, ldc, M,
+                           N / 4, nslab, accumulate, blocks, rs_part, rs_out);
+        return;
+    }
+    int blocks = (int)((total + 255) / 256);
+    if (blocks > 2048) blocks = 2048;
+    if (rs_part)
+        hipLaunchKernelGGL(slab_reduce_rowsum_kernel, dim3(blocks + rs_blocks), dim3(256), 0, st, slabs, out, ldc, M,
+                           N, nslab, accumulate, blocks, rs_part, rs_out);
+    else
+        hipLaunchKernelGGL(slab_reduce_kernel, dim3(blocks), dim3(256), 0, st, slabs, out, ldc, M, N, nslab,
+                           accumulate);
+}
+
 // Split-K reduce with the full GEMM epilogue: skinny-M GEMMs (autoregressive decode:
 // M = a few dozen rows) have too few output tiles to fill the chip, so their reduction
 // is split over grid.z and bias / residual / activation are applied here.
@@ -951,11 +1035,7 @@ static int gemm_dispatch(const float* A, int64_t lda, int a_kcontig, const float
     }
     QARIG_CHECK_LAUNCH("gemm");
     if (a_rowsum && splitk > 1 && plain) {   // both reductions of a weight-gradient GEMM in one launch
-        const int64_t total = (int64_t)M * N;
-        int blocks = (int)((total + 255) / 256);
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(slab_reduce_rowsum_kernel, dim3(blocks + (M + 255) / 256), dim3(256), 0, st, slabs, C,
-                           ldc, M, N, splitk, accumulate, blocks, rs_part, a_rowsum);
+        launch_slab_reduce(st, slabs, C, ldc, M, N, splitk, accumulate, rs_part, a_rowsum);
         QARIG_CHECK_LAUNCH("gemm slab + rowsum reduce");
         return QARIG_OK;
     }
@@ -965,15 +1045,15 @@ static int gemm_dispatch(const float* A, int64_t lda, int a_kcontig, const float
         QARIG_CHECK_LAUNCH("gemm rowsum reduce");
     }
     if (splitk > 1) {
-        const int64_t total = (int64_t)M * N;
-        int blocks = (int)((total + 255) / 256);
-        if (blocks > 2048) blocks = 2048;
-        if (plain)
-            hipLaunchKernelGGL(slab_reduce_kernel, dim3(blocks), dim3(256), 0, st, slabs, C, ldc, M, N,
-                               splitk, accumulate);
-        else
+        if (plain) {
+            launch_slab_reduce(st, slabs, C, ldc, M, N, splitk, accumulate, nullptr, nullptr);
+        } else {
+            const int64_t total = (int64_t)M * N;
+            int blocks = (int)((total + 255) / 256);
+            if (blocks > 2048) blocks = 2048;
             hipLaunchKernelGGL(slab_reduce_epilogue_kernel, dim3(blocks), dim3(256), 0, st, slabs, ep,
                                M, N, splitk);
+        }
         QARIG_CHECK_LAUNCH("gemm slab reduce");
     }
     return QARIG_OK;
@@ -982,11 +1062,22 @@ static int gemm_dispatch(const float* A, int64_t lda, int a_kcontig, const float
 // Internal helper shared with conv.hip: out[M][N] (ld ldc) = sum_z slabs[z][M][N].
 extern "C" int qarig_slab_reduce_f32(const float* slabs, float* out, int64_t ldc, int M, int N,
                                      int nslab, int accumulate, void* stream) {
-    const int64_t total = (int64_t)M * N;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, slabs, out,
-                       ldc, M, N, nslab, accumulate);
+    launch_slab_reduce((hipStream_t)stream, slabs, out, ldc, M, N, nslab, accumulate, nullptr, nullptr);
+    QARIG_CHECK_LAUNCH("slab reduce");
+    return QARIG_OK;
+}
+
+// The split-K reductions of a GEMM as an entry of their own (what qarig_gemm_f32 launches behind a split
+// product): out[M][N] (ld ldc) (+)= sum_z slabs[z][M][N], z ascending from 0.0f, and, where rs_part is given,
+// rs_out[M] (+)= sum_z rs_part[z][M].  16-B accesses when N % 4 == 0, ldc % 4 == 0 and slabs / out are 16-B
+// aligned, scalar otherwise; the same bits either way.
+extern "C" int qarig_slab_reduce_rowsum_f32(const float* slabs, float* out, int64_t ldc, int M, int N, int nslab,
+                                            int accumulate, const float* rs_part, float* rs_out, void* stream) {
+    QARIG_CHECK_ARG(slabs && out && nslab > 0 && nslab <= 4096 && ldc >= N && (rs_part == nullptr) == (rs_out == nullptr),
+                    "slab_reduce_rowsum: bad arguments");
+    QARIG_CHECK_DIMS("slab_reduce_rowsum", M, N);
+    QARIG_CHECK_DIMS("slab_reduce_rowsum", M, ldc);
+    launch_slab_reduce((hipStream_t)stream, slabs, out, ldc, M, N, nslab, accumulate, rs_part, rs_out);
     QARIG_CHECK_LAUNCH("slab reduce");
     return QARIG_OK;
 }

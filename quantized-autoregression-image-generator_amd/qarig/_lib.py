@@ -79,6 +79,9 @@ SIGNATURES = {
     "qarig_segment_sum": (I, [P, P, P, I, I, P, P]),
     "qarig_mul_rows_fwd": (I, [P, P, P, P, I, I, P]),
     "qarig_mul_rows_bwd": (I, [P, P, P, P, P, P, I, I, P]),
+    "qarig_layernorm_bwd_table": (I, [P, P, P, P, P, P, P, I, I, I, P, P, P, P, P]),
+    "qarig_mul_rows_bwd_table": (I, [P, P, P, P, P, I, I, I, P, P, P]),
+    "qarig_slab_reduce_rowsum_f32": (I, [P, P, L, I, I, I, I, P, P, P]),
     "qarig_attention_fwd": (I, [P, P, P, I, I, I, I, I, I, F, P, P, P]),
     "qarig_attention_lp_fwd": (I, [P, P, P, I, I, I, I, I, I, F, P, P, P]),
     "qarig_attention_lp_bwd": (I, [P, P, P, P, P, P, I, I, I, I, I, I, F, P, P, P, P, P]),

@@ -967,6 +967,11 @@ class _TableProjections(torch.autograd.Function):
         return tuple(grads)
 
 
+# which path the table consumers' backward passes took, counted per call (ops.table_bwd_fused decides): the
+# fused kernels of csrc/condtable.hip, or the per-token kernel followed by segment_sum
+TABLE_BWD_CALLS = {"fused": 0, "two_step": 0}
+
+
 class _LayerNormModTable(torch.autograd.Function):
     """AdaLNZero with scale/shift given per POSITION: y = scale_tab[idx] * LN(x) + shift_tab[idx]."""
 
@@ -985,6 +990,12 @@ class _LayerNormModTable(torch.autograd.Function):
     def backward(ctx, dy, dskip=None):
         x2, st, mean, rstd, idx, offsets, rows = ctx.saved_tensors
         dy2, add = _skip_grads(dy, dskip, x2)
+        M, D = x2.shape
+        if ops.table_bwd_fused(M, st.shape[0], D, dy2, x2, st, add):
+            TABLE_BWD_CALLS["fused"] += 1
+            dx, dscale, dshift = ops.layernorm_bwd_table(dy2, x2, mean, rstd, st, offsets, rows, dx_add=add)
+            return dx.reshape(ctx.shape), dscale, dshift, None, None, None, None, None
+        TABLE_BWD_CALLS["two_step"] += 1
         dx, dscale_tok = ops.layernorm_bwd(dy2, x2, mean, rstd, scale=st, want_dy_xhat=True,
                                            mod_idx=idx, dx_add=add)
         dscale = ops.segment_sum(dscale_tok, offsets, rows)
@@ -1015,7 +1026,13 @@ class _MulTable(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x2, gt, idx, offsets, rows = ctx.saved_tensors
-        dx, dg_tok = ops.mul_rows_bwd(_2d(f32c(dy)), x2, gt, idx)
+        dy2 = _2d(f32c(dy))
+        if ops.table_bwd_fused(x2.shape[0], gt.shape[0], x2.shape[1], dy2, x2, gt):
+            TABLE_BWD_CALLS["fused"] += 1
+            dx, dg = ops.mul_rows_bwd_table(dy2, x2, gt, offsets, rows)
+            return dx.reshape(dy.shape), dg, None, None, None
+        TABLE_BWD_CALLS["two_step"] += 1
+        dx, dg_tok = ops.mul_rows_bwd(dy2, x2, gt, idx)
         return dx.reshape(dy.shape), ops.segment_sum(dg_tok, offsets, rows), None, None, None
 
 

@@ -1069,6 +1069,67 @@ def mul_rows_bwd(dy, a, tab, idx):
     return da, db
 
 
+# Backward of the table consumers with the table sums inside (csrc/condtable.hip): one workgroup per table
+# position.  Taken when the tokens per table row, M / P (known on the host; the used rows are at most P, so the
+# mean per used row is no smaller), reach this value: measured faster than the two-step path at every M / P from
+# 1.8 (2,048 tokens over 1,152 rows) to 42.7, never measured on sparser row maps, where most of a workgroup's 8
+# waves find no token (profiles/r18_table_bwd_bench.txt).
+TABLE_BWD_MIN_TOKENS_PER_ROW = 2
+TABLE_BWD_WIDTHS = (256, 512, 1024)
+
+
+def table_bwd_fused(M, P, D, *tensors):
+    """Whether a table backward of M tokens over P positions takes the fused kernel (else: the per-token
+    kernel and segment_sum)."""
+    return (D in TABLE_BWD_WIDTHS and M >= TABLE_BWD_MIN_TOKENS_PER_ROW * P
+            and all(t is None or t.data_ptr() % 16 == 0 for t in tensors))
+
+
+def layernorm_bwd_table(dy, x2d, mean, rstd, scale_tab, offsets, rows, dx_add=None):
+    """(dx, dscale, dshift): layernorm_bwd(scale=scale_tab, mod_idx=idx, want_dy_xhat=True) and the two
+    segment_sum launches over its results in one kernel, bit-identical to them."""
+    M, D = x2d.shape
+    P = offsets.numel() - 1
+    assert dy.shape == x2d.shape and dy.is_contiguous() and x2d.is_contiguous() and rows.numel() == M
+    assert scale_tab.shape == (P, D) and scale_tab.is_contiguous()
+    if dx_add is not None:
+        assert dx_add.shape == x2d.shape and dx_add.dtype == torch.float32 and dx_add.is_contiguous()
+    dx = torch.empty_like(x2d)
+    dscale = torch.empty((P, D), dtype=torch.float32, device=x2d.device)
+    dshift = torch.empty((P, D), dtype=torch.float32, device=x2d.device)
+    check(_lib.load().qarig_layernorm_bwd_table(ptr(dy), ptr(x2d), ptr(mean), ptr(rstd), ptr(scale_tab),
+                                                ptr(offsets), ptr(rows), M, P, D, ptr(dx), ptr(dx_add),
+                                                ptr(dscale), ptr(dshift), stream()), "qarig_layernorm_bwd_table")
+    return dx, dscale, dshift
+
+
+def mul_rows_bwd_table(dy, a, tab, offsets, rows):
+    """(da, dg): mul_rows_bwd and the segment_sum of its per-token products in one kernel, bit-identical."""
+    M, D = a.shape
+    P = offsets.numel() - 1
+    assert dy.shape == a.shape and dy.is_contiguous() and a.is_contiguous() and rows.numel() == M
+    assert tab.shape == (P, D) and tab.is_contiguous()
+    da = torch.empty_like(a)
+    dg = torch.empty((P, D), dtype=torch.float32, device=a.device)
+    check(_lib.load().qarig_mul_rows_bwd_table(ptr(dy), ptr(a), ptr(tab), ptr(offsets), ptr(rows), M, P, D,
+                                               ptr(da), ptr(dg), stream()), "qarig_mul_rows_bwd_table")
+    return da, dg
+
+
+def slab_reduce(slabs, out, M, N, accumulate=False, rs_part=None, rs_out=None):
+    """out[:M, :N] (+)= slabs (nslab, M, N) summed over the slabs in ascending order; with rs_part (nslab, M):
+    rs_out[:M] (+)= its sum too, in the same launch -- the reductions behind a split-K gemm()."""
+    nslab = slabs.shape[0]
+    assert slabs.is_contiguous() and slabs.dtype == torch.float32 and slabs.shape[1:] == (M, N)
+    assert out.dtype == torch.float32 and out.stride(1) == 1 and out.shape[0] >= M and out.shape[1] >= N
+    if rs_part is not None:
+        assert rs_part.is_contiguous() and rs_part.shape == (nslab, M) and rs_out.is_contiguous()
+    check(_lib.load().qarig_slab_reduce_rowsum_f32(ptr(slabs), ptr(out), out.stride(0), M, N, nslab,
+                                                   int(accumulate), ptr(rs_part), ptr(rs_out), stream()),
+          "qarig_slab_reduce_rowsum_f32")
+    return out
+
+
 ATTENTION_HEAD_DIMS = (4, 8, 16, 32, 64, 128)   # csrc/attention.hip instantiations; 128: csrc/attention_wide.hip
 # Head dims cached generation takes by default: decode_attention_kernel's instantiations and 128 (the grouped kernel's
 # full bucket).  The other multiples of 4 up to 124 run on the grouped kernel too, opt-in (DECODE_PADDED_HEAD_DIMS:
