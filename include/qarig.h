@@ -599,6 +599,22 @@ int qarig_attention_decode(const float* q, const float* k_new, const float* v_ne
 int qarig_cross_entropy_fwd(const float* logits, const int64_t* target, int M, int C, float* loss,
                             float* dlogits, float* row_ws, int* bad_flag, void* stream);
 
+/* Held-out evaluation (additive; the reference has none), csrc/score.hip.
+ * qarig_token_score: logits (M,C) fp32 contiguous, target int64 (M).  Per row, in the shifted form of the
+ * cross-entropy kernel: row_nll = log sum_c exp(x[c] - max) - (x[t] - max) (nats) and
+ * row_rank = #{c : x[c] > x[t]} + #{c < t : x[c] == x[t]} -- 0: the target is the arg-max, ties go to the
+ * smaller index.  A row whose target equals ignore_index gives (0, -1); any other target outside [0,C) gives
+ * (0, -1) and sets *bad_flag.  A row holding NaN or +-inf is undefined in that row alone.
+ * qarig_score_reduce: rows r = n S + s of one scored batch, column s at absolute position pos0 + s < P, ADDED
+ * into accumulators the caller zeroed once: img_nll (N) += sum_s row_nll, pos_nll (P)[pos0 + s] += sum_n
+ * row_nll (both fp64), pos_cnt (P)[pos0 + s] += #{n : rank >= 0}, totals (3) += {rows with rank >= 0, with
+ * rank == 0, with 0 <= rank < topk} (int64).  Every output element belongs to one wave, the fp64 sums run in
+ * one fixed order and nothing is added atomically: equal inputs give equal bits.  N S < 2^31. */
+int qarig_token_score(const float* logits, const int64_t* target, int M, int C, int64_t ignore_index,
+                      float* row_nll, int* row_rank, int* bad_flag, void* stream);
+int qarig_score_reduce(const float* row_nll, const int* row_rank, int N, int S, int pos0, int P, int topk,
+                       double* img_nll, double* pos_nll, int64_t* pos_cnt, int64_t* totals, void* stream);
+
 /* F.mse_loss (mean) + d/dpred -- train_autoencoder.py:215-217, train_codebook.py:233-235. */
 size_t qarig_mse_workspace_bytes(void);
 int qarig_mse_fwd(const float* pred, const float* target, int64_t n, float* loss, float* dpred,

@@ -1398,6 +1398,39 @@ def cross_entropy_fwd(logits2d, target, want_grad=True):
     return loss, dl
 
 
+def token_score(logits2d, target, ignore_index=-100):
+    """(row_nll fp32 (M,), row_rank int32 (M,)) of logits (M,C) against int64 targets: the negative
+    log-likelihood in nats and the number of classes ranked before the target (0: arg-max, ties to the smaller
+    index).  Rows whose target is ignore_index give (0, -1); other targets outside [0,C) give the same and set
+    the device index flag (check_index_flag)."""
+    require_cuda(logits2d, target)
+    assert logits2d.dtype == torch.float32 and logits2d.dim() == 2 and logits2d.is_contiguous()
+    M, C = logits2d.shape
+    target = _i64c(target).reshape(-1)
+    assert target.numel() == M
+    nll = torch.empty(M, dtype=torch.float32, device=logits2d.device)
+    rank = torch.empty(M, dtype=torch.int32, device=logits2d.device)
+    check(_lib.load().qarig_token_score(ptr(logits2d), ptr(target), M, C, int(ignore_index), ptr(nll), ptr(rank),
+                                        ptr(_bad_flag(logits2d.device)), stream()), "qarig_token_score")
+    return nll, rank
+
+
+def score_reduce(row_nll, row_rank, N, S, pos0, topk, img_nll, pos_nll, pos_cnt, totals):
+    """Adds the (N,S) rows of one token_score call into the accumulators of an evaluation: img_nll fp64 (N,),
+    pos_nll fp64 (P,) and pos_cnt int64 (P,) at positions pos0 ... pos0 + S - 1, totals int64 (3,) = {rows
+    counted, rank == 0, rank < topk}.  Fixed-order fp64 sums, no atomics: deterministic."""
+    require_cuda(row_nll, row_rank, img_nll, pos_nll, pos_cnt, totals)
+    assert row_nll.dtype == torch.float32 and row_rank.dtype == torch.int32
+    assert row_nll.is_contiguous() and row_rank.is_contiguous() and row_nll.numel() == row_rank.numel() == N * S
+    assert img_nll.dtype == pos_nll.dtype == torch.float64 and pos_cnt.dtype == totals.dtype == torch.int64
+    for t in (img_nll, pos_nll, pos_cnt, totals):
+        assert t.dim() == 1 and t.is_contiguous()
+    P = pos_nll.numel()
+    assert img_nll.numel() == N and pos_cnt.numel() == P and totals.numel() == 3
+    check(_lib.load().qarig_score_reduce(ptr(row_nll), ptr(row_rank), N, S, int(pos0), P, int(topk), ptr(img_nll),
+                                         ptr(pos_nll), ptr(pos_cnt), ptr(totals), stream()), "qarig_score_reduce")
+
+
 def adam_step(p, g, m, v, beta1, beta2, eps, step_size, bc2_sqrt, grad_scale=1.0, dev_step=None, shadow=None):
     """shadow: optional bf16 tensor of p's numel that receives the updated parameters (reduced precision)."""
     assert shadow is None or (shadow.dtype == torch.bfloat16 and shadow.numel() == p.numel())

@@ -57,6 +57,20 @@ def num_windows(seq_len, window):
     return seq_len - window + 1
 
 
+def eval_windows(seq_len, window):
+    """The deterministic windows of an evaluation: [(start, skip), ...], window k starting at
+    min(k window, seq_len - window) and its first skip = k window - start rows already counted by window
+    k - 1 -- every target position of a sequence is scored exactly once, each token seeing at most its window
+    (the training objective).  window None or >= seq_len: [(None, 0)], the whole sequence."""
+    if window is None or window >= seq_len:
+        return [(None, 0)]
+    out = []
+    for k in range(-(-seq_len // window)):
+        start = min(k * window, seq_len - window)
+        out.append((start, k * window - start))
+    return out
+
+
 def train_step(model, optim, hr_input, lr_input, hr_target, pos_idx, dp=True, pos_bound=None):
     """forward + CE + backward + gradient all-reduce + Adam.  Returns the loss tensor
     (device scalar; callers decide when to .item()).  pos_bound: exclusive upper bound of

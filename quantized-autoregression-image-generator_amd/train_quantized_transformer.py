@@ -81,6 +81,16 @@ def parse_args():
                         "own launch with the usual warm-up min(D, (1 + n) / (10 + n)).  Checkpoints then also "
                         "carry 'model_ema' / 'model_ema_meta' (generate_images.py --use-ema samples from it) and "
                         "every checkpoint writes a second sample grid, high_res_recon_ema_<steps>")
+    p.add_argument("--val-dataset-path", type=pathlib.Path, default=None,
+                   help="(additive; the reference never evaluates) feature map dataset json file of held-out latents: "
+                        "every --val-step steps rank 0 scores it (qarig/evaluate.py: the training objective on "
+                        "deterministic windows, every token once), logs Val Loss | bits/token | top-1 and appends "
+                        "one JSON line to <out-dir>/val_log.jsonl; with --ema-decay the averaged weights are "
+                        "scored too")
+    p.add_argument("--val-step", type=int, default=None,
+                   help="(additive) steps between two evaluations of --val-dataset-path (default: --checkpoint-step).")
+    p.add_argument("--val-batches", type=int, default=None,
+                   help="(additive) score only the first batches of --val-dataset-path.")
     return vars(p.parse_args())
 
 
@@ -263,6 +273,37 @@ def main():
         model.train()
         torch.cuda.empty_cache()
 
+    val_loader = None
+    if args["val_dataset_path"] is not None and rank == 0:
+        import json
+        import os
+        from qarig import evaluate
+        val_step = args["val_step"] if args["val_step"] is not None else args["checkpoint_step"]
+        val_set = FeatureMapDataset(dataset_path=args["val_dataset_path"], load_image=False, return_filepaths=False)
+        # in order; a generator of its own, so that the training run draws what it draws without validation
+        val_loader = torch.utils.data.DataLoader(val_set, batch_size=args["batch_size"], num_workers=2, shuffle=False,
+                                                 generator=torch.Generator())
+        info(f"Validation: {len(val_set):,} latents every {val_step:,} steps")
+
+    def validate(global_steps):
+        """Rank 0 alone, like checkpoint(): the other ranks wait at their next exchange."""
+        def score():
+            scorer = evaluate.TokenScorer(model, lr_codebook, hr_codebook, train_base_model,
+                                          sliding_window if use_sliding_window else None)
+            evaluate.score_loader(scorer, val_loader, device, args["val_batches"])
+            r = scorer.result()
+            del r["per_image_nll"]          # (evaluate_transformer.py reports it; the log keeps one line per evaluation)
+            return r
+
+        entry = {"step": global_steps, "model": score()}
+        info(evaluate.summary_line("Val", entry["model"]))
+        if ema_decay:
+            with optim.ema_weights():
+                entry["model_ema"] = score()
+            info(evaluate.summary_line("Val EMA", entry["model_ema"]))
+        with open(os.path.join(out_dir, "val_log.jsonl"), "a") as f:
+            f.write(json.dumps(entry) + "\n")
+
     graphed = None
     batch_size = args["batch_size"]
     lr_pH, lr_pW = lr_d["patch_dim"]
@@ -308,6 +349,8 @@ def main():
                 cc.halve_lr(optim)
             if global_steps % args["checkpoint_step"] == 0 and global_steps >= 0 and rank == 0:
                 checkpoint(global_steps)
+            if val_loader is not None and global_steps % val_step == 0:
+                validate(global_steps)
             info("Cum. Steps: {:,} | Steps: {:,} / {:,} | L.R.: {:.8f} | Recon Loss: {:.5f}".format(
                 global_steps + 1, index + 1, len(loader), optim.param_groups[0]["lr"],
                 total_loss / iteration_count))
