@@ -112,17 +112,27 @@ class Transformer(nn.Module):
             return QF.CondTokens(cond, groups=self._cond_linear_groups())
         return cond
 
+    def _decoder_blocks(self):
+        """Per decoder layer, its blocks in evaluation order as (name, block, norm, res): "self", "cross" (when the
+        layer has one), "ffn" with the block's AdaLN / LayerNorm module and its residual layer.  The order of the
+        `cond` projections met on this walk (AdaLN scale, AdaLN shift, residual scale per block) is the layout of
+        every stacked copy of them (kvcache.DecodeCache._proj_w / _table / _proj_idx)."""
+        for layer in self.decoder_layers:
+            blk = layer.self_attn_block
+            blocks = [("self", blk, blk.self_attn_norm, blk.self_attn_res)]
+            if layer.use_cross_attn:
+                blk = layer.cross_attn_block
+                blocks.append(("cross", blk, blk.cross_attn_norm, blk.cross_attn_res))
+            blk = layer.feedforward_block
+            blocks.append(("ffn", blk, blk.feedforward_norm, blk.feedforward_res))
+            yield blocks
+
     def _cond_linears_per_layer(self):
         """Per decoder layer, the nn.Linear modules that project `cond` inside its blocks."""
         per_layer = []
-        for layer in self.decoder_layers:
+        for blocks in self._decoder_blocks():
             out = []
-            blocks = [(layer.self_attn_block, "self_attn_norm", "self_attn_res")]
-            if layer.use_cross_attn:
-                blocks.append((layer.cross_attn_block, "cross_attn_norm", "cross_attn_res"))
-            blocks.append((layer.feedforward_block, "feedforward_norm", "feedforward_res"))
-            for blk, norm_attr, res_attr in blocks:
-                norm, res = getattr(blk, norm_attr), getattr(blk, res_attr)
+            for _, blk, norm, res in blocks:
                 if blk.use_adaln0:
                     out += [norm.scale_layer.scale, norm.shift_layer.shift]
                 if res.use_scale_layer:

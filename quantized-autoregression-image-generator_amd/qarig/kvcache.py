@@ -91,6 +91,48 @@ def _rows(t, B):
     return t if t.dim() == 2 else t.expand(B, t.shape[0]).contiguous()
 
 
+def window_pad(rows, tokens):
+    """Whether a full-window evaluation of `rows` sequences of `tokens` tokens takes one duplicate of the last
+    token behind it.  A slid window is window - 1 tokens: rows x 255 is no whole number of 128-row GEMM tiles and
+    runs the guarded kernels.  One more token behind the last makes it one (16 x 256 = 4,096 rows) and changes
+    nothing before it -- self-attention is causal, everything else is per token -- so the logits wanted are those
+    of the last token but one."""
+    return (rows * tokens) % 128 != 0 and (rows * (tokens + 1)) % 128 == 0
+
+
+def _warm_capture(dev, forward):
+    """`forward()` as a captured graph: one eager run on a side stream first (kernel loads and the growth of the
+    GEMM workspaces cannot happen inside a capture), then the capture.  Returns (graph, what forward returned
+    inside the capture)."""
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side), torch.no_grad():
+        forward()
+    torch.cuda.current_stream(dev).wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph), torch.no_grad():
+        out = forward()
+    return graph, out
+
+
+@torch.no_grad()
+def _cross_kv(model, enc):
+    """Per decoder layer: the encoder memory's (k, v) of its cross-attention, token-major (N, S, D), or None."""
+    out = []
+    for layer in model.decoder_layers:
+        at = layer.cross_attn_block.cross_attn if layer.use_cross_attn else None
+        out.append(None if at is None else (_mlp2_forward(at.k_block, enc), _mlp2_forward(at.v_block, enc)))
+    return out
+
+
+def _copy_cross_kv(kept, new):
+    """The k / v of another encoder memory into the tensors the captured graphs read."""
+    for old, kv in zip(kept, new):
+        if old is not None:
+            old[0].copy_(kv[0])
+            old[1].copy_(kv[1])
+
+
 class DecodeCache:
     def __init__(self, model, enc, batch, max_len, graph=None, positions=None, weights="f32"):
         """positions: optional sequence of max_len floats, the `pos_cond` value of the token at each
@@ -136,17 +178,14 @@ class DecodeCache:
         if graph:
             self._capture()
 
-    @torch.no_grad()
     def _cross_kv(self, enc):
         """Per decoder layer: the encoder memory's (k, v) of its cross-attention, head-major, or None."""
         out = []
-        for layer in self.model.decoder_layers:
-            if layer.use_cross_attn:
-                at = layer.cross_attn_block.cross_attn
-                hm = lambda t: t.reshape(t.shape[0], t.shape[1], at.heads, -1).permute(0, 2, 1, 3).contiguous()
-                out.append((hm(_mlp2_forward(at.k_block, enc)), hm(_mlp2_forward(at.v_block, enc))))
-            else:
-                out.append(None)
+        for layer, kv in zip(self.model.decoder_layers, _cross_kv(self.model, enc)):
+            if kv is not None:
+                heads = layer.cross_attn_block.cross_attn.heads
+                kv = tuple(t.reshape(t.shape[0], t.shape[1], heads, -1).permute(0, 2, 1, 3).contiguous() for t in kv)
+            out.append(kv)
         return out
 
     @torch.no_grad()
@@ -158,10 +197,7 @@ class DecodeCache:
         the encoder memory's shape differs (the caller builds a new cache)."""
         if (None if enc is None else tuple(enc.shape)) != self._enc_shape:
             return False
-        for old, new in zip(self.cross, self._cross_kv(enc)):
-            if old is not None:
-                old[0].copy_(new[0])
-                old[1].copy_(new[1])
+        _copy_cross_kv(self.cross, self._cross_kv(enc))
         self._cross_tm = None
         self.ctl.zero_()
         return True
@@ -173,15 +209,7 @@ class DecodeCache:
         self._ids = torch.zeros(self.batch, dtype=torch.int64, device=dev)
         self._pos = torch.zeros(self.batch, dtype=torch.float32, device=dev)
         self.ctl.zero_()
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side), torch.no_grad():
-            self._forward(self._ids, self._pos, 0, self.ctl)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph), torch.no_grad():
-            self._out = self._forward(self._ids, self._pos, 0, self.ctl)
-        self._graph = graph
+        self._graph, self._out = _warm_capture(dev, lambda: self._forward(self._ids, self._pos, 0, self.ctl))
 
     @torch.no_grad()
     def step(self, ids, pos, length):
@@ -224,14 +252,9 @@ class DecodeCache:
             return len(ws) - 1
 
         ok = True
-        for layer in model.decoder_layers:
+        for blocks in model._decoder_blocks():
             idx = {}
-            blocks = [("self", layer.self_attn_block, "self_attn_norm", "self_attn_res")]
-            if layer.use_cross_attn:
-                blocks.append(("cross", layer.cross_attn_block, "cross_attn_norm", "cross_attn_res"))
-            blocks.append(("ffn", layer.feedforward_block, "feedforward_norm", "feedforward_res"))
-            for name, blk, norm_attr, res_attr in blocks:
-                norm, res = getattr(blk, norm_attr), getattr(blk, res_attr)
+            for name, blk, norm, res in blocks:
                 if blk.use_adaln0:
                     idx[name + "_norm"] = (add(norm.scale_layer.scale), add(norm.shift_layer.shift))
                 if res.use_scale_layer:
@@ -337,14 +360,9 @@ class DecodeCache:
             pick = lambda v: (allp[v[0]], allp[v[1]]) if isinstance(v, tuple) else allp[v]
             return [{k: pick(v) for k, v in idx.items()} for idx in self._proj_idx]
         out = []
-        for layer in layers:
+        for blocks in self.model._decoder_blocks():
             proj = {}
-            blocks = [("self", layer.self_attn_block, "self_attn_norm", "self_attn_res")]
-            if layer.use_cross_attn:
-                blocks.append(("cross", layer.cross_attn_block, "cross_attn_norm", "cross_attn_res"))
-            blocks.append(("ffn", layer.feedforward_block, "feedforward_norm", "feedforward_res"))
-            for name, blk, norm_attr, res_attr in blocks:
-                norm, res = getattr(blk, norm_attr), getattr(blk, res_attr)
+            for name, blk, norm, res in blocks:
                 if blk.use_adaln0:
                     proj[name + "_norm"] = (norm.scale_layer(cond).reshape(B, D), norm.shift_layer(cond).reshape(B, D))
                 if res.use_scale_layer:
@@ -780,9 +798,7 @@ class WindowStep:
             raise ValueError("WindowStep: needs causal decoder self-attention")
         R, D = self.rows, self.dim
         self.W1 = self.window - 1
-        # rows x (window - 1) is no whole number of 128-row GEMM tiles; one duplicate of the last token behind
-        # it makes one and changes nothing before it (causal attention, everything else per token)
-        self.pad = (R * self.W1) % 128 != 0 and (R * (self.W1 + 1)) % 128 == 0
+        self.pad = window_pad(R, self.W1)
         self.Wp = self.W1 + int(self.pad)
         self.pos_off = int(pos_off)
         self.ring = torch.zeros((R, int(capacity)), dtype=torch.int64, device=dev)
@@ -795,9 +811,8 @@ class WindowStep:
         with torch.no_grad():
             if model.use_pos_cond:
                 self._build_table(pos_bound)
-            self.cross = [None] * len(model.decoder_layers)
+            self.cross = _cross_kv(model, enc)
             self._enc_shape = None if enc is None else tuple(enc.shape)
-            self._cross_kv(enc)
             self._img = None        # bf16 mode: the images exist before the capture
             if weights == "bf16":
                 seqs = (model.decoder_layers[-1].self_attn_block.self_attn.q_block, model.classifier)
@@ -829,25 +844,12 @@ class WindowStep:
         self.cond.idx, self.cond_last.idx = self.rowmap, self.last_map
         self.P = P
 
-    def _cross_kv(self, enc):
-        for li, layer in enumerate(self.model.decoder_layers):
-            if not layer.use_cross_attn:
-                continue
-            at = layer.cross_attn_block.cross_attn
-            k, v = _mlp2_forward(at.k_block, enc), _mlp2_forward(at.v_block, enc)
-            if self.cross[li] is None:
-                self.cross[li] = (k, v)
-            else:
-                self.cross[li][0].copy_(k)
-                self.cross[li][1].copy_(v)
-
-    @torch.no_grad()
     def rebind(self, enc):
         """The step for another stage with the same weights and shapes: the encoder output's cross-attention
         k / v are recomputed into the tensors the graph reads.  False when its shape differs."""
         if (None if enc is None else tuple(enc.shape)) != self._enc_shape:
             return False
-        self._cross_kv(enc)
+        _copy_cross_kv(self.cross, _cross_kv(self.model, enc))
         return True
 
     @torch.no_grad()
@@ -871,14 +873,7 @@ class WindowStep:
         dev = self.ring.device
         saved = self.ctl.clone()
         self.ctl[ops.CTL_RING:ops.CTL_RING + 1].fill_(self.W1)     # a valid window for the warm-up
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side), torch.no_grad():
-            self._forward()                      # kernel loads and workspace growth happen outside the capture
-        torch.cuda.current_stream(dev).wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph), torch.no_grad():
-            self._forward()
+        graph, _ = _warm_capture(dev, self._forward)
         self.ctl.copy_(saved)
         self._graph = graph
 

@@ -24,12 +24,14 @@ Reference quirks kept on purpose (drop-in behaviour):
  - "generate" numbers the appended window positions cur_len + tok + 1 (position 1 is
    never used: 0, 2, 3, ...), "train" numbers them 0, 1, 2, ...;
  - "generate" loops while len < total_seq, so beam_width must divide total_seq."""
+import dataclasses
 import os
+import weakref
 
 import torch
 
 from . import ops
-from .kvcache import DecodeCache, WindowStep, check_decode_weights
+from .kvcache import DecodeCache, WindowStep, check_decode_weights, window_pad
 
 
 def filter_probs(probs, top_k=0, top_p=1.0):
@@ -65,18 +67,55 @@ def filter_probs(probs, top_k=0, top_p=1.0):
     return out
 
 
-def _sample(logits, temperature, end_token, mode, rows, comb, top_k=0, top_p=1.0):
+@dataclasses.dataclass(frozen=True)
+class _Stage:
+    """What is constant over one generate_tokens call (built there once): its arguments and what follows from them.
+    stop_len: the loops run while the sequence is shorter; pos_off: the position numbering (`_positions`);
+    pos_bound: exclusive bound of the positions the loops can reach; limit: the decode cache's rows (`_cache_limit`)."""
+    temperature: float
+    end_token: int
+    shift: int
+    num_beam: int
+    beam_width: int
+    mode: str
+    use_sliding_window: bool
+    sliding_window: int
+    total_seq: int
+    stop_len: int
+    pos_off: int
+    pos_bound: int
+    limit: int
+    top_k: int
+    top_p: float
+    decode_weights: str
+    progress: object
+    batch_beams: bool
+
+    def prefix_pos(self, tokens):
+        """The `pos_cond` values (N, S) of the sequences `tokens` (N, S); None for a stage without a sliding window
+        (its model is not position-conditioned)."""
+        if not self.use_sliding_window:
+            return None
+        return _prefix_pos(tokens.shape[0], tokens.shape[1], self.pos_off, tokens.device)
+
+
+def _sample(logits, st, rows, comb):
     """One sampling draw as the reference makes it; returns (next ids (B,1), comb)."""
-    probs = torch.softmax(logits / temperature, dim=1)
-    if mode == "generate":
-        probs[:, end_token] = 0.0              # <end> removed from consideration
-    if top_k > 0 or top_p < 1.0:
-        probs = filter_probs(probs, top_k, top_p)
+    probs = torch.softmax(logits / st.temperature, dim=1)
+    if st.mode == "generate":
+        probs[:, st.end_token] = 0.0           # <end> removed from consideration
+    if st.top_k > 0 or st.top_p < 1.0:
+        probs = filter_probs(probs, st.top_k, st.top_p)
     nxt = torch.multinomial(probs, 1)
     comb = comb * probs[rows, nxt.squeeze(1)]
-    if mode == "train":
-        nxt[nxt == end_token] = 0              # reference HACK: <end> -> index 0
+    if st.mode == "train":
+        nxt[nxt == st.end_token] = 0           # reference HACK: <end> -> index 0
     return nxt, comb
+
+
+def _repeat(t, B):
+    """Each row of `t` B times, the copies adjacent (the candidates of an image as rows of one batch); None stays."""
+    return t if t is None or B == 1 else t.repeat_interleave(B, dim=0)
 
 
 # Head dims the training path zero-pads (the multiples of 4 up to 124 other than 4 ... 64: ops.DECODE_PADDED_HEAD_DIMS)
@@ -85,20 +124,33 @@ def _sample(logits, temperature, end_token, mode, rows, comb, top_k=0, top_p=1.0
 CACHE_PADDED_HEADS = False
 
 
+def _positions(lo, hi, pos_off):
+    """The `pos_cond` values of sequence indices lo .. hi - 1: index 0 gets 0, index L >= 1 gets L + pos_off -- the
+    reference appends cur_len + tok + 1 in "generate" (generate_images.py:306-322: position 1 is never used) and
+    0, 1, 2, ... in training's sampler.  Every numbering of this module comes from here: a prefix, the decode
+    cache's per-position table, the prefill, the value appended behind each drawn token."""
+    return [float(L + pos_off) if L else 0.0 for L in range(lo, hi)]
+
+
 def _prefix_pos(N, S0, pos_off, device):
     """`pos_cond` values (N, S0) of a prefix as the loop would have numbered them had it produced the tokens
-    itself: index 0 gets 0, index L >= 1 gets L + pos_off (the `positions` _generate_fused builds)."""
-    if S0 == 1:
-        return torch.zeros((N, 1), device=device)
-    vals = torch.tensor([0.0] + [float(L + pos_off) for L in range(1, S0)], device=device)
-    return vals[None].expand(N, -1).contiguous()
+    itself (`_positions`)."""
+    return torch.tensor(_positions(0, S0, pos_off), device=device)[None].expand(N, -1).contiguous()
+
+
+def _reach(stop_len, beam_width):
+    """Exclusive bound of the tokens a sequence reaches: the loops overshoot stop_len by up to beam_width - 1
+    tokens (the reference's `while len < total`)."""
+    return stop_len + beam_width
 
 
 def _cache_limit(hr_input, total_seq, use_sliding_window, sliding_window, beam_width, mode):
     """Rows of the decode cache of a stage (_generate_fused / _generate_cached: the tokens the loop reaches,
     overshoot included, or the window)."""
-    stop_len = total_seq if mode == "generate" else hr_input.shape[1] + total_seq
-    cap = stop_len + beam_width
+    # with the overshoot in, the last chunk of a sequence shorter than the window is cached like the others,
+    # instead of falling to the full-window loop (whose ragged row counts run the guarded GEMM kernels: 14 % of a
+    # 3-stage cascade)
+    cap = _reach(total_seq if mode == "generate" else hr_input.shape[1] + total_seq, beam_width)
     return min(cap, sliding_window) if use_sliding_window else cap
 
 
@@ -171,8 +223,13 @@ class _Timer:
 # every parameter (data pointer, torch's version counter, the owning FlatAdam's step count) plus ops.LP_EPOCH,
 # which every write into a flat parameter buffer bumps; a write into the weights that none of those sees
 # (p.data arithmetic) needs decode_cache_clear().
+# Window steps (kvcache.WindowStep: the slid window's evaluation as one captured graph, generate_tokens(
+# window_graph=True)) are kept the same way: the step holds projections of the weights too (conditioning table,
+# cross-attention k / v).
 _DECODE_CACHES = {}
 DECODE_CACHE_SLOTS = 8
+_WINDOW_STEPS = {}
+WINDOW_STEP_SLOTS = 4
 
 
 def decode_cache_clear():
@@ -190,158 +247,193 @@ def _weights_key(model):
     return tuple(key)
 
 
+def _kept(store, slots, model, enc, shape, build):
+    """The object `store` keeps for `model` and `shape` (plus the encoder memory's shape), re-bound to `enc`, when
+    the model's weights have not changed since it was built; `build()` otherwise.  Either way it becomes the
+    store's youngest entry (model weakref, weights' state, object); the oldest leaves beyond `slots` entries."""
+    slot = (id(model), None if enc is None else tuple(enc.shape)) + shape
+    wkey = _weights_key(model)
+    hit = store.pop(slot, None)
+    if hit is not None and hit[0]() is model and hit[1] == wkey and hit[2].rebind(enc):
+        kept = hit[2]
+    else:
+        kept = build()
+    if len(store) >= slots:
+        store.pop(next(iter(store)))
+    store[slot] = (weakref.ref(model), wkey, kept)
+    return kept
+
+
 def decode_cache(model, enc, batch, limit, positions, weights="f32"):
     """A DecodeCache(model, enc, batch, limit, positions=positions, weights=weights) -- a kept one re-bound to
     `enc` when the model's weights have not changed since it was built, a new one otherwise."""
-    import weakref
-    slot = (id(model), batch, limit, None if positions is None else tuple(positions),
-            None if enc is None else tuple(enc.shape), weights)
-    wkey = _weights_key(model)
-    hit = _DECODE_CACHES.get(slot)
-    if hit is not None and hit[0]() is model and hit[1] == wkey and hit[2].rebind(enc):
-        return hit[2]
-    cache = DecodeCache(model, enc, batch, limit, graph=False, positions=positions, weights=weights)
-    if len(_DECODE_CACHES) >= DECODE_CACHE_SLOTS:
-        _DECODE_CACHES.pop(next(iter(_DECODE_CACHES)))
-    _DECODE_CACHES[slot] = (weakref.ref(model), wkey, cache)
-    return cache
-
-
-# Window steps (kvcache.WindowStep: the slid window's evaluation as one captured graph, generate_tokens(
-# window_graph=True)) kept per model like the decode caches.  Their key adds ops.LP_EPOCH to the weights' state:
-# every write into the flat parameter buffer (FlatAdam's steps, load_state_dict, parallel.broadcast_params) bumps
-# it, and the step holds projections of the weights (conditioning table, cross-attention k / v).
-_WINDOW_STEPS = {}
-WINDOW_STEP_SLOTS = 4
+    return _kept(_DECODE_CACHES, DECODE_CACHE_SLOTS, model, enc,
+                 (batch, limit, None if positions is None else tuple(positions), weights),
+                 lambda: DecodeCache(model, enc, batch, limit, graph=False, positions=positions, weights=weights))
 
 
 def window_step(model, enc, rows, window, capacity, pos_bound, pos_off, weights="f32"):
     """A WindowStep for these shapes -- a kept one re-bound to `enc` when the weights have not changed since it
     was built, a new one otherwise."""
-    import weakref
-    slot = (id(model), rows, window, capacity, pos_bound, pos_off, None if enc is None else tuple(enc.shape), weights)
-    wkey = (_weights_key(model), ops.LP_EPOCH)
-    hit = _WINDOW_STEPS.pop(slot, None)
-    if hit is not None and hit[0]() is model and hit[1] == wkey and hit[2].rebind(enc):
-        step = hit[2]
-    else:
-        hit = None
-        step = WindowStep(model, enc, rows, window, capacity, pos_bound, pos_off, weights=weights)
-    if len(_WINDOW_STEPS) >= WINDOW_STEP_SLOTS:
-        _WINDOW_STEPS.pop(next(iter(_WINDOW_STEPS)))
-    _WINDOW_STEPS[slot] = (weakref.ref(model), wkey, step)
-    return step
+    return _kept(_WINDOW_STEPS, WINDOW_STEP_SLOTS, model, enc, (rows, window, capacity, pos_bound, pos_off, weights),
+                 lambda: WindowStep(model, enc, rows, window, capacity, pos_bound, pos_off, weights=weights))
 
 
-def _window_graph_fits(model, cache, hr_input, sliding_window, beam_width, stop_len):
+def _window_graph_fits(model, cache, hr_input, st):
     """The window step applies to this tail: a Transformer whose evaluation rows (images x candidates) and
     self-attention heads fit the window kernels, and an evaluation of the tail slides the window."""
     s = cache._search
     if s is None or not hasattr(model, "_cond"):
         return False
     heads = model.decoder_layers[-1].self_attn_block.self_attn.heads
-    if s.N * s.NB > DECODE_ROWS or not ops.window_step_supported(s.N * s.NB, sliding_window, cache.dim, heads):
+    if s.N * s.NB > DECODE_ROWS or not ops.window_step_supported(s.N * s.NB, st.sliding_window, cache.dim, heads):
         return False
     cur = hr_input.shape[1]
-    chunks = max(0, -(-(stop_len - cur) // beam_width))
-    return chunks > 0 and cur + chunks * beam_width - 1 >= sliding_window
+    chunks = max(0, -(-(st.stop_len - cur) // st.beam_width))
+    return chunks > 0 and cur + chunks * st.beam_width - 1 >= st.sliding_window
 
 
-def _window_tail(model, cache, hr_input, enc, sliding_window, beam_width, progress, total_seq, stop_len, pos_off,
-                 pos_bound):
+def _replay_step(cache, ids, index):
+    """Logits of the token `ids` at window index `index`, which the decode cache still holds the rows in front of:
+    a replay of the search's step graph (the tails' evaluations that come before the window slides)."""
+    s = cache._search
+    s.ids.copy_(ids)
+    cache.ctl[0:1].fill_(index)
+    s.g_step.replay()
+    return s.logits
+
+
+def _replays_below(cache, st):
+    """Sequences shorter than this draw their next token from a replay of the cache's step graph (`_replay_step`):
+    the last token's row fits the cache, and with a sliding window the evaluation does not slide it yet."""
+    return min(cache.max_len + 1, st.sliding_window) if st.use_sliding_window else cache.max_len + 1
+
+
+def _decide(cache, last):
+    """Behind a candidate chunk of a tail: the decide kernel keeps it if it beats the kept one; behind the `last`
+    candidate the search moves on to the next chunk position."""
+    s = cache._search
+    ops.decode_decide(cache.ctl, s.N, s.NB, s.bw, s.comb, s.chunk, s.best_p, s.best_chunk, s.take, draws=s.per_set)
+    if last:
+        ops.decode_advance(cache.ctl, s.bw)
+        s.used += s.candidates * s.per_set
+
+
+def _window_tail(model, cache, hr_input, enc, st):
     """_fused_tail with the slid evaluations replayed from a WindowStep's graph: the same draws, decisions and
     draw numbers (every launch of the search is the one _fused_tail enqueues), the tokens in the step's device
     ring instead of host-side torch.cat.  Evaluations that still fit the window replay the cache's step graph as
     there.  Enqueues only; nothing is read back."""
     s = cache._search
-    N, NB, bw, ctl = s.N, s.NB, s.bw, cache.ctl
-    enc_eval = enc.repeat_interleave(NB, dim=0) if (enc is not None and NB > 1) else enc
-    step = window_step(model, enc_eval, N * NB, sliding_window, stop_len + bw, pos_bound, pos_off,
-                       weights=cache.weights)
-    step.load(hr_input.repeat_interleave(NB, dim=0) if NB > 1 else hr_input)
-    cur = hr_input.shape[1]
-    while cur < stop_len:
-        for _ in range(s.candidates):
+    N, NB, bw = s.N, s.NB, s.bw
+    step = window_step(model, _repeat(enc, NB), N * NB, st.sliding_window, _reach(st.stop_len, bw), st.pos_bound,
+                       st.pos_off, weights=cache.weights)
+    step.load(_repeat(hr_input, NB))
+    cur, replays = hr_input.shape[1], _replays_below(cache, st)
+    while cur < st.stop_len:
+        for c in range(s.candidates):
             step.rewind(cur)
             for tok in range(bw):
                 n = cur + tok                    # tokens in the sequence; the next one is drawn from the last's logits
-                if n - 1 < cache.max_len and n < sliding_window:
-                    s.ids.copy_(step.ring[:, n - 1])
-                    ctl[0:1].fill_(n - 1)
-                    s.g_step.replay()
-                    logits = s.logits
+                if n < replays:
+                    logits = _replay_step(cache, step.ring[:, n - 1], n - 1)
                 else:
                     logits = step.evaluate()
-                ops.decode_sample(logits, s.T, s.end, s.gen, s.shift, s.uniforms, ctl, tok, bw, s.ids, s.chunk,
-                                  s.comb, forced=s.forced, probs_log=s.probs, inc_len=False, beams=s.beams,
-                                  top_k=s.top_k, top_p=s.top_p)
+                cache._draw(tok, logits, False)
                 step.append(s.ids)
-            ops.decode_decide(ctl, N, NB, bw, s.comb, s.chunk, s.best_p, s.best_chunk, s.take, draws=s.per_set)
-        ops.decode_advance(ctl, bw)
-        s.used += s.candidates * s.per_set
+            _decide(cache, c == s.candidates - 1)
         step.ring.view(N, NB, -1)[:, :, cur:cur + bw].copy_(s.best_chunk[:, None, :])     # the kept chunk
         cur += bw
-        if progress is not None:
-            progress(cur - 1, total_seq)
+        if st.progress is not None:
+            st.progress(cur - 1, st.total_seq)
     return step.ring[::NB, :cur].clone()
 
 
-def _generate_fused(model, hr_input, enc, total_seq, temperature, use_sliding_window,
-                    sliding_window, end_token, shift, num_beam, beam_width, mode, progress,
-                    stop_len, pos_off, batch_beams, top_k=0, top_p=1.0, decode_weights="f32"):
+def _generate_fused(model, hr_input, enc, st):
     """The cached search with sampling, candidate bookkeeping and the decoder steps replayed from
     captured graphs (kvcache.DecodeCache.begin_search); nothing is read back before the stage ends.
     Returns (hr_input, pos, cache), or None when the model does not fit the fused kernels; the cache (rows of
     the kept tokens but the last) serves the evaluations of the next chunk that come before the window slides.
     top_k / top_p go to the search state (begin_search): _fused_tail and _window_tail draw with them too.
-    decode_weights: the cache's `weights` mode (kvcache.DECODE_WEIGHTS)."""
-    device = hr_input.device
-    N = hr_input.shape[0]
+    st.decode_weights: the cache's `weights` mode (kvcache.DECODE_WEIGHTS)."""
+    N, bw = hr_input.shape[0], st.beam_width
     # The candidate chunks of a position are independent given the kept prefix: they run as rows of one batch
     # either way.  Without --batch-beams every draw keeps the number the reference's candidate loop gives it
     # (begin_search reference_order: same draws -> same tokens as one candidate after the other); ORDERED_ROWS = 0
     # runs the candidates literally one after the other (tests, A/B).
-    ordered = not batch_beams and num_beam > 1 and N * num_beam <= ORDERED_ROWS
-    B = num_beam if (batch_beams or ordered) and num_beam > 1 else 1
-    cap = stop_len + beam_width
-    limit = min(cap, sliding_window) if use_sliding_window else cap
+    ordered = not st.batch_beams and st.num_beam > 1 and N * st.num_beam <= ORDERED_ROWS
+    B = st.num_beam if (st.batch_beams or ordered) and st.num_beam > 1 else 1
     cur = hr_input.shape[1]
-    pos = _prefix_pos(N, cur, pos_off, device) if use_sliding_window else None
     chunks = 0
-    while cur + chunks * beam_width < stop_len and cur + (chunks + 1) * beam_width <= limit:
+    while cur + chunks * bw < st.stop_len and cur + (chunks + 1) * bw <= st.limit:
         chunks += 1
     if chunks == 0:
-        return hr_input, pos, None
-    positions = [0.0] + [float(L + pos_off) for L in range(1, limit)] if use_sliding_window else None
-    enc_b = enc.repeat_interleave(B, dim=0) if (enc is not None and B > 1) else enc
+        return hr_input, st.prefix_pos(hr_input), None
+    positions = _positions(0, st.limit, st.pos_off) if st.use_sliding_window else None
     tm = _Timer()
-    cache = decode_cache(model, enc_b, N * B, limit, positions, decode_weights)
+    cache = decode_cache(model, _repeat(enc, B), N * B, st.limit, positions, st.decode_weights)
     if cache.dim % 4 or (model.use_pos_cond and cache._table is None):
         return None
     tm.mark("cache")
     dbg = FUSED_DEBUG or {}
-    after = cur + chunks * beam_width                      # tokens (first included) once the cached chunks are in
-    tail_chunks = max(0, -(-(stop_len - after) // beam_width))          # chunks _fused_tail draws for
+    after = cur + chunks * bw                              # tokens (first included) once the cached chunks are in
+    tail_chunks = max(0, -(-(st.stop_len - after) // bw))               # chunks _fused_tail draws for
     # a prefix of cur > 1 tokens: its first cur - 1 rows are prefilled, the search starts at window index cur
-    cache.begin_search(hr_input[:, 0] if cur == 1 else hr_input, N, B, beam_width, temperature, end_token, shift, mode == "generate",
-                       chunks + tail_chunks, 1 if B > 1 else num_beam, forced=dbg.get("forced"),
-                       log_probs=bool(dbg.get("log")), reference_order=ordered, top_k=top_k, top_p=top_p)
+    cache.begin_search(hr_input[:, 0] if cur == 1 else hr_input, N, B, bw, st.temperature, st.end_token, st.shift,
+                       st.mode == "generate", chunks + tail_chunks, 1 if B > 1 else st.num_beam,
+                       forced=dbg.get("forced"), log_probs=bool(dbg.get("log")), reference_order=ordered,
+                       top_k=st.top_k, top_p=st.top_p)
     tm.mark("capture")
     for c in range(chunks):
         cache.run_chunk(last=c == chunks - 1)
-        if progress is not None:
-            progress(cur + (c + 1) * beam_width - 1, total_seq)
+        if st.progress is not None:
+            st.progress(cur + (c + 1) * bw - 1, st.total_seq)
     hr_input = cache.finish_search()
     tm.mark(f"{chunks} chunks")
     tm.report()
-    if use_sliding_window:
-        new = torch.tensor([float(L + pos_off) for L in range(cur, hr_input.shape[1])], device=device)
-        pos = torch.cat((pos, new[None].expand(N, -1)), dim=1)
-    return hr_input, pos, cache
+    return hr_input, st.prefix_pos(hr_input), cache
 
 
-def _fused_tail(model, cache, hr_input, pos, enc, use_sliding_window, sliding_window, beam_width, progress,
-                total_seq, stop_len, pos_off, pos_bound):
+class _Window:
+    """The sequences of one candidate in a loop that evaluates the whole window: tokens (rows, n), the `pos_cond`
+    value of every token still in the window (None for a stage without a sliding window) and the index the
+    window starts at."""
+
+    __slots__ = ("tokens", "pos", "start", "window", "pos_off")
+
+    def __init__(self, st, tokens, pos, start):
+        self.tokens, self.pos, self.start, self.pos_off = tokens, pos, start, st.pos_off
+        self.window = st.sliding_window if st.use_sliding_window else None
+
+    def slide(self):
+        """In front of an evaluation: a full window drops its oldest token (generate_images.py:275-286)."""
+        if self.window is not None and self.tokens.shape[1] >= self.window:
+            self.start += 1
+            self.pos = self.pos[:, 1:]
+
+    def view(self):
+        """(tokens, positions) of the window as the model evaluates it."""
+        return self.tokens[:, self.start:], self.pos
+
+    def append(self, ids):
+        """ids (rows, 1) join the sequences under the loop's position numbering (`_positions`)."""
+        n = self.tokens.shape[1]
+        self.tokens = torch.cat((self.tokens, ids), dim=1)
+        if self.window is not None:
+            value = _positions(n, n + 1, self.pos_off)[0]
+            self.pos = torch.cat((self.pos, torch.full((ids.shape[0], 1), value, device=ids.device)), dim=1)
+
+
+def _decode_window(model, tokens, pos, enc, st):
+    """Logits (rows, S, V) of a window: the reference's full-window evaluation."""
+    # the loop's positions are whole numbers (cur + tok + pos_off): as int64 the model evaluates the
+    # conditioning path once per POSITION instead of once per token (Transformer._cond; same values)
+    if pos is None or not hasattr(model, "_cond"):
+        return model.decode(tokens.contiguous(), enc, pos)
+    return model.decode(tokens.contiguous(), enc, pos.long(), pos_bound=st.pos_bound)
+
+
+def _fused_tail(model, cache, hr_input, pos, enc, st):
     """The chunks behind the cached ones (the window slides inside them: every evaluation from there on is the
     reference's full-window evaluation, generate_images.py:275-286) on the state of the fused search: the candidates
     stay rows of one batch, every draw is made by the sampling kernel from the search's uniforms under the
@@ -349,110 +441,74 @@ def _fused_tail(model, cache, hr_input, pos, enc, use_sliding_window, sliding_wi
     window (the chunk in which it starts to slide: all but its last) are replays of the cache's step graph.
     Enqueues only; nothing is read back."""
     s = cache._search
-    N, NB, bw, ctl = s.N, s.NB, s.bw, cache.ctl
-    B = N * NB
-    device = hr_input.device
-    enc_eval = enc.repeat_interleave(NB, dim=0) if (enc is not None and NB > 1) else enc
-    whole = hasattr(model, "_cond")        # a Transformer: whole-number positions as int64 (one conditioning row each)
-    start = 0
-    while hr_input.shape[1] < stop_len:
-        cur = hr_input.shape[1]
-        for _ in range(s.candidates):
-            t_in = hr_input.repeat_interleave(NB, dim=0) if NB > 1 else hr_input
-            t_pos = (pos.repeat_interleave(NB, dim=0) if NB > 1 else pos) if use_sliding_window else None
-            t_start = start
-            for tok in range(bw):
-                if use_sliding_window and t_in.shape[1] >= sliding_window:
-                    t_start += 1
-                    t_pos = t_pos[:, 1:]
-                n = t_in.shape[1]
-                if n - 1 < cache.max_len and (not use_sliding_window or n < sliding_window):
-                    s.ids.copy_(t_in[:, -1])
-                    ctl[0:1].fill_(n - 1)
-                    s.g_step.replay()
-                    logits = s.logits
+    NB = s.NB
+    enc_eval = _repeat(enc, NB)
+    start, replays = 0, _replays_below(cache, st)
+    while hr_input.shape[1] < st.stop_len:
+        for c in range(s.candidates):
+            w = _Window(st, _repeat(hr_input, NB), _repeat(pos, NB), start)
+            for tok in range(s.bw):
+                w.slide()
+                n = w.tokens.shape[1]
+                if n < replays:
+                    logits = _replay_step(cache, w.tokens[:, -1], n - 1)
                 else:
-                    # A slid window is window - 1 tokens: rows x 255 is no whole number of GEMM tiles and runs the
-                    # guarded kernels.  One more token behind the last makes it one (16 x 256 = 4,096 rows) and
-                    # changes nothing before it -- self-attention is causal, everything else is per token -- so the
-                    # logits wanted are those of the last token but one.
-                    win, wpos = t_in[:, t_start:], t_pos
-                    rows_ = win.shape[0] * win.shape[1]
-                    pad = rows_ % 128 != 0 and (rows_ + win.shape[0]) % 128 == 0
-                    if pad:
+                    win, wpos = w.view()
+                    pad = window_pad(win.shape[0], win.shape[1])
+                    if pad:             # the logits wanted are then those of the last token but one
                         win = torch.cat((win, win[:, -1:]), dim=1)
                         wpos = None if wpos is None else torch.cat((wpos, wpos[:, -1:]), dim=1)
-                    if wpos is None or not whole:
-                        logits = model.decode(win.contiguous(), enc_eval, wpos)
-                    else:
-                        logits = model.decode(win.contiguous(), enc_eval, wpos.long(), pos_bound=pos_bound)
-                    logits = logits[:, -2 if pad else -1, :]
-                ops.decode_sample(logits, s.T, s.end, s.gen, s.shift, s.uniforms, ctl, tok, bw, s.ids, s.chunk,
-                                  s.comb, forced=s.forced, probs_log=s.probs, inc_len=False, beams=s.beams,
-                                  top_k=s.top_k, top_p=s.top_p)
-                t_in = torch.cat((t_in, s.ids[:, None]), dim=1)
-                if use_sliding_window:
-                    t_pos = torch.cat((t_pos, torch.full((B, 1), float(cur + tok + pos_off), device=device)), dim=1)
-            ops.decode_decide(ctl, N, NB, bw, s.comb, s.chunk, s.best_p, s.best_chunk, s.take, draws=s.per_set)
-        ops.decode_advance(ctl, bw)
-        s.used += s.candidates * s.per_set
+                    logits = _decode_window(model, win, wpos, enc_eval, st)[:, -2 if pad else -1, :]
+                cache._draw(tok, logits, False)
+                w.append(s.ids[:, None])
+            _decide(cache, c == s.candidates - 1)
         hr_input = torch.cat((hr_input, s.best_chunk), dim=1)
-        start = t_start
-        if use_sliding_window:
-            pos = t_pos[::NB] if NB > 1 else t_pos
-        if progress is not None:
-            progress(hr_input.shape[1] - 1, total_seq)
+        start, pos = w.start, w.pos if w.pos is None else w.pos[::NB]
+        if st.progress is not None:
+            st.progress(hr_input.shape[1] - 1, st.total_seq)
     return hr_input
 
 
-def _generate_cached(model, hr_input, enc, total_seq, temperature, use_sliding_window,
-                     sliding_window, end_token, shift, num_beam, beam_width, mode, progress,
-                     stop_len, pos_off, batch_beams, top_k=0, top_p=1.0, decode_weights="f32"):
-    """The same search as the loops below, evaluating one token per model call from a
+def _generate_cached(model, hr_input, enc, st):
+    """The same search as `_generate_window`, evaluating one token per model call from a
     `DecodeCache` for as long as no evaluation of the next chunk would slide the window.
     Sampling draws are made in the reference's order (same shapes, same generator), so the
     sequential variant reproduces the full-window loop whenever the logits round alike.
     Returns (hr_input, pos) for the windowed loops to continue from."""
     device = hr_input.device
-    N = hr_input.shape[0]
-    B = num_beam if batch_beams and num_beam > 1 else 1
-    # the loop overshoots stop_len by up to beam_width - 1 tokens (the reference's `while len < total`):
-    # the last chunk of a sequence shorter than the window is cached like the others, instead of falling to
-    # the full-window loop (whose ragged row counts run the guarded GEMM kernels: 14 % of a 3-stage cascade)
-    cap = stop_len + beam_width
-    limit = min(cap, sliding_window) if use_sliding_window else cap
+    N, bw = hr_input.shape[0], st.beam_width
+    B = st.num_beam if st.batch_beams and st.num_beam > 1 else 1
     cur = hr_input.shape[1]
-    pos = _prefix_pos(N, cur, pos_off, device) if use_sliding_window else None
-    if cur + beam_width > limit:
-        return hr_input, pos
-    enc_b = enc.repeat_interleave(B, dim=0) if (enc is not None and B > 1) else enc
-    cache = DecodeCache(model, enc_b, N * B, limit, weights=decode_weights)
+    if cur + bw > st.limit:
+        return hr_input, st.prefix_pos(hr_input)
+    cache = DecodeCache(model, _repeat(enc, B), N * B, st.limit, weights=st.decode_weights)
     rows = torch.arange(N * B, device=device)
 
-    def positions(value):
-        return torch.full((N * B,), float(value), device=device) if use_sliding_window else None
+    def position(index):
+        """(N * B,) `pos_cond` of the token at sequence index `index`."""
+        if not st.use_sliding_window:
+            return None
+        return torch.full((N * B,), _positions(index, index + 1, st.pos_off)[0], device=device)
 
     # a prefix: rows [0, cur - 1) are prefilled, its last token is the first step (from scratch: token 0 at index 0)
-    pvals = [0.0] + [float(L + pos_off) for L in range(1, cur)]
     if cur > 1:
-        cache.prefill(hr_input[:, :cur - 1], pos=pvals)
-    last = cache.step(hr_input[:, cur - 1].repeat_interleave(B), positions(pvals[cur - 1]), cur - 1)
-    while cur < stop_len and cur + beam_width <= limit:
+        cache.prefill(hr_input[:, :cur - 1], pos=_positions(0, cur - 1, st.pos_off))
+    last = cache.step(hr_input[:, cur - 1].repeat_interleave(B), position(cur - 1), cur - 1)
+    while cur < st.stop_len and cur + bw <= st.limit:
         best_chunk = best_p = best_rows = None
-        for _ in range(1 if B > 1 else num_beam):
+        for _ in range(1 if B > 1 else st.num_beam):
             comb = torch.ones(N * B, device=device)
             logits, new = last, []
-            for tok in range(beam_width):
-                nxt, comb = _sample(logits, temperature, end_token, mode, rows, comb, top_k, top_p)
-                new.append(nxt + shift)
-                if tok < beam_width - 1:
-                    logits = cache.step(new[-1].squeeze(1), positions(cur + tok + pos_off),
-                                        cur + tok)
+            for tok in range(bw):
+                nxt, comb = _sample(logits, st, rows, comb)
+                new.append(nxt + st.shift)
+                if tok < bw - 1:
+                    logits = cache.step(new[-1].squeeze(1), position(cur + tok), cur + tok)
             chunk = torch.cat(new, dim=1)
-            if B > 1 or num_beam == 1:
+            if B > 1 or st.num_beam == 1:
                 best_chunk, best_p = chunk, comb
                 continue
-            saved = cache.rows(cur, cur + beam_width - 1).clone() if beam_width > 1 else None
+            saved = cache.rows(cur, cur + bw - 1).clone() if bw > 1 else None
             if best_p is None:
                 best_chunk, best_p, best_rows = chunk, comb, saved
             else:   # per sample, keep the candidate chunk with the larger probability product
@@ -461,25 +517,58 @@ def _generate_cached(model, hr_input, enc, total_seq, temperature, use_sliding_w
                 best_chunk = torch.where(keep[:, None], best_chunk, chunk)
                 if saved is not None:
                     best_rows = torch.where(keep[None, None, :, None, None, None], best_rows, saved)
-        if B > 1:       # first beam with the maximal product wins, as in _generate_batched
+        if B > 1:       # first beam with the maximal product wins, as in _generate_window
             pick = torch.arange(N, device=device) * B + best_p.view(N, B).argmax(dim=1)
             best_chunk = best_chunk[pick]
-            if beam_width > 1:
-                r = cache.rows(cur, cur + beam_width - 1)
+            if bw > 1:
+                r = cache.rows(cur, cur + bw - 1)
                 r.copy_(r[:, :, pick].repeat_interleave(B, dim=2))
         elif best_rows is not None:
-            cache.rows(cur, cur + beam_width - 1).copy_(best_rows)
+            cache.rows(cur, cur + bw - 1).copy_(best_rows)
         hr_input = torch.cat((hr_input, best_chunk.long()), dim=1)
-        if use_sliding_window:
-            pos = torch.cat([pos] + [torch.full((N, 1), float(cur + tok + pos_off), device=device)
-                                     for tok in range(beam_width)], dim=1)
-        cur += beam_width
-        if progress is not None:
-            progress(cur - 1, total_seq)
-        if cur < stop_len and cur + beam_width <= limit:   # another cached chunk follows
-            last = cache.step(best_chunk[:, -1].repeat_interleave(B),
-                              positions(cur - 1 + pos_off), cur - 1)
-    return hr_input, pos
+        cur += bw
+        if st.progress is not None:
+            st.progress(cur - 1, st.total_seq)
+        if cur < st.stop_len and cur + bw <= st.limit:     # another cached chunk follows
+            last = cache.step(best_chunk[:, -1].repeat_interleave(B), position(cur - 1), cur - 1)
+    return hr_input, st.prefix_pos(hr_input)
+
+
+def _generate_window(model, hr_input, pos, enc, st):
+    """The search with every token drawn from an evaluation of the whole window, as the reference runs it
+    (generate_images.py:256-345).  Without --batch-beams the `num_beam` candidate chunks of a position run one
+    after the other, each drawing on its own N rows.  With it (additive option) they are ONE batch of N*num_beam
+    sequences per model call, the beams of an image adjacent: 1/num_beam of the model calls; the device generator
+    is consumed in a different order, so samples differ from the sequential candidates for a given seed."""
+    device = hr_input.device
+    N = hr_input.shape[0]
+    B = st.num_beam if st.batch_beams and st.num_beam > 1 else 1
+    enc_eval = _repeat(enc, B)
+    rows = torch.arange(N * B, device=device)
+    start = 0
+    while hr_input.shape[1] < st.stop_len:
+        best_in = best_p = None
+        for _ in range(1 if B > 1 else st.num_beam):
+            comb = torch.ones(N * B, device=device)
+            w = _Window(st, _repeat(hr_input, B), _repeat(pos, B), start)
+            for tok in range(st.beam_width):
+                w.slide()
+                logits = _decode_window(model, *w.view(), enc_eval, st)[:, -1, :]
+                nxt, comb = _sample(logits, st, rows, comb)
+                w.append(nxt + st.shift)
+            if best_p is None:
+                best_in, best_p = w.tokens, comb
+            else:  # keep, per sample, the candidate chunk with the larger probability product
+                keep = best_p >= comb
+                best_p = torch.where(keep, best_p, comb)
+                best_in = torch.where(keep[:, None], best_in, w.tokens)
+        if B > 1:   # first beam with the maximal product wins (sequential candidates keep the earlier one on ties)
+            best_in = best_in[torch.arange(N, device=device) * B + best_p.view(N, B).argmax(dim=1)]
+        hr_input = best_in.long()
+        start, pos = w.start, w.pos if w.pos is None else w.pos[::B]
+        if st.progress is not None:
+            st.progress(hr_input.shape[1] - 1, st.total_seq)
+    return hr_input
 
 
 @torch.no_grad()
@@ -516,8 +605,6 @@ def generate_tokens(model, hr_input, lr_input, total_seq, temperature, use_slidi
     assert mode in ("generate", "train")
     check_decode_weights(decode_weights)
     top_k, top_p = ops.check_sample_filter(top_k, top_p)
-    filtered = top_k > 0 or top_p < 1.0
-    device = hr_input.device
     N = hr_input.shape[0]
     fused = (sampler or os.environ.get("QARIG_SAMPLER", DEFAULT_SAMPLER)) == "fused"
     # The single-token kernels behind the fused search take up to 16 rows (images x candidates).  A somewhat
@@ -528,8 +615,8 @@ def generate_tokens(model, hr_input, lr_input, total_seq, temperature, use_slidi
     group = max(1, DECODE_ROWS // max(1, num_beam))
     rows_all = N * max(1, num_beam)
     limit = _cache_limit(hr_input, total_seq, use_sliding_window, sliding_window, beam_width, mode)
-    if fused and GROUP_IMAGES and use_kv_cache and N > group and DECODE_ROWS < rows_all < GROUP_BELOW_ROWS and \
-            _cacheable(model, hr_input, use_sliding_window, cache_padded_heads, beam_width, limit):
+    cacheable = use_kv_cache and _cacheable(model, hr_input, use_sliding_window, cache_padded_heads, beam_width, limit)
+    if fused and GROUP_IMAGES and N > group and DECODE_ROWS < rows_all < GROUP_BELOW_ROWS and cacheable:
         outs = []
         for g0 in range(0, N, group):
             sub = slice(g0, min(N, g0 + group))
@@ -542,142 +629,34 @@ def generate_tokens(model, hr_input, lr_input, total_seq, temperature, use_slidi
         return torch.cat(outs, dim=0)
     enc = model.encode(lr_input) if model.use_encoder else None
     pos_off = 1 if mode == "generate" else 0
-    pos = _prefix_pos(N, hr_input.shape[1], pos_off, device) if use_sliding_window else None
-    start = 0
-    rows = torch.arange(N, device=device)
     stop_len = total_seq if mode == "generate" else hr_input.shape[1] + total_seq
-    cache = None
-    if use_kv_cache and _cacheable(model, hr_input, use_sliding_window, cache_padded_heads, beam_width, limit):
-        args = (model, hr_input, enc, total_seq, temperature, use_sliding_window, sliding_window, end_token,
-                shift, num_beam, beam_width, mode, progress, stop_len, pos_off, batch_beams, top_k, top_p,
-                decode_weights)
-        done = None
-        if fused:
-            done = _generate_fused(*args)
+    st = _Stage(temperature=temperature, end_token=end_token, shift=shift, num_beam=num_beam, beam_width=beam_width,
+                mode=mode, use_sliding_window=use_sliding_window, sliding_window=sliding_window, total_seq=total_seq,
+                stop_len=stop_len, pos_off=pos_off, pos_bound=_reach(stop_len, beam_width) + pos_off + 1, limit=limit,
+                top_k=top_k, top_p=top_p, decode_weights=decode_weights, progress=progress, batch_beams=batch_beams)
+    pos, cache = st.prefix_pos(hr_input), None
+    if cacheable:
+        done = _generate_fused(model, hr_input, enc, st) if fused else None
         if done is not None:
             hr_input, pos, cache = done
         else:
-            hr_input, pos = _generate_cached(*args)
+            hr_input, pos = _generate_cached(model, hr_input, enc, st)
 
-    pos_bound = stop_len + beam_width + pos_off + 1
+    tail = _Timer()
     if cache is not None and cache._search is not None:
-        tail = _Timer()
-        if window_graph and use_sliding_window and \
-                _window_graph_fits(model, cache, hr_input, sliding_window, beam_width, stop_len):
-            hr_input = _window_tail(model, cache, hr_input, enc, sliding_window, beam_width, progress, total_seq,
-                                    stop_len, pos_off, pos_bound)
+        if window_graph and use_sliding_window and _window_graph_fits(model, cache, hr_input, st):
+            hr_input = _window_tail(model, cache, hr_input, enc, st)
             tail.mark("windowed tail (window graph)")
         else:
-            hr_input = _fused_tail(model, cache, hr_input, pos, enc, use_sliding_window, sliding_window, beam_width,
-                                   progress, total_seq, stop_len, pos_off, pos_bound)
+            hr_input = _fused_tail(model, cache, hr_input, pos, enc, st)
             tail.mark("windowed tail (fused draws)")
         tail.report()
         if FUSED_DEBUG is not None:
             FUSED_DEBUG["probs"] = cache._search.probs
             FUSED_DEBUG["draws"] = cache._search.used
         return hr_input
-
-    def last_logits(t_in, t_start, t_pos):
-        """Logits of the window's last token: the reference's full-window evaluation."""
-        # the loop's positions are whole numbers (cur + tok + pos_off): as int64 the model evaluates the
-        # conditioning path once per POSITION instead of once per token (Transformer._cond; same values)
-        if t_pos is None or not hasattr(model, "_cond"):
-            return model.decode(t_in[:, t_start:].contiguous(), enc_eval, t_pos)[:, -1, :]
-        return model.decode(t_in[:, t_start:].contiguous(), enc_eval, t_pos.long(), pos_bound=pos_bound)[:, -1, :]
-
-    tail = _Timer()
-    enc_eval = enc
-    if batch_beams and num_beam > 1:
-        enc_eval = enc.repeat_interleave(num_beam, dim=0) if enc is not None else None
-        out = _generate_batched(model, hr_input, last_logits, total_seq, temperature, use_sliding_window,
-                                sliding_window, end_token, shift, num_beam, beam_width, mode,
-                                progress, stop_len, pos_off, pos, top_k, top_p)
-        tail.mark("windowed tail (batched beams)")
-        tail.report()
-        return out
-    while hr_input.shape[1] < stop_len:
-        cur = hr_input.shape[1]
-        best_in = best_p = None
-        for _ in range(num_beam):
-            comb = torch.ones(N, device=device)
-            t_start, t_in, t_pos = start, hr_input, pos
-            for tok in range(beam_width):
-                if use_sliding_window and t_in.shape[1] >= sliding_window:
-                    t_start += 1
-                    t_pos = t_pos[:, 1:]
-                logits = last_logits(t_in, t_start, t_pos)
-                probs = torch.softmax(logits / temperature, dim=1)
-                if mode == "generate":
-                    probs[:, end_token] = 0.0          # <end> removed from consideration
-                if filtered:
-                    probs = filter_probs(probs, top_k, top_p)
-                nxt = torch.multinomial(probs, 1)
-                comb = comb * probs[rows, nxt.squeeze(1)]
-                if mode == "train":
-                    nxt[nxt == end_token] = 0          # reference HACK: <end> -> index 0
-                t_in = torch.cat((t_in, nxt + shift), dim=1)
-                if use_sliding_window:
-                    t_pos = torch.cat((t_pos, torch.full((N, 1), float(cur + tok + pos_off),
-                                                         device=device)), dim=1)
-            if best_p is None:
-                best_in, best_p = t_in, comb
-            else:  # keep, per sample, the candidate chunk with the larger probability product
-                keep = best_p >= comb
-                best_p = torch.where(keep, best_p, comb)
-                best_in = torch.where(keep[:, None], best_in, t_in)
-        start = t_start
-        hr_input = best_in.long()
-        if use_sliding_window:
-            pos = t_pos
-        if progress is not None:
-            progress(hr_input.shape[1] - 1, total_seq)
-    tail.mark("windowed tail")
+    hr_input = _generate_window(model, hr_input, pos, enc, st)
+    tail.mark("windowed tail (batched beams)" if batch_beams and num_beam > 1 else "windowed tail")
     tail.report()
     return hr_input
 
-
-def _generate_batched(model, hr_input, last_logits, total_seq, temperature, use_sliding_window,
-                      sliding_window, end_token, shift, num_beam, beam_width, mode, progress,
-                      stop_len, pos_off, pos, top_k=0, top_p=1.0):
-    """Same search, with the `num_beam` independent candidate chunks evaluated as ONE batch
-    of N*num_beam sequences per model call (the reference runs them one after the other).
-    Additive option: 1/num_beam of the model calls; the device generator is consumed in a
-    different order, so samples differ from the sequential loop for a given seed."""
-    device = hr_input.device
-    N, B = hr_input.shape[0], num_beam
-    start = 0
-    rows = torch.arange(N * B, device=device)
-    while hr_input.shape[1] < stop_len:
-        cur = hr_input.shape[1]
-        t_in = hr_input.repeat_interleave(B, dim=0)                 # (N*B, S): beams of image n adjacent
-        t_pos = pos.repeat_interleave(B, dim=0) if use_sliding_window else None
-        comb = torch.ones(N * B, device=device)
-        t_start = start
-        for tok in range(beam_width):
-            if use_sliding_window and t_in.shape[1] >= sliding_window:
-                t_start += 1
-                t_pos = t_pos[:, 1:]
-            logits = last_logits(t_in, t_start, t_pos)
-            probs = torch.softmax(logits / temperature, dim=1)
-            if mode == "generate":
-                probs[:, end_token] = 0.0
-            if top_k > 0 or top_p < 1.0:
-                probs = filter_probs(probs, top_k, top_p)
-            nxt = torch.multinomial(probs, 1)
-            comb = comb * probs[rows, nxt.squeeze(1)]
-            if mode == "train":
-                nxt[nxt == end_token] = 0
-            t_in = torch.cat((t_in, nxt + shift), dim=1)
-            if use_sliding_window:
-                t_pos = torch.cat((t_pos, torch.full((N * B, 1), float(cur + tok + pos_off),
-                                                     device=device)), dim=1)
-        # first beam with the maximal product wins (the sequential loop keeps the earlier one on ties)
-        best = comb.view(N, B).argmax(dim=1)
-        pick = torch.arange(N, device=device) * B + best
-        hr_input = t_in[pick].long()
-        start = t_start
-        if use_sliding_window:
-            pos = t_pos[pick]
-        if progress is not None:
-            progress(hr_input.shape[1] - 1, total_seq)
-    return hr_input
