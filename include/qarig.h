@@ -615,6 +615,31 @@ int qarig_token_score(const float* logits, const int64_t* target, int M, int C, 
 int qarig_score_reduce(const float* row_nll, const int* row_rank, int N, int S, int pos0, int P, int topk,
                        double* img_nll, double* pos_nll, int64_t* pos_cnt, int64_t* totals, void* stream);
 
+/* Reconstruction evaluation (additive; the reference has none), csrc/recon.hip.  Both entries write their
+ * outputs (they do not add), use no floating-point atomics and sum in one fixed order, so equal inputs give
+ * equal bits; every partial sum belongs to one image, so an image's value does not depend on which other
+ * images share its launch.  NaN or +-inf in an image stays in that image's outputs.
+ * qarig_pair_error: a, b = N contiguous images of E fp32 elements, base pointers 4-byte aligned (16-byte loads
+ * where an image's address allows them, 4-byte loads otherwise: the same values in the same order either way).
+ * out (N,3) fp64 = {sum (a-b)^2, sum |a-b|, max |a-b|} per image; differences, squares and sums in fp64.  One
+ * workgroup per 4,096-element chunk of an image writes a partial triple to ws, one wave per image adds the
+ * chunk partials in ascending order.  ws: qarig_pair_error_workspace_bytes(N, E) bytes (0: bad extents).
+ * qarig_ssim: a, b (N,C,H,W) fp32 contiguous; out (N) fp64 = mean structural similarity (Wang et al. 2004) per
+ * image, per channel, over the (H - taps + 1) x (W - taps + 1) "valid" positions only.  The window is separable
+ * with 1-D weights win, a HOST array of `taps` doubles (taps odd, 1 ... 15) that reaches the kernel by value.
+ * With w over the window: mx = sum w x, sx2 = sum w x^2 - mx^2, sxy = sum w x y - mx my,
+ * map = (2 mx my + c1)(2 sxy + c2) / ((mx^2 + my^2 + c1)(sx2 + sy2 + c2)).  The five window moments are
+ * accumulated in fp64 from the fp32 pixels (sum w x^2 - mx^2 cancels almost completely on smooth regions, where
+ * c2 decides the score).  H < taps or W < taps is an argument error.  One workgroup per (image, channel,
+ * 16 x 16 tile of outputs) writes a partial to ws, one wave per image adds them in ascending (channel, tile)
+ * order.  ws: qarig_ssim_workspace_bytes(N, C, H, W, taps) bytes (0: bad arguments). */
+size_t qarig_pair_error_workspace_bytes(int N, int64_t E);
+int qarig_pair_error(const float* a, const float* b, int N, int64_t E, double* out, void* ws, size_t ws_bytes,
+                     void* stream);
+size_t qarig_ssim_workspace_bytes(int N, int C, int H, int W, int taps);
+int qarig_ssim(const float* a, const float* b, int N, int C, int H, int W, const double* win, int taps, double c1,
+               double c2, double* out, void* ws, size_t ws_bytes, void* stream);
+
 /* F.mse_loss (mean) + d/dpred -- train_autoencoder.py:215-217, train_codebook.py:233-235. */
 size_t qarig_mse_workspace_bytes(void);
 int qarig_mse_fwd(const float* pred, const float* target, int64_t n, float* loss, float* dpred,

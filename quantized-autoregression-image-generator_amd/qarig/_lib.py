@@ -18,6 +18,7 @@ I = c_int
 L = c_int64
 Z = c_size_t
 F = c_float
+D = ctypes.c_double
 
 # name -> (restype, argtypes); must list every symbol include/qarig.h declares
 # (tests/test_abi.py cross-checks the two).
@@ -111,6 +112,10 @@ SIGNATURES = {
     "qarig_cross_entropy_fwd": (I, [P, P, I, I, P, P, P, P, P]),
     "qarig_token_score": (I, [P, P, I, I, L, P, P, P, P]),
     "qarig_score_reduce": (I, [P, P, I, I, I, I, I, P, P, P, P, P]),
+    "qarig_pair_error_workspace_bytes": (Z, [I, L]),
+    "qarig_pair_error": (I, [P, P, I, L, P, P, Z, P]),
+    "qarig_ssim_workspace_bytes": (Z, [I, I, I, I, I]),
+    "qarig_ssim": (I, [P, P, I, I, I, I, P, I, D, D, P, P, Z, P]),
     "qarig_mse_workspace_bytes": (Z, []),
     "qarig_mse_fwd": (I, [P, P, L, P, P, P, P]),
     "qarig_adam_step": (I, [P, P, P, P, L, F, F, F, F, F, F, P, P, P]),

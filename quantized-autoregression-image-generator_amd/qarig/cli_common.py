@@ -102,6 +102,29 @@ class ShardedLoader:
             yield torch.utils.data.default_collate([self.dataset[i] for i in idx])
 
 
+def build_validation(args, rank, info):
+    """--val-dataset-path / --val-step of a training command line: (loader, step) on rank 0 when the flag is given,
+    (None, None) otherwise.  The held-out latents are read in order, with a generator of the loader's own, so that
+    the training run draws what it draws without validation."""
+    if args.get("val_dataset_path") is None or rank != 0:
+        return None, None
+    from dataset_loader.feature_map_dataset import FeatureMapDataset
+    step = args["val_step"] if args.get("val_step") is not None else args["checkpoint_step"]
+    val_set = FeatureMapDataset(dataset_path=args["val_dataset_path"], load_image=False, return_filepaths=False)
+    loader = torch.utils.data.DataLoader(val_set, batch_size=args["batch_size"], num_workers=2, shuffle=False,
+                                         generator=torch.Generator())
+    info(f"Validation: {len(val_set):,} latents every {step:,} steps")
+    return loader, step
+
+
+def validate(out_dir, entry, lines, info):
+    """One evaluation of a training run: its log lines, and `entry` appended to <out-dir>/val_log.jsonl."""
+    for line in lines:
+        info(line)
+    with open(os.path.join(out_dir, "val_log.jsonl"), "a") as f:
+        f.write(json.dumps(entry) + "\n")
+
+
 def check_prompt_args(prompt_fmaps, prompt_fraction):
     """generate_images.py --prompt-fmaps / --prompt-fraction: both or neither, the fraction inside (0, 1).
     Returns whether the run is prompted."""

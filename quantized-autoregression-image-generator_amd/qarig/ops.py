@@ -3,6 +3,8 @@
 Shapes/dtypes/contiguity are validated here, before the call, so the C side only
 sees well-formed arguments (SURVEY.md 8b "Errors").
 """
+import ctypes
+import math
 import os
 
 import torch
@@ -1429,6 +1431,50 @@ def score_reduce(row_nll, row_rank, N, S, pos0, topk, img_nll, pos_nll, pos_cnt,
     assert img_nll.numel() == N and pos_cnt.numel() == P and totals.numel() == 3
     check(_lib.load().qarig_score_reduce(ptr(row_nll), ptr(row_rank), N, S, int(pos0), P, int(topk), ptr(img_nll),
                                          ptr(pos_nll), ptr(pos_cnt), ptr(totals), stream()), "qarig_score_reduce")
+
+
+def pair_error(a, b):
+    """(N,3) fp64 = {sum (a-b)^2, sum |a-b|, max |a-b|} per image of two equally shaped fp32 batches (the first
+    axis counts the images).  fp64 throughout, one fixed summation order, independent of the batch an image is in."""
+    require_cuda(a, b)
+    if a.shape != b.shape or a.dim() < 1 or a.numel() == 0:
+        raise ValueError(f"pair_error: shapes {tuple(a.shape)} and {tuple(b.shape)}")
+    a, b = f32c(a), f32c(b)
+    N = a.shape[0]
+    E = a.numel() // N
+    lib = _lib.load()
+    out = torch.empty((N, 3), dtype=torch.float64, device=a.device)
+    ws = _lib.workspace(lib.qarig_pair_error_workspace_bytes(N, E), a.device, tag="recon")
+    check(lib.qarig_pair_error(ptr(a), ptr(b), N, E, ptr(out), ptr(ws), ws.numel(), stream()), "qarig_pair_error")
+    return out
+
+
+def gaussian_window(taps, sigma):
+    """1-D Gaussian weights exp(-(i - taps // 2)^2 / 2 sigma^2), normalised to sum 1, as Python floats."""
+    w = [math.exp(-((i - taps // 2) ** 2) / (2.0 * sigma * sigma)) for i in range(taps)]
+    s = math.fsum(w)
+    return [v / s for v in w]
+
+
+def ssim(a, b, data_range=2.0, sigma=1.5, taps=11, k1=0.01, k2=0.03, window=None):
+    """(N,) fp64 mean structural similarity of two (N,C,H,W) fp32 batches, per channel over the valid positions
+    of a separable window: Gaussian (sigma, taps) unless `window` gives the 1-D weights themselves.  Window
+    moments in fp64; c1 = (k1 data_range)^2, c2 = (k2 data_range)^2."""
+    require_cuda(a, b)
+    if a.shape != b.shape or a.dim() != 4:
+        raise ValueError(f"ssim: need two (N,C,H,W) batches, got {tuple(a.shape)} and {tuple(b.shape)}")
+    a, b = f32c(a), f32c(b)
+    N, C, H, W = a.shape
+    w = [float(v) for v in window] if window is not None else gaussian_window(int(taps), float(sigma))
+    taps = len(w)
+    win = (ctypes.c_double * max(taps, 1))(*w)
+    c1, c2 = (k1 * data_range) ** 2, (k2 * data_range) ** 2
+    lib = _lib.load()
+    out = torch.empty(N, dtype=torch.float64, device=a.device)
+    ws = _lib.workspace(lib.qarig_ssim_workspace_bytes(N, C, H, W, taps), a.device, tag="recon")
+    check(lib.qarig_ssim(ptr(a), ptr(b), N, C, H, W, ctypes.cast(win, ctypes.c_void_p), taps, c1, c2, ptr(out),
+                         ptr(ws), ws.numel(), stream()), "qarig_ssim")
+    return out
 
 
 def adam_step(p, g, m, v, beta1, beta2, eps, step_size, bc2_sqrt, grad_scale=1.0, dev_step=None, shadow=None):

@@ -30,6 +30,13 @@ def parse_args():
     p.add_argument("--config-path", required=True, type=pathlib.Path)
     p.add_argument("--out-dir", required=True, type=pathlib.Path)
     p.add_argument("--max-steps", type=int, default=None, help="(additive) stop after N steps.")
+    p.add_argument("--val-dataset-path", type=pathlib.Path, default=None,
+                   help="(additive; the reference never evaluates) feature map dataset json file of held-out latents: "
+                        "every --val-step steps rank 0 scores the codebook on it (qarig/recon_eval.py: hard "
+                        "quantisation, the decoded image against the autoencoder's own), logs Val Latent MSE | PSNR | "
+                        "SSIM | used | perplexity and appends one JSON line to <out-dir>/val_log.jsonl")
+    p.add_argument("--val-step", type=int, default=None, help="Steps between evaluations (default: --checkpoint-step).")
+    p.add_argument("--val-batches", type=int, default=None, help="Score the first batches of the held-out set only.")
     return vars(p.parse_args())
 
 
@@ -68,6 +75,17 @@ def main():
     dataset = FeatureMapDataset(dataset_path=args["dataset_path"], load_image=False,
                                 return_filepaths=False)
     loader = cc.ShardedLoader(dataset, args["batch_size"], num_workers=4, shuffle=True)
+    val_loader, val_step = cc.build_validation(args, rank, info)
+
+    def validate(global_steps):
+        """Rank 0 alone, like the checkpoint: the other ranks wait at their next exchange."""
+        from qarig import recon_eval
+        scorer = recon_eval.ReconScorer(decoder_model, {"codebook": codebook})
+        recon_eval.score_loader(scorer, val_loader, device, args["val_batches"])
+        block = recon_eval.without_per_image(scorer.result()["codebooks"]["codebook"])
+        cc.validate(out_dir, {"step": global_steps, "codebook": block},
+                    [recon_eval.recon_summary_line("Val", block)], info)
+
     info(f"{project_name}")
     info(f"Output Dir: {out_dir}")
     info(f"Patch dim: {patch_dim} | Image dim: {image_dim} | Num Embeddings: {codebook.num_embeddings:,}")
@@ -106,6 +124,8 @@ def main():
                 ok = save_model(model_dict=d, dest_path=out_dir, file_name=f"codebook_{global_steps}.pt",
                                 logging=info)
                 info("Successfully saved model." if ok else "Error occured saving model.")
+            if val_loader is not None and global_steps % val_step == 0:
+                validate(global_steps)
             info("Cum. Steps: {:,} | Steps: {:,} / {:,} | L.R.: {:.8f} | Recon Loss: {:.5f} | "
                  "Neighbourhood Range: {}".format(global_steps + 1, index + 1, len(loader),
                                                   optim.param_groups[0]["lr"], total / iteration_count,

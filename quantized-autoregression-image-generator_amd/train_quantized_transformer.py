@@ -273,17 +273,9 @@ def main():
         model.train()
         torch.cuda.empty_cache()
 
-    val_loader = None
-    if args["val_dataset_path"] is not None and rank == 0:
-        import json
-        import os
+    val_loader, val_step = cc.build_validation(args, rank, info)     # (None, None) without the flag or off rank 0
+    if val_loader is not None:
         from qarig import evaluate
-        val_step = args["val_step"] if args["val_step"] is not None else args["checkpoint_step"]
-        val_set = FeatureMapDataset(dataset_path=args["val_dataset_path"], load_image=False, return_filepaths=False)
-        # in order; a generator of its own, so that the training run draws what it draws without validation
-        val_loader = torch.utils.data.DataLoader(val_set, batch_size=args["batch_size"], num_workers=2, shuffle=False,
-                                                 generator=torch.Generator())
-        info(f"Validation: {len(val_set):,} latents every {val_step:,} steps")
 
     def validate(global_steps):
         """Rank 0 alone, like checkpoint(): the other ranks wait at their next exchange."""
@@ -301,8 +293,7 @@ def main():
             with optim.ema_weights():
                 entry["model_ema"] = score()
             info(evaluate.summary_line("Val EMA", entry["model_ema"]))
-        with open(os.path.join(out_dir, "val_log.jsonl"), "a") as f:
-            f.write(json.dumps(entry) + "\n")
+        cc.validate(out_dir, entry, (), info)
 
     graphed = None
     batch_size = args["batch_size"]

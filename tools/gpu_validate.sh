@@ -25,3 +25,4 @@ step 200 $O/${TAG}_decode_chain_rows4.json python tools/decode_chain_bench.py --
 step 200 $O/${TAG}_decode_chain_rows16.json python tools/decode_chain_bench.py --rows 16; cat $O/${TAG}_decode_chain_rows16.json
 step 200 $O/${TAG}_bmu_bench.log python tools/bmu_bench.py; tail -12 $O/${TAG}_bmu_bench.log
 step 200 $O/${TAG}_c1_autoencoder.log python tools/c1_autoencoder.py; tail -2 $O/${TAG}_c1_autoencoder.log
+step 200 $O/${TAG}_recon_metrics.json python tools/recon_bench.py; tail -12 $O/${TAG}_recon_metrics.json
