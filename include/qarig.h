@@ -640,6 +640,26 @@ size_t qarig_ssim_workspace_bytes(int N, int C, int H, int W, int taps);
 int qarig_ssim(const float* a, const float* b, int N, int C, int H, int W, const double* win, int taps, double c1,
                double c2, double* out, void* ws, size_t ws_bytes, void* stream);
 
+/* Training against SSIM (additive), csrc/recon.hip.  With x = a (the prediction), y = b (data) and, per valid
+ * position, A1 = 2 mx my + c1, A2 = 2 sxy + c2, B1 = mx^2 + my^2 + c1, B2 = sx2 + sy2 + c2, v = A1 A2 / (B1 B2):
+ *   P = dv/dmx = 2 my (A2 - A1) / (B1 B2) - 2 mx v (1/B1 - 1/B2),  Q = dv/d(sum w x^2) = -v / B2,
+ *   R = dv/d(sum w x y) = 2 A1 / (B1 B2).
+ * qarig_ssim_fwd_maps: qarig_ssim (out bit-identical, same ws) that also writes maps (3,N,C,oh,ow) fp64 =
+ * {P, Q, R}, oh = H - taps + 1, ow = W - taps + 1; qarig_ssim_maps_bytes gives its size (0: bad arguments).
+ * qarig_ssim_bwd: da (N,C,H,W) fp32, written in full (not added to) =
+ *   da(q) = g[n] / (C oh ow) * sum_ij w_i w_j [P + 2 a(q) Q + b(q) R](q - (i,j))   over the valid q - (i,j),
+ * the gradient of sum_n g[n] out[n] with respect to a; g (N) fp64 on the device, win and taps as in the forward
+ * (a HOST array, applied in correlation order: no symmetry assumed).  One workgroup per (image, channel, 16 x 16
+ * tile of input pixels), the maps' halo and a horizontal pass in LDS, fp64 fma throughout, one rounding to fp32;
+ * no atomics, every pixel written by one thread, image n's gradient a function of image n and g[n] alone.  Maps
+ * and moments stay fp64: the terms of da(q) cancel to 1e-4 of their magnitude sum.  Both entries check their
+ * arguments as qarig_ssim does, with N C ceil(H/16) ceil(W/16) < 2^31, and refuse outputs that alias inputs. */
+size_t qarig_ssim_maps_bytes(int N, int C, int H, int W, int taps);
+int qarig_ssim_fwd_maps(const float* a, const float* b, int N, int C, int H, int W, const double* win, int taps,
+                        double c1, double c2, double* out, double* maps, void* ws, size_t ws_bytes, void* stream);
+int qarig_ssim_bwd(const float* a, const float* b, const double* maps, const double* g, int N, int C, int H, int W,
+                   const double* win, int taps, float* da, void* stream);
+
 /* F.mse_loss (mean) + d/dpred -- train_autoencoder.py:215-217, train_codebook.py:233-235. */
 size_t qarig_mse_workspace_bytes(void);
 int qarig_mse_fwd(const float* pred, const float* target, int64_t n, float* loss, float* dpred,

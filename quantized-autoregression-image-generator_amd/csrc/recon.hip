@@ -2,6 +2,8 @@
 // two batches of fp32 images, in fp64.  Each quantity is a sum of per-workgroup partials that depend on one
 // image alone, added by one wave per image in one fixed order: no floating-point atomics, equal inputs give
 // equal bits, and an image's value does not depend on which other images share its launch.
+// Training against SSIM (ssim_tile_maps_kernel, ssim_bwd_kernel): the forward also writes the three partial
+// derivatives of every window's score, the backward correlates them with the window once more; fp64 as well.
 #include "qarig_common.h"
 
 namespace qarig {
@@ -131,10 +133,15 @@ __global__ __launch_bounds__(256) void pair_error_finish_kernel(const double* __
 // of (16 + taps - 1)^2 pixels goes to LDS (zero past the image: only outputs outside the valid region read it,
 // and those are dropped), a horizontal pass leaves the five window moments of every (halo row, output column)
 // in LDS as doubles, a vertical pass gives each thread its output.  part[block] = sum of the tile's map.
-__global__ __launch_bounds__(256) void ssim_tile_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                        int C, int H, int W, int taps, SsimWindow win, double c1,
-                                                        double c2, int tiles_x, int tiles_y,
-                                                        double* __restrict__ part) {
+//
+// MAPS: each valid position also writes the derivatives of its score v = A1 A2 / (B1 B2) with respect to the
+// window moments of a, P = dv/dmx, Q = dv/dxx, R = dv/dxy, to maps (3, planes, oh, ow).  v itself, and with it
+// part[], is computed by the same instructions either way.
+template <bool MAPS>
+__device__ __forceinline__ void ssim_tile(const float* __restrict__ a, const float* __restrict__ b, int H, int W,
+                                          int taps, const SsimWindow& win, double c1, double c2, int tiles_x,
+                                          int tiles_y, double* __restrict__ part, double* __restrict__ maps,
+                                          int64_t planes) {
     __shared__ float sa[SSIM_MAX_HALO * SSIM_MAX_HALO];
     __shared__ float sb[SSIM_MAX_HALO * SSIM_MAX_HALO];
     __shared__ double hm[5][SSIM_MAX_HALO * SSIM_TILE];
@@ -190,10 +197,101 @@ __global__ __launch_bounds__(256) void ssim_tile_kernel(const float* __restrict_
     const double vx = xx - mx * mx, vy = yy - my * my, cov = xy - mx * my;
     const double v = ((2.0 * mx * my + c1) * (2.0 * cov + c2)) / ((mx * mx + my * my + c1) * (vx + vy + c2));
     const bool valid = ty0 + oy < H - taps + 1 && tx0 + ox < W - taps + 1;
+    if (MAPS && valid) {
+        const int oh = H - taps + 1, ow = W - taps + 1;
+        const double a1 = 2.0 * mx * my + c1, a2 = 2.0 * cov + c2;
+        const double b1 = mx * mx + my * my + c1, b2 = vx + vy + c2;
+        const double rb = 1.0 / (b1 * b2);
+        const int64_t map = (int64_t)oh * ow;
+        double* m = maps + plane * map + (int64_t)(ty0 + oy) * ow + (tx0 + ox);
+        m[0] = 2.0 * my * (a2 - a1) * rb - 2.0 * mx * v * (1.0 / b1 - 1.0 / b2);
+        m[planes * map] = -v / b2;
+        m[2 * planes * map] = 2.0 * a1 * rb;
+    }
     double s = recon_wave_sum(valid ? v : 0.0);
     if (lane == 0) red[wave] = s;
     __syncthreads();
     if (tid == 0) part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+__global__ __launch_bounds__(256) void ssim_tile_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                        int C, int H, int W, int taps, SsimWindow win, double c1,
+                                                        double c2, int tiles_x, int tiles_y,
+                                                        double* __restrict__ part) {
+    ssim_tile<false>(a, b, H, W, taps, win, c1, c2, tiles_x, tiles_y, part, nullptr, 0);
+}
+
+__global__ __launch_bounds__(256) void ssim_tile_maps_kernel(const float* __restrict__ a,
+                                                             const float* __restrict__ b, int H, int W, int taps,
+                                                             SsimWindow win, double c1, double c2, int tiles_x,
+                                                             int tiles_y, double* __restrict__ part,
+                                                             double* __restrict__ maps, int64_t planes) {
+    ssim_tile<true>(a, b, H, W, taps, win, c1, c2, tiles_x, tiles_y, part, maps, planes);
+}
+
+// Workgroup (plane, tile): the 16 x 16 INPUT pixels at (ty 16, tx 16) of plane n C + c.  A pixel q belongs to the
+// windows of the positions q - (i,j), 0 <= i, j < taps, with weight w_i w_j, so
+//   da(q) = g[n] / count * sum_ij w_i w_j [P + 2 a(q) Q + b(q) R](q - (i,j))
+// over the valid positions: three correlations of the maps with the window, combined with the thread's own
+// pixels.  The halo of (16 + taps - 1)^2 entries of each map starts taps - 1 before the tile and is zero past
+// the valid region; a horizontal pass into LDS, a vertical pass with one pixel per thread, all fp64 fma.  Every
+// pixel of da is written by exactly one thread.
+__global__ __launch_bounds__(256) void ssim_bwd_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                       const double* __restrict__ maps,
+                                                       const double* __restrict__ g, int C, int H, int W, int taps,
+                                                       SsimWindow win, double count, int tiles_x, int tiles_y,
+                                                       int64_t planes, float* __restrict__ da) {
+    __shared__ double sm[3][SSIM_MAX_HALO * SSIM_MAX_HALO];
+    __shared__ double hm[3][SSIM_MAX_HALO * SSIM_TILE];
+    const int tid = threadIdx.x;
+    const int tiles = tiles_x * tiles_y;
+    const int64_t plane = (int64_t)blockIdx.x / tiles;            // n C + c
+    const int tile = (int)((int64_t)blockIdx.x - plane * tiles);
+    const int ty0 = (tile / tiles_x) * SSIM_TILE, tx0 = (tile % tiles_x) * SSIM_TILE;
+    const int halo = SSIM_TILE + taps - 1;
+    const int oh = H - taps + 1, ow = W - taps + 1;
+    const int64_t map = (int64_t)oh * ow;
+    const double* pm = maps + plane * map;
+    for (int i = tid; i < halo * halo; i += 256) {
+        const int r = i / halo, q = i - r * halo;
+        const int y = ty0 - (taps - 1) + r, x = tx0 - (taps - 1) + q;
+        const bool in = y >= 0 && y < oh && x >= 0 && x < ow;
+        const int64_t at = (int64_t)y * ow + x;
+        sm[0][i] = in ? pm[at] : 0.0;
+        sm[1][i] = in ? pm[planes * map + at] : 0.0;
+        sm[2][i] = in ? pm[2 * planes * map + at] : 0.0;
+    }
+    __syncthreads();
+    for (int i = tid; i < halo * SSIM_TILE; i += 256) {
+        const int r = i >> 4, ox = i & 15;
+        const int at = r * halo + ox + taps - 1;                  // position q.x - j is halo column ox + taps - 1 - j
+        double p = 0.0, q = 0.0, rr = 0.0;
+        for (int k = 0; k < taps; ++k) {
+            const double w = win.w[k];
+            p = fma(w, sm[0][at - k], p);
+            q = fma(w, sm[1][at - k], q);
+            rr = fma(w, sm[2][at - k], rr);
+        }
+        hm[0][i] = p;
+        hm[1][i] = q;
+        hm[2][i] = rr;
+    }
+    __syncthreads();
+    const int oy = tid >> 4, ox = tid & 15;
+    double p = 0.0, q = 0.0, rr = 0.0;
+    for (int k = 0; k < taps; ++k) {
+        const double w = win.w[k];
+        const int at = (oy + taps - 1 - k) * SSIM_TILE + ox;
+        p = fma(w, hm[0][at], p);
+        q = fma(w, hm[1][at], q);
+        rr = fma(w, hm[2][at], rr);
+    }
+    const int y = ty0 + oy, x = tx0 + ox;
+    if (y < H && x < W) {
+        const int64_t at = plane * H * W + (int64_t)y * W + x;
+        const double d = fma((double)b[at], rr, fma(2.0 * (double)a[at], q, p));
+        da[at] = (float)(d * (g[plane / C] / count));
+    }
 }
 
 // One wave per image: lane l adds partials l, l + 64, ... of the image's C x tiles in ascending (channel,
@@ -298,5 +396,82 @@ extern "C" int qarig_ssim(const float* a, const float* b, int N, int C, int H, i
     hipLaunchKernelGGL(ssim_finish_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, (hipStream_t)stream, part, N,
                        per_image, count, out);
     QARIG_CHECK_LAUNCH("ssim (finish)");
+    return QARIG_OK;
+}
+
+// the backward runs one workgroup per (image, channel, 16 x 16 tile of INPUT pixels): at least as many as the
+// forward, so this bound covers both launches of the pair
+static inline bool ssim_bwd_grid_ok(int N, int C, int H, int W) {
+    return (int64_t)N * C * (((int64_t)H + SSIM_TILE - 1) / SSIM_TILE) * (((int64_t)W + SSIM_TILE - 1) / SSIM_TILE) <
+           (1LL << 31);
+}
+
+extern "C" size_t qarig_ssim_maps_bytes(int N, int C, int H, int W, int taps) {
+    int64_t tx, ty;
+    if (!ssim_geometry(N, C, H, W, taps, &tx, &ty) || !ssim_bwd_grid_ok(N, C, H, W)) return 0;
+    return (size_t)3 * (size_t)N * (size_t)C * (size_t)(H - taps + 1) * (size_t)(W - taps + 1) * sizeof(double);
+}
+
+// the argument checks qarig_ssim_fwd_maps and qarig_ssim_bwd share (those of qarig_ssim, with the backward's grid)
+#define SSIM_CHECK_SHAPE(what)                                                                                        \
+    QARIG_CHECK_DIMS(what, N, C, H, W);                                                                               \
+    QARIG_CHECK_ARG(taps >= 1 && taps <= SSIM_MAX_TAPS && (taps & 1), what ": taps must be odd, 1 <= taps <= 15, got %d", \
+                    taps);                                                                                            \
+    QARIG_CHECK_ARG(H >= taps && W >= taps, what ": image of %d x %d is smaller than the window of %d taps", H, W, taps); \
+    QARIG_CHECK_ARG(ssim_bwd_grid_ok(N, C, H, W), what ": N C ceil(H/16) ceil(W/16) must be below 2^31")
+
+// qarig_ssim that also writes maps (3,N,C,oh,ow) fp64 = {dv/dmx, dv/dxx, dv/dxy} of every valid position's score
+// v (the moments of a); out is bit-identical to qarig_ssim's.  ws as for qarig_ssim.
+extern "C" int qarig_ssim_fwd_maps(const float* a, const float* b, int N, int C, int H, int W, const double* win,
+                                   int taps, double c1, double c2, double* out, double* maps, void* ws,
+                                   size_t ws_bytes, void* stream) {
+    QARIG_CHECK_ARG(a && b && win && out && maps && ws, "ssim_fwd_maps: null pointer");
+    SSIM_CHECK_SHAPE("ssim_fwd_maps");
+    int64_t tx = 0, ty = 0;
+    ssim_geometry(N, C, H, W, taps, &tx, &ty);
+    const int64_t per_image = (int64_t)C * tx * ty;
+    QARIG_CHECK_ARG(((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 3) == 0 &&
+                        ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(ws) |
+                          reinterpret_cast<uintptr_t>(win) | reinterpret_cast<uintptr_t>(maps)) & 7) == 0,
+                    "ssim_fwd_maps: a and b must be 4-byte aligned, win, out, maps and ws 8-byte aligned");
+    QARIG_CHECK_ARG((const void*)maps != (const void*)a && (const void*)maps != (const void*)b &&
+                        (const void*)maps != (const void*)out && (const void*)maps != ws,
+                    "ssim_fwd_maps: maps must not alias a, b, out or ws");
+    const size_t need = (size_t)N * (size_t)per_image * sizeof(double);
+    QARIG_CHECK_ARG(ws_bytes >= need, "ssim_fwd_maps: workspace of %zu bytes, %zu needed", ws_bytes, need);
+    SsimWindow wv;
+    for (int k = 0; k < SSIM_MAX_TAPS; ++k) wv.w[k] = k < taps ? win[k] : 0.0;
+    double* part = static_cast<double*>(ws);
+    hipLaunchKernelGGL(ssim_tile_maps_kernel, dim3((unsigned)(per_image * N)), dim3(256), 0, (hipStream_t)stream, a, b,
+                       H, W, taps, wv, c1, c2, (int)tx, (int)ty, part, maps, (int64_t)N * C);
+    QARIG_CHECK_LAUNCH("ssim_fwd_maps");
+    const double count = (double)C * (double)(H - taps + 1) * (double)(W - taps + 1);
+    hipLaunchKernelGGL(ssim_finish_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, (hipStream_t)stream, part, N,
+                       per_image, count, out);
+    QARIG_CHECK_LAUNCH("ssim_fwd_maps (finish)");
+    return QARIG_OK;
+}
+
+// da (N,C,H,W) fp32, written in full: the gradient of sum_n g[n] out[n] with respect to a, from the maps of
+// qarig_ssim_fwd_maps on the same a, b, win and taps.  g (N) fp64 on the device; win a HOST array as above.
+// One launch, no atomics; image n's gradient depends on image n and g[n] alone.
+extern "C" int qarig_ssim_bwd(const float* a, const float* b, const double* maps, const double* g, int N, int C, int H,
+                              int W, const double* win, int taps, float* da, void* stream) {
+    QARIG_CHECK_ARG(a && b && maps && g && win && da, "ssim_bwd: null pointer");
+    SSIM_CHECK_SHAPE("ssim_bwd");
+    QARIG_CHECK_ARG(((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(da)) &
+                     3) == 0 &&
+                        ((reinterpret_cast<uintptr_t>(maps) | reinterpret_cast<uintptr_t>(g) |
+                          reinterpret_cast<uintptr_t>(win)) & 7) == 0,
+                    "ssim_bwd: a, b and da must be 4-byte aligned, maps, g and win 8-byte aligned");
+    QARIG_CHECK_ARG(da != a && da != b && (const void*)da != (const void*)maps && (const void*)da != (const void*)g,
+                    "ssim_bwd: da must not alias a, b, maps or g");
+    SsimWindow wv;
+    for (int k = 0; k < SSIM_MAX_TAPS; ++k) wv.w[k] = k < taps ? win[k] : 0.0;
+    const int tx = (W + SSIM_TILE - 1) / SSIM_TILE, ty = (H + SSIM_TILE - 1) / SSIM_TILE;
+    const double count = (double)C * (double)(H - taps + 1) * (double)(W - taps + 1);
+    hipLaunchKernelGGL(ssim_bwd_kernel, dim3((unsigned)((int64_t)N * C * tx * ty)), dim3(256), 0, (hipStream_t)stream, a, b,
+                       maps, g, C, H, W, taps, wv, count, tx, ty, (int64_t)N * C, da);
+    QARIG_CHECK_LAUNCH("ssim_bwd");
     return QARIG_OK;
 }

@@ -116,6 +116,9 @@ SIGNATURES = {
     "qarig_pair_error": (I, [P, P, I, L, P, P, Z, P]),
     "qarig_ssim_workspace_bytes": (Z, [I, I, I, I, I]),
     "qarig_ssim": (I, [P, P, I, I, I, I, P, I, D, D, P, P, Z, P]),
+    "qarig_ssim_maps_bytes": (Z, [I, I, I, I, I]),
+    "qarig_ssim_fwd_maps": (I, [P, P, I, I, I, I, P, I, D, D, P, P, P, Z, P]),
+    "qarig_ssim_bwd": (I, [P, P, P, P, I, I, I, I, P, I, P, P]),
     "qarig_mse_workspace_bytes": (Z, []),
     "qarig_mse_fwd": (I, [P, P, L, P, P, P, P]),
     "qarig_adam_step": (I, [P, P, P, P, L, F, F, F, F, F, F, P, P, P]),

@@ -755,6 +755,40 @@ def mse_loss(pred, target):
     return _MSELoss.apply(pred, target)
 
 
+class _SSIMIndex(torch.autograd.Function):
+    """ops.ssim(pred, target) per image with gradient to pred (the target is data): the forward keeps the maps of
+    ops.ssim_fwd_maps, the backward hands the incoming (N,) fp64 gradient to ops.ssim_bwd on the device."""
+
+    @staticmethod
+    def forward(ctx, pred, target, kw):
+        require_cuda(pred, target)
+        pred, target = f32c(pred), f32c(target.detach())
+        out, maps = ops.ssim_fwd_maps(pred, target, **kw)
+        ctx.save_for_backward(pred, target, maps)
+        ctx.kw = kw
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        pred, target, maps = ctx.saved_tensors
+        return ops.ssim_bwd(pred, target, maps, dout.double(), **ctx.kw), None, None
+
+
+def ssim_index(pred, target, data_range=2.0, sigma=1.5, taps=11, k1=0.01, k2=0.03, window=None):
+    """(N,) fp64 mean structural similarity of each image of pred with target (ops.ssim's arguments),
+    differentiable with respect to pred."""
+    kw = dict(data_range=data_range, sigma=sigma, taps=taps, k1=k1, k2=k2,
+              window=None if window is None else [float(v) for v in window])
+    if _no_grad() or not pred.requires_grad:
+        return ops.ssim(pred, target.detach(), **kw)
+    return _SSIMIndex.apply(pred, target, kw)
+
+
+def ssim_loss(pred, target, data_range=2.0, sigma=1.5, taps=11, k1=0.01, k2=0.03, window=None):
+    """1 - mean SSIM over the batch, fp32 scalar: the structural term beside mse_loss."""
+    return (1.0 - ssim_index(pred, target, data_range, sigma, taps, k1, k2, window).mean()).float()
+
+
 # ---------------------------------------------------------------- position-table conditioning
 # `cond` is a function of the token's integer position alone, so the conditioning MLP and
 # every ScaleLayer/ShiftLayer projection are evaluated once per distinct position (a (P,D)

@@ -1456,25 +1456,65 @@ def gaussian_window(taps, sigma):
     return [v / s for v in w]
 
 
+def _ssim_args(what, a, b, data_range, sigma, taps, k1, k2, window):
+    """The arguments the SSIM entries share: (a, b) fp32 contiguous, the window as a ctypes array of doubles (kept
+    alive by the caller until the call returns), taps, c1, c2."""
+    require_cuda(a, b)
+    if a.shape != b.shape or a.dim() != 4:
+        raise ValueError(f"{what}: need two (N,C,H,W) batches, got {tuple(a.shape)} and {tuple(b.shape)}")
+    w = [float(v) for v in window] if window is not None else gaussian_window(int(taps), float(sigma))
+    taps = len(w)
+    win = (ctypes.c_double * max(taps, 1))(*w)
+    return f32c(a), f32c(b), win, taps, (k1 * data_range) ** 2, (k2 * data_range) ** 2
+
+
 def ssim(a, b, data_range=2.0, sigma=1.5, taps=11, k1=0.01, k2=0.03, window=None):
     """(N,) fp64 mean structural similarity of two (N,C,H,W) fp32 batches, per channel over the valid positions
     of a separable window: Gaussian (sigma, taps) unless `window` gives the 1-D weights themselves.  Window
     moments in fp64; c1 = (k1 data_range)^2, c2 = (k2 data_range)^2."""
-    require_cuda(a, b)
-    if a.shape != b.shape or a.dim() != 4:
-        raise ValueError(f"ssim: need two (N,C,H,W) batches, got {tuple(a.shape)} and {tuple(b.shape)}")
-    a, b = f32c(a), f32c(b)
+    a, b, win, taps, c1, c2 = _ssim_args("ssim", a, b, data_range, sigma, taps, k1, k2, window)
     N, C, H, W = a.shape
-    w = [float(v) for v in window] if window is not None else gaussian_window(int(taps), float(sigma))
-    taps = len(w)
-    win = (ctypes.c_double * max(taps, 1))(*w)
-    c1, c2 = (k1 * data_range) ** 2, (k2 * data_range) ** 2
     lib = _lib.load()
     out = torch.empty(N, dtype=torch.float64, device=a.device)
     ws = _lib.workspace(lib.qarig_ssim_workspace_bytes(N, C, H, W, taps), a.device, tag="recon")
     check(lib.qarig_ssim(ptr(a), ptr(b), N, C, H, W, ctypes.cast(win, ctypes.c_void_p), taps, c1, c2, ptr(out),
                          ptr(ws), ws.numel(), stream()), "qarig_ssim")
     return out
+
+
+def ssim_fwd_maps(a, b, data_range=2.0, sigma=1.5, taps=11, k1=0.01, k2=0.03, window=None):
+    """(out, maps): ops.ssim(a, b, ...) bit for bit, and maps (3,N,C,oh,ow) fp64, the derivatives of every valid
+    position's score with respect to the window moments sum w a, sum w a^2 and sum w a b -- what ssim_bwd needs."""
+    a, b, win, taps, c1, c2 = _ssim_args("ssim_fwd_maps", a, b, data_range, sigma, taps, k1, k2, window)
+    N, C, H, W = a.shape
+    lib = _lib.load()
+    out = torch.empty(N, dtype=torch.float64, device=a.device)
+    # (0 bytes for arguments the entry refuses: it is called all the same, and names what is wrong)
+    maps = torch.empty(lib.qarig_ssim_maps_bytes(N, C, H, W, taps) // 8, dtype=torch.float64, device=a.device)
+    ws = _lib.workspace(lib.qarig_ssim_workspace_bytes(N, C, H, W, taps), a.device, tag="recon")
+    check(lib.qarig_ssim_fwd_maps(ptr(a), ptr(b), N, C, H, W, ctypes.cast(win, ctypes.c_void_p), taps, c1, c2,
+                                  ptr(out), ptr(maps), ptr(ws), ws.numel(), stream()), "qarig_ssim_fwd_maps")
+    return out, maps.view(3, N, C, H - taps + 1, W - taps + 1)
+
+
+def ssim_bwd(a, b, maps, g, data_range=2.0, sigma=1.5, taps=11, k1=0.01, k2=0.03, window=None):
+    """da (N,C,H,W) fp32: the gradient of sum_n g[n] ssim(a, b)[n] with respect to a, from the maps of
+    ssim_fwd_maps on the same arguments; g (N,) fp64 on the device.  Deterministic, image by image."""
+    a, b, win, taps, _, _ = _ssim_args("ssim_bwd", a, b, data_range, sigma, taps, k1, k2, window)
+    require_cuda(maps, g)
+    N, C, H, W = a.shape
+    lib = _lib.load()
+    if maps.dtype != torch.float64 or not maps.is_contiguous() or maps.numel() * 8 != lib.qarig_ssim_maps_bytes(
+            N, C, H, W, taps) or maps.numel() == 0:
+        raise ValueError(f"ssim_bwd: maps of {tuple(maps.shape)} {maps.dtype} do not belong to images of "
+                         f"{tuple(a.shape)} and a window of {taps} taps")
+    if g.dtype != torch.float64 or g.numel() != N:
+        raise ValueError(f"ssim_bwd: g must hold {N} fp64 weights, got {tuple(g.shape)} {g.dtype}")
+    g = g.contiguous()
+    da = torch.empty_like(a)
+    check(lib.qarig_ssim_bwd(ptr(a), ptr(b), ptr(maps), ptr(g), N, C, H, W, ctypes.cast(win, ctypes.c_void_p), taps,
+                             ptr(da), stream()), "qarig_ssim_bwd")
+    return da
 
 
 def adam_step(p, g, m, v, beta1, beta2, eps, step_size, bc2_sqrt, grad_scale=1.0, dev_step=None, shadow=None):

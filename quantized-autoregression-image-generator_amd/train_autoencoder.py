@@ -3,7 +3,10 @@
 checkpoint dict and log lines as the reference's train_autoencoder.py."""
 import argparse
 import logging
+import math
 import pathlib
+
+import torch
 
 from models.Autoencoder import Autoencoder
 from qarig import cli_common as cc
@@ -15,7 +18,14 @@ from utils.model_utils import load_model, save_model
 from dataset_loader.image_dataset import ImageDataset
 
 
-def parse_args():
+def _ssim_weight(text):
+    v = float(text)
+    if not math.isfinite(v) or v < 0.0:
+        raise argparse.ArgumentTypeError(f"--ssim-weight must be finite and >= 0, got {text}")
+    return v
+
+
+def parse_args(argv=None):
     p = argparse.ArgumentParser(description="Train Autoencoder models.")
     p.add_argument("--device", choices=["cpu", "cuda"], type=str, default="cpu")
     p.add_argument("--dataset-path", required=True, type=pathlib.Path)
@@ -28,7 +38,9 @@ def parse_args():
     p.add_argument("--config-path", required=True, type=pathlib.Path)
     p.add_argument("--out-dir", required=True, type=pathlib.Path)
     p.add_argument("--max-steps", type=int, default=None, help="(additive) stop after N steps.")
-    return vars(p.parse_args())
+    p.add_argument("--ssim-weight", type=_ssim_weight, default=0.0,
+                   help="(additive) lambda > 0: the loss is MSE + lambda (1 - mean SSIM); 0: MSE alone.")
+    return vars(p.parse_args(argv))
 
 
 def main():
@@ -72,21 +84,33 @@ def main():
     info(f"Model size: {sum(p.numel() for p in model.parameters()):,}")
     info("#" * 100)
 
+    ssim_weight = args["ssim_weight"]
     global_steps, done = 0, False
     for _ in range(0, args["max_epoch"]):
         total, iteration_count = 0.0, 0
+        total_mse, total_ssim = 0.0, 0.0       # (--ssim-weight only)
         for index, image in enumerate(loader):
             image = image.to(device)
             iteration_count += 1
             model.train()
             optim.zero_grad()
             recon = model(image)
-            loss = QF.mse_loss(recon, image)
+            if ssim_weight > 0:
+                mse = QF.mse_loss(recon, image)
+                ssim_term = QF.ssim_loss(recon, image)
+                loss = mse + ssim_weight * ssim_term
+            else:
+                loss = QF.mse_loss(recon, image)
             loss.backward()
             if world > 1:
                 parallel.allreduce_flat(optim.flat_grad)
             optim.step(grad_scale=1.0 / world)
-            lv = loss.item()
+            if ssim_weight > 0:      # one read-back for the three numbers
+                lv, mv, sv = torch.stack((loss.detach(), mse.detach(), ssim_term.detach())).tolist()
+                total_mse += mv
+                total_ssim += 1.0 - sv
+            else:
+                lv = loss.item()
             if lv != lv:
                 raise Exception("NaN encountered during training")
             total += lv
@@ -96,14 +120,20 @@ def main():
                 d = dict(hp)
                 d["model"] = {k: v.detach().clone() for k, v in model.state_dict().items()}
                 d["model_optimizer"] = optim.state_dict()
+                if ssim_weight > 0:
+                    d["ssim_weight"] = ssim_weight
                 ok = save_model(model_dict=d, dest_path=out_dir, file_name=f"model_{global_steps}.pt",
                                 logging=info)
                 info("Successfully saved model." if ok else "Error occured saving model.")
                 save_images(image, f"ground_truth_{global_steps}", out_dir, logging=info)
                 save_images(recon.detach(), f"recon_{global_steps}", out_dir, logging=info)
-            info("Cum. Steps: {:,} | Steps: {:,} / {:,} | L.R.: {:.8f} | Recon Loss: {:.5f}".format(
+            line = "Cum. Steps: {:,} | Steps: {:,} / {:,} | L.R.: {:.8f} | Recon Loss: {:.5f}".format(
                 global_steps + 1, index + 1, len(loader), optim.param_groups[0]["lr"],
-                total / iteration_count))
+                total / iteration_count)
+            if ssim_weight > 0:
+                line += " | MSE: {:.5f} | SSIM: {:.5f}".format(total_mse / iteration_count,
+                                                              total_ssim / iteration_count)
+            info(line)
             global_steps += 1
             if args["max_steps"] is not None and global_steps >= args["max_steps"]:
                 done = True
