@@ -599,6 +599,24 @@ int qarig_attention_decode(const float* q, const float* k_new, const float* v_ne
 int qarig_cross_entropy_fwd(const float* logits, const int64_t* target, int M, int C, float* loss,
                             float* dlogits, float* row_ws, int* bad_flag, void* stream);
 
+/* Cross-entropy with label smoothing and z-loss (additive; the reference trains with neither):
+ * F.cross_entropy(logits, target, label_smoothing = eps) + zeta mean_r(logsumexp(logits[r])^2), in one rows
+ * launch and one mean launch.  Per row, mx = max x, s = sum exp(x - mx), logs = log s, lse = mx + logs:
+ *   nll = logs - (x[t] - mx),  u = logs - (1 / C) sum_c (x[c] - mx),  obj = (1 - eps) nll + eps u + zeta lse^2,
+ *   d obj / d x[c] = exp((x[c] - mx) - logs) (1 + 2 zeta lse) - (1 - eps) [c == t] - eps / C.
+ * label_smoothing in [0, 1), z_loss finite and >= 0, anything else is refused.  loss: 2 floats = {mean obj, mean
+ * plain nll}.  dlogits (M,C) or NULL = d(mean obj)/d(logits); NULL leaves the losses bit for bit.  row_ws: 2 M
+ * floats, the row objectives then the row nlls.  A term whose coefficient is 0 is not evaluated: with both 0 every
+ * output carries the bits qarig_cross_entropy_fwd writes (both halves of row_ws its row losses), and
+ * label_smoothing = 0 never forms 0 * inf on rows with -inf entries.  With label_smoothing > 0 such a row's
+ * objective, and loss[0], are +inf as torch's are; its nll and its gradient stay finite, the -inf columns getting
+ * (-eps / C) / M.  A target outside [0,C) sets *bad_flag and its row adds 0 to both means.  A row's outputs depend
+ * on that row alone (no floating-point atomics, one fixed summation order, 4-byte loads at every alignment); a row
+ * holding NaN is undefined in that row alone. */
+int qarig_cross_entropy_reg_fwd(const float* logits, const int64_t* target, int M, int C, float label_smoothing,
+                                float z_loss, float* loss, float* dlogits, float* row_ws, int* bad_flag,
+                                void* stream);
+
 /* Held-out evaluation (additive; the reference has none), csrc/score.hip.
  * qarig_token_score: logits (M,C) fp32 contiguous, target int64 (M).  Per row, in the shifted form of the
  * cross-entropy kernel: row_nll = log sum_c exp(x[c] - max) - (x[t] - max) (nats) and

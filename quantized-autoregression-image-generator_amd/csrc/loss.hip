@@ -121,3 +121,141 @@ extern "C" int qarig_cross_entropy_fwd(const float* logits, const int64_t* targe
     QARIG_CHECK_LAUNCH("cross_entropy mean");
     return QARIG_OK;
 }
+
+// ---- cross-entropy with label smoothing and z-loss (additive; the reference trains with neither) ----------------
+// Per row, mx = max x, s = sum exp(x - mx), logs = log s, lse = mx + logs, p = exp((x - mx) - logs):
+//   nll = logs - (x[t] - mx),  u = logs - (1 / C) sum (x - mx)  (cross-entropy against the uniform distribution),
+//   obj = (1 - eps) nll + eps u + zeta lse^2,  d obj / d x[c] = p (1 + 2 zeta lse) - (1 - eps) [c == t] - eps / C.
+// u comes from the SHIFTED sum, accumulated in the sweep that forms s: sum x - C mx rounds at the magnitude of the
+// logits (0.03 at logits near 1000), the shifted sum at the magnitude of the loss.  Only lse^2 sees ulp(|mx|): it
+// is the quantity the z-loss penalises.  A term whose coefficient is 0 is not evaluated (EPS / ZL are compiled
+// out), so eps = 0 never forms 0 * inf on a row with -inf entries, and <false, false> is ce_rows_kernel's
+// arithmetic operation for operation: the same bits.  The sweeps are token_score_kernel's: four trips' loads in
+// flight, the sum in its own order (lane partial sums in ascending trips, then the butterfly).  4-byte loads only:
+// column c stays on lane c % 64 whatever the row's alignment (C = 513 rows are 4-byte aligned).
+namespace qarig {
+
+template <bool EPS, bool ZL>
+__global__ __launch_bounds__(256) void ce_reg_rows_kernel(const float* __restrict__ logits,
+                                                          const int64_t* __restrict__ target, int M, int C,
+                                                          float inv_m, float eps, float zeta,
+                                                          float* __restrict__ row_obj, float* __restrict__ row_nll,
+                                                          float* __restrict__ dlogits, int* __restrict__ bad) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    const float* x = logits + (int64_t)row * C;
+    const int64_t t = target[row];
+    const bool ok = t >= 0 && t < C;
+    const float xt = ok ? x[t] : 0.0f;
+    float mx = -INFINITY;
+    int c = lane;
+    for (; c + 192 < C; c += 256) {
+        const float v0 = x[c], v1 = x[c + 64], v2 = x[c + 128], v3 = x[c + 192];
+        mx = fmaxf(fmaxf(mx, v0), fmaxf(fmaxf(v1, v2), v3));
+    }
+    for (; c < C; c += 64) mx = fmaxf(mx, x[c]);
+    mx = wave_max(mx);
+    float s = 0.0f, sh = 0.0f;
+    c = lane;
+    for (; c + 192 < C; c += 256) {
+        const float v0 = x[c], v1 = x[c + 64], v2 = x[c + 128], v3 = x[c + 192];
+        const float d0 = v0 - mx, d1 = v1 - mx, d2 = v2 - mx, d3 = v3 - mx;
+        s += expf(d0);
+        s += expf(d1);
+        s += expf(d2);
+        s += expf(d3);
+        if (EPS) {
+            sh += d0;
+            sh += d1;
+            sh += d2;
+            sh += d3;
+        }
+    }
+    for (; c < C; c += 64) {
+        const float d = x[c] - mx;
+        s += expf(d);
+        if (EPS) sh += d;
+    }
+    s = wave_sum(s);
+    const float logs = logf(s);
+    const float nll = logs - (xt - mx);
+    float obj = nll, f = 1.0f;
+    if (EPS) {
+        sh = wave_sum(sh);
+        const float u = logs - sh / (float)C;        // +inf on a row with -inf entries, as torch gives
+        obj = fmaf(eps, u, (1.0f - eps) * nll);
+    }
+    if (ZL) {
+        const float lse = mx + logs, zl = zeta * lse;
+        obj = fmaf(zl, lse, obj);
+        f = fmaf(2.0f, zl, 1.0f);
+    }
+    if (lane == 0) {
+        if (!ok) atomicExch(bad, 1);
+        row_obj[row] = ok ? obj : 0.0f;
+        row_nll[row] = ok ? nll : 0.0f;
+    }
+    if (!dlogits) return;
+    float* d = dlogits + (int64_t)row * C;
+    const float hot = EPS ? 1.0f - eps : 1.0f, epsc = eps / (float)C;
+    auto grad = [&](float v, int col) {
+        const float p = expf((v - mx) - logs);
+        const float h = (int64_t)col == t ? hot : 0.0f;
+        float g = ZL ? fmaf(p, f, -h) : p - h;
+        if (EPS) g -= epsc;
+        return g * inv_m;
+    };
+    c = lane;
+    for (; c + 192 < C; c += 256) {
+        const float v0 = x[c], v1 = x[c + 64], v2 = x[c + 128], v3 = x[c + 192];
+        d[c] = grad(v0, c);
+        d[c + 64] = grad(v1, c + 64);
+        d[c + 128] = grad(v2, c + 128);
+        d[c + 192] = grad(v3, c + 192);
+    }
+    for (; c < C; c += 64) d[c] = grad(x[c], c);
+}
+
+// mean_kernel on both columns of row_ws in one launch: block b reduces v[b M ... b M + M) into out[b], each in
+// mean_kernel's order.
+__global__ __launch_bounds__(256) void mean2_kernel(const float* __restrict__ v, int M, float inv_m,
+                                                    float* __restrict__ out) {
+    __shared__ float red[256];
+    v += (int64_t)blockIdx.x * M;
+    float s = 0.0f;
+    for (int i = threadIdx.x; i < M; i += 256) s += v[i];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[blockIdx.x] = red[0] * inv_m;
+}
+
+}  // namespace qarig
+
+// F.cross_entropy(logits, target, label_smoothing = eps) + zeta mean(logsumexp(logits)^2) and its gradient.
+// loss: 2 floats {mean objective, mean plain nll}.  row_ws: 2 M floats, the row objectives then the row nlls.
+extern "C" int qarig_cross_entropy_reg_fwd(const float* logits, const int64_t* target, int M, int C,
+                                           float label_smoothing, float z_loss, float* loss, float* dlogits,
+                                           float* row_ws, int* bad_flag, void* stream) {
+    QARIG_CHECK_ARG(logits && target && loss && row_ws && bad_flag && M > 0 && C > 0,
+                    "cross_entropy_reg: bad arguments");
+    QARIG_CHECK_DIMS("cross_entropy_reg", M, C);
+    QARIG_CHECK_ARG(label_smoothing >= 0.0f && label_smoothing < 1.0f,
+                    "cross_entropy_reg: label_smoothing must lie in [0, 1)");
+    QARIG_CHECK_ARG(z_loss >= 0.0f && z_loss < INFINITY, "cross_entropy_reg: z_loss must be finite and >= 0");
+    hipStream_t st = (hipStream_t)stream;
+    const float inv_m = 1.0f / (float)M;
+    const bool e = label_smoothing > 0.0f, z = z_loss > 0.0f;
+    auto kernel = e ? (z ? ce_reg_rows_kernel<true, true> : ce_reg_rows_kernel<true, false>)
+                    : (z ? ce_reg_rows_kernel<false, true> : ce_reg_rows_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3((M + 3) / 4), dim3(256), 0, st, logits, target, M, C, inv_m, label_smoothing,
+                       z_loss, row_ws, row_ws + M, dlogits, bad_flag);
+    QARIG_CHECK_LAUNCH("cross_entropy_reg rows");
+    hipLaunchKernelGGL(mean2_kernel, dim3(2), dim3(256), 0, st, row_ws, M, inv_m, loss);
+    QARIG_CHECK_LAUNCH("cross_entropy_reg mean");
+    return QARIG_OK;
+}

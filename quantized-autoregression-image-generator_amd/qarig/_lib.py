@@ -110,6 +110,7 @@ SIGNATURES = {
     "qarig_window_append": (I, [P, P, P, I, L, P, P]),
     "qarig_attention_bwd": (I, [P, P, P, P, P, P, I, I, I, I, I, I, F, P, P, P, P, P]),
     "qarig_cross_entropy_fwd": (I, [P, P, I, I, P, P, P, P, P]),
+    "qarig_cross_entropy_reg_fwd": (I, [P, P, I, I, F, F, P, P, P, P, P]),
     "qarig_token_score": (I, [P, P, I, I, L, P, P, P, P]),
     "qarig_score_reduce": (I, [P, P, I, I, I, I, I, P, P, P, P, P]),
     "qarig_pair_error_workspace_bytes": (Z, [I, L]),

@@ -125,6 +125,44 @@ def validate(out_dir, entry, lines, info):
         f.write(json.dumps(entry) + "\n")
 
 
+def label_smoothing_arg(text):
+    """argparse type of --label-smoothing: a float in [0, 1)."""
+    import argparse
+    try:
+        v = float(text)
+    except ValueError:
+        v = float("nan")
+    if not 0.0 <= v < 1.0:
+        raise argparse.ArgumentTypeError(f"--label-smoothing must lie in [0, 1), got {text}")
+    return v
+
+
+def z_loss_arg(text):
+    """argparse type of --z-loss: a finite float >= 0."""
+    import argparse
+    try:
+        v = float(text)
+    except ValueError:
+        v = float("nan")
+    if not 0.0 <= v < float("inf"):
+        raise argparse.ArgumentTypeError(f"--z-loss must be finite and >= 0, got {text}")
+    return v
+
+
+def add_regulariser_args(p):
+    """--label-smoothing / --z-loss of a Transformer training command line (both additive, both 0 by default)."""
+    p.add_argument("--label-smoothing", type=label_smoothing_arg, default=0.0,
+                   help="(additive; the reference trains with plain cross-entropy) epsilon in [0, 1): train against "
+                        "torch.nn.CrossEntropyLoss(label_smoothing=epsilon); 0 = off.  Costs the step nothing: the "
+                        "term lives in the fused cross-entropy launch.  The step line then shows the objective as "
+                        "Recon Loss and the plain loss as NLL; validation and evaluate_transformer.py always report "
+                        "the plain nll, so their numbers stay comparable across regularisation settings")
+    p.add_argument("--z-loss", type=z_loss_arg, default=0.0,
+                   help="(additive) zeta >= 0: add zeta * mean(logsumexp(logits)^2) to the training loss (keeps the "
+                        "classifier's log-partition from drifting, e.g. 1e-4; 0 = off), inside the same fused launch.  "
+                        "Logged and evaluated as --label-smoothing describes")
+
+
 def check_prompt_args(prompt_fmaps, prompt_fraction):
     """generate_images.py --prompt-fmaps / --prompt-fraction: both or neither, the fraction inside (0, 1).
     Returns whether the run is prompted."""

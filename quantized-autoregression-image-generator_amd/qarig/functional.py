@@ -642,8 +642,49 @@ class _CrossEntropy(torch.autograd.Function):
         return ops.scale_by(dl, f32c(dloss).reshape(1)).reshape(ctx.shape), None
 
 
-def cross_entropy(logits, target):
-    return _CrossEntropy.apply(logits, target)
+class _CrossEntropyReg(torch.autograd.Function):
+    """mean CE with label smoothing and z-loss over rows (ops.cross_entropy_reg_fwd): the objective, and the
+    {objective, plain nll} pair as a second, non-differentiable output."""
+
+    @staticmethod
+    def forward(ctx, logits, target, label_smoothing, z_loss):
+        require_cuda(logits, target)
+        l2 = _2d(f32c(logits))
+        t = target.reshape(-1)
+        if t.dtype != torch.int64:
+            t = t.long()
+        pair, dl = ops.cross_entropy_reg_fwd(l2, t.contiguous(), label_smoothing, z_loss, want_grad=True)
+        ctx.save_for_backward(dl)
+        ctx.shape = logits.shape
+        ctx.mark_non_differentiable(pair)
+        ctx.set_materialize_grads(False)
+        return pair[0], pair
+
+    @staticmethod
+    def backward(ctx, dloss, _dpair):
+        (dl,) = ctx.saved_tensors
+        return ops.scale_by(dl, f32c(dloss).reshape(1)).reshape(ctx.shape), None, None, None
+
+
+def cross_entropy(logits, target, label_smoothing=0.0, z_loss=0.0):
+    """Mean cross-entropy over rows.  With label_smoothing = z_loss = 0 (the default) the plain node and launch.
+    Otherwise F.cross_entropy(..., label_smoothing=...) + z_loss * mean(logsumexp^2) from the fused launch; the
+    returned objective then carries `.pair`, the detached device tensor {objective, plain mean nll}, and `.nll`,
+    its second element (what validation and evaluate_transformer.py report), for logging."""
+    eps, zeta = ops.check_ce_regularisers(label_smoothing, z_loss)
+    if eps == 0.0 and zeta == 0.0:
+        return _CrossEntropy.apply(logits, target)
+    loss, pair = _CrossEntropyReg.apply(logits, target, eps, zeta)
+    loss.pair = pair
+    loss.nll = pair[1]
+    return loss
+
+
+def loss_pair(loss):
+    """{objective, plain mean nll} of a cross_entropy result as one detached (2,) device tensor, without a launch:
+    the regularised node's own pair, or the plain loss seen twice."""
+    pair = getattr(loss, "pair", None)
+    return loss.detach().expand(2) if pair is None else pair
 
 
 class _Activation(torch.autograd.Function):

@@ -1400,6 +1400,34 @@ def cross_entropy_fwd(logits2d, target, want_grad=True):
     return loss, dl
 
 
+def check_ce_regularisers(label_smoothing, z_loss):
+    """(label_smoothing, z_loss) as floats, or ValueError: what qarig_cross_entropy_reg_fwd accepts."""
+    eps, zeta = float(label_smoothing), float(z_loss)
+    if not 0.0 <= eps < 1.0:
+        raise ValueError(f"label_smoothing must lie in [0, 1), got {label_smoothing}")
+    if not (0.0 <= zeta < float("inf")):
+        raise ValueError(f"z_loss must be finite and >= 0, got {z_loss}")
+    return eps, zeta
+
+
+def cross_entropy_reg_fwd(logits2d, target, label_smoothing, z_loss, want_grad=True):
+    """F.cross_entropy(logits2d, target, label_smoothing=...) + z_loss * mean(logsumexp(logits2d)^2) in the fused
+    launch: (loss, dlogits), loss = {mean objective, mean plain nll} as one (2,) tensor, dlogits the gradient of
+    the objective (None unless want_grad).  With both numbers 0 the bits of cross_entropy_fwd."""
+    require_cuda(logits2d, target)
+    assert logits2d.dtype == torch.float32 and logits2d.dim() == 2 and logits2d.is_contiguous()
+    assert target.dtype == torch.int64 and target.is_contiguous() and target.numel() == logits2d.shape[0]
+    eps, zeta = check_ce_regularisers(label_smoothing, z_loss)
+    M, C = logits2d.shape
+    loss = torch.empty(2, dtype=torch.float32, device=logits2d.device)
+    dl = torch.empty_like(logits2d) if want_grad else None
+    rows = torch.empty(2 * M, dtype=torch.float32, device=logits2d.device)
+    check(_lib.load().qarig_cross_entropy_reg_fwd(ptr(logits2d), ptr(target), M, C, eps, zeta, ptr(loss), ptr(dl),
+                                                  ptr(rows), ptr(_bad_flag(logits2d.device)), stream()),
+          "qarig_cross_entropy_reg_fwd")
+    return loss, dl
+
+
 def token_score(logits2d, target, ignore_index=-100):
     """(row_nll fp32 (M,), row_rank int32 (M,)) of logits (M,C) against int64 targets: the negative
     log-likelihood in nats and the number of classes ranked before the target (0: arg-max, ties to the smaller

@@ -71,14 +71,22 @@ def eval_windows(seq_len, window):
     return out
 
 
-def train_step(model, optim, hr_input, lr_input, hr_target, pos_idx, dp=True, pos_bound=None):
+def loss_pair(loss):
+    """{objective, plain mean nll} of what train_step / GraphedTrainStep returned, as one (2,) device tensor: one
+    read-back gives both numbers.  Without regularisers the two are the same value; no launch either way."""
+    return QF.loss_pair(loss)
+
+
+def train_step(model, optim, hr_input, lr_input, hr_target, pos_idx, dp=True, pos_bound=None,
+               label_smoothing=0.0, z_loss=0.0):
     """forward + CE + backward + gradient all-reduce + Adam.  Returns the loss tensor
     (device scalar; callers decide when to .item()).  pos_bound: exclusive upper bound of
     pos_idx (the un-windowed sequence length) -- sizes the model's position table without
-    a device read-back."""
+    a device read-back.  label_smoothing, z_loss: the regularisers of QF.cross_entropy (0, 0: the
+    plain loss and launch); the returned objective then has the plain nll beside it, loss_pair()."""
     optim.zero_grad()
     logits = model(x_dec=hr_input, x_enc=lr_input, pos_cond=pos_idx, pos_bound=pos_bound)
-    loss = QF.cross_entropy(logits.view(-1, logits.shape[-1]), hr_target.flatten())
+    loss = QF.cross_entropy(logits.view(-1, logits.shape[-1]), hr_target.flatten(), label_smoothing, z_loss)
     loss.backward()
     w = parallel.world_size() if dp else 1
     if dp and not optim.finish_allreduce() and w > 1:   # overlapped buckets, else one exchange
@@ -207,7 +215,10 @@ class GraphedTrainStep:
     all-reduces issued between them, and Adam (which must wait for the last collective) is one eager
     launch behind them."""
 
-    def __init__(self, model, optim, lr_codebook, hr_codebook, train_base_model, window, warmup=2):
+    def __init__(self, model, optim, lr_codebook, hr_codebook, train_base_model, window, warmup=2,
+                 label_smoothing=0.0, z_loss=0.0):
+        from . import ops
+        self.label_smoothing, self.z_loss = ops.check_ce_regularisers(label_smoothing, z_loss)   # fixed at capture
         self.segmented = parallel.world_size() > 1 or optim._overlap
         self.model, self.optim = model, optim
         self.lr_cb, self.hr_cb = lr_codebook, hr_codebook
@@ -225,7 +236,8 @@ class GraphedTrainStep:
             (lr_seq if self.base else 1)
         self.optim.zero_grad()
         logits = self.model(x_dec=hr_in, x_enc=lr_in, pos_cond=pos, pos_bound=seq)
-        loss = QF.cross_entropy(logits.view(-1, logits.shape[-1]), hr_tg.flatten())
+        loss = QF.cross_entropy(logits.view(-1, logits.shape[-1]), hr_tg.flatten(), self.label_smoothing,
+                                self.z_loss)
         loss.backward()
         if self.segmented:
             if not captured:
@@ -234,7 +246,10 @@ class GraphedTrainStep:
             self.optim.step_captured()
         else:
             self.optim.step()
-        return loss.detach()
+        out = loss.detach()
+        if hasattr(loss, "pair"):      # {objective, nll}: under replay the graph's static output, as the loss is
+            out.pair = loss.pair
+        return out
 
     def _exchange_and_step(self):
         w = parallel.world_size()
@@ -244,7 +259,8 @@ class GraphedTrainStep:
 
     def __call__(self, z, rand):
         """z: latent batch on the device; rand: int64 window offsets (host or device).
-        Returns the loss (device scalar; a view of the graph's static output after capture)."""
+        Returns the loss (device scalar; a view of the graph's static output after capture); loss_pair() of it is
+        the {objective, plain nll} tensor, static likewise."""
         self.calls += 1
         if rand is None:                       # no sliding window: nothing to slice
             rand = torch.zeros(z.shape[0], dtype=torch.int64)

@@ -91,6 +91,7 @@ def parse_args():
                    help="(additive) steps between two evaluations of --val-dataset-path (default: --checkpoint-step).")
     p.add_argument("--val-batches", type=int, default=None,
                    help="(additive) score only the first batches of --val-dataset-path.")
+    cc.add_regulariser_args(p)
     return vars(p.parse_args())
 
 
@@ -158,6 +159,9 @@ def main():
         if resumed:
             optim.load_ema(saved["model_ema"], model, meta.get("count", 0))
     optim.enable_allreduce_overlap()     # no-op at world 1
+    # argparse has checked both; once more before anything is launched with them
+    label_smoothing, z_loss = ops.check_ce_regularisers(args["label_smoothing"], args["z_loss"])
+    regularised = label_smoothing > 0 or z_loss > 0
 
     dataset = FeatureMapDataset(dataset_path=args["dataset_path"], load_image=False,
                                 return_filepaths=False)
@@ -212,6 +216,9 @@ def main():
     info(f"Model Checkpoint step: {args['checkpoint_step']:,}")
     if ema_decay:
         info(f"EMA decay: {ema_decay}")
+    if regularised:
+        info(f"Label Smoothing: {label_smoothing}")
+        info(f"Z-Loss: {z_loss}")
     info("#" * 100)
     info("Sampling Parameters.")
     info(f"Temperature: {temperature:,}")
@@ -232,6 +239,10 @@ def main():
         if ema_decay:
             model_dict["model_ema"] = optim.ema_state_dict(model)
             model_dict["model_ema_meta"] = optim.ema_meta()
+        if label_smoothing > 0:     # informational: a resumed run takes its values from its own command line
+            model_dict["label_smoothing"] = label_smoothing
+        if z_loss > 0:
+            model_dict["z_loss"] = z_loss
         ok = save_model(model_dict=model_dict, dest_path=out_dir, file_name=f"model_{global_steps}.pt",
                         logging=info)
         info("Successfully saved model." if ok else "Error occured saving model.")
@@ -302,11 +313,12 @@ def main():
     graphed_seq = total_hr_Seq + ((img_H // lr_pH) * (img_W // lr_pW) if train_base_model else 1)
     if args["graph_step"]:
         graphed = pipeline.GraphedTrainStep(model, optim, lr_codebook, hr_codebook, train_base_model,
-                                            sliding_window if use_sliding_window else None)
+                                            sliding_window if use_sliding_window else None,
+                                            label_smoothing=label_smoothing, z_loss=z_loss)
     global_steps = 0
     done = False
     for epoch in range(0, args["max_epoch"]):
-        total_loss, iteration_count = 0.0, 0
+        total_loss, total_nll, iteration_count = 0.0, 0.0, 0      # total_nll: with a regulariser only
         for index, feature_map in enumerate(loader):
             iteration_count += 1
             feature_map = feature_map.to(device)
@@ -330,8 +342,13 @@ def main():
                     feature_map, lr_codebook, hr_codebook, train_base_model,
                     sliding_window if use_sliding_window else None, rand)
                 loss = pipeline.train_step(model, optim, hr_in, lr_in, hr_tg, pos_idx,
-                                           pos_bound=seq_total)
-            loss_val = loss.item()                                   # the reference's per-step sync
+                                           pos_bound=seq_total, label_smoothing=label_smoothing,
+                                           z_loss=z_loss)
+            if regularised:                                          # one read-back for the two numbers
+                loss_val, nll_val = pipeline.loss_pair(loss).tolist()
+                total_nll += nll_val
+            else:
+                loss_val = loss.item()                               # the reference's per-step sync
             ops.check_index_flag(device, "training batch")
             if loss_val != loss_val:
                 raise Exception("NaN encountered during training.")
@@ -344,7 +361,8 @@ def main():
                 validate(global_steps)
             info("Cum. Steps: {:,} | Steps: {:,} / {:,} | L.R.: {:.8f} | Recon Loss: {:.5f}".format(
                 global_steps + 1, index + 1, len(loader), optim.param_groups[0]["lr"],
-                total_loss / iteration_count))
+                total_loss / iteration_count) +
+                (" | NLL: {:.5f}".format(total_nll / iteration_count) if regularised else ""))
             global_steps += 1
             if args["max_steps"] is not None and global_steps >= args["max_steps"]:
                 done = True

@@ -27,3 +27,4 @@ step 200 $O/${TAG}_bmu_bench.log python tools/bmu_bench.py; tail -12 $O/${TAG}_b
 step 200 $O/${TAG}_c1_autoencoder.log python tools/c1_autoencoder.py; tail -2 $O/${TAG}_c1_autoencoder.log
 step 200 $O/${TAG}_recon_metrics.json python tools/recon_bench.py; tail -12 $O/${TAG}_recon_metrics.json
 step 200 $O/${TAG}_ssim_loss.json python tools/ssim_loss_bench.py; tail -12 $O/${TAG}_ssim_loss.json
+step 300 $O/${TAG}_ce_reg.json python tools/ce_reg_bench.py; tail -12 $O/${TAG}_ce_reg.json
