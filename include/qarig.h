@@ -713,6 +713,20 @@ int qarig_act_fwd(const float* x, float* y, int64_t n, int act, void* stream);
 int qarig_act_bwd(const float* dy, const float* z, float* dz, int64_t n, int act, void* stream);
 int qarig_scale_by(const float* x, const float* s, float* y, int64_t n, void* stream);
 
+/* Counter-based dropout (additive: the reference has none).  y[e] = x[e] * scale where element e is kept, +0.0
+ * where it is dropped (a dropped NaN or inf becomes 0), e the flat index into n contiguous fp32 elements.  The
+ * keep-bit is a pure function of (seed, rank, step, site, e): Philox4x32-10 (multipliers D2511F53 / CD9E8D57,
+ * Weyl constants 9E3779B9 / BB67AE85) with key (seed_lo, seed_hi) and counter (e >> 3, site, step, rank); of the
+ * call's four words element e reads word (e & 7) >> 1, its low 16 bits when e is even and its high 16 bits when
+ * odd, and is kept iff that value >= threshold.  The drop rate is threshold / 65536 and the caller passes
+ * scale = 65536 / (65536 - threshold) rounded to fp32 once.  key: DEVICE uint32[4] {seed_lo, seed_hi, step,
+ * rank}, read by the kernel (a replayed graph sees the step its host wrote last).  Backward is the same call
+ * on dy.  16-byte accesses where x and y are both 16-byte aligned, element by element otherwise and in the
+ * tail; the mask never depends on the path.  y may be x; any other overlap, null pointers, n outside
+ * [1, 2^34] and threshold outside [1, 58982] (p <= 0.9) are refused (-1) without a launch. */
+int qarig_dropout(const float* x, float* y, int64_t n, uint32_t threshold, float scale, uint32_t site,
+                  const uint32_t* key, void* stream);
+
 /* ---- Conv autoencoder ----------------------------------------------------------- */
 
 /* nn.Conv2d(k<=4, stride, padding) + bias + activation, NCHW -- ConvLayer /

@@ -9,7 +9,7 @@ from qarig import functional as QF
 from qarig import ops
 
 from ._loading import load_matching
-from .layers import LinearLayer, TransformerBlock, _mlp2_forward
+from .layers import LinearLayer, TransformerBlock, _mlp2_forward, dropout_active
 
 
 class Transformer(nn.Module):
@@ -57,9 +57,60 @@ class Transformer(nn.Module):
             LinearLayer(in_dim=transformer_hidden_dim, out_dim=transformer_out_dim,
                         use_activation=False))
         self._pe_cache = {}
+        self._dropout = None        # (p, key) while enable_dropout is in force
 
     def custom_load_state_dict(self, state_dict):
         load_matching(self, state_dict)
+
+    # -- dropout (additive: the reference has none) ------------------------------------------
+    def _residual_layers(self):
+        """Every ResidualLinearLayer in evaluation order, encoder first: the dropout sites behind the two
+        embedding sites."""
+        out = []
+        if self.use_encoder:
+            for layer in self.encoder_layers:
+                out += [layer.self_attn_block.self_attn_res, layer.feedforward_block.feedforward_res]
+        for blocks in self._decoder_blocks():
+            out += [res for _, _, _, res in blocks]
+        return out
+
+    def enable_dropout(self, p, seed, rank=0):
+        """Residual and embedding dropout with probability p (0 < p <= 0.9; 0 disables) in training steps
+        (train mode and gradients enabled; nowhere else).  Sites, each with a fixed ordinal that is part of
+        the mask's counter: 0 the encoder's embedding + position output, 1 the decoder's, then the sublayer
+        output entering every ResidualLinearLayer, encoder layers first, in evaluation order.  The mask is a
+        pure function of (seed, rank, step, site, element): the training step writes the step number into
+        the key (qarig.pipeline), so eager, checkpointed and replayed steps draw the same masks.  Served in
+        every precision mode: all sites are fp32 tensors in all of them (a site that were not would raise at
+        its launch; nothing is ever cast).  Returns the key (qarig.dropout.DropoutKey)."""
+        if p == 0:
+            self.disable_dropout()
+            return None
+        from qarig.dropout import DropoutKey, threshold_and_scale
+        threshold_and_scale(p)      # ValueError outside (0, 0.9]
+        device = self.dec_embedding.weight.device
+        if device.type != "cuda":
+            raise RuntimeError("Transformer.enable_dropout needs the model on the GPU (call model.to(device) first)")
+        key = DropoutKey(seed, rank, device)
+        self._dropout = (float(p), key)
+        for i, res in enumerate(self._residual_layers()):
+            res._dropout = (float(p), 2 + i, key)
+        return key
+
+    def disable_dropout(self):
+        self._dropout = None
+        for res in self._residual_layers():
+            res._dropout = None
+
+    @property
+    def dropout_key(self):
+        """The DropoutKey whose step word the training step sets, or None while dropout is off."""
+        return self._dropout[1] if self._dropout is not None else None
+
+    def _embedding_dropout(self, x, site):
+        if self._dropout is not None and dropout_active(self):
+            return QF.dropout(x, self._dropout[0], site, self._dropout[1])
+        return x
 
     def _sequence_pe(self, seq, dim, device):
         """sinusoid of positions 1..seq (reference Transformer.py:130-139,159-167);
@@ -77,6 +128,7 @@ class Transformer(nn.Module):
         table = self.enc_embedding.weight
         enc = QF.embedding_pos(x_enc, table, self._sequence_pe(x_enc.shape[1], table.shape[1],
                                                                table.device))
+        enc = self._embedding_dropout(enc, 0)
         for layer in self.encoder_layers:
             if self.use_activation_checkpoint and torch.is_grad_enabled():
                 enc = checkpoint.checkpoint(layer, enc, use_reentrant=False)
@@ -185,6 +237,7 @@ class Transformer(nn.Module):
         N, S = x_dec.shape
         D = table.shape[1]
         x = QF.embedding_pos(x_dec, table, self._sequence_pe(S, D, table.device))
+        x = self._embedding_dropout(x, 1)
         cond = None
         if self.use_pos_cond:
             cond = self._cond(pos_cond, N, S, D, pos_bound)

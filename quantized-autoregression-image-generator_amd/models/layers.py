@@ -8,6 +8,7 @@ nn.Parameters owned by torch; the nn.Linear / nn.Conv2d children exist to hold t
 CUDA(HIP) tensors only: a CPU tensor raises (no fallback; the CPU restatement is the
 test oracle under oracle/).
 """
+import torch
 import torch.nn as nn
 
 from qarig import functional as QF
@@ -36,6 +37,13 @@ def get_activation(activation_type):
 # reference models/layers.py:83-96
 def get_positional_embeddings(emb_dim, pos_index):
     return ops.posemb(pos_index, emb_dim)
+
+
+def dropout_active(module):
+    """Dropout (additive: the reference has none) runs in training steps alone: the module in train mode AND
+    gradients enabled.  model.eval() sampling, validation and generation under torch.no_grad(), and the
+    KV-cache decode paths therefore never launch it; a checkpoint's recomputation (gradients on) does."""
+    return module.training and torch.is_grad_enabled()
 
 
 def _lin_params(layer):
@@ -190,8 +198,11 @@ class ResidualLinearLayer(nn.Module):
             self.skip_linear = nn.Identity()
         self.activation = get_activation(activation_type=activation_type)
         self._act = act_id(activation_type)
+        self._dropout = None     # (p, site, key) while models.Transformer.enable_dropout is in force
 
     def forward(self, x, x_skip, cond=None):
+        if self._dropout is not None and dropout_active(self):
+            x = QF.dropout(x, *self._dropout)        # the sublayer output, before the conditioning scale
         if self.use_scale_layer:
             if isinstance(cond, QF.CondTable):
                 x = QF.mul_table(x, cond.projection(self.scale_layer.scale), cond)

@@ -19,6 +19,7 @@ L = c_int64
 Z = c_size_t
 F = c_float
 D = ctypes.c_double
+U = ctypes.c_uint32
 
 # name -> (restype, argtypes); must list every symbol include/qarig.h declares
 # (tests/test_abi.py cross-checks the two).
@@ -130,6 +131,7 @@ SIGNATURES = {
     "qarig_act_fwd": (I, [P, P, L, I, P]),
     "qarig_act_bwd": (I, [P, P, P, L, I, P]),
     "qarig_scale_by": (I, [P, P, P, L, P]),
+    "qarig_dropout": (I, [P, P, L, U, F, U, P, P]),
     "qarig_conv2d_fwd": (I, [P, I, I, I, I, P, P, I, I, I, I, I, P, P, P]),
     "qarig_conv2d_fwd_workspace_bytes": (Z, [I, I, I]),
     "qarig_conv2d_fwd_workspace_bytes_n": (Z, [I, I, I, I, I, I, I]),

@@ -163,6 +163,56 @@ def add_regulariser_args(p):
                         "Logged and evaluated as --label-smoothing describes")
 
 
+def dropout_arg(text):
+    """argparse type of --dropout: 0 (off) or a probability qarig.dropout.threshold_and_scale accepts."""
+    import argparse
+    from .dropout import threshold_and_scale
+    try:
+        v = float(text)
+        if v != 0.0:
+            threshold_and_scale(v)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--dropout must be 0 or lie in (0, 0.9], got {text}")
+    return v
+
+
+def dropout_seed_arg(text):
+    """argparse type of --dropout-seed: an unsigned 64-bit integer (decimal, or 0x... hexadecimal)."""
+    import argparse
+    try:
+        v = int(text, 0)
+    except ValueError:
+        v = -1
+    if not 0 <= v < 1 << 64:
+        raise argparse.ArgumentTypeError(f"--dropout-seed must be an integer in [0, 2^64), got {text}")
+    return v
+
+
+def add_dropout_args(p):
+    """--dropout / --dropout-seed of a Transformer training command line (both additive, both 0 by default)."""
+    p.add_argument("--dropout", type=dropout_arg, default=0.0,
+                   help="(additive; the reference has no dropout) drop probability P in (0, 0.9] of the residual and "
+                        "embedding dropout (0 = off, nothing is launched): applied to the two embedding outputs and "
+                        "to every sublayer output entering its residual layer, in training steps only (sampling, "
+                        "validation and generation never see it).  The mask is a counter-based function of "
+                        "(--dropout-seed, rank, optimizer step, site, element): no generator state, the same masks "
+                        "with --graph-step and --use-activation-checkpoint, and a run resumed with --load-optim "
+                        "continues the sequence")
+    p.add_argument("--dropout-seed", type=dropout_seed_arg, default=0,
+                   help="(additive) 64-bit seed of the --dropout masks (default 0).")
+
+
+def check_dropout_args(dropout, dropout_seed):
+    """(p, seed) once more before anything is launched with them (argparse has checked both), or ValueError."""
+    from .dropout import threshold_and_scale
+    p, seed = float(dropout), int(dropout_seed)
+    if p != 0.0:
+        threshold_and_scale(p)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"--dropout-seed must be an integer in [0, 2^64), got {dropout_seed}")
+    return p, seed
+
+
 def check_prompt_args(prompt_fmaps, prompt_fraction):
     """generate_images.py --prompt-fmaps / --prompt-fraction: both or neither, the fraction inside (0, 1).
     Returns whether the run is prompted."""

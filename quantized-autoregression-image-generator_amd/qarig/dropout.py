@@ -1,0 +1,61 @@
+"""Host side of the counter-based dropout (csrc/dropout.hip): the (threshold, scale) rule and the
+four-word device key {seed_lo, seed_hi, step, rank} every launch of a model reads.
+
+Nothing here draws a random number: the keep-bit of an element is a pure function of (seed, rank, step, site,
+element index), so the only per-step state is the step word, which the training step writes before its forward
+(pipeline.train_step / GraphedTrainStep) from the optimizer's step count."""
+import struct
+
+import torch
+
+MAX_THRESHOLD = 58982       # round(0.9 * 65536)
+
+
+def threshold_and_scale(p):
+    """(T, s) of drop probability p: T = round(p 65536), the true drop rate being T / 65536, and
+    s = 65536 / (65536 - T) evaluated in double and rounded to fp32 once (returned as the Python float of that
+    fp32 value).  ValueError unless 0 < T <= 58982 (p <= 0.9); NaN is refused."""
+    p = float(p)
+    if not 0.0 < p < 1.0:        # (NaN fails both comparisons)
+        raise ValueError(f"dropout probability must lie in (0, 0.9], got {p}")
+    t = int(round(p * 65536.0))
+    if not 0 < t <= MAX_THRESHOLD:
+        raise ValueError(f"dropout probability must lie in (0, 0.9] and be at least 1/131072, got {p}")
+    return t, struct.unpack("f", struct.pack("f", 65536.0 / (65536.0 - t)))[0]
+
+
+def _i32(word):
+    """A 32-bit word as the int32 value with the same bits."""
+    word &= 0xFFFFFFFF
+    return word - (1 << 32) if word >= 1 << 31 else word
+
+
+class DropoutKey:
+    """The device key of one model replica: int32[4] {seed_lo, seed_hi, step, rank} (the kernel reads the bits
+    as uint32).  set_step writes the step word through a pinned ring (pipeline.PinnedFeed): a non-blocking
+    copy on the current stream, the host never waits, and the launches behind it on that stream -- eager
+    or replayed from a graph -- read the new step."""
+
+    def __init__(self, seed, rank, device):
+        seed, rank = int(seed), int(rank)
+        if not 0 <= seed < 1 << 64:
+            raise ValueError(f"dropout seed must fit 64 bits unsigned, got {seed}")
+        if not 0 <= rank < 1 << 32:
+            raise ValueError(f"dropout rank must fit 32 bits unsigned, got {rank}")
+        self.seed, self.rank, self.step = seed, rank, 0
+        self._host = torch.tensor([_i32(seed), _i32(seed >> 32), 0, _i32(rank)], dtype=torch.int32)
+        self.buffer = self._host.to(device)
+        from .pipeline import PinnedFeed
+        self._feed = PinnedFeed(self.buffer)
+
+    def set_step(self, step):
+        step = int(step)
+        if not 0 <= step < 1 << 32:
+            raise ValueError(f"dropout step must fit 32 bits unsigned, got {step}")
+        self.step = step
+        self._host[2] = _i32(step)
+        self._feed.push(self._host)
+
+    @staticmethod
+    def threshold_and_scale(p):
+        return threshold_and_scale(p)

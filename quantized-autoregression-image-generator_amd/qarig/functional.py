@@ -451,6 +451,36 @@ def mul(a, b):
     return _Mul.apply(a, b)
 
 
+class _Dropout(torch.autograd.Function):
+    """Counter-based dropout: nothing is saved but the arguments -- backward regenerates the mask from
+    (key, site) and applies the same map to dy, and so does a checkpoint's recomputation of the forward."""
+
+    @staticmethod
+    def forward(ctx, x, threshold, scale, site, key):
+        ctx.args = (threshold, scale, site, key)
+        return ops.dropout(x, threshold, scale, site, key.buffer)
+
+    @staticmethod
+    def backward(ctx, dy):
+        threshold, scale, site, key = ctx.args
+        return ops.dropout(f32c(dy), threshold, scale, site, key.buffer), None, None, None, None
+
+
+def dropout(x, p, site, key):
+    """x with each element dropped with probability T / 65536, T = round(p 65536), and the kept ones scaled
+    by 65536 / (65536 - T); the mask is the function of (key, site, element index) that include/qarig.h
+    qarig_dropout defines (key: qarig.dropout.DropoutKey).  p == 0: x itself, no launch.  fp32 contiguous
+    CUDA tensors only: anything else raises, nothing is cast."""
+    if p == 0:
+        return x
+    from .dropout import threshold_and_scale
+    threshold, scale = threshold_and_scale(p)
+    require_cuda(x)
+    if _no_grad() or not x.requires_grad:
+        return ops.dropout(x, threshold, scale, site, key.buffer)
+    return _Dropout.apply(x, threshold, scale, site, key)
+
+
 def _with_skip(y, x, with_skip):
     """(y, alias of x) for a normalisation node that also hands x to the block's skip connection."""
     return (y, x.view_as(x)) if with_skip else y

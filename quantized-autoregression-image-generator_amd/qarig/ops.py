@@ -1608,6 +1608,37 @@ def scale_by(x, s):
     return y
 
 
+# Launch geometry of qarig_dropout (csrc/dropout_philox.h): 256 threads, eight elements per thread-iteration, at
+# most 8192 workgroups -- a launch of more than DROPOUT_SWEEP elements wraps the grid-stride loop.
+DROPOUT_MAX_THRESHOLD = 58982
+DROPOUT_SWEEP = 8192 * 256 * 8
+
+
+def dropout(x, threshold, scale, site, key, out=None):
+    """y = x * scale where kept, +0 where dropped; the keep-bit of flat element e is a pure function of
+    (key = device int32[4] {seed_lo, seed_hi, step, rank}, site, e) -- include/qarig.h qarig_dropout.
+    threshold: 1 ... 58982, drop rate threshold / 65536; scale: 65536 / (65536 - threshold) as fp32
+    (qarig.dropout.threshold_and_scale gives both).  out: None (a new tensor), x itself (in place) or a
+    contiguous fp32 tensor of x's size that does not overlap x."""
+    require_cuda(x, key, out)
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise TypeError(f"dropout: a contiguous fp32 tensor, got {x.dtype}"
+                        f"{'' if x.is_contiguous() else ' (not contiguous)'}; nothing is cast or copied here")
+    if key.dtype != torch.int32 or key.numel() != 4 or not key.is_contiguous():
+        raise TypeError("dropout: key is a contiguous int32 tensor of 4 words {seed_lo, seed_hi, step, rank}")
+    y = torch.empty_like(x) if out is None else out
+    if y.dtype != torch.float32 or not y.is_contiguous() or y.numel() != x.numel():
+        raise TypeError("dropout: out must be a contiguous fp32 tensor of x's size")
+    threshold, site = int(threshold), int(site)
+    if not 1 <= threshold <= DROPOUT_MAX_THRESHOLD:
+        raise ValueError(f"dropout: threshold must lie in [1, {DROPOUT_MAX_THRESHOLD}], got {threshold}")
+    if not 0 <= site < 2 ** 32:
+        raise ValueError(f"dropout: site must fit 32 bits, got {site}")
+    check(_lib.load().qarig_dropout(ptr(x), ptr(y), x.numel(), threshold, float(scale), site, ptr(key), stream()),
+          "qarig_dropout")
+    return y
+
+
 # -------------------------------------------------------------------------- conv
 def _conv_workspace(weight, nbytes, geom, tag, inference):
     """(scratch tensor, flags) of a conv forward.  Training (`inference` False -- the caller decides, outside

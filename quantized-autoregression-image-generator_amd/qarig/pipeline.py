@@ -77,6 +77,16 @@ def loss_pair(loss):
     return QF.loss_pair(loss)
 
 
+def set_dropout_step(model, optim):
+    """With dropout enabled on the model (models.Transformer.enable_dropout): the number of the optimizer step
+    this forward belongs to goes into the mask key's step word -- a non-blocking copy on the current stream,
+    ahead of the forward, eager or replayed.  The step number is the optimizer's, so a run resumed with its
+    optimizer state continues the mask sequence.  Without dropout: nothing."""
+    key = getattr(model, "dropout_key", None)
+    if key is not None:
+        key.set_step(optim.step_count + 1)
+
+
 def train_step(model, optim, hr_input, lr_input, hr_target, pos_idx, dp=True, pos_bound=None,
                label_smoothing=0.0, z_loss=0.0):
     """forward + CE + backward + gradient all-reduce + Adam.  Returns the loss tensor
@@ -84,6 +94,7 @@ def train_step(model, optim, hr_input, lr_input, hr_target, pos_idx, dp=True, po
     pos_idx (the un-windowed sequence length) -- sizes the model's position table without
     a device read-back.  label_smoothing, z_loss: the regularisers of QF.cross_entropy (0, 0: the
     plain loss and launch); the returned objective then has the plain nll beside it, loss_pair()."""
+    set_dropout_step(model, optim)
     optim.zero_grad()
     logits = model(x_dec=hr_input, x_enc=lr_input, pos_cond=pos_idx, pos_bound=pos_bound)
     loss = QF.cross_entropy(logits.view(-1, logits.shape[-1]), hr_target.flatten(), label_smoothing, z_loss)
@@ -264,9 +275,17 @@ class GraphedTrainStep:
         self.calls += 1
         if rand is None:                       # no sliding window: nothing to slice
             rand = torch.zeros(z.shape[0], dtype=torch.int64)
+        # dropout's step word: written here, outside the capture, for warm-up calls, the capturing call and every
+        # replay alike.  The key's device buffer and its pinned feed exist since enable_dropout, i.e. before the
+        # capture (for the reason _dev_step_buffer() is created below); the captured launches hold its address.
+        set_dropout_step(self.model, self.optim)
         if self.calls <= self.warmup:
             return self._body(z, rand.to(z.device), captured=False)
+        if self.graph is not None and getattr(self.model, "dropout_key", None) is not self._dropout_key:
+            raise RuntimeError("GraphedTrainStep: dropout was enabled, disabled or re-keyed after the step was "
+                               "captured; the graph holds the launches and the key of its capture")
         if self.graph is None:
+            self._dropout_key = getattr(self.model, "dropout_key", None)
             self._z = z.clone()
             self._rand = rand.to(z.device).clone()
             self.optim._dev_step_buffer()      # must exist BEFORE capture: created inside, its

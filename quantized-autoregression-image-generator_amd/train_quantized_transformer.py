@@ -92,6 +92,7 @@ def parse_args():
     p.add_argument("--val-batches", type=int, default=None,
                    help="(additive) score only the first batches of --val-dataset-path.")
     cc.add_regulariser_args(p)
+    cc.add_dropout_args(p)
     return vars(p.parse_args())
 
 
@@ -162,6 +163,10 @@ def main():
     # argparse has checked both; once more before anything is launched with them
     label_smoothing, z_loss = ops.check_ce_regularisers(args["label_smoothing"], args["z_loss"])
     regularised = label_smoothing > 0 or z_loss > 0
+    dropout, dropout_seed = cc.check_dropout_args(args["dropout"], args["dropout_seed"])
+    if dropout > 0:
+        # the step word of the mask key follows optim.step_count: with --load-optim the sequence continues
+        model.enable_dropout(dropout, dropout_seed, rank=parallel.rank())
 
     dataset = FeatureMapDataset(dataset_path=args["dataset_path"], load_image=False,
                                 return_filepaths=False)
@@ -219,6 +224,9 @@ def main():
     if regularised:
         info(f"Label Smoothing: {label_smoothing}")
         info(f"Z-Loss: {z_loss}")
+    if dropout > 0:
+        info(f"Dropout: {dropout}")
+        info(f"Dropout Seed: {dropout_seed}")
     info("#" * 100)
     info("Sampling Parameters.")
     info(f"Temperature: {temperature:,}")
@@ -243,6 +251,9 @@ def main():
             model_dict["label_smoothing"] = label_smoothing
         if z_loss > 0:
             model_dict["z_loss"] = z_loss
+        if dropout > 0:             # informational likewise
+            model_dict["dropout"] = dropout
+            model_dict["dropout_seed"] = dropout_seed
         ok = save_model(model_dict=model_dict, dest_path=out_dir, file_name=f"model_{global_steps}.pt",
                         logging=info)
         info("Successfully saved model." if ok else "Error occured saving model.")
