@@ -700,6 +700,31 @@ int qarig_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema
                         float beta2, float eps, float step_size, float bc2_sqrt, float ema_w,
                         float grad_scale, const float* dev_step, void* shadow_bf16, void* stream);
 
+/* AdamW: the same step behind a decoupled weight decay (additive: the reference trains without), as
+ * torch.optim.AdamW with a decayed and an undecayed group, from one launch.  Normative, per element i:
+ *   decay_mask[i >> 3] != 0:  pd = fmaf(-decay, p[i], p[i])    one rounding; decay = fp32(lr * lambda), the
+ *                             product taken in double on the host and rounded once.  (Not p * fp32(1 - lr lambda):
+ *                             below 1 fp32 steps by 2^-24, so at lr lambda = 1e-6 that factor is 1 - 17 x 2^-24, a
+ *                             decay 1.3 % off, and the error grows without bound as lr lambda falls to 2^-25.)
+ *   decay_mask[i >> 3] == 0:  pd = p[i], its bits untouched.
+ *   then qarig_adam_step's expressions with pd in the place of p[i]:
+ *     gi = g[i] * grad_scale;  w = 1 - beta1;  mn = w < 0.5 ? m + w (gi - m) : gi - (gi - m)(1 - w);
+ *     vn = v beta2 + (1 - beta2) gi gi;  denom = sqrtf(vn) / bc2_sqrt + eps;  pn = pd - step_size (mn / denom);
+ *     ema (when given) <- the two-branch lerp of ema towards pn by ema_w;  shadow_bf16 (when given) <- the
+ *     nearest-even bf16 of pn.
+ * decay_mask: ceil(n / 8) bytes on the device, one per group of 8 consecutive elements (FlatAdam's slices start
+ * on multiples of 8 floats, so a group never spans two parameters).  ema may be NULL.  dev_step (optional) is
+ * ALWAYS a device float[4] here, {step_size, bc2_sqrt, ema_w, decay}, and overrides the four host values (ema_w
+ * is ignored without ema).  One thread-iteration moves one group with 16-byte accesses; the last group of an n
+ * that is no multiple of 8 goes element by element and nothing at or behind n is written.  With a mask of zeros
+ * p, m, v, ema and shadow_bf16 come out bit-identical to qarig_adam_step / qarig_adam_ema_step.
+ * Refused (-1) without a launch: null p, g, m, v or decay_mask; n outside [1, 2^40]; p, g, m, v, ema or
+ * shadow_bf16 not 16-byte aligned; a host decay outside [0, 1) or NaN; ema or shadow_bf16 overlapping p. */
+int qarig_adamw_step(float* p, const float* g, float* m, float* v, float* ema, const unsigned char* decay_mask,
+                     int64_t n, float beta1, float beta2, float eps, float step_size, float bc2_sqrt,
+                     float ema_w, float decay, float grad_scale, const float* dev_step, void* shadow_bf16,
+                     void* stream);
+
 /* Exchanges two fp32 buffers of n elements in place, bit for bit (NaN payloads included): 16-byte accesses
  * where both buffers are 16-byte aligned, with a scalar tail; scalar throughout otherwise.  The buffers must
  * not overlap; null pointers, n <= 0 and overlapping ranges are refused (-1) without a launch. */

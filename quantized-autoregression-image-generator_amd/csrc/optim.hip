@@ -2,7 +2,8 @@
 // allocation; so do their gradients and moments): one launch per step, and the same
 // flat gradient buffer is what the DP all-reduce moves.  Semantics of
 // torch.optim.Adam(lr, betas) without weight decay / amsgrad
-// (train_quantized_transformer.py:317-320; train_autoencoder.py:133-136).
+// (train_quantized_transformer.py:317-320; train_autoencoder.py:133-136).  Additive: adamw_kernel, the same update
+// behind a decoupled weight decay of the groups a mask selects (torch.optim.AdamW with two parameter groups).
 #include "qarig_common.h"
 
 namespace qarig {
@@ -45,6 +46,108 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
             typedef float f32x2_t __attribute__((ext_vector_type(2)));
             const f32x2_t f = {pn, 0.0f};
             shadow[i] = (unsigned short)(__builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2_t)) & 0xffffu);
+        }
+    }
+}
+
+// AdamW: decoupled weight decay in front of the same update, on groups of 8 elements.  One element's arithmetic:
+// pd = fma(-decay, p, p) where the element is decayed (one rounding; decay = fp32(lr * lambda)), p's own bits
+// where it is not, then adam_kernel's expressions with pd in the place of p[i].  Returns the new parameter.
+template <bool EMA>
+__device__ __forceinline__ float adamw_element(float pi, float graw, float& mi, float& vi, float& ei, bool decayed,
+                                               float beta1, float beta2, float eps, float step_size,
+                                               float bc2_sqrt, float ema_w, float decay, float grad_scale) {
+    const float pd = decayed ? __builtin_fmaf(-decay, pi, pi) : pi;
+    const float gi = graw * grad_scale;
+    const float w = 1.0f - beta1;
+    const float mn = w < 0.5f ? mi + w * (gi - mi) : gi - (gi - mi) * (1.0f - w);
+    const float vn = vi * beta2 + (1.0f - beta2) * gi * gi;
+    const float denom = sqrtf(vn) / bc2_sqrt + eps;
+    const float pn = pd - step_size * (mn / denom);
+    mi = mn;
+    vi = vn;
+    if (EMA) ei = ema_w < 0.5f ? ei + ema_w * (pn - ei) : pn - (pn - ei) * (1.0f - ema_w);
+    return pn;
+}
+
+// two floats -> two nearest-even bf16 in one dword (low half: a), the conversion of adam_kernel's shadow
+__device__ __forceinline__ unsigned pack_bf16x2(float a, float b) {
+    typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+    typedef float f32x2_t __attribute__((ext_vector_type(2)));
+    const f32x2_t f = {a, b};
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2_t));
+}
+
+// One thread-iteration = one group of 8 elements = one mask byte: two 16-byte loads per input stream, all of them
+// ahead of the first store, two 16-byte stores per fp32 output stream and one for the 8 bf16 of the shadow.  The
+// last group of an n that is no multiple of 8 goes element by element and touches nothing at or behind n.
+// 7 (9 with the EMA) streams of 4 bytes per element as adam_kernel, plus n / 8 mask bytes.
+template <bool EMA>
+__global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                             float* __restrict__ v, float* __restrict__ ema,
+                             const unsigned char* __restrict__ mask, int64_t n, float beta1, float beta2,
+                             float eps, float step_size, float bc2_sqrt, float ema_w, float decay,
+                             float grad_scale, const float* __restrict__ dev_step,
+                             unsigned short* __restrict__ shadow) {
+    if (dev_step) {     // captured-graph replay: always four floats {step_size, bc2_sqrt, ema_w, decay}
+        step_size = dev_step[0];
+        bc2_sqrt = dev_step[1];
+        if (EMA) ema_w = dev_step[2];
+        decay = dev_step[3];
+    }
+    const int64_t full = n >> 3, groups = (n + 7) >> 3;
+    for (int64_t gr = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; gr < groups;
+         gr += (int64_t)gridDim.x * blockDim.x) {
+        const bool decayed = mask[gr] != 0;
+        const int64_t base = gr << 3;
+        if (gr < full) {
+            f32x4 pv[2], gv[2], mv[2], vv[2], ev[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                pv[h] = *(const f32x4*)(p + base + 4 * h);
+                gv[h] = *(const f32x4*)(g + base + 4 * h);
+                mv[h] = *(const f32x4*)(m + base + 4 * h);
+                vv[h] = *(const f32x4*)(v + base + 4 * h);
+                if (EMA) ev[h] = *(const f32x4*)(ema + base + 4 * h);
+            }
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    float mi = mv[h][k], vi = vv[h][k], ei = EMA ? ev[h][k] : 0.0f;
+                    pv[h][k] = adamw_element<EMA>(pv[h][k], gv[h][k], mi, vi, ei, decayed, beta1, beta2, eps,
+                                                  step_size, bc2_sqrt, ema_w, decay, grad_scale);
+                    mv[h][k] = mi;
+                    vv[h][k] = vi;
+                    if (EMA) ev[h][k] = ei;
+                }
+            }
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                *(f32x4*)(p + base + 4 * h) = pv[h];
+                *(f32x4*)(m + base + 4 * h) = mv[h];
+                *(f32x4*)(v + base + 4 * h) = vv[h];
+                if (EMA) *(f32x4*)(ema + base + 4 * h) = ev[h];
+            }
+            if (shadow) {
+                uint4 s;
+                s.x = pack_bf16x2(pv[0][0], pv[0][1]);
+                s.y = pack_bf16x2(pv[0][2], pv[0][3]);
+                s.z = pack_bf16x2(pv[1][0], pv[1][1]);
+                s.w = pack_bf16x2(pv[1][2], pv[1][3]);
+                *(uint4*)(shadow + base) = s;
+            }
+        } else {
+            for (int64_t i = base; i < n; ++i) {
+                float mi = m[i], vi = v[i], ei = EMA ? ema[i] : 0.0f;
+                const float pn = adamw_element<EMA>(p[i], g[i], mi, vi, ei, decayed, beta1, beta2, eps, step_size,
+                                                    bc2_sqrt, ema_w, decay, grad_scale);
+                p[i] = pn;
+                m[i] = mi;
+                v[i] = vi;
+                if (EMA) ema[i] = ei;
+                if (shadow) shadow[i] = (unsigned short)(pack_bf16x2(pn, 0.0f) & 0xffffu);
+            }
         }
     }
 }
@@ -106,6 +209,36 @@ extern "C" int qarig_adam_ema_step(float* p, const float* g, float* m, float* v,
                        beta1, beta2, eps, step_size, bc2_sqrt, ema_w, grad_scale, dev_step,
                        (unsigned short*)shadow_bf16);
     QARIG_CHECK_LAUNCH("adam_ema");
+    return QARIG_OK;
+}
+
+// AdamW (include/qarig.h has the normative arithmetic): decay_mask holds one byte per group of 8 elements,
+// ceil(n / 8) of them; ema may be NULL (the plain instantiation); dev_step, when given, is always four floats
+// {step_size, bc2_sqrt, ema_w, decay} and the host's values of the four are ignored.
+extern "C" int qarig_adamw_step(float* p, const float* g, float* m, float* v, float* ema,
+                                const unsigned char* decay_mask, int64_t n, float beta1, float beta2, float eps,
+                                float step_size, float bc2_sqrt, float ema_w, float decay, float grad_scale,
+                                const float* dev_step, void* shadow_bf16, void* stream) {
+    QARIG_CHECK_ARG(p && g && m && v && decay_mask && n > 0 && n <= (1LL << 40), "adamw: bad arguments");
+    const uintptr_t up = (uintptr_t)p, ue = (uintptr_t)ema, us = (uintptr_t)shadow_bf16;
+    QARIG_CHECK_ARG(up % 16 == 0 && (uintptr_t)g % 16 == 0 && (uintptr_t)m % 16 == 0 && (uintptr_t)v % 16 == 0 &&
+                        ue % 16 == 0 && us % 16 == 0,
+                    "adamw: p, g, m, v, ema and shadow_bf16 must be 16-byte aligned");
+    QARIG_CHECK_ARG(decay >= 0.0f && decay < 1.0f, "adamw: decay must lie in [0, 1)");      // (NaN fails both)
+    const uint64_t bytes = 4 * (uint64_t)n;
+    QARIG_CHECK_ARG(!ema || ue + bytes <= up || up + bytes <= ue, "adamw: ema overlaps p");
+    QARIG_CHECK_ARG(!shadow_bf16 || us + bytes / 2 <= up || up + bytes <= us, "adamw: shadow_bf16 overlaps p");
+    int64_t b = ((n + 7) / 8 + 255) / 256;
+    if (b > 8192) b = 8192;
+    if (ema)
+        hipLaunchKernelGGL(adamw_kernel<true>, dim3((int)b), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema,
+                           decay_mask, n, beta1, beta2, eps, step_size, bc2_sqrt, ema_w, decay, grad_scale,
+                           dev_step, (unsigned short*)shadow_bf16);
+    else
+        hipLaunchKernelGGL(adamw_kernel<false>, dim3((int)b), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+                           (float*)nullptr, decay_mask, n, beta1, beta2, eps, step_size, bc2_sqrt, 0.0f, decay,
+                           grad_scale, dev_step, (unsigned short*)shadow_bf16);
+    QARIG_CHECK_LAUNCH("adamw");
     return QARIG_OK;
 }
 

@@ -213,6 +213,100 @@ def check_dropout_args(dropout, dropout_seed):
     return p, seed
 
 
+def weight_decay_arg(text):
+    """argparse type of --weight-decay: 0 (off) or a float in (0, 1]."""
+    import argparse
+    try:
+        v = float(text)
+    except ValueError:
+        v = float("nan")
+    if not 0.0 <= v <= 1.0:
+        raise argparse.ArgumentTypeError(f"--weight-decay must lie in [0, 1], got {text}")
+    return v
+
+
+def lr_min_ratio_arg(text):
+    """argparse type of --lr-min-ratio: a float in [0, 1]."""
+    import argparse
+    try:
+        v = float(text)
+    except ValueError:
+        v = float("nan")
+    if not 0.0 <= v <= 1.0:
+        raise argparse.ArgumentTypeError(f"--lr-min-ratio must lie in [0, 1], got {text}")
+    return v
+
+
+def _steps_arg(flag, least):
+    def parse(text):
+        import argparse
+        try:
+            v = int(text)
+        except ValueError:
+            v = least - 1
+        if v < least:
+            raise argparse.ArgumentTypeError(f"{flag} must be an integer >= {least}, got {text}")
+        return v
+    return parse
+
+
+def add_optimizer_args(p):
+    """--weight-decay and the --lr-* schedule flags of a Transformer training command line (all additive; at their
+    defaults the loop is the reference's: plain Adam, the learning rate halved every --lr-step)."""
+    p.add_argument("--weight-decay", type=weight_decay_arg, default=0.0,
+                   help="(additive; the reference trains without) decoupled weight decay lambda in (0, 1], as "
+                        "torch.optim.AdamW (0 = off, the plain Adam launch): every step shrinks the decayed "
+                        "parameters by lr x lambda, at that step's learning rate, inside the optimiser's one launch.  "
+                        "Decayed: the `weight` of every nn.Linear module.  Not decayed: every bias, every "
+                        "nn.LayerNorm affine, every nn.Embedding table, every bare nn.Parameter.  A checkpoint's "
+                        "own value is ignored on --load-optim: the command line governs")
+    p.add_argument("--lr-schedule", choices=["step", "cosine"], default="step",
+                   help="(additive) 'step' (default): the learning rate halves every --lr-step steps, the "
+                        "reference's rule.  'cosine': base x (r + (1 - r)(1 + cos(pi u)) / 2) with u running from 0 "
+                        "at the end of the warm-up to 1 at --lr-decay-steps, r = --lr-min-ratio; constant base x r "
+                        "afterwards.  The schedule is a function of the optimizer's step count: a run resumed with "
+                        "--load-optim continues it")
+    p.add_argument("--lr-warmup-steps", type=_steps_arg("--lr-warmup-steps", 0), default=0,
+                   help="(additive) linear warm-up, with either schedule: step t <= W runs at t / W of the "
+                        "schedule's rate (default 0 = none).")
+    p.add_argument("--lr-decay-steps", type=_steps_arg("--lr-decay-steps", 1), default=None,
+                   help="(additive) the step at which --lr-schedule cosine reaches its floor (required with it, "
+                        "not before the end of the warm-up).")
+    p.add_argument("--lr-min-ratio", type=lr_min_ratio_arg, default=0.0,
+                   help="(additive) floor of --lr-schedule cosine as a fraction of the base rate, in [0, 1] "
+                        "(default 0).")
+
+
+def check_optimizer_args(weight_decay, lr_schedule, lr_warmup_steps, lr_decay_steps, lr_min_ratio):
+    """The five values once more before anything is launched with them (argparse has checked each on its own;
+    what only holds between them -- cosine needs --lr-decay-steps, at or past the warm-up -- is checked here), or
+    ValueError.  Returns them: (weight_decay, lr_schedule, lr_warmup_steps, lr_decay_steps, lr_min_ratio)."""
+    wd, ratio = float(weight_decay), float(lr_min_ratio)
+    if not 0.0 <= wd <= 1.0:                 # (NaN fails both comparisons)
+        raise ValueError(f"--weight-decay must lie in [0, 1], got {weight_decay}")
+    if lr_schedule not in ("step", "cosine"):
+        raise ValueError(f"--lr-schedule must be 'step' or 'cosine', got {lr_schedule!r}")
+    if int(lr_warmup_steps) != lr_warmup_steps or lr_warmup_steps < 0:
+        raise ValueError(f"--lr-warmup-steps must be an integer >= 0, got {lr_warmup_steps}")
+    if not 0.0 <= ratio <= 1.0:
+        raise ValueError(f"--lr-min-ratio must lie in [0, 1], got {lr_min_ratio}")
+    if lr_decay_steps is not None and (int(lr_decay_steps) != lr_decay_steps or lr_decay_steps < 1):
+        raise ValueError(f"--lr-decay-steps must be an integer >= 1, got {lr_decay_steps}")
+    if lr_schedule == "cosine":
+        if lr_decay_steps is None:
+            raise ValueError("--lr-schedule cosine needs --lr-decay-steps")
+        if lr_decay_steps < lr_warmup_steps:
+            raise ValueError(f"--lr-decay-steps ({lr_decay_steps}) lies before the end of --lr-warmup-steps "
+                             f"({lr_warmup_steps})")
+    return wd, lr_schedule, int(lr_warmup_steps), None if lr_decay_steps is None else int(lr_decay_steps), ratio
+
+
+def optimizer_args_are_default(weight_decay, lr_schedule, lr_warmup_steps, lr_decay_steps, lr_min_ratio):
+    """True when the training loop is the reference's: no decay, the halving rule, no warm-up."""
+    return weight_decay == 0 and lr_schedule == "step" and lr_warmup_steps == 0 and lr_decay_steps is None \
+        and lr_min_ratio == 0
+
+
 def check_prompt_args(prompt_fmaps, prompt_fraction):
     """generate_images.py --prompt-fmaps / --prompt-fraction: both or neither, the fraction inside (0, 1).
     Returns whether the run is prompted."""

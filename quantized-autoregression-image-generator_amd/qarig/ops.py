@@ -1566,6 +1566,22 @@ def adam_ema_step(p, g, m, v, ema, beta1, beta2, eps, step_size, bc2_sqrt, ema_w
           "qarig_adam_ema_step")
 
 
+def adamw_step(p, g, m, v, ema, decay_mask, beta1, beta2, eps, step_size, bc2_sqrt, ema_w, decay, grad_scale=1.0,
+               dev_step=None, shadow=None):
+    """adam_step / adam_ema_step (ema may be None) behind a decoupled weight decay: the elements of the groups of 8
+    whose byte in `decay_mask` (uint8, ceil(numel / 8) entries) is non-zero are first moved to fma(-decay, p, p),
+    decay = fp32(lr * lambda).  dev_step, when given, holds four floats: {step_size, bc2_sqrt, ema_w, decay}."""
+    assert shadow is None or (shadow.dtype == torch.bfloat16 and shadow.numel() == p.numel())
+    assert ema is None or (ema.dtype == torch.float32 and ema.numel() == p.numel() and ema.is_contiguous())
+    assert decay_mask.dtype == torch.uint8 and decay_mask.is_contiguous() and decay_mask.is_cuda \
+        and decay_mask.numel() == (p.numel() + 7) // 8
+    assert dev_step is None or dev_step.numel() == 4
+    check(_lib.load().qarig_adamw_step(ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), ptr(decay_mask), p.numel(), beta1,
+                                       beta2, eps, step_size, bc2_sqrt, ema_w, decay, grad_scale, ptr(dev_step),
+                                       ptr(shadow), stream()),
+          "qarig_adamw_step")
+
+
 def swap_(a, b):
     """Exchanges the contents of two fp32 tensors of equal size in place, bit for bit.  They must not overlap."""
     require_cuda(a, b)

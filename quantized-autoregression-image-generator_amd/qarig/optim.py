@@ -7,6 +7,9 @@ moves over RCCL (qarig.parallel).  Semantics and state_dict layout follow
 torch.optim.Adam as the reference uses it (betas=(0.5, 0.999), eps 1e-8, no weight
 decay; train_quantized_transformer.py:317-334), so "model_optimizer" entries of
 reference checkpoints load and save unchanged.
+
+Additive: enable_weight_decay (AdamW: decoupled decay of selected parameters from the same launch, through a
+mask of one byte per 8 elements) and LRSchedule (linear warm-up; the reference's halving rule or a cosine decay).
 """
 import contextlib
 import math
@@ -31,6 +34,90 @@ def ema_weight(count, decay, warmup=True):
     if warmup:
         d = min(d, (1.0 + count) / (10.0 + count))
     return struct.unpack("f", struct.pack("f", 1.0 - d))[0]
+
+
+def fp32(x):
+    """The double `x` rounded to fp32 once (the value a kernel receives for it)."""
+    return struct.unpack("f", struct.pack("f", float(x)))[0]
+
+
+def decay_group_mask(sizes, offsets, total, decayed):
+    """The decay mask of qarig_adamw_step for a flat buffer of `total` floats whose parameter k occupies
+    [offsets[k], offsets[k] + sizes[k]): a uint8 CPU tensor with one entry per group of 8 elements, 1 on the groups
+    of the parameters flagged in `decayed`, 0 elsewhere (the padding groups between slices included).  Slices
+    start on multiples of 8, so no group belongs to two parameters; anything else is refused."""
+    sizes, offsets, decayed = list(sizes), list(offsets), list(decayed)
+    if not (len(sizes) == len(offsets) == len(decayed)):
+        raise ValueError("decay_group_mask: sizes, offsets and decayed must have one entry per parameter")
+    if total < 0 or total % 8:
+        raise ValueError(f"decay_group_mask: total must be a non-negative multiple of 8, got {total}")
+    mask = torch.zeros(total // 8, dtype=torch.uint8)
+    for s, o, d in zip(sizes, offsets, decayed):
+        if o % 8:
+            raise ValueError(f"decay_group_mask: offset {o} is not a multiple of 8")
+        if s < 0 or o < 0 or o + s > total:
+            raise ValueError(f"decay_group_mask: slice [{o}, {o + s}) outside a buffer of {total}")
+        if d:
+            mask[o // 8:(o + s + 7) // 8] = 1
+    return mask
+
+
+def decay_parameters(model):
+    """The parameters --weight-decay decays: the `weight` of every nn.Linear module of `model`, and nothing else
+    (no bias, no nn.LayerNorm affine, no nn.Embedding table, no bare nn.Parameter)."""
+    out, seen = [], set()
+    for mod in model.modules():
+        if isinstance(mod, torch.nn.Linear) and id(mod.weight) not in seen:
+            seen.add(id(mod.weight))
+            out.append(mod.weight)
+    return out
+
+
+class LRSchedule:
+    """Learning rate of the 1-based optimizer step t, a pure function computed in double.
+
+    warm(t) = min(1, t / warmup_steps), or 1 when warmup_steps == 0.
+    kind "step":   base * warm(t) * 0.5 ** h(t), h(1) = 0 and h(t) = floor((t - 2) / lr_step): the halvings the
+                   training loop's `--lr-step` rule has applied before step t.
+    kind "cosine": u = clamp((t - 1 - warmup_steps) / max(1, decay_steps - warmup_steps), 0, 1) and
+                   base * warm(t) * (min_ratio + (1 - min_ratio) * (1 + cos(pi u)) / 2)."""
+
+    def __init__(self, base_lr, kind="step", lr_step=None, warmup_steps=0, decay_steps=None, min_ratio=0.0):
+        base_lr = float(base_lr)
+        if not (0.0 < base_lr < float("inf")):
+            raise ValueError(f"LRSchedule: base_lr must be finite and positive, got {base_lr}")
+        if kind not in ("step", "cosine"):
+            raise ValueError(f"LRSchedule: kind must be 'step' or 'cosine', got {kind!r}")
+        if int(warmup_steps) != warmup_steps or warmup_steps < 0:
+            raise ValueError(f"LRSchedule: warmup_steps must be an integer >= 0, got {warmup_steps}")
+        min_ratio = float(min_ratio)
+        if not (0.0 <= min_ratio <= 1.0):
+            raise ValueError(f"LRSchedule: min_ratio must lie in [0, 1], got {min_ratio}")
+        if kind == "step":
+            if lr_step is None or int(lr_step) != lr_step or lr_step < 1:
+                raise ValueError(f"LRSchedule: kind 'step' needs an integer lr_step >= 1, got {lr_step}")
+        else:
+            if decay_steps is None or int(decay_steps) != decay_steps or decay_steps < 1:
+                raise ValueError(f"LRSchedule: kind 'cosine' needs an integer decay_steps >= 1, got {decay_steps}")
+            if decay_steps < warmup_steps:
+                raise ValueError(f"LRSchedule: decay_steps ({decay_steps}) ends before the warm-up "
+                                 f"({warmup_steps})")
+        self.base_lr, self.kind, self.min_ratio = base_lr, kind, min_ratio
+        self.lr_step = None if lr_step is None else int(lr_step)
+        self.warmup_steps = int(warmup_steps)
+        self.decay_steps = None if decay_steps is None else int(decay_steps)
+
+    def lr(self, t):
+        if int(t) != t or t < 1:
+            raise ValueError(f"LRSchedule.lr: the optimizer step is 1-based, got {t}")
+        t = int(t)
+        warm = min(1.0, t / self.warmup_steps) if self.warmup_steps else 1.0
+        if self.kind == "step":
+            h = 0 if t == 1 else (t - 2) // self.lr_step
+            return self.base_lr * warm * 0.5 ** h
+        u = (t - 1 - self.warmup_steps) / max(1, self.decay_steps - self.warmup_steps)
+        u = min(1.0, max(0.0, u))
+        return self.base_lr * warm * (self.min_ratio + (1.0 - self.min_ratio) * 0.5 * (1.0 + math.cos(math.pi * u)))
 
 
 class FlatAdam:
@@ -61,6 +148,7 @@ class FlatAdam:
         self._capture_cut = None    # set by pipeline._SegmentedCapture while it records a step
         self.flat_ema = None        # enable_ema
         self._ema_swapped = False   # inside ema_weights()
+        self.decay_mask = None      # enable_weight_decay
         with torch.no_grad():
             for p, o, s in zip(self.params, offs, sizes):
                 view = self.flat_param[o:o + s].view(p.shape)
@@ -197,7 +285,12 @@ class FlatAdam:
         return v
 
     def _adam(self, b1, b2, eps, step_size, bc2_sqrt, ema_w, grad_scale, dev_step, shadow):
-        if self.flat_ema is None:
+        if self.decay_mask is not None:
+            ops.adamw_step(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, self.flat_ema,
+                           self.decay_mask, b1, b2, eps, step_size, bc2_sqrt, ema_w,
+                           0.0 if dev_step is not None else self._decay(), grad_scale, dev_step=dev_step,
+                           shadow=shadow)
+        elif self.flat_ema is None:
             ops.adam_step(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, b1, b2,
                           eps, step_size, bc2_sqrt, grad_scale, dev_step=dev_step, shadow=shadow)
         else:
@@ -230,9 +323,10 @@ class FlatAdam:
     # -- graph replay (qarig.pipeline.GraphedTrainStep) -----------------------------------
     def _dev_step_buffer(self):
         if not hasattr(self, "_dev_step"):
-            # {step_size, bc2_sqrt} and, with the EMA on, its weight
-            self._dev_step = torch.zeros(2 if self.flat_ema is None else 3, dtype=torch.float32,
-                                         device=self.flat_param.device)
+            # {step_size, bc2_sqrt} and, with the EMA on, its weight; with weight decay always four,
+            # {step_size, bc2_sqrt, ema_w, decay}
+            size = 4 if self.decay_mask is not None else 2 if self.flat_ema is None else 3
+            self._dev_step = torch.zeros(size, dtype=torch.float32, device=self.flat_param.device)
         return self._dev_step
 
     def step_captured(self, grad_scale=1.0):
@@ -261,11 +355,49 @@ class FlatAdam:
         if self.flat_ema is not None:
             scalars.append(ema_weight(self.ema_count, self.ema_decay, self.ema_warmup))
             self.ema_count += 1
+        if self.decay_mask is not None:
+            if len(scalars) == 2:
+                scalars.append(0.0)         # (the EMA weight's slot: ignored without an EMA)
+            scalars.append(self._decay())
         if not hasattr(self, "_dev_step_feed"):
             from .pipeline import PinnedFeed
             self._dev_step_feed = PinnedFeed(self._dev_step_buffer())
         self._dev_step_feed.push(torch.tensor(scalars, dtype=torch.float32))
         ops.lp_invalidate()
+
+    # -- decoupled weight decay (AdamW; additive: the reference trains without) --------------------------
+    def _decay(self):
+        """lr * weight_decay of this step, in double, rounded to fp32 once."""
+        g = self.param_groups[0]
+        return fp32(float(g["lr"]) * float(g["weight_decay"]))
+
+    def enable_weight_decay(self, weight_decay, params):
+        """Decoupled weight decay from here on: every step first shrinks the parameters listed in `params` by
+        lr * weight_decay (p <- fma(-lr * weight_decay, p, p), the learning rate of that step), then applies
+        Adam's update to the result -- torch.optim.AdamW with two groups, from one launch (qarig_adamw_step).
+        The mask has one byte per 8 elements of the flat buffer.  Must be called before a step is captured: the
+        captured launch reads four scalars from a device buffer that has to exist, at its final size, before the
+        capture."""
+        wd = float(weight_decay)
+        if not (0.0 < wd <= 1.0):            # (NaN fails both comparisons)
+            raise ValueError(f"weight decay must be finite and lie in (0, 1], got {weight_decay}")
+        params = list(params)
+        index = {id(p): i for i, p in enumerate(self.params)}
+        for p in params:
+            if id(p) not in index:
+                raise ValueError("FlatAdam.enable_weight_decay: a parameter this optimizer does not own")
+        if hasattr(self, "_dev_step"):
+            raise RuntimeError("FlatAdam.enable_weight_decay: a captured step was already recorded (its launch "
+                               "reads a scalar buffer without the decay and has no mask); enable weight decay "
+                               "before the first captured step")
+        if self._ema_swapped:
+            raise RuntimeError("FlatAdam.enable_weight_decay inside ema_weights()")
+        flags = [False] * len(self.params)
+        for p in params:
+            flags[index[id(p)]] = True
+        mask = decay_group_mask([p.numel() for p in self.params], self.offsets, self.total, flags)
+        self.decay_mask = mask.to(self.flat_param.device)
+        self.param_groups[0]["weight_decay"] = wd
 
     # -- exponential moving average of the parameters (additive: the reference keeps none) ----------------
     def enable_ema(self, decay, warmup=True):

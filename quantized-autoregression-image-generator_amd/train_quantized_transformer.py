@@ -15,7 +15,7 @@ import torch
 from models.Transformer import Transformer
 from qarig import cli_common as cc
 from qarig import ops, parallel, pipeline, sampling
-from qarig.optim import FlatAdam
+from qarig.optim import FlatAdam, LRSchedule, decay_parameters
 from utils.image_utils import save_images
 from utils.model_utils import load_model, save_model
 from dataset_loader.feature_map_dataset import FeatureMapDataset
@@ -93,7 +93,14 @@ def parse_args():
                    help="(additive) score only the first batches of --val-dataset-path.")
     cc.add_regulariser_args(p)
     cc.add_dropout_args(p)
-    return vars(p.parse_args())
+    cc.add_optimizer_args(p)
+    args = vars(p.parse_args())
+    try:        # what holds only between the flags (cosine needs --lr-decay-steps, at or past the warm-up)
+        cc.check_optimizer_args(args["weight_decay"], args["lr_schedule"], args["lr_warmup_steps"],
+                                args["lr_decay_steps"], args["lr_min_ratio"])
+    except ValueError as e:
+        p.error(str(e))
+    return args
 
 
 def main():
@@ -160,6 +167,16 @@ def main():
         if resumed:
             optim.load_ema(saved["model_ema"], model, meta.get("count", 0))
     optim.enable_allreduce_overlap()     # no-op at world 1
+    weight_decay, lr_schedule, lr_warmup_steps, lr_decay_steps, lr_min_ratio = cc.check_optimizer_args(
+        args["weight_decay"], args["lr_schedule"], args["lr_warmup_steps"], args["lr_decay_steps"],
+        args["lr_min_ratio"])
+    schedule = None         # the reference's loop: halve_lr every --lr-step
+    if not cc.optimizer_args_are_default(weight_decay, lr_schedule, lr_warmup_steps, lr_decay_steps, lr_min_ratio):
+        # a function of the optimizer's step count: with --load-optim the schedule continues where it was
+        schedule = LRSchedule(model_lr, lr_schedule, lr_step=args["lr_step"], warmup_steps=lr_warmup_steps,
+                              decay_steps=lr_decay_steps, min_ratio=lr_min_ratio)
+    if weight_decay > 0:
+        optim.enable_weight_decay(weight_decay, decay_parameters(model))
     # argparse has checked both; once more before anything is launched with them
     label_smoothing, z_loss = ops.check_ce_regularisers(args["label_smoothing"], args["z_loss"])
     regularised = label_smoothing > 0 or z_loss > 0
@@ -227,6 +244,14 @@ def main():
     if dropout > 0:
         info(f"Dropout: {dropout}")
         info(f"Dropout Seed: {dropout_seed}")
+    if weight_decay > 0:
+        info(f"Weight Decay: {weight_decay}")
+    if schedule is not None:
+        info(f"LR Schedule: {lr_schedule}")
+        info(f"LR Warmup Steps: {lr_warmup_steps:,}")
+        if lr_decay_steps is not None:
+            info(f"LR Decay Steps: {lr_decay_steps:,}")
+        info(f"LR Min Ratio: {lr_min_ratio}")
     info("#" * 100)
     info("Sampling Parameters.")
     info(f"Temperature: {temperature:,}")
@@ -254,6 +279,13 @@ def main():
         if dropout > 0:             # informational likewise
             model_dict["dropout"] = dropout
             model_dict["dropout_seed"] = dropout_seed
+        if weight_decay > 0:        # informational likewise
+            model_dict["weight_decay"] = weight_decay
+        if schedule is not None:
+            model_dict["lr_schedule"] = lr_schedule
+            model_dict["lr_warmup_steps"] = lr_warmup_steps
+            model_dict["lr_decay_steps"] = lr_decay_steps
+            model_dict["lr_min_ratio"] = lr_min_ratio
         ok = save_model(model_dict=model_dict, dest_path=out_dir, file_name=f"model_{global_steps}.pt",
                         logging=info)
         info("Successfully saved model." if ok else "Error occured saving model.")
@@ -335,6 +367,8 @@ def main():
             feature_map = feature_map.to(device)
             N = feature_map.shape[0]
             model.train()
+            if schedule is not None:     # before every step, eager or replayed (advance_captured reads the group)
+                optim.param_groups[0]["lr"] = schedule.lr(optim.step_count + 1)
             if graphed is not None and N == batch_size:
                 rand = None
                 if use_sliding_window:
@@ -364,7 +398,7 @@ def main():
             if loss_val != loss_val:
                 raise Exception("NaN encountered during training.")
             total_loss += loss_val
-            if global_steps % args["lr_step"] == 0 and global_steps > 0:
+            if schedule is None and global_steps % args["lr_step"] == 0 and global_steps > 0:
                 cc.halve_lr(optim)
             if global_steps % args["checkpoint_step"] == 0 and global_steps >= 0 and rank == 0:
                 checkpoint(global_steps)
