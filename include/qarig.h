@@ -115,7 +115,23 @@ int qarig_bmu_prepare(const float* codebook, int K, int D, void* image, void* st
  * sum_k A(m,k) (added to it when accumulate): with A = dT^T this is the bias gradient,
  * computed from the A tiles the weight-gradient GEMM stages anyway.
  * Replaces nn.Linear (+activation) inside LinearLayer / ResidualLinearLayer
- * (models/layers.py:234-304) forward, and the three autograd contractions. */
+ * (models/layers.py:234-304) forward, and the three autograd contractions.
+ * Ragged weight gradient (qarig_gemm_ragged_tn(M, N, K) != 0: a_kcontig = b_kcontig = 0, M = 128 q + r
+ * output rows with q >= 2 and 1 <= r <= 8, N % 128 == 0, reduction K >= 4096 in whole 16-deep tiles --
+ * the classifier's 513 = K_hr + 1 rows, models/Transformer.py:82-102 -- plain epilogue, 16-B aligned
+ * operands, workspace given): the first 128 q rows run as the product of that shape, the last r rows
+ * through per-row-block partials in the workspace summed in ascending order (no atomics: the same bits
+ * on every run).  qarig_gemm_workspace_bytes(M, N, splitk) knows neither the layout nor K, so it includes the
+ * partials (128 * r * (N + 1) floats) for EVERY M = 128 q + r with q >= 2, 1 <= r <= 8, whether the route is
+ * taken or not.  A caller picks splitk for 128 q rows; without a workspace the call keeps its old kernels. */
+int qarig_gemm_ragged_tn(int M, int N, int K);
+/* Ragged forward product (qarig_gemm_ragged_nt(M, N, K) != 0: a_kcontig = b_kcontig = 1, N = 128 q + r output
+ * columns with q >= 2 and 1 <= r <= 8, M >= 4096 rows in whole 128-row tiles, K in whole 16-deep tiles,
+ * r * K <= 16384; taken with splitk = 1, no residual / gradz / accumulate / a_rowsum, 16-B aligned operands
+ * and ldc, ldp multiples of 4 -- a dense (M, 513) output keeps the kernels it had): the first 128 q columns
+ * run as the product of that shape at the caller's ldc, the last r columns on a kernel that streams A once,
+ * with the same bias / pre-activation / activation epilogue and one fixed summation order. */
+int qarig_gemm_ragged_nt(int M, int N, int K);
 size_t qarig_gemm_workspace_bytes(int M, int N, int splitk);
 int qarig_gemm_f32(const float* A, int64_t lda, int a_kcontig, const float* B, int64_t ldb,
                    int b_kcontig, float* C, int64_t ldc, int M, int N, int K, const float* bias,
@@ -143,6 +159,17 @@ int qarig_gemm_f32_grouped(int groups, const float* const* A, int64_t lda, int a
                            int64_t ldp, int act, const float* const* gradz, int64_t ldz, int gact,
                            int splitk, int accumulate, int sum_groups, float* const* a_rowsum,
                            void* workspace, size_t ws_bytes, void* stream);
+
+/* Strided groups: C_g = act(A W_g^T + bias_g) for any number of groups that share A (M, K), with
+ * W_g = W + g * w_gs (N, K), C_g = C + g * c_gs (M, N) and bias_g = bias + g * bias_gs (bias may be
+ * NULL), as ONE launch of groups * (M / 128) * (N / 128) tiles on the kernel of qarig_gemm_f32's
+ * interior shapes; a tile's result does not depend on the group count.  The training forward of
+ * every ScaleLayer / ShiftLayer projection of a position table (models/layers.py:100-153, 258-304)
+ * whose row count is a multiple of 128.  Shapes: qarig_gemm_grouped_supported(M, N, K, 1); 16-B
+ * aligned operands, strides multiples of 4 elements, groups must not overlap. */
+int qarig_gemm_f32_strided(const float* A, int64_t lda, const float* W, int64_t ldw, int64_t w_gs,
+                           float* C, int64_t ldc, int64_t c_gs, const float* bias, int64_t bias_gs,
+                           int groups, int M, int N, int K, int act, void* stream);
 
 /* Opt-in reduced precision (BASELINE config 5: "fp8/bf16 MFMA attn/FFN"; never the fp32 parity
  * mode).  The Linear contractions of models/layers.py:234-304, 330-340, 389-418 with bf16
@@ -598,6 +625,16 @@ int qarig_attention_decode(const float* q, const float* k_new, const float* v_ne
  * train_quantized_transformer.py:337,496-502.  row_ws: M floats. */
 int qarig_cross_entropy_fwd(const float* logits, const int64_t* target, int M, int C, float* loss,
                             float* dlogits, float* row_ws, int* bad_flag, void* stream);
+/* The same loss (train_quantized_transformer.py:337,496-502) on rows with leading dimensions: logits rows at
+ * ld_logits >= C, whose columns C .. ld_logits - 1 are never read; dlogits rows at ld_dlogits >= C, whose
+ * columns C .. ld_dlogits - 1 receive exact zeros (the classifier's logits stay in their (M, 528) GEMM output
+ * buffer and the input-gradient GEMM reduces over the zero columns); nothing behind row M - 1's ld_dlogits
+ * columns is written.  loss, row_ws and dlogits[:, :C] carry the bits of qarig_cross_entropy_fwd, which is
+ * the ld == C case.  The regularised entry below has no such form: a step with label smoothing or z-loss
+ * passes dense logits. */
+int qarig_cross_entropy_ld_fwd(const float* logits, int64_t ld_logits, const int64_t* target, int M, int C,
+                               float* loss, float* dlogits, int64_t ld_dlogits, float* row_ws, int* bad_flag,
+                               void* stream);
 
 /* Cross-entropy with label smoothing and z-loss (additive; the reference trains with neither):
  * F.cross_entropy(logits, target, label_smoothing = eps) + zeta mean_r(logsumexp(logits[r])^2), in one rows

@@ -829,6 +829,191 @@ __global__ __launch_bounds__(1024) void gemm_skinny_kernel(const float* __restri
     }
 }
 
+// ---------------------------------------------------------------------------------
+// Ragged weight gradient: the last r = M % 128 (1..8) output rows of a TN product whose first
+// M - r rows run on the ring (the classifier's 513 = 4 * 128 + 1 rows over 16,384 tokens: the
+// ring then runs the 512-row product at one split per XCD instead of a 640-row padded one).
+//   part[blk][j][n] = sum_{k in row block blk, ascending} A[k][j] B[k][n],  rs[blk][j] = sum_k A[k][j]
+// A points at column M - r of the [K][M] operand.  B is streamed once with 16-B loads (it is the
+// whole cost: 134 MB at 16,384 x 2,048); the r-wide A rows of 64 reduction steps sit in LDS and are
+// read as broadcasts.  The second stage adds the row blocks in ascending order: no atomics, the
+// same bits on every run.
+constexpr int TAIL_MAX_ROWS = 8;
+constexpr int TAIL_BLOCKS = 128;      // row blocks of the reduction (partials per output)
+constexpr int TAIL_CHUNK = 64;        // reduction steps staged in LDS at a time
+
+static inline int tail_rows_per_block(int K) { return ((K + TAIL_BLOCKS - 1) / TAIL_BLOCKS + 7) / 8 * 8; }
+
+__global__ __launch_bounds__(256) void gemm_tn_tail_kernel(const float* __restrict__ A, int64_t lda,
+                                                           const float* __restrict__ B, int64_t ldb, int N,
+                                                           int K, int r, int rows_per_blk,
+                                                           float* __restrict__ part, float* __restrict__ rs_part) {
+    __shared__ float a_s[TAIL_CHUNK * TAIL_MAX_ROWS];
+    const int k0 = blockIdx.y * rows_per_blk, k1 = min(K, k0 + rows_per_blk);
+    const int c = (blockIdx.x * 256 + threadIdx.x) * 4;
+    float acc[TAIL_MAX_ROWS][4];
+#pragma unroll
+    for (int j = 0; j < TAIL_MAX_ROWS; ++j) acc[j][0] = acc[j][1] = acc[j][2] = acc[j][3] = 0.0f;
+    float rs = 0.0f;
+    auto fma_row = [&](int kk, const float4& b) {
+#pragma unroll
+        for (int j = 0; j < TAIL_MAX_ROWS; ++j) {
+            const float a = a_s[kk * TAIL_MAX_ROWS + j];
+            acc[j][0] = fmaf(a, b.x, acc[j][0]); acc[j][1] = fmaf(a, b.y, acc[j][1]);
+            acc[j][2] = fmaf(a, b.z, acc[j][2]); acc[j][3] = fmaf(a, b.w, acc[j][3]);
+        }
+    };
+    for (int kc = k0; kc < k1; kc += TAIL_CHUNK) {
+        const int n = min(TAIL_CHUNK, k1 - kc);
+        __syncthreads();
+        for (int i = threadIdx.x; i < TAIL_CHUNK * TAIL_MAX_ROWS; i += 256) {   // rows past r, steps past n: zero
+            const int kk = i / TAIL_MAX_ROWS, j = i - kk * TAIL_MAX_ROWS;
+            a_s[i] = (kk < n && j < r) ? A[(int64_t)(kc + kk) * lda + j] : 0.0f;
+        }
+        __syncthreads();
+        if (c < N) {
+            const float* bp = B + (int64_t)kc * ldb + c;
+            int kk = 0;
+            for (; kk + 8 <= n; kk += 8) {          // eight loads in flight, consumed k ascending
+                float4 b[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) b[u] = *reinterpret_cast<const float4*>(bp + (int64_t)(kk + u) * ldb);
+#pragma unroll
+                for (int u = 0; u < 8; ++u) fma_row(kk + u, b[u]);
+            }
+            for (; kk < n; ++kk) fma_row(kk, *reinterpret_cast<const float4*>(bp + (int64_t)kk * ldb));
+        }
+        if (blockIdx.x == 0 && (int)threadIdx.x < r)
+            for (int kk = 0; kk < n; ++kk) rs += a_s[kk * TAIL_MAX_ROWS + threadIdx.x];
+    }
+    if (c < N) {
+#pragma unroll
+        for (int j = 0; j < TAIL_MAX_ROWS; ++j)
+            if (j < r)
+                *reinterpret_cast<float4*>(part + ((int64_t)blockIdx.y * r + j) * N + c) =
+                    make_float4(acc[j][0], acc[j][1], acc[j][2], acc[j][3]);
+    }
+    if (rs_part && blockIdx.x == 0 && (int)threadIdx.x < r) rs_part[blockIdx.y * r + threadIdx.x] = rs;
+}
+
+// C[j][n] (+)= sum_blk part[blk][j][n], blk ascending; the r entries behind them: the row sums.
+__global__ __launch_bounds__(256) void gemm_tn_tail_reduce_kernel(const float* __restrict__ part,
+                                                                  const float* __restrict__ rs_part,
+                                                                  float* __restrict__ C, int64_t ldc,
+                                                                  float* __restrict__ rowsum, int N, int r,
+                                                                  int nblk, int accumulate) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    const int total = r * N;
+    if (idx < total) {
+        const int j = idx / N, n = idx - j * N;
+        float s = 0.0f;
+        for (int b0 = 0; b0 < nblk; b0 += 16) {       // sixteen loads in flight, added blk ascending
+            float v[16];
+#pragma unroll
+            for (int u = 0; u < 16; ++u)
+                if (b0 + u < nblk) v[u] = part[((int64_t)(b0 + u) * r + j) * N + n];
+#pragma unroll
+            for (int u = 0; u < 16; ++u)
+                if (b0 + u < nblk) s += v[u];
+        }
+        float* dst = C + (int64_t)j * ldc + n;
+        *dst = accumulate ? *dst + s : s;
+    } else if (rowsum && idx < total + r) {
+        const int j = idx - total;
+        float s = 0.0f;
+        for (int b = 0; b < nblk; ++b) s += rs_part[b * r + j];
+        rowsum[j] = accumulate ? rowsum[j] + s : s;
+    }
+}
+
+// Ragged forward product: the last r = N % 128 (1..8) output columns of an NT product whose first
+// N - r columns run on the ring:  C[m][j] = epilogue(A[m,:] . B[j,:]),  B, bias, C and preact pointing
+// at column N - r.  The r weight rows sit in LDS (r * K <= 16,384 floats); a wave owns a row of A,
+// streams it once with 16-B loads (all of them in flight before the first multiply), each lane sums
+// its k = 256 i + 4 lane .. + 3 in ascending i and the 64 lane sums meet in one fixed butterfly.
+constexpr int TAILCOL_W_FLOATS = 16384;
+constexpr int TAILCOL_ROWS = 16;      // rows of A per workgroup (4 per wave)
+
+__global__ __launch_bounds__(256) void gemm_nt_tail_kernel(const float* __restrict__ A, int64_t lda,
+                                                           const float* __restrict__ B, int64_t ldb,
+                                                           GemmEpilogue ep, int M, int K, int r) {
+    __shared__ __attribute__((aligned(16))) float w_s[TAILCOL_W_FLOATS];
+    const int K4 = K >> 2;
+    for (int i = threadIdx.x; i < r * K4; i += 256) {
+        const int j = i / K4, k4 = i - j * K4;
+        reinterpret_cast<float4*>(w_s)[i] = *reinterpret_cast<const float4*>(B + (int64_t)j * ldb + 4 * k4);
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int q = 0; q < TAILCOL_ROWS / 4; ++q) {
+        const int m = blockIdx.x * TAILCOL_ROWS + q * 4 + wave;       // wave-uniform
+        if (m >= M) break;
+        const float4* ap = reinterpret_cast<const float4*>(A + (int64_t)m * lda);
+        float acc[TAIL_MAX_ROWS];
+#pragma unroll
+        for (int j = 0; j < TAIL_MAX_ROWS; ++j) acc[j] = 0.0f;
+        for (int k0 = 0; k0 < K4; k0 += 8 * 64) {
+            float4 a[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int k4 = k0 + u * 64 + lane;
+                a[u] = k4 < K4 ? ap[k4] : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int k4 = k0 + u * 64 + lane;
+                if (k4 < K4) {
+#pragma unroll
+                    for (int j = 0; j < TAIL_MAX_ROWS; ++j)
+                        if (j < r) {
+                            const float4 w = reinterpret_cast<const float4*>(w_s)[j * K4 + k4];
+                            acc[j] = fmaf(a[u].w, w.w, fmaf(a[u].z, w.z, fmaf(a[u].y, w.y, fmaf(a[u].x, w.x, acc[j]))));
+                        }
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < TAIL_MAX_ROWS; ++j)
+            if (j < r) {
+                float t = wave_sum(acc[j]);
+                if (lane == 0) {
+                    if (ep.bias) t += ep.bias[j];
+                    if (ep.preact) ep.preact[(int64_t)m * ep.ldp + j] = t;
+                    ep.C[(int64_t)m * ep.ldc + j] = act_fwd(t, ep.act);
+                }
+            }
+    }
+}
+
+// Strided-groups form: any number of NT products that SHARE A, group g's B, bias and C at base +
+// g * stride (the projections of one position table by G stacked weights: 42 in BASELINE config 2,
+// more than the 16 pointer sets above carry by value).  Flat grid, workgroup -> (group, tile) on
+// the scalar unit; no reduction split -- the groups fill the chip.  One tile's arithmetic is the
+// plain kernel's, whichever group count it is launched with.
+__global__ __launch_bounds__(NTHREADS, 2) void gemm_dma_pf_strided_kernel(const float* __restrict__ A, int64_t lda,
+                                                                          const float* __restrict__ B, int64_t ldb,
+                                                                          int64_t b_gs, GemmEpilogue ep,
+                                                                          int64_t c_gs, int64_t bias_gs, int M,
+                                                                          int N, int K, int tiles_n, int tiles) {
+    __shared__ __attribute__((aligned(16))) float lds[PF_STAGES * DMA_STAGE_FLOATS];   // 64 KB
+    const int lin = xcd_remap(blockIdx.x, gridDim.x);
+    const int g = lin / tiles;
+    const int tile = lin - g * tiles;
+    const int tm = tile / tiles_n, tn = tile - tm * tiles_n;
+    const int m0 = tm * BM, n0 = tn * BN;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    ep.C += (int64_t)g * c_gs;
+    if (ep.bias) ep.bias += (int64_t)g * bias_gs;
+
+    Acc acc;
+    acc_zero(acc);
+    float rs = 0.0f;
+    pf_ring<true, true>(acc, rs, false, lds, A, lda, B + (int64_t)g * b_gs, ldb, m0, n0, 0, K / BK, wave, lane, tid);
+    __syncthreads();                      // ring no longer in use: the epilogue stages through it
+    gemm_epilogue_wide<2>(acc, ep, lds, m0, n0, M, N, 1, nullptr);
+}
+
 }  // namespace qarig
 
 using namespace qarig;
@@ -846,11 +1031,33 @@ extern "C" int qarig_ring_stamps_read(uint64_t* host, int slots) {
 }
 #endif
 
+// Row-block partials of the ragged weight gradient's tail rows (gemm_tn_tail_kernel) and their row sums.
+static size_t tail_workspace_bytes(int r, int N) { return (size_t)TAIL_BLOCKS * r * ((size_t)N + 1) * sizeof(float); }
+
+// The shape rule of the ragged weight-gradient route (TN: both operands reduction-strided; M output rows,
+// N output columns, reduction length K): M = 128 q + r with q >= 2 and 1 <= r <= 8, whole tiles otherwise,
+// and a reduction long enough that the product is a weight gradient over thousands of token rows.
+extern "C" int qarig_gemm_ragged_tn(int M, int N, int K) {
+    const int r = M % BM;
+    return M > 2 * BM && r >= 1 && r <= TAIL_MAX_ROWS && N >= BN && N % BN == 0 && K >= 4096 && K % BK == 0 ? 1 : 0;
+}
+
+// The shape rule of the ragged forward route (NT: both operands reduction-contiguous; M rows, N output columns):
+// N = 128 q + r with q >= 2 and 1 <= r <= 8, thousands of whole 128-row tiles, r weight rows that fit the LDS.
+extern "C" int qarig_gemm_ragged_nt(int M, int N, int K) {
+    const int r = N % BN;
+    return N > 2 * BN && r >= 1 && r <= TAIL_MAX_ROWS && M >= 4096 && M % BM == 0 && K % BK == 0 &&
+                   (long)r * K <= TAILCOL_W_FLOATS ? 1 : 0;
+}
+
 extern "C" size_t qarig_gemm_workspace_bytes(int M, int N, int splitk) {
     if (M < 1 || N < 1 || splitk > (1 << 16)) return 0;
     // split-K slabs + (always) room for the per-split A row sums
     const size_t sk = splitk > 1 ? splitk : 1;
-    return (splitk > 1 ? sk * M * N * sizeof(float) : 0) + sk * M * sizeof(float);
+    const size_t ring = (splitk > 1 ? sk * M * N * sizeof(float) : 0) + sk * M * sizeof(float);
+    // (the ragged route's ring part needs less than `ring`; its tail partials lie behind that part)
+    const int r = M % BM;
+    return ring + (M > 2 * BM && r >= 1 && r <= TAIL_MAX_ROWS ? tail_workspace_bytes(r, N) : 0);
 }
 
 
@@ -907,6 +1114,44 @@ static int gemm_dispatch(const float* A, int64_t lda, int a_kcontig, const float
     QARIG_CHECK_ARG(splitk <= 4096, "gemm: splitk %d too large", splitk);
     QARIG_CHECK_ARG(act >= 0 && act <= 3 && gact >= 0 && gact <= 3, "gemm: bad activation id");
     if (splitk < 1) splitk = 1;
+    // Ragged weight gradient (qarig_gemm_ragged_tn): the first 128 q rows as the product of that shape, on the
+    // ring; the last r rows on the tail kernels, partials behind the ring's share of the workspace.
+    if (!a_kcontig && !b_kcontig && qarig_gemm_ragged_tn(M, N, K) && !bias && !residual && !preact && !gradz &&
+        act == ACT_NONE && workspace && ws_bytes >= qarig_gemm_workspace_bytes(M, N, splitk) &&
+        (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15) == 0 && lda % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0) {
+        const int r = M % BM, Mq = M - r;
+        const size_t ring_bytes = qarig_gemm_workspace_bytes(Mq, N, splitk);
+        const int rc = gemm_dispatch(A, lda, 0, B, ldb, 0, C, ldc, Mq, N, K, nullptr, nullptr, 0, nullptr, 0, ACT_NONE,
+                                     nullptr, 0, ACT_NONE, splitk, accumulate, a_rowsum, workspace, ring_bytes, stream);
+        if (rc != QARIG_OK) return rc;
+        hipStream_t st = (hipStream_t)stream;
+        const int rpb = tail_rows_per_block(K), nblk = (K + rpb - 1) / rpb;
+        float* part = reinterpret_cast<float*>((char*)workspace + ring_bytes);
+        float* rs_part = a_rowsum ? part + (size_t)TAIL_BLOCKS * r * N : nullptr;
+        hipLaunchKernelGGL(gemm_tn_tail_kernel, dim3((N / 4 + 255) / 256, nblk), dim3(256), 0, st, A + Mq, lda, B, ldb,
+                           N, K, r, rpb, part, rs_part);
+        QARIG_CHECK_LAUNCH("gemm ragged tail");
+        hipLaunchKernelGGL(gemm_tn_tail_reduce_kernel, dim3((r * N + r + 255) / 256), dim3(256), 0, st, part, rs_part,
+                           C + (int64_t)Mq * ldc, ldc, a_rowsum ? a_rowsum + Mq : nullptr, N, r, nblk, accumulate);
+        QARIG_CHECK_LAUNCH("gemm ragged tail reduce");
+        return QARIG_OK;
+    }
+    // Ragged forward product (qarig_gemm_ragged_nt): the first 128 q columns as the product of that shape, on the
+    // ring at the caller's ldc; the last r columns on the tail kernel with the same bias / activation epilogue.
+    if (a_kcontig && b_kcontig && qarig_gemm_ragged_nt(M, N, K) && splitk == 1 && !accumulate && !residual && !gradz &&
+        !a_rowsum && (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C | (uintptr_t)bias | (uintptr_t)preact) & 15) == 0 &&
+        lda % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0 && ldp % 4 == 0) {
+        const int r = N % BN, Nq = N - r;
+        const int rc = gemm_dispatch(A, lda, 1, B, ldb, 1, C, ldc, M, Nq, K, bias, nullptr, 0, preact, ldp, act,
+                                     nullptr, 0, ACT_NONE, 1, 0, nullptr, nullptr, 0, stream);
+        if (rc != QARIG_OK) return rc;
+        GemmEpilogue ept{C + Nq, ldc, bias ? bias + Nq : nullptr, nullptr, 0, preact ? preact + Nq : nullptr, ldp, act,
+                         nullptr, 0, ACT_NONE, nullptr};
+        hipLaunchKernelGGL(gemm_nt_tail_kernel, dim3((M + TAILCOL_ROWS - 1) / TAILCOL_ROWS), dim3(256), 0,
+                           (hipStream_t)stream, A, lda, B + (int64_t)Nq * ldb, ldb, ept, M, K, r);
+        QARIG_CHECK_LAUNCH("gemm ragged tail columns");
+        return QARIG_OK;
+    }
     if (accumulate) {
         // C += A B^T (gradient accumulation straight into a parameter's .grad)
         QARIG_CHECK_ARG(!bias && !residual && !preact && !gradz && act == ACT_NONE,
@@ -1230,6 +1475,35 @@ extern "C" int qarig_gemm_f32_grouped(int groups, const float* const* A, int64_t
                                nslab, accumulate, nb, rs_part);
         QARIG_CHECK_LAUNCH("gemm_grouped reduce");
     }
+    return QARIG_OK;
+}
+
+// Strided groups (gemm_dma_pf_strided_kernel): C_g = act(A W_g^T + bias_g), A (M, K) shared, W_g = W + g * w_gs
+// (N, K), C_g = C + g * c_gs (M, N), bias_g = bias + g * bias_gs -- the training forward of every projection of
+// a position table (ScaleLayer / ShiftLayer of all layers, models/layers.py:100-153, 258-304) as ONE ring launch
+// of groups * (M / 128) * (N / 128) tiles.  Shapes: qarig_gemm_grouped_supported(M, N, K, 1).
+extern "C" int qarig_gemm_f32_strided(const float* A, int64_t lda, const float* W, int64_t ldw, int64_t w_gs,
+                                      float* C, int64_t ldc, int64_t c_gs, const float* bias, int64_t bias_gs,
+                                      int groups, int M, int N, int K, int act, void* stream) {
+    QARIG_CHECK_ARG(A && W && C, "gemm_strided: null operand");
+    QARIG_CHECK_ARG(groups >= 1 && groups <= 65535, "gemm_strided: 1 <= groups <= 65535 (got %d)", groups);
+    QARIG_CHECK_ARG(qarig_gemm_grouped_supported(M, N, K, 1),
+                    "gemm_strided: needs M %% 128 == 0, N %% 128 == 0, K %% 16 == 0 (M=%d N=%d K=%d)", M, N, K);
+    QARIG_CHECK_ARG(act >= 0 && act <= 3, "gemm_strided: bad activation id");
+    QARIG_CHECK_ARG((((uintptr_t)A | (uintptr_t)W | (uintptr_t)C | (uintptr_t)bias) & 15) == 0 && lda % 4 == 0 &&
+                        ldw % 4 == 0 && ldc % 4 == 0 && w_gs % 4 == 0 && c_gs % 4 == 0 && bias_gs % 4 == 0,
+                    "gemm_strided: operands must be 16-B aligned");
+    QARIG_CHECK_ARG(lda >= K && ldw >= K && ldc >= N && w_gs >= (int64_t)N * ldw && c_gs >= (int64_t)M * ldc &&
+                        (!bias || bias_gs >= N),
+                    "gemm_strided: groups must not overlap (ldw=%lld w_gs=%lld ldc=%lld c_gs=%lld)",
+                    (long long)ldw, (long long)w_gs, (long long)ldc, (long long)c_gs);
+    const int tiles_n = N / BN, tiles = (M / BM) * tiles_n;
+    const long total_wg = (long)tiles * groups;
+    QARIG_CHECK_ARG(total_wg <= (1L << 30), "gemm_strided: grid too large");
+    GemmEpilogue ep{C, ldc, bias, nullptr, 0, nullptr, 0, act, nullptr, 0, 0, nullptr};
+    hipLaunchKernelGGL(gemm_dma_pf_strided_kernel, dim3((unsigned)total_wg), dim3(NTHREADS), 0, (hipStream_t)stream,
+                       A, lda, W, ldw, w_gs, ep, c_gs, bias_gs, M, N, K, tiles_n, tiles);
+    QARIG_CHECK_LAUNCH("gemm_strided");
     return QARIG_OK;
 }
 

@@ -6,15 +6,18 @@
 namespace qarig {
 
 __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ logits,
+                                                      int64_t ld_logits,
                                                       const int64_t* __restrict__ target, int M,
                                                       int C, float inv_m,
                                                       float* __restrict__ row_loss,
-                                                      float* __restrict__ dlogits,
+                                                      float* __restrict__ dlogits, int64_t ld_dlogits,
                                                       int* __restrict__ bad) {
+    // rows at leading dimensions ld_logits / ld_dlogits >= C: columns C .. ld_logits - 1 of the logits are never
+    // read, columns C .. ld_dlogits - 1 of the gradient receive exact zeros (a GEMM reduces over them)
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= M) return;
-    const float* x = logits + (int64_t)row * C;
+    const float* x = logits + (int64_t)row * ld_logits;
     float mx = -INFINITY;
     for (int c = lane; c < C; c += 64) mx = fmaxf(mx, x[c]);
     mx = wave_max(mx);
@@ -31,11 +34,12 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ 
         row_loss[row] = ok ? logs - (x[t] - mx) : 0.0f;
     }
     if (dlogits) {
-        float* d = dlogits + (int64_t)row * C;
+        float* d = dlogits + (int64_t)row * ld_dlogits;
         for (int c = lane; c < C; c += 64) {
             const float p = expf((x[c] - mx) - logs);
             d[c] = (p - ((int64_t)c == t ? 1.0f : 0.0f)) * inv_m;
         }
+        for (int64_t c = C + lane; c < ld_dlogits; c += 64) d[c] = 0.0f;
     }
 }
 
@@ -106,20 +110,34 @@ extern "C" int qarig_mse_fwd(const float* pred, const float* target, int64_t n, 
 // logits (M,C) fp32, target int64 (M,).  loss: 1 float.  dlogits (M,C) or NULL =
 // d(mean CE)/d(logits).  row_ws: M floats of scratch.  *bad_flag set on a target
 // outside [0,C).
-extern "C" int qarig_cross_entropy_fwd(const float* logits, const int64_t* target, int M, int C,
-                                       float* loss, float* dlogits, float* row_ws, int* bad_flag,
-                                       void* stream) {
+// The same with leading dimensions: logits rows at ld_logits >= C (columns C .. ld_logits - 1 are never read),
+// dlogits rows at ld_dlogits >= C, columns C .. ld_dlogits - 1 written as exact zeros -- the classifier's
+// (M, 528) logits buffer and the zero-padded dlogits its input-gradient GEMM reduces over.  Loss, row_ws and
+// dlogits[:, :C] carry the bits of the dense entry, which is the ld == C case of this one.
+extern "C" int qarig_cross_entropy_ld_fwd(const float* logits, int64_t ld_logits, const int64_t* target, int M, int C,
+                                          float* loss, float* dlogits, int64_t ld_dlogits, float* row_ws,
+                                          int* bad_flag, void* stream) {
     QARIG_CHECK_ARG(logits && target && loss && row_ws && bad_flag && M > 0 && C > 0,
                     "cross_entropy: bad arguments");
     QARIG_CHECK_DIMS("cross_entropy", M, C);
+    QARIG_CHECK_ARG(ld_logits >= C && (!dlogits || ld_dlogits >= C) && ld_logits <= (1LL << 31) &&
+                        ld_dlogits <= (1LL << 31),
+                    "cross_entropy: leading dimensions must be at least C = %d (got %lld, %lld)", C,
+                    (long long)ld_logits, (long long)ld_dlogits);
     hipStream_t st = (hipStream_t)stream;
     const float inv_m = 1.0f / (float)M;
-    hipLaunchKernelGGL(ce_rows_kernel, dim3((M + 3) / 4), dim3(256), 0, st, logits, target, M, C,
-                       inv_m, row_ws, dlogits, bad_flag);
+    hipLaunchKernelGGL(ce_rows_kernel, dim3((M + 3) / 4), dim3(256), 0, st, logits, ld_logits, target, M, C,
+                       inv_m, row_ws, dlogits, ld_dlogits, bad_flag);
     QARIG_CHECK_LAUNCH("cross_entropy rows");
     hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, st, row_ws, M, inv_m, loss);
     QARIG_CHECK_LAUNCH("cross_entropy mean");
     return QARIG_OK;
+}
+
+extern "C" int qarig_cross_entropy_fwd(const float* logits, const int64_t* target, int M, int C,
+                                       float* loss, float* dlogits, float* row_ws, int* bad_flag,
+                                       void* stream) {
+    return qarig_cross_entropy_ld_fwd(logits, C, target, M, C, loss, dlogits, C, row_ws, bad_flag, stream);
 }
 
 // ---- cross-entropy with label smoothing and z-loss (additive; the reference trains with neither) ----------------

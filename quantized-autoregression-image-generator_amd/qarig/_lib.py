@@ -36,6 +36,8 @@ SIGNATURES = {
     "qarig_bmu_fwd_coarse_ws": (I, [P, I, I, I, I, I, I, P, I, I, P, P, P, P, Z, P]),
     "qarig_bmu_prepare_bytes": (Z, [I, I]),
     "qarig_bmu_prepare": (I, [P, I, I, P, P]),
+    "qarig_gemm_ragged_tn": (I, [I, I, I]),
+    "qarig_gemm_ragged_nt": (I, [I, I, I]),
     "qarig_gemm_workspace_bytes": (Z, [I, I, I]),
     "qarig_gemm_f32": (I, [P, L, I, P, L, I, P, L, I, I, I, P, P, L, P, L, I, P, L, I, I, I, P, P, Z,
                            P]),
@@ -45,6 +47,7 @@ SIGNATURES = {
     "qarig_gemm_grouped_workspace_bytes": (Z, [I, I, I, I, I]),
     "qarig_gemm_f32_grouped": (I, [I, P, L, I, P, L, I, P, L, I, I, I, P, P, L, P, L, I, P, L, I, I, I, I, P,
                                    P, Z, P]),
+    "qarig_gemm_f32_strided": (I, [P, L, P, L, L, P, L, L, P, L, I, I, I, I, I, P]),
     "qarig_gemm_lp_supported": (I, [I, I, I, I]),
     "qarig_gemm_lp_workspace_bytes": (Z, [I, I, I]),
     "qarig_gemm_lp": (I, [P, L, P, L, I, P, L, I, I, I, P, P, L, P, L, I, P, L, I, I, I, I, P, L, P, L, P, Z,
@@ -111,6 +114,7 @@ SIGNATURES = {
     "qarig_window_append": (I, [P, P, P, I, L, P, P]),
     "qarig_attention_bwd": (I, [P, P, P, P, P, P, I, I, I, I, I, I, F, P, P, P, P, P]),
     "qarig_cross_entropy_fwd": (I, [P, P, I, I, P, P, P, P, P]),
+    "qarig_cross_entropy_ld_fwd": (I, [P, L, P, I, I, P, P, L, P, P, P]),
     "qarig_cross_entropy_reg_fwd": (I, [P, P, I, I, F, F, P, P, P, P, P]),
     "qarig_token_score": (I, [P, P, I, I, L, P, P, P, P]),
     "qarig_score_reduce": (I, [P, P, I, I, I, I, I, P, P, P, P, P]),

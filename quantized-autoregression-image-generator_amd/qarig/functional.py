@@ -48,7 +48,7 @@ def _wgrad(dT, X, param=None, bias_param=None, want_bias=False, flop_frac=1.0):
     (or not requested)."""
     M, N = dT.shape
     K = X.shape[1]
-    sk = ops.pick_splitk(N, K, M)
+    sk = ops.pick_splitk(ops.wgrad_ring_rows(N, K, M), K, M)
     wslot = _grad_slot(param)
     bslot = _grad_slot(bias_param) if want_bias else None
     if wslot is not None and (not want_bias or bslot is not None):
@@ -133,6 +133,21 @@ def linear_act(x, weight, bias=None, residual=None, act=0):
     return _LinearAct.apply(x, weight, bias, residual, act)
 
 
+def _zero_padded_rows(dy, M, N, ld):
+    """dy (..., N) as an (M, ld) fp32 matrix whose columns N .. ld - 1 are zero: the dense (M, ld) tensor dy is
+    the leading-column view of, as it lies (what _CrossEntropy hands back on strided logits; a GEMM that reduces
+    over the columns behind N multiplies them by zero rows of the padded weight), else a zero-filled copy."""
+    base = dy._base
+    if (dy.dtype == torch.float32 and base is not None and base.dtype == torch.float32 and base.shape == (M, ld)
+            and base.is_contiguous() and dy.data_ptr() == base.data_ptr() and dy.stride(-1) == 1):
+        d2 = dy.reshape(M, N)
+        if d2.data_ptr() == base.data_ptr() and d2.stride() == (ld, 1):
+            return base
+    out = torch.zeros((M, ld), dtype=torch.float32, device=dy.device)
+    out[:, :N].copy_(dy.reshape(M, N))
+    return out
+
+
 class _MLP2(torch.autograd.Function):
     """y = act2(act1(x W1^T + b1) W2^T + b2): the two-layer MLPs that make up q/k/v
     blocks, the FFN, the pos-cond MLP and the classifier (reference
@@ -155,7 +170,20 @@ class _MLP2(torch.autograd.Function):
         h, t1 = ops.gemm(x2, w1, bias=b1, want_preact=True, act=act1)
         N, K = w2.shape
         ctx.pad = _MLP2._padded_out(x2.shape[0], N, K, act2, b2)
-        if ctx.pad:
+        ctx.native = ctx.pad and ops.ragged_output_native(x2.shape[0], N, K)
+        if ctx.native:
+            # the GEMM entry takes the true width: ring on the first 128 q columns, tail kernel on the rest,
+            # into rows of whole 16-float groups; only the backward's zero-row-padded weight image is built
+            Kp = (N + 15) // 16 * 16
+            w2p = torch.zeros((Kp, K), dtype=torch.float32, device=w2.device)
+            w2p[:N].copy_(w2.detach())
+            ybuf = torch.empty((x2.shape[0], Kp), dtype=torch.float32, device=w2.device)
+            ops.gemm(h, w2.detach(), bias=b2.detach(), out=ybuf[:, :N])
+            ops.RAGGED_CALLS["forward"] += 1
+            # the logits stay in their buffer: a column slice, which cross_entropy reads at its row stride
+            y, t2 = ybuf[:, :N], None
+            ctx.save_for_backward(x2, w1, w2p, t1, h, t2)
+        elif ctx.pad:
             Np = (N + 127) // 128 * 128
             w2p = torch.zeros((Np, K), dtype=torch.float32, device=w2.device)
             w2p[:N].copy_(w2.detach())
@@ -176,8 +204,22 @@ class _MLP2(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x2, w1, w2, t1, h, t2 = ctx.saved_tensors
-        dy2 = _2d(f32c(dy))
         dx = dw1 = db1 = dw2 = db2 = None
+        if ctx.native:
+            # dlogits in rows of Kp floats with zero columns behind N (the cross-entropy node's buffer as it
+            # lies, else a zero-filled copy): the input gradient reduces over K' = Kp against the zero-row-padded
+            # weight image, the weight gradient takes the true 128 q + r rows straight into the .grad slots
+            N = ctx.params[2].shape[0]
+            dT2 = _zero_padded_rows(dy, x2.shape[0], N, w2.shape[0])
+            dT1 = ops.gemm(dT2, w2, a_kcontig=True, b_kcontig=False, gradz=t1, gact=ctx.act1,
+                           flop_frac=N / w2.shape[0])
+            if ctx.needs_input_grad[3]:
+                dw2, db2 = _wgrad(dT2[:, :N], h, ctx.params[2], ctx.params[3], ctx.needs_input_grad[4])
+                ops.RAGGED_CALLS["wgrad"] += 1
+            elif ctx.needs_input_grad[4]:
+                db2 = _bgrad(dT2[:, :N], ctx.params[3])
+            return (*_MLP2._backward_layer1(ctx, dy, dT1, x2, w1), dw2, db2, None, None)
+        dy2 = _2d(f32c(dy))
         if ctx.pad:
             N = ctx.params[2].shape[0]
             Np = w2.shape[0]                      # w2 here is the zero-padded copy
@@ -206,6 +248,11 @@ class _MLP2(torch.autograd.Function):
                 dw2, db2 = _wgrad(dT2, h, ctx.params[2], ctx.params[3], ctx.needs_input_grad[4])
             elif ctx.needs_input_grad[4]:
                 db2 = _bgrad(dT2, ctx.params[3])
+        return (*_MLP2._backward_layer1(ctx, dy, dT1, x2, w1), dw2, db2, None, None)
+
+    @staticmethod
+    def _backward_layer1(ctx, dy, dT1, x2, w1):
+        dx = dw1 = db1 = None
         if ctx.needs_input_grad[0]:
             dx = ops.gemm(dT1, w1, a_kcontig=True, b_kcontig=False).reshape(
                 *dy.shape[:-1], w1.shape[1])
@@ -213,7 +260,7 @@ class _MLP2(torch.autograd.Function):
             dw1, db1 = _wgrad(dT1, x2, ctx.params[0], ctx.params[1], ctx.needs_input_grad[2])
         elif ctx.needs_input_grad[2]:
             db1 = _bgrad(dT1, ctx.params[1])
-        return dx, dw1, db1, dw2, db2, None, None
+        return dx, dw1, db1
 
 
 def mlp2(x, w1, b1, w2, b2, act1, act2=0):
@@ -651,25 +698,51 @@ def embedding_pos(ids, table, pe=None):
     return _EmbeddingPos.apply(ids, table, pe)
 
 
+def _strided_rows(logits):
+    """logits (..., C) as an (M, C) view with unit column stride and a row stride > C, when they are such a slice
+    of a wider fp32 buffer (no copy); None for dense or otherwise laid out logits."""
+    if logits.dtype != torch.float32 or logits.dim() < 2 or logits.is_contiguous() or logits.stride(-1) != 1:
+        return None
+    C = logits.shape[-1]
+    M = logits.numel() // C
+    if M < 2:
+        return None
+    l2 = logits.reshape(M, C)
+    if l2.data_ptr() != logits.data_ptr() or l2.stride(1) != 1 or l2.stride(0) <= C:
+        return None
+    return l2
+
+
 class _CrossEntropy(torch.autograd.Function):
     """mean CE over rows; the logits gradient is produced in the forward pass."""
 
     @staticmethod
     def forward(ctx, logits, target):
         require_cuda(logits, target)
-        l2 = _2d(f32c(logits))
         t = target.reshape(-1)
         if t.dtype != torch.int64:
             t = t.long()
-        loss, dl = ops.cross_entropy_fwd(l2, t.contiguous(), want_grad=True)
-        ctx.save_for_backward(dl)
         ctx.shape = logits.shape
+        ctx.cols = None
+        l2 = _strided_rows(logits)
+        if l2 is not None:
+            # logits left in a wider buffer by their producer (the classifier's (M, 528) GEMM output): read at
+            # their row stride; the gradient goes back in rows of the same stride, zero behind the classes
+            loss, dl = ops.cross_entropy_ld_fwd(l2, t.contiguous(), want_grad=True)
+            ops.RAGGED_CALLS["ce_ld"] += 1
+            ctx.cols = l2.shape[1]
+        else:
+            loss, dl = ops.cross_entropy_fwd(_2d(f32c(logits)), t.contiguous(), want_grad=True)
+        ctx.save_for_backward(dl)
         return loss
 
     @staticmethod
     def backward(ctx, dloss):
         (dl,) = ctx.saved_tensors
-        return ops.scale_by(dl, f32c(dloss).reshape(1)).reshape(ctx.shape), None
+        g = ops.scale_by(dl, f32c(dloss).reshape(1))
+        if ctx.cols is not None:
+            return g[:, :ctx.cols].reshape(ctx.shape), None
+        return g.reshape(ctx.shape), None
 
 
 class _CrossEntropyReg(torch.autograd.Function):
@@ -928,7 +1001,7 @@ class CondTable:
         if group is None:
             return linear_act(self.table, linear.weight, linear.bias)
         params = [t for l in group for t in (l.weight, l.bias)]
-        outs = _TableProjections.apply(self.table, *params)
+        outs = table_projections(self.table, params)
         for l, o in zip(group, outs):
             self._proj[id(l)] = o
         return self._proj[id(linear)]
@@ -979,14 +1052,19 @@ class CondTokens:
 
 class _TableProjections(torch.autograd.Function):
     """G projections of the same (P,D) table, out_g = table W_g^T + b_g.  Up to 512 rows: one grouped
-    skinny launch; backward as two GEMMs over the concatenated gradients (d-table with K = G*D,
-    d-weights as one (G*D, D) product) instead of 2G small ones.  Longer tables: grouped 128 x 128-tile
+    skinny launch (_TableProjectionsRing: one strided-groups launch on the ring); backward as two GEMMs
+    over the concatenated gradients (d-table with K = G*D, d-weights as one (G*D, D) product) instead of 2G
+    small ones.  Longer tables: grouped 128 x 128-tile
     launches of up to 16 members on the parameters where they lie (no stacked copy) -- forward, the
     d-table sum over the members, and the weight gradients with their bias row sums accumulated
     straight into the .grad slots."""
 
     @staticmethod
     def forward(ctx, table, *params):
+        return _TableProjections._forward(ctx, False, table, *params)
+
+    @staticmethod
+    def _forward(ctx, ring, table, *params):
         require_cuda(table)
         weights, biases = params[0::2], params[1::2]
         tab = f32c(table)
@@ -1004,7 +1082,10 @@ class _TableProjections(torch.autograd.Function):
             return tuple(out.unbind(0))
         W = torch.stack([w.detach() for w in weights])             # (G, D, D)
         b = torch.stack([v.detach() for v in biases])               # (G, D)
-        out = ops.gemm_grouped_skinny(tab, W, b, shared_a=True)     # (G, P, D)
+        if ring:
+            out = ops.gemm_strided(tab, W, b)                       # (G, P, D)
+        else:
+            out = ops.gemm_grouped_skinny(tab, W, b, shared_a=True)     # (G, P, D)
         ctx.save_for_backward(tab, W)
         return tuple(out.unbind(0))
 
@@ -1070,6 +1151,31 @@ class _TableProjections(torch.autograd.Function):
             for g in range(G):
                 grads += [dW[g], db[g]]
         return tuple(grads)
+
+
+class _TableProjectionsRing(torch.autograd.Function):
+    """_TableProjections with its forward as ONE launch of G * (P/128) * (D/128) tiles on the fp32 ring
+    (ops.gemm_strided) and the same backward; table_projections chooses it.  A node of its own, not a subclass:
+    whatever wraps _TableProjections.apply (tests count its calls) does not reach this one."""
+
+    @staticmethod
+    def forward(ctx, table, *params):
+        return _TableProjections._forward(ctx, True, table, *params)
+
+    @staticmethod
+    def backward(ctx, *douts):
+        return _TableProjections.backward(ctx, *douts)
+
+
+def table_projections(table, params):
+    """_TableProjections of `table` by params = [w_0, b_0, w_1, b_1, ...].  Training (grad mode on), whole 128-row
+    tiles and a launch that fills the chip (BASELINE config 2: 42 projections of 384 positions): the ring node;
+    no-grad callers (generation) and every other shape keep the skinny / tiled launches and their bits."""
+    P, D = table.shape
+    if (torch.is_grad_enabled() and P <= 512 and D % 256 == 0
+            and ops.table_forward_ring(len(params) // 2, P, D)):
+        return _TableProjectionsRing.apply(table, *params)
+    return _TableProjections.apply(table, *params)
 
 
 # which path the table consumers' backward passes took, counted per call (ops.table_bwd_fused decides): the

@@ -200,7 +200,8 @@ def gemm(A, B, a_kcontig=True, b_kcontig=True, bias=None, residual=None, want_pr
     nws = 0
     if a_rowsum is not None:
         assert a_rowsum.shape == (M,) and a_rowsum.is_contiguous() and a_rowsum.dtype == torch.float32
-    if splitk > 1 or a_rowsum is not None:
+    # (the ragged weight-gradient route keeps its tail partials in the workspace at any split)
+    if splitk > 1 or a_rowsum is not None or (not a_kcontig and not b_kcontig and lib.qarig_gemm_ragged_tn(M, N, K)):
         nws = lib.qarig_gemm_workspace_bytes(M, N, splitk)
         ws = workspace(nws, A.device, "gemm")
         nws = ws.numel()
@@ -581,6 +582,50 @@ def gemm_grouped_skinny(A, W, bias=None, act=0, shared_a=False):
     return C
 
 
+# launches of the strided-groups ring product, counted per call (tests assert the training forward of a
+# position table took it)
+STRIDED_CALLS = {"gemm_strided": 0}
+# ragged-width routes taken by the Linear and loss nodes, counted per call: the classifier forward on its true width,
+# its weight gradient on the true rows, the cross-entropy launch on logits left in their padded buffer
+RAGGED_CALLS = {"forward": 0, "wgrad": 0, "ce_ld": 0}
+
+
+def gemm_strided_supported(M, N, K):
+    """Shapes gemm_strided takes: whole 128 x 128 tiles and 16-deep k-tiles (include/qarig.h)."""
+    return bool(_lib.load().qarig_gemm_grouped_supported(int(M), int(N), int(K), 1))
+
+
+def table_forward_ring(G, P, D):
+    """The training forward of G (D, D) projections of a (P, D) position table goes to gemm_strided when the
+    shape is one of its own and the launch gives every one of the 256 CUs a workgroup (BASELINE config 2: 42
+    projections of 384 positions, 504 tiles); a smaller launch leaves CUs idle behind lone waves, and the
+    skinny launch is kept (config 4's 256 encoder positions: 240 tiles)."""
+    return gemm_strided_supported(P, D, D) and G * (P // 128) * (D // 128) >= 256
+
+
+def gemm_strided(A, W, bias=None, act=0):
+    """out[g] = act(A @ W[g].T + bias[g]) for any number of groups that share A, as one launch of
+    G * (M/128) * (N/128) tiles on the fp32 ring (include/qarig.h qarig_gemm_f32_strided).
+    A: (M, K); W: (G, N, K); bias: (G, N) or None.  Returns (G, M, N)."""
+    require_cuda(A, W, bias)
+    G, N, K = W.shape
+    M, Ka = A.shape
+    assert Ka == K and W.is_contiguous() and A.is_contiguous() and A.dtype == W.dtype == torch.float32
+    if bias is not None:
+        assert bias.shape == (G, N) and bias.is_contiguous() and bias.dtype == torch.float32
+    C = torch.empty((G, M, N), dtype=torch.float32, device=A.device)
+    ev0 = _event_begin()
+    check(_lib.load().qarig_gemm_f32_strided(
+        ptr(A), K, ptr(W), K, N * K, ptr(C), N, M * N, ptr(bias), N, G, M, N, K, act, stream()),
+        "qarig_gemm_f32_strided")
+    STRIDED_CALLS["gemm_strided"] += 1
+    _event_end(ev0, M, G * N, K, lambda: (
+        "f32g" if lp_mode() else "",
+        f"f32 NT strided {G}x {M}x{N}x{K} out C in {'b' if bias is not None else '-'} act{act}",
+        4.0 * (M * K + G * N * K + G * M * N)))
+    return C
+
+
 def gemm_skinny_ln(x, W, bias=None, act=0, gamma=None, beta=None, scale=None, shift=None, eps=1e-5, mul=None):
     """out[g] = act(LN(x) @ W[g].T + bias[g]) [* mul]: the decode step's Linear with the LayerNorm in
     front of it (affine gamma/beta (K,) or AdaLN scale/shift (M, K); neither: none) and the gate
@@ -772,6 +817,24 @@ def _tile64_splitk(M, N, K):
     while tiles * s < 256 and K % (2 * s) == 0 and (K // (2 * s)) % 16 == 0 and K // (2 * s) >= 128:
         s *= 2
     return s
+
+
+def wgrad_ring_rows(M, N, K):
+    """Output rows of a weight gradient (M x N over a reduction of K rows) that run on the 128-tile ring:
+    M, or M - M % 128 where the GEMM entry takes its ragged route (qarig_gemm_ragged_tn: the last 1..8
+    rows go to the tail kernels) -- the row count a caller picks the reduction split for."""
+    if not lp_mode() and _lib.load().qarig_gemm_ragged_tn(int(M), int(N), int(K)):
+        return M - M % 128
+    return M
+
+
+def ragged_output_native(M, N, K):
+    """A Linear with N = 128 q + r output columns (1 <= r <= 8) over M rows of K features whose forward
+    product and weight gradient both take the GEMM entry's ragged routes (include/qarig.h): callers then
+    pass the true width instead of zero-padded copies."""
+    lib = _lib.load()
+    return (not lp_mode() and bool(lib.qarig_gemm_ragged_nt(int(M), int(N), int(K)))
+            and bool(lib.qarig_gemm_ragged_tn(int(N), int(K), int(M))))
 
 
 def pick_splitk(M, N, K):
@@ -1397,6 +1460,27 @@ def cross_entropy_fwd(logits2d, target, want_grad=True):
     check(_lib.load().qarig_cross_entropy_fwd(ptr(logits2d), ptr(target), M, C, ptr(loss), ptr(dl),
                                               ptr(rows), ptr(_bad_flag(logits2d.device)), stream()),
           "qarig_cross_entropy_fwd")
+    return loss, dl
+
+
+def cross_entropy_ld_fwd(logits2d, target, ld_grad=None, want_grad=True):
+    """cross_entropy_fwd on logits rows with a leading dimension (a column slice of a wider buffer; the columns
+    behind the slice are never read): (loss, dlogits), dlogits an (M, ld_grad) buffer (ld_grad >= C, default the
+    logits' row stride) whose columns C .. ld_grad - 1 are exact zeros.  include/qarig.h
+    qarig_cross_entropy_ld_fwd; the bits of cross_entropy_fwd on a dense copy."""
+    require_cuda(logits2d, target)
+    assert logits2d.dtype == torch.float32 and logits2d.dim() == 2 and logits2d.stride(1) == 1
+    assert target.dtype == torch.int64 and target.is_contiguous() and target.numel() == logits2d.shape[0]
+    M, C = logits2d.shape
+    ld = logits2d.stride(0) if M > 1 else max(C, logits2d.stride(0))
+    ld_grad = ld if ld_grad is None else int(ld_grad)
+    assert ld >= C and ld_grad >= C
+    loss = torch.empty((), dtype=torch.float32, device=logits2d.device)
+    dl = torch.empty((M, ld_grad), dtype=torch.float32, device=logits2d.device) if want_grad else None
+    rows = torch.empty(M, dtype=torch.float32, device=logits2d.device)
+    check(_lib.load().qarig_cross_entropy_ld_fwd(ptr(logits2d), ld, ptr(target), M, C, ptr(loss), ptr(dl), ld_grad,
+                                                 ptr(rows), ptr(_bad_flag(logits2d.device)), stream()),
+          "qarig_cross_entropy_ld_fwd")
     return loss, dl
 
 
