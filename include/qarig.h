@@ -762,6 +762,48 @@ int qarig_adamw_step(float* p, const float* g, float* m, float* v, float* ema, c
                      float ema_w, float decay, float grad_scale, const float* dev_step, void* shadow_bf16,
                      void* stream);
 
+/* Global-norm gradient clipping with a guard for non-finite gradients (additive: the reference trains without),
+ * torch.nn.utils.clip_grad_norm_'s rule on one flat buffer, decided and applied on the device.
+ *
+ * qarig_grad_clip_coef -- two launches.  Normative:
+ *   s_i  = fp32(g[i] * grad_scale)                  the value the Adam entries use, one fp32 rounding
+ *   sum  = sum_i (double)s_i * (double)s_i          every product exact (48 bits in 53), accumulated in fp64
+ *   norm = sqrt(sum)                                fp64; cannot overflow (2^40 squares of fp32 values < 1e90)
+ *   coef = fp32(min(1, max_norm / (norm + 1e-6)))   evaluated in double, rounded once; max_norm = +inf gives 1
+ *   norm not finite (<=> some s_i is not finite):   coef = 0 and the step counts as skipped
+ * Summation order (fixed: the same data give the same bits on every call and every rank).  Stage 1 runs
+ * B = min(ceil(n / 1024), QARIG_GRAD_NORM_PARTIALS) workgroups of 256 threads.  Lane l of workgroup b owns the
+ * 16-byte vectors j = 256 b + l + 256 B t, t = 0, 1, ...; it adds their elements to ONE fp64 accumulator, trips
+ * ascending, the four elements of a vector in index order (four trips' loads are in flight before the first
+ * use).  The lane whose sequence reaches j = floor(n / 4) then adds the n % 4 tail elements in order; nothing at
+ * or behind n is read.  A wave adds its 64 accumulators by the xor butterfly with offsets 32, 16, 8, 4, 2, 1 (x
+ * <- x + x[lane ^ o]); the workgroup adds its four wave sums as ((w0 + w1) + w2) + w3 and stores partials[b] (a
+ * vector store).  Stage 2, one workgroup: thread t adds partials[t], partials[t + 256], ... ascending, then the
+ * same butterfly and wave order.
+ * state: FOUR doubles that live across steps.  The call writes state[0] = norm and state[1] = coef, adds 1 to
+ * state[2] (steps skipped so far) when norm is not finite, and adds 1 to state[3] (steps clipped so far) when
+ * norm is finite and coef < 1.  The caller zeroes state once.  partials: QARIG_GRAD_NORM_PARTIALS doubles of
+ * scratch (the first B are written).  No atomics.
+ * Refused (-1) without a launch: null g, partials or state; n outside [1, 2^40]; g not 16-byte aligned
+ * (partials, state: 8-byte); max_norm not > 0, or NaN; grad_scale not finite.
+ *
+ * qarig_adam_clip_step -- qarig_adamw_step's arguments plus clip_state (the four doubles above, read only).
+ * Every thread first reads clip_state[0] and clip_state[1].  If clip_state[0] is not finite the kernel returns at
+ * once: p, m, v, ema and shadow_bf16 keep their bits (the step is skipped).  Otherwise, per element,
+ *   gi = fp32(fp32(g[i] * grad_scale) * coef),  coef = fp32(clip_state[1])       two roundings, no contraction
+ * and the rest is qarig_adamw_step's arithmetic with this gi.  decay_mask may be NULL (no element is decayed and
+ * the host decay is not looked at); ema may be NULL; dev_step (optional) is ALWAYS a device float[4], {step_size,
+ * bc2_sqrt, ema_w, decay}.  At coef == 1 every output is bit-identical to qarig_adam_step / qarig_adam_ema_step
+ * (no mask) or qarig_adamw_step (mask) on the same inputs.  Refused (-1) without a launch: as qarig_adamw_step
+ * (a null decay_mask excepted), plus a null or misaligned clip_state. */
+#define QARIG_GRAD_NORM_PARTIALS 2048
+int qarig_grad_clip_coef(const float* g, int64_t n, float grad_scale, double max_norm, double* partials,
+                         double* state, void* stream);
+int qarig_adam_clip_step(float* p, const float* g, float* m, float* v, float* ema, const unsigned char* decay_mask,
+                         int64_t n, float beta1, float beta2, float eps, float step_size, float bc2_sqrt,
+                         float ema_w, float decay, float grad_scale, const float* dev_step, void* shadow_bf16,
+                         const double* clip_state, void* stream);
+
 /* Exchanges two fp32 buffers of n elements in place, bit for bit (NaN payloads included): 16-byte accesses
  * where both buffers are 16-byte aligned, with a scalar tail; scalar throughout otherwise.  The buffers must
  * not overlap; null pointers, n <= 0 and overlapping ranges are refused (-1) without a launch. */

@@ -130,6 +130,8 @@ SIGNATURES = {
     "qarig_adam_step": (I, [P, P, P, P, L, F, F, F, F, F, F, P, P, P]),
     "qarig_adam_ema_step": (I, [P, P, P, P, P, L, F, F, F, F, F, F, F, P, P, P]),
     "qarig_adamw_step": (I, [P, P, P, P, P, P, L, F, F, F, F, F, F, F, F, P, P, P]),
+    "qarig_grad_clip_coef": (I, [P, L, F, D, P, P, P]),
+    "qarig_adam_clip_step": (I, [P, P, P, P, P, P, L, F, F, F, F, F, F, F, F, P, P, P, P]),
     "qarig_swap_f32": (I, [P, P, L, P]),
     "qarig_mul_fwd": (I, [P, P, P, L, P]),
     "qarig_mul_bwd": (I, [P, P, P, P, P, L, P]),

@@ -307,6 +307,42 @@ def optimizer_args_are_default(weight_decay, lr_schedule, lr_warmup_steps, lr_de
         and lr_min_ratio == 0
 
 
+def clip_grad_norm_arg(text):
+    """argparse type of --clip-grad-norm: a float > 0, or inf (the non-finite guard alone)."""
+    import argparse
+    try:
+        v = float(text)
+    except ValueError:
+        v = float("nan")
+    if not v > 0.0:
+        raise argparse.ArgumentTypeError(f"--clip-grad-norm must be > 0 (or inf), got {text}")
+    return v
+
+
+def add_grad_clip_args(p):
+    """--clip-grad-norm and --max-skipped-steps of a Transformer training command line (additive; without the first
+    the loop is the reference's)."""
+    p.add_argument("--clip-grad-norm", type=clip_grad_norm_arg, default=None,
+                   help="(additive; the reference trains without) clip the global L2 norm of all gradients to C > 0 "
+                        "before the optimiser step, torch.nn.utils.clip_grad_norm_'s rule, measured and applied on "
+                        "the device; `inf` clips nothing.  With the flag a step whose gradients are not all finite "
+                        "is skipped on the device (parameters, moments and EMA keep their bits) instead of ending "
+                        "the run, and the log line carries Grad Norm | Clipped | Skipped")
+    p.add_argument("--max-skipped-steps", type=_steps_arg("--max-skipped-steps", 0), default=10,
+                   help="(additive; with --clip-grad-norm) end the run once more than this many consecutive steps "
+                        "were skipped (default 10).")
+
+
+def check_grad_clip_args(clip_grad_norm, max_skipped_steps):
+    """The two values once more before anything is launched with them, or ValueError.  Returns them:
+    (clip_grad_norm or None, max_skipped_steps)."""
+    if clip_grad_norm is not None and not float(clip_grad_norm) > 0.0:       # (NaN fails the comparison)
+        raise ValueError(f"--clip-grad-norm must be > 0 (or inf), got {clip_grad_norm}")
+    if isinstance(max_skipped_steps, bool) or int(max_skipped_steps) != max_skipped_steps or max_skipped_steps < 0:
+        raise ValueError(f"--max-skipped-steps must be an integer >= 0, got {max_skipped_steps}")
+    return None if clip_grad_norm is None else float(clip_grad_norm), int(max_skipped_steps)
+
+
 def check_prompt_args(prompt_fmaps, prompt_fraction):
     """generate_images.py --prompt-fmaps / --prompt-fraction: both or neither, the fraction inside (0, 1).
     Returns whether the run is prompted."""

@@ -1666,6 +1666,39 @@ def adamw_step(p, g, m, v, ema, decay_mask, beta1, beta2, eps, step_size, bc2_sq
           "qarig_adamw_step")
 
 
+GRAD_NORM_PARTIALS = 2048       # include/qarig.h QARIG_GRAD_NORM_PARTIALS: doubles in grad_clip_coef's scratch buffer
+
+
+def grad_clip_coef(g, grad_scale, max_norm, partials, state):
+    """Global norm of fp32(g * grad_scale) and the clip coefficient fp32(min(1, max_norm / (norm + 1e-6))), left
+    on the device: state (4 doubles) receives {norm, coef} and counts skipped (non-finite norm) and clipped steps
+    in state[2] and state[3].  partials: GRAD_NORM_PARTIALS doubles of scratch.  Two launches, no read-back."""
+    require_cuda(g, partials, state)
+    assert g.dtype == torch.float32 and g.is_contiguous()
+    assert partials.dtype == torch.float64 and partials.is_contiguous() and partials.numel() >= GRAD_NORM_PARTIALS
+    assert state.dtype == torch.float64 and state.is_contiguous() and state.numel() == 4
+    check(_lib.load().qarig_grad_clip_coef(ptr(g), g.numel(), grad_scale, max_norm, ptr(partials), ptr(state),
+                                           stream()),
+          "qarig_grad_clip_coef")
+
+
+def adam_clip_step(p, g, m, v, ema, decay_mask, beta1, beta2, eps, step_size, bc2_sqrt, ema_w, decay, clip_state,
+                   grad_scale=1.0, dev_step=None, shadow=None):
+    """adamw_step with the gradient also scaled by clip_state[1], skipped on the device when clip_state[0] is not
+    finite (clip_state: the four doubles grad_clip_coef leaves).  ema and decay_mask may be None.  dev_step, when
+    given, holds four floats: {step_size, bc2_sqrt, ema_w, decay}."""
+    assert shadow is None or (shadow.dtype == torch.bfloat16 and shadow.numel() == p.numel())
+    assert ema is None or (ema.dtype == torch.float32 and ema.numel() == p.numel() and ema.is_contiguous())
+    assert decay_mask is None or (decay_mask.dtype == torch.uint8 and decay_mask.is_contiguous()
+                                  and decay_mask.is_cuda and decay_mask.numel() == (p.numel() + 7) // 8)
+    assert dev_step is None or dev_step.numel() == 4
+    assert clip_state.dtype == torch.float64 and clip_state.is_cuda and clip_state.numel() == 4
+    check(_lib.load().qarig_adam_clip_step(ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), ptr(decay_mask), p.numel(),
+                                           beta1, beta2, eps, step_size, bc2_sqrt, ema_w, decay, grad_scale,
+                                           ptr(dev_step), ptr(shadow), ptr(clip_state), stream()),
+          "qarig_adam_clip_step")
+
+
 def swap_(a, b):
     """Exchanges the contents of two fp32 tensors of equal size in place, bit for bit.  They must not overlap."""
     require_cuda(a, b)

@@ -9,7 +9,9 @@ decay; train_quantized_transformer.py:317-334), so "model_optimizer" entries of
 reference checkpoints load and save unchanged.
 
 Additive: enable_weight_decay (AdamW: decoupled decay of selected parameters from the same launch, through a
-mask of one byte per 8 elements) and LRSchedule (linear warm-up; the reference's halving rule or a cosine decay).
+mask of one byte per 8 elements), LRSchedule (linear warm-up; the reference's halving rule or a cosine decay) and
+enable_grad_clip (global-norm gradient clipping and a guard that skips a step with non-finite gradients, both decided
+on the device: two launches in the place of the one).
 """
 import contextlib
 import math
@@ -149,6 +151,7 @@ class FlatAdam:
         self.flat_ema = None        # enable_ema
         self._ema_swapped = False   # inside ema_weights()
         self.decay_mask = None      # enable_weight_decay
+        self.clip_max_norm = None   # enable_grad_clip
         with torch.no_grad():
             for p, o, s in zip(self.params, offs, sizes):
                 view = self.flat_param[o:o + s].view(p.shape)
@@ -260,6 +263,9 @@ class FlatAdam:
         if getattr(self, "flat_shadow", None) is None:
             self.flat_shadow = torch.empty(self.total, dtype=torch.bfloat16, device=self.flat_param.device)
             self._shadow_views = {}
+            if self.clip_max_norm is not None:
+                # a skipped step leaves the image as it is: it must hold the parameters before the first step
+                self.flat_shadow.copy_(self.flat_param)
         return self.flat_shadow
 
     def _shadow_written(self):
@@ -285,7 +291,15 @@ class FlatAdam:
         return v
 
     def _adam(self, b1, b2, eps, step_size, bc2_sqrt, ema_w, grad_scale, dev_step, shadow):
-        if self.decay_mask is not None:
+        if self.clip_max_norm is not None:
+            # the norm of the gradients as they stand now (behind any all-reduce: identical bits on every rank),
+            # then the step that reads its verdict from the device
+            ops.grad_clip_coef(self.flat_grad, grad_scale, self.clip_max_norm, self._clip_partials, self.clip_state)
+            decay = 0.0 if dev_step is not None or self.decay_mask is None else self._decay()
+            ops.adam_clip_step(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, self.flat_ema,
+                               self.decay_mask, b1, b2, eps, step_size, bc2_sqrt, ema_w, decay, self.clip_state,
+                               grad_scale, dev_step=dev_step, shadow=shadow)
+        elif self.decay_mask is not None:
             ops.adamw_step(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, self.flat_ema,
                            self.decay_mask, b1, b2, eps, step_size, bc2_sqrt, ema_w,
                            0.0 if dev_step is not None else self._decay(), grad_scale, dev_step=dev_step,
@@ -323,9 +337,10 @@ class FlatAdam:
     # -- graph replay (qarig.pipeline.GraphedTrainStep) -----------------------------------
     def _dev_step_buffer(self):
         if not hasattr(self, "_dev_step"):
-            # {step_size, bc2_sqrt} and, with the EMA on, its weight; with weight decay always four,
-            # {step_size, bc2_sqrt, ema_w, decay}
-            size = 4 if self.decay_mask is not None else 2 if self.flat_ema is None else 3
+            # {step_size, bc2_sqrt} and, with the EMA on, its weight; with weight decay or the gradient clip always
+            # four, {step_size, bc2_sqrt, ema_w, decay}
+            four = self.decay_mask is not None or self.clip_max_norm is not None
+            size = 4 if four else 2 if self.flat_ema is None else 3
             self._dev_step = torch.zeros(size, dtype=torch.float32, device=self.flat_param.device)
         return self._dev_step
 
@@ -355,10 +370,10 @@ class FlatAdam:
         if self.flat_ema is not None:
             scalars.append(ema_weight(self.ema_count, self.ema_decay, self.ema_warmup))
             self.ema_count += 1
-        if self.decay_mask is not None:
+        if self.decay_mask is not None or self.clip_max_norm is not None:
             if len(scalars) == 2:
                 scalars.append(0.0)         # (the EMA weight's slot: ignored without an EMA)
-            scalars.append(self._decay())
+            scalars.append(self._decay() if self.decay_mask is not None else 0.0)
         if not hasattr(self, "_dev_step_feed"):
             from .pipeline import PinnedFeed
             self._dev_step_feed = PinnedFeed(self._dev_step_buffer())
@@ -398,6 +413,41 @@ class FlatAdam:
         mask = decay_group_mask([p.numel() for p in self.params], self.offsets, self.total, flags)
         self.decay_mask = mask.to(self.flat_param.device)
         self.param_groups[0]["weight_decay"] = wd
+
+    # -- global-norm gradient clipping and the non-finite guard (additive: the reference trains without) ---------
+    def enable_grad_clip(self, max_norm):
+        """From here on every step first measures the global norm of the scaled gradients (qarig_grad_clip_coef:
+        fp64, one fixed summation order) and then runs qarig_adam_clip_step in the place of the plain launch: the
+        gradients enter Adam times coef = min(1, max_norm / (norm + 1e-6)), torch.nn.utils.clip_grad_norm_'s rule,
+        and a step whose norm is not finite changes nothing on the device.  max_norm = inf keeps the guard alone.
+        Norm, coefficient and both counts stay on the device (clip_state; clip_stats() reads them back).  A skipped
+        step still advances step_count, the EMA's update count and whatever else the host counts: the host does
+        not learn of the skip.  Must be called before a step is captured: the captured launches are different
+        ones and read a four-float scalar buffer."""
+        c = float(max_norm)
+        if not c > 0.0:                          # (NaN fails the comparison)
+            raise ValueError(f"gradient clipping: max_norm must be > 0 (inf: guard only), got {max_norm}")
+        if hasattr(self, "_dev_step"):
+            raise RuntimeError("FlatAdam.enable_grad_clip: a captured step was already recorded (its launch has "
+                               "no clip and reads a scalar buffer of another size); enable the clip before the "
+                               "first captured step")
+        if self._ema_swapped:
+            raise RuntimeError("FlatAdam.enable_grad_clip inside ema_weights()")
+        dev = self.flat_param.device
+        if self.clip_max_norm is None:
+            self.clip_state = torch.zeros(4, dtype=torch.float64, device=dev)
+            self._clip_partials = torch.zeros(ops.GRAD_NORM_PARTIALS, dtype=torch.float64, device=dev)
+            if getattr(self, "flat_shadow", None) is not None:
+                self.flat_shadow.copy_(self.flat_param)
+        self.clip_max_norm = c
+
+    def clip_stats(self):
+        """One read-back of clip_state: the last step's norm and coefficient, and how many steps were skipped
+        (non-finite norm) and clipped (coef < 1) so far."""
+        if self.clip_max_norm is None:
+            raise RuntimeError("FlatAdam: no gradient clip (call enable_grad_clip first)")
+        norm, coef, skipped, clipped = self.clip_state.tolist()
+        return {"norm": norm, "coef": coef, "skipped": int(skipped), "clipped": int(clipped)}
 
     # -- exponential moving average of the parameters (additive: the reference keeps none) ----------------
     def enable_ema(self, decay, warmup=True):

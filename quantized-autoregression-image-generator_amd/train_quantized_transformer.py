@@ -8,6 +8,7 @@ data parallelism (--batch-size is then per GPU; one RCCL all-reduce of the flat 
 buffer per step; rank 0 logs, checkpoints and samples)."""
 import argparse
 import logging
+import math
 import pathlib
 
 import torch
@@ -94,10 +95,12 @@ def parse_args():
     cc.add_regulariser_args(p)
     cc.add_dropout_args(p)
     cc.add_optimizer_args(p)
+    cc.add_grad_clip_args(p)
     args = vars(p.parse_args())
     try:        # what holds only between the flags (cosine needs --lr-decay-steps, at or past the warm-up)
         cc.check_optimizer_args(args["weight_decay"], args["lr_schedule"], args["lr_warmup_steps"],
                                 args["lr_decay_steps"], args["lr_min_ratio"])
+        cc.check_grad_clip_args(args["clip_grad_norm"], args["max_skipped_steps"])
     except ValueError as e:
         p.error(str(e))
     return args
@@ -177,6 +180,10 @@ def main():
                               decay_steps=lr_decay_steps, min_ratio=lr_min_ratio)
     if weight_decay > 0:
         optim.enable_weight_decay(weight_decay, decay_parameters(model))
+    clip_grad_norm, max_skipped_steps = cc.check_grad_clip_args(args["clip_grad_norm"], args["max_skipped_steps"])
+    if clip_grad_norm is not None:
+        # the norm is taken in optim.step(), behind the gradient exchange: the same bits on every rank
+        optim.enable_grad_clip(clip_grad_norm)
     # argparse has checked both; once more before anything is launched with them
     label_smoothing, z_loss = ops.check_ce_regularisers(args["label_smoothing"], args["z_loss"])
     regularised = label_smoothing > 0 or z_loss > 0
@@ -252,6 +259,9 @@ def main():
         if lr_decay_steps is not None:
             info(f"LR Decay Steps: {lr_decay_steps:,}")
         info(f"LR Min Ratio: {lr_min_ratio}")
+    if clip_grad_norm is not None:
+        info(f"Clip Grad Norm: {clip_grad_norm}")
+        info(f"Max Skipped Steps: {max_skipped_steps:,}")
     info("#" * 100)
     info("Sampling Parameters.")
     info(f"Temperature: {temperature:,}")
@@ -286,6 +296,8 @@ def main():
             model_dict["lr_warmup_steps"] = lr_warmup_steps
             model_dict["lr_decay_steps"] = lr_decay_steps
             model_dict["lr_min_ratio"] = lr_min_ratio
+        if clip_grad_norm is not None:      # informational likewise
+            model_dict["clip_grad_norm"] = clip_grad_norm
         ok = save_model(model_dict=model_dict, dest_path=out_dir, file_name=f"model_{global_steps}.pt",
                         logging=info)
         info("Successfully saved model." if ok else "Error occured saving model.")
@@ -360,8 +372,10 @@ def main():
                                             label_smoothing=label_smoothing, z_loss=z_loss)
     global_steps = 0
     done = False
+    skipped_before, skipped_run = 0, 0      # --clip-grad-norm: the device's count so far, consecutive skips
     for epoch in range(0, args["max_epoch"]):
         total_loss, total_nll, iteration_count = 0.0, 0.0, 0      # total_nll: with a regulariser only
+        averaged = 0            # --clip-grad-norm: the steps in the two running sums (skipped ones are left out)
         for index, feature_map in enumerate(loader):
             iteration_count += 1
             feature_map = feature_map.to(device)
@@ -389,15 +403,30 @@ def main():
                 loss = pipeline.train_step(model, optim, hr_in, lr_in, hr_tg, pos_idx,
                                            pos_bound=seq_total, label_smoothing=label_smoothing,
                                            z_loss=z_loss)
+            nll_val = 0.0
             if regularised:                                          # one read-back for the two numbers
                 loss_val, nll_val = pipeline.loss_pair(loss).tolist()
-                total_nll += nll_val
             else:
                 loss_val = loss.item()                               # the reference's per-step sync
             ops.check_index_flag(device, "training batch")
-            if loss_val != loss_val:
-                raise Exception("NaN encountered during training.")
-            total_loss += loss_val
+            clip = None
+            if clip_grad_norm is None:
+                if loss_val != loss_val:
+                    raise Exception("NaN encountered during training.")
+                total_loss += loss_val
+                total_nll += nll_val
+            else:
+                # the device has already decided: a step with a non-finite gradient changed nothing
+                clip = optim.clip_stats()
+                skipped_run = skipped_run + 1 if clip["skipped"] > skipped_before else 0
+                skipped_before = clip["skipped"]
+                if skipped_run > max_skipped_steps:
+                    raise Exception(f"{skipped_run} consecutive steps skipped for non-finite gradients "
+                                    f"(--max-skipped-steps {max_skipped_steps}).")
+                if math.isfinite(loss_val) and math.isfinite(clip["norm"]) and math.isfinite(nll_val):
+                    total_loss += loss_val
+                    total_nll += nll_val
+                    averaged += 1
             if schedule is None and global_steps % args["lr_step"] == 0 and global_steps > 0:
                 cc.halve_lr(optim)
             if global_steps % args["checkpoint_step"] == 0 and global_steps >= 0 and rank == 0:
@@ -406,8 +435,11 @@ def main():
                 validate(global_steps)
             info("Cum. Steps: {:,} | Steps: {:,} / {:,} | L.R.: {:.8f} | Recon Loss: {:.5f}".format(
                 global_steps + 1, index + 1, len(loader), optim.param_groups[0]["lr"],
-                total_loss / iteration_count) +
-                (" | NLL: {:.5f}".format(total_nll / iteration_count) if regularised else ""))
+                total_loss / (iteration_count if clip is None else max(averaged, 1))) +
+                (" | NLL: {:.5f}".format(total_nll / (iteration_count if clip is None else max(averaged, 1)))
+                 if regularised else "") +
+                ("" if clip is None else " | Grad Norm: {:.5f} | Clipped: {:,} | Skipped: {:,}".format(
+                    clip["norm"], clip["clipped"], clip["skipped"])))
             global_steps += 1
             if args["max_steps"] is not None and global_steps >= args["max_steps"]:
                 done = True
