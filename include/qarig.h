@@ -876,6 +876,10 @@ size_t qarig_conv2d_bwd_data_workspace_bytes(int Cin, int Cout, int k);
 /* ... plus room for the split slabs of a few-image launch (3x3 / stride 1; the stride-2 input gradient is never
  * split; see qarig_conv2d_fwd_workspace_bytes_n) */
 size_t qarig_conv2d_bwd_data_workspace_bytes_n(int N, int Cin, int H, int W, int Cout, int k, int stride);
+/* qarig_conv2d_bwd_data accepts k 1..4, stride 1..2 and 0 <= pad < k (anything else: QARIG_ERR_ARG,
+ * "conv2d_bwd_data: unsupported geometry", nothing launched) and writes every element of dx: input positions
+ * that no output window reads (rows and columns past the last window, the odd positions of a 1x1 / stride-2
+ * layer) receive zero. */
 int qarig_conv2d_bwd_data(const float* dT, int N, int Cout, int Ho, int Wo, const float* w, int Cin,
                           int k, int stride, int pad, int H, int W, float* dx, void* workspace,
                           size_t ws_bytes, void* stream);

@@ -1408,7 +1408,9 @@ static int conv2d_fwd_impl(const float* x, int N, int Cin, int H, int W, const f
 
     QARIG_CHECK_ARG(act >= 0 && act <= 3, "conv2d: bad activation id");
     const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
-    QARIG_CHECK_ARG(Ho > 0 && Wo > 0, "conv2d: empty output");
+    // (the window must fit: a negative numerator truncates towards zero, so Ho alone would read 1 at stride > 1)
+    QARIG_CHECK_ARG(H + 2 * pad >= k && W + 2 * pad >= k && Ho > 0 && Wo > 0, "conv2d: empty output");
+    QARIG_CHECK_ARG(y, "conv2d: null pointer");
     QARIG_CHECK_ARG((int64_t)N * Ho * Wo < INT32_MAX && (int64_t)Cin * k * k < INT32_MAX &&
                         (int64_t)Cin * H * W < INT32_MAX,
                     "conv2d: too large");
@@ -1565,6 +1567,14 @@ extern "C" int qarig_conv2d_bwd_data(const float* dT, int N, int Cout, int Ho, i
         if (H == s * Ho && W == s * Wo && conv_ring_usable(p, dT, o, workspace, ws_bytes))
             return run_conv_ring(p, dT, w, o, workspace, ws_bytes, false, st);
     }
+    // k < stride (1x1 / stride 2): the parity classes that no tap reaches are input positions no output reads.
+    // Their gradient is zero: one clear of dx, then only the classes with taps are launched.  (Every other
+    // geometry has taps in every class and clears nothing; positions past the last window read nothing of dT
+    // and are written as zero by their class.)
+    if (k < s && hipMemsetAsync(dx, 0, (size_t)N * Cin * H * W * sizeof(float), st) != hipSuccess) {
+        qarig_set_error("conv2d_bwd_data: clearing dx failed");
+        return QARIG_ERR_LAUNCH;
+    }
     for (int ry = 0; ry < s; ++ry)
         for (int rx = 0; rx < s; ++rx) {
             const int gh = (H - ry + s - 1) / s, gw = (W - rx + s - 1) / s;
@@ -1572,10 +1582,10 @@ extern "C" int qarig_conv2d_bwd_data(const float* dT, int N, int Cout, int Ho, i
             const int ky0 = (ry + pad) % s, kx0 = (rx + pad) % s;
             const int nty = ky0 < k ? (k - ky0 + s - 1) / s : 0;
             const int ntx = kx0 < k ? (k - kx0 + s - 1) / s : 0;
+            if (nty == 0 || ntx == 0) continue;              // only for k < stride: cleared above
             ConvGeom g{dT, N, Cout, Ho, Wo, gh, gw, 1, nty, ntx, (ry + pad - ky0) / s, -1,
                        (rx + pad - kx0) / s, -1, Cout * nty * ntx, N * gh * gw};
             ConvOut o{dx, nullptr, nullptr, Cin, H, W, s, ry, rx, ACT_NONE};
-            if (nty == 0 || ntx == 0) return QARIG_ERR_ARG;  // cannot happen for pad < k
             hipLaunchKernelGGL(conv_bwd_pack_kernel, dim3(pack_grid((int64_t)Cin * Cout * nty * ntx)), dim3(256), 0, st, w,
                                Cout, Cin, k, s, ky0, kx0, nty, ntx, packed);
             QARIG_CHECK_LAUNCH("conv2d_bwd_data pack");
