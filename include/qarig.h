@@ -603,6 +603,31 @@ int qarig_attention_lp_bwd(const float* q, const float* k, const float* v, const
                            int causal, float sqrt_d, float* dq, float* dk, float* dv, float* delta,
                            void* stream);
 
+/* The four entries above with attention-probability dropout: o = ((M s) . softmax(S)) V, where the
+ * keep bit M of element (n, h, i, j) -- query i against key j, head h, sequence n -- comes from the Philox call
+ * of qarig_dropout below with counter ((n H + h) Sq + i, 2^31 | site << 23 | j >> 3, step, rank): one call
+ * serves the keys j & ~7 ... j | 7 of one query, key j reads word (j & 7) >> 1, low half when j is even, and is
+ * kept iff that value >= threshold.  The mask is regenerated in registers by the forward and both backward
+ * passes; lse is that of the undropped softmax; dS = P (M s dP - delta), dV = s sum_i M P dO.  threshold and
+ * scale as for qarig_dropout; key: DEVICE uint32[4] {seed_lo, seed_hi, step, rank}.  Refused (-1) without a
+ * launch: a null key, head dim 128, threshold outside [1, 58982], site >= 256, Sk > 2^26, N H Sq >= 2^32. */
+int qarig_attention_dropout_fwd(const float* q, const float* k, const float* v, int N, int Sq, int Sk, int H,
+                                int d, int causal, float sqrt_d, float* o, float* lse, void* stream,
+                                uint32_t threshold, float scale, uint32_t site, const uint32_t* key);
+int qarig_attention_dropout_bwd(const float* q, const float* k, const float* v, const float* o,
+                                const float* dO, const float* lse, int N, int Sq, int Sk, int H, int d,
+                                int causal, float sqrt_d, float* dq, float* dk, float* dv, float* delta,
+                                void* stream, uint32_t threshold, float scale, uint32_t site,
+                                const uint32_t* key);
+int qarig_attention_dropout_lp_fwd(const float* q, const float* k, const float* v, int N, int Sq, int Sk, int H,
+                                   int d, int causal, float sqrt_d, float* o, float* lse, void* stream,
+                                   uint32_t threshold, float scale, uint32_t site, const uint32_t* key);
+int qarig_attention_dropout_lp_bwd(const float* q, const float* k, const float* v, const float* o,
+                                   const float* dO, const float* lse, int N, int Sq, int Sk, int H, int d,
+                                   int causal, float sqrt_d, float* dq, float* dk, float* dv, float* delta,
+                                   void* stream, uint32_t threshold, float scale, uint32_t site,
+                                   const uint32_t* key);
+
 /* Single-token decode step against a KV cache.  The reference has no cache: it re-runs the
  * whole window for every sampled token (generate_images.py:283-307,
  * train_quantized_transformer.py:600-640); this computes the same attention row

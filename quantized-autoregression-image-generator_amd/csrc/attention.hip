@@ -39,6 +39,7 @@
 // 0.5 |L| 2^-24 ln 2, which only scores far from zero (|L| in the hundreds) make visible.
 #include <stdlib.h>
 
+#include "dropout_philox.h"
 #include "qarig_common.h"
 
 namespace qarig {
@@ -48,6 +49,30 @@ struct AttnDims {
     float c2;   // log2(e) / sqrt(d)
     float rsd;  // 1 / sqrt(d)
 };
+// Attention-probability dropout (DROP = true instantiations): the mask of csrc/dropout_philox.h is
+// regenerated in registers by all three passes; `key` is the device key {seed_lo, seed_hi, step, rank}.  The plain
+// kernels keep AttnDims as their argument, so their argument segment and code are what they were.
+struct AttnDropDims : AttnDims {
+    uint32_t threshold;
+    float scale;
+    uint32_t c1;            // 2^31 | site << 23
+    const uint32_t* key;
+};
+template <bool DROP> struct DimsOf { typedef AttnDims T; };
+template <> struct DimsOf<true> { typedef AttnDropDims T; };
+
+// y[g'] bit r = x[r] bit g' within every aligned group of eight lanes (g = lane & 7): an 8 x 8 bit transpose in
+// three butterfly exchanges (lane ^ 4, ^ 2, ^ 1), each one swizzle and a select.
+template <int S, uint32_t LO>
+__device__ __forceinline__ uint32_t transpose8_stage(uint32_t x, int lane) {
+    const uint32_t y = (uint32_t)__builtin_amdgcn_ds_swizzle((int)x, 0x1f | (S << 10));   // lane ^ S, within 32
+    return (lane & S) ? (((y >> S) & LO) | (x & ~LO)) : ((x & LO) | ((y & LO) << S));
+}
+__device__ __forceinline__ uint32_t transpose8(uint32_t x, int lane) {
+    x = transpose8_stage<4, 0x0fu>(x, lane);
+    x = transpose8_stage<2, 0x33u>(x, lane);
+    return transpose8_stage<1, 0x55u>(x, lane);
+}
 
 __device__ __forceinline__ float exp2_fast(float x) { return __builtin_amdgcn_exp2f(x); }
 
@@ -183,10 +208,11 @@ __device__ __forceinline__ void acc_cols(f32x4& o, const T* trp, const Vals<LP>&
 }
 
 // Forward.  Lane = query; wave = (head hh = wave % 4, query slice qq = wave / 4).
-template <int HD, int MAXT, bool LP>
+template <int HD, int MAXT, bool LP, bool DROP>
 __global__ __launch_bounds__(MAXT) void attn_fwd_kernel(const float* __restrict__ q,
                                                         const float* __restrict__ k,
-                                                        const float* __restrict__ v, AttnDims a,
+                                                        const float* __restrict__ v,
+                                                        typename DimsOf<DROP>::T a,
                                                         float* __restrict__ o,
                                                         float* __restrict__ lse) {
     typedef typename Elem<LP>::T T;
@@ -295,6 +321,29 @@ __global__ __launch_bounds__(MAXT) void attn_fwd_kernel(const float* __restrict_
             }
             l += lsum[0] + lsum[1];
             m = mn;
+            if constexpr (DROP) {
+                // l, m and lr are those of the undropped softmax; the PV product takes +0 where dropped.  One call
+                // per eight keys, made by every lane (the key words and c0 are loop invariants); masked keys have
+                // p = 0 already.
+                const uint32_t dc0 = attn_dropout_c0((uint32_t)n, (uint32_t)a.H, (uint32_t)h, (uint32_t)a.Sq, (uint32_t)i);
+                bool keep[KS];
+#pragma unroll
+                for (int e = 0; e < KS / 8; ++e) {
+                    uint32_t w[4];
+                    philox4x32_10(dc0, a.c1 | (uint32_t)((j0 >> 3) + e), a.key[2], a.key[3], a.key[0], a.key[1], w);
+#pragma unroll
+                    for (int r = 0; r < 8; ++r) keep[8 * e + r] = dropout_value(w[r >> 1], r, a.threshold);
+                }
+#pragma unroll
+                for (int u = 0; u < NQ; ++u) {
+                    if constexpr (LP) lr += sum4_bf16(pack4_bf16(p[4 * u], p[4 * u + 1], p[4 * u + 2], p[4 * u + 3]));
+                    const Vals<LP> pv = make_vals<LP>(keep[4 * u] ? p[4 * u] : 0.0f, keep[4 * u + 1] ? p[4 * u + 1] : 0.0f,
+                                                      keep[4 * u + 2] ? p[4 * u + 2] : 0.0f,
+                                                      keep[4 * u + 3] ? p[4 * u + 3] : 0.0f);
+#pragma unroll
+                    for (int g = 0; g < G; ++g) acc_cols<LP>(ov[g], Vc + (4 * g + li) * TS + jj + 4 * u, pv);
+                }
+            } else {
             // PV: keys ascending per output column group
 #pragma unroll
             for (int u = 0; u < NQ; ++u) {
@@ -302,6 +351,7 @@ __global__ __launch_bounds__(MAXT) void attn_fwd_kernel(const float* __restrict_
                 if constexpr (LP) lr += sum4_bf16(pv.b);
 #pragma unroll
                 for (int g = 0; g < G; ++g) acc_cols<LP>(ov[g], Vc + (4 * g + li) * TS + jj + 4 * u, pv);
+            }
             }
         }
         if (t + 1 < nchunks) {
@@ -312,22 +362,30 @@ __global__ __launch_bounds__(MAXT) void attn_fwd_kernel(const float* __restrict_
     }
     if (active) {
         float* op = o + ((int64_t)n * a.Sq + i) * D + h * HD;
+        if constexpr (DROP) {
+            const float inv = a.scale / (LP ? lr : l);
+#pragma unroll
+            for (int g = 0; g < G; ++g)
+                *reinterpret_cast<float4*>(op + 4 * g) =
+                    make_float4(ov[g][0] * inv, ov[g][1] * inv, ov[g][2] * inv, ov[g][3] * inv);
+        } else {
         const float inv = 1.0f / (LP ? lr : l);
 #pragma unroll
         for (int g = 0; g < G; ++g)
             *reinterpret_cast<float4*>(op + 4 * g) =
                 make_float4(ov[g][0] * inv, ov[g][1] * inv, ov[g][2] * inv, ov[g][3] * inv);
+        }
         lse[((int64_t)n * a.H + h) * a.Sq + i] = m + log2f(l);   // base-2 units
     }
 }
 
 // dQ pass: lane = query; per chunk the K rows, V rows and K transposed.  Also emits
 // delta[i] = sum_c dO[i][c] * O[i][c].
-template <int HD, int MAXT, bool LP>
+template <int HD, int MAXT, bool LP, bool DROP>
 __global__ __launch_bounds__(MAXT) void attn_bwd_dq_kernel(
     const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
     const float* __restrict__ o, const float* __restrict__ dO, const float* __restrict__ lse,
-    AttnDims a, float* __restrict__ dq, float* __restrict__ delta) {
+    typename DimsOf<DROP>::T a, float* __restrict__ dq, float* __restrict__ delta) {
     typedef typename Elem<LP>::T T;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     T* smem = reinterpret_cast<T*>(smem_raw);
@@ -413,6 +471,19 @@ __global__ __launch_bounds__(MAXT) void attn_bwd_dq_kernel(
                 dot_rows<LP, HD>(s[u], kr + 4 * u * Geo<HD>::RS, qv);
                 dot_rows<LP, HD>(dpv[u], vr + 4 * u * Geo<HD>::RS, dov);
             }
+            if constexpr (DROP) {          // dS = P (M s dPd - delta): a dropped element still carries -P delta
+                const uint32_t dc0 = attn_dropout_c0((uint32_t)n, (uint32_t)a.H, (uint32_t)h, (uint32_t)a.Sq, (uint32_t)i);
+#pragma unroll
+                for (int e = 0; e < KS / 8; ++e) {
+                    uint32_t w[4];
+                    philox4x32_10(dc0, a.c1 | (uint32_t)((j0 >> 3) + e), a.key[2], a.key[3], a.key[0], a.key[1], w);
+#pragma unroll
+                    for (int r = 0; r < 8; ++r) {
+                        const float x = dpv[2 * e + (r >> 2)][r & 3];
+                        dpv[2 * e + (r >> 2)][r & 3] = dropout_value(w[r >> 1], r, a.threshold) ? x * a.scale : 0.0f;
+                    }
+                }
+            }
             float ds[KS];
 #pragma unroll
             for (int u = 0; u < NQ; ++u)
@@ -450,11 +521,11 @@ __global__ __launch_bounds__(MAXT) void attn_bwd_dq_kernel(
 
 // dK/dV pass: lane = key; per chunk of queries the Q rows, dO rows and both transposed, plus
 // the chunk's LSE and delta values (wave-uniform per query: read as LDS broadcasts).
-template <int HD, int MAXT, bool LP>
+template <int HD, int MAXT, bool LP, bool DROP>
 __global__ __launch_bounds__(MAXT) void attn_bwd_dkv_kernel(
     const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
     const float* __restrict__ dO, const float* __restrict__ lse, const float* __restrict__ delta,
-    AttnDims a, float* __restrict__ dk, float* __restrict__ dv) {
+    typename DimsOf<DROP>::T a, float* __restrict__ dk, float* __restrict__ dv) {
     typedef typename Elem<LP>::T T;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     T* smem = reinterpret_cast<T*>(smem_raw);
@@ -568,10 +639,29 @@ __global__ __launch_bounds__(MAXT) void attn_bwd_dkv_kernel(
                 for (int r = 0; r < 8; ++r)
                     if (i0 + r >= i1 || (a.causal && j > i0 + r)) p[r] = 0.0f;
             }
+            if constexpr (DROP) {
+                // lane g = lane & 7 of an aligned group of eight makes the call of query i0 + g for the group's
+                // eight keys (k0 is a multiple of 64, so the group shares j >> 3); the group then transposes its
+                // 8 x 8 keep bits
+                uint32_t w[4];
+                philox4x32_10(attn_dropout_c0((uint32_t)n, (uint32_t)a.H, (uint32_t)h, (uint32_t)a.Sq,
+                                              (uint32_t)(i0 + (lane & 7))),
+                              a.c1 | ((uint32_t)j >> 3), a.key[2], a.key[3], a.key[0], a.key[1], w);
+                const uint32_t mk = transpose8(attn_dropout_keep8(w, a.threshold), lane);   // bit r: query i0 + r
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                ds[r] = p[r] * (d0[r] - Da[r]);
-                ds[4 + r] = p[4 + r] * (d1[r] - Db[r]);
+                for (int r = 0; r < 4; ++r) {
+                    const bool ka = (mk >> r) & 1u, kb = (mk >> (4 + r)) & 1u;
+                    ds[r] = p[r] * ((ka ? d0[r] * a.scale : 0.0f) - Da[r]);
+                    ds[4 + r] = p[4 + r] * ((kb ? d1[r] * a.scale : 0.0f) - Db[r]);
+                    p[r] = ka ? p[r] : 0.0f;              // dV = s sum M P dO: s at the store
+                    p[4 + r] = kb ? p[4 + r] : 0.0f;
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    ds[r] = p[r] * (d0[r] - Da[r]);
+                    ds[4 + r] = p[4 + r] * (d1[r] - Db[r]);
+                }
             }
             const Vals<LP> pa = make_vals<LP>(p[0], p[1], p[2], p[3]);
             const Vals<LP> pb = make_vals<LP>(p[4], p[5], p[6], p[7]);
@@ -620,6 +710,7 @@ __global__ __launch_bounds__(MAXT) void attn_bwd_dkv_kernel(
         for (int g = 0; g < G; ++g) {
             *reinterpret_cast<float4*>(dk + roff + 4 * g) =
                 make_float4(dka[g][0] * a.rsd, dka[g][1] * a.rsd, dka[g][2] * a.rsd, dka[g][3] * a.rsd);
+            if constexpr (DROP) dva[g] *= a.scale;
             *reinterpret_cast<float4*>(dv + roff + 4 * g) =
                 make_float4(dva[g][0], dva[g][1], dva[g][2], dva[g][3]);
         }
@@ -711,10 +802,45 @@ static size_t attn_lds_bytes(int threads, int d, int rows, int tr, bool ld, int 
     return ((img + 15) & ~(size_t)15) + (ld ? 2 * sizeof(float) * 2 * HPB * CH : 0);
 }
 
-template <bool LP>
+// The arguments the dropout entries add, and what they refuse before any launch.
+struct AttnDropArgs {
+    uint32_t threshold;
+    float scale;
+    uint32_t site;
+    const uint32_t* key;
+};
+static int attn_drop_check(const AttnDropArgs& dr, int N, int Sq, int Sk, int H, int d) {
+    QARIG_CHECK_ARG(dr.key, "attention dropout: null key");
+    QARIG_CHECK_ARG(d != 128, "attention dropout: head dim 128 (the wide-head kernels) is not supported");
+    QARIG_CHECK_ARG(dr.threshold >= 1 && dr.threshold <= QARIG_DROPOUT_MAX_THRESHOLD,
+                    "attention dropout: threshold must lie in [1, 58982] (0 < p <= 0.9)");
+    QARIG_CHECK_ARG(dr.scale > 0.0f && dr.scale <= 16.0f, "attention dropout: scale must lie in (0, 16]");
+    QARIG_CHECK_ARG(dr.site < QARIG_ATTN_DROPOUT_SITES, "attention dropout: site must be below 256");
+    QARIG_CHECK_ARG(Sk <= QARIG_ATTN_DROPOUT_MAX_SK, "attention dropout: more than 2^26 keys");
+    QARIG_CHECK_ARG(N <= 0 || Sq <= 0 || H <= 0 || (long long)N * H * Sq < (1LL << 32),
+                    "attention dropout: N * H * Sq must stay below 2^32 (one counter word)");
+    return QARIG_OK;
+}
+template <bool DROP>
+static typename DimsOf<DROP>::T attn_dims(const AttnDims& a, const AttnDropArgs* dr) {
+    typename DimsOf<DROP>::T ad;
+    static_cast<AttnDims&>(ad) = a;
+    if constexpr (DROP) {
+        ad.threshold = dr->threshold;
+        ad.scale = dr->scale;
+        ad.c1 = attn_dropout_c1(dr->site, 0);
+        ad.key = dr->key;
+    }
+    return ad;
+}
+
+template <bool LP, bool DROP = false>
 static int attention_fwd_impl(const float* q, const float* k, const float* v, int N, int Sq, int Sk,
-                              int H, int d, int causal, float sqrt_d, float* o, float* lse, void* stream) {
+                              int H, int d, int causal, float sqrt_d, float* o, float* lse, void* stream,
+                              const AttnDropArgs* dr = nullptr) {
     QARIG_CHECK_ARG(q && k && v && o && lse, "attention_fwd: null pointer");
+    if constexpr (DROP)
+        if (int e = attn_drop_check(*dr, N, Sq, Sk, H, d)) return e;
     if (d == 128) {
         if (int e = attn_wide_check(N, Sq, Sk, H, causal)) return e;
         QARIG_CHECK_ARG(sqrt_d > 0.0f, "attention: sqrt_d must be positive");
@@ -729,22 +855,25 @@ static int attention_fwd_impl(const float* q, const float* k, const float* v, in
     const int threads = 256 * W, rows = 64 * W;
     const size_t lds = attn_lds_bytes(threads, d, 1, 1, false, LP);
     dim3 grid((unsigned)(N * ((H + HPB - 1) / HPB) * ((Sq + rows - 1) / rows))), block(threads);
+    const typename DimsOf<DROP>::T ad = attn_dims<DROP>(a, dr);
     QARIG_HD_DISPATCH(d, {
-        auto kern = attn_fwd_kernel<HD, QARIG_FWD_MAXT(HD), LP>;
+        auto kern = attn_fwd_kernel<HD, QARIG_FWD_MAXT(HD), LP, DROP>;
         if (int e = attn_set_lds(kern, lds, "attention_fwd")) return e;
-        hipLaunchKernelGGL(kern, grid, block, lds, (hipStream_t)stream, q, k, v, a, o, lse);
+        hipLaunchKernelGGL(kern, grid, block, lds, (hipStream_t)stream, q, k, v, ad, o, lse);
     });
     QARIG_CHECK_LAUNCH("attention_fwd");
     return QARIG_OK;
 }
 
-template <bool LP>
+template <bool LP, bool DROP = false>
 static int attention_bwd_impl(const float* q, const float* k, const float* v, const float* o,
                               const float* dO, const float* lse, int N, int Sq, int Sk, int H, int d,
                               int causal, float sqrt_d, float* dq, float* dk, float* dv, float* delta,
-                              void* stream) {
+                              void* stream, const AttnDropArgs* dr = nullptr) {
     QARIG_CHECK_ARG(q && k && v && o && dO && lse && dq && dk && dv && delta,
                     "attention_bwd: null pointer");
+    if constexpr (DROP)
+        if (int e = attn_drop_check(*dr, N, Sq, Sk, H, d)) return e;
     if (d == 128) {
         if (int e = attn_wide_check(N, Sq, Sk, H, causal)) return e;
         QARIG_CHECK_ARG(sqrt_d > 0.0f, "attention: sqrt_d must be positive");
@@ -754,15 +883,16 @@ static int attention_bwd_impl(const float* q, const float* k, const float* v, co
     if (int e = attn_check(N, Sq, Sk, H, d, causal)) return e;
     AttnDims a{N, Sq, Sk, H, causal, 1.4426950408889634f / sqrt_d, 1.0f / sqrt_d};
     const int hgroups = (H + HPB - 1) / HPB;
+    const typename DimsOf<DROP>::T ad = attn_dims<DROP>(a, dr);
     {
         const int W = attn_waves(Sq, d, g_qarig_opt.attn_bw, 2, 2);
         const int threads = 256 * W, rows = 64 * W;
         const size_t lds = attn_lds_bytes(threads, d, 2, 1, false, LP);
         dim3 grid((unsigned)(N * hgroups * ((Sq + rows - 1) / rows))), block(threads);
         QARIG_HD_DISPATCH(d, {
-            auto kern = attn_bwd_dq_kernel<HD, 512, LP>;
+            auto kern = attn_bwd_dq_kernel<HD, 512, LP, DROP>;
             if (int e = attn_set_lds(kern, lds, "attention_bwd dq")) return e;
-            hipLaunchKernelGGL(kern, grid, block, lds, (hipStream_t)stream, q, k, v, o, dO, lse, a, dq, delta);
+            hipLaunchKernelGGL(kern, grid, block, lds, (hipStream_t)stream, q, k, v, o, dO, lse, ad, dq, delta);
         });
         QARIG_CHECK_LAUNCH("attention_bwd dq");
     }
@@ -772,9 +902,9 @@ static int attention_bwd_impl(const float* q, const float* k, const float* v, co
         const size_t lds = attn_lds_bytes(threads, d, 2, 2, true, LP);
         dim3 grid((unsigned)(N * hgroups * ((Sk + rows - 1) / rows))), block(threads);
         QARIG_HD_DISPATCH(d, {
-            auto kern = attn_bwd_dkv_kernel<HD, 512, LP>;
+            auto kern = attn_bwd_dkv_kernel<HD, 512, LP, DROP>;
             if (int e = attn_set_lds(kern, lds, "attention_bwd dkv")) return e;
-            hipLaunchKernelGGL(kern, grid, block, lds, (hipStream_t)stream, q, k, v, dO, lse, delta, a, dk, dv);
+            hipLaunchKernelGGL(kern, grid, block, lds, (hipStream_t)stream, q, k, v, dO, lse, delta, ad, dk, dv);
         });
         QARIG_CHECK_LAUNCH("attention_bwd dkv");
     }
@@ -812,6 +942,43 @@ extern "C" int qarig_attention_lp_bwd(const float* q, const float* k, const floa
                                       float* delta, void* stream) {
     return attention_bwd_impl<true>(q, k, v, o, dO, lse, N, Sq, Sk, H, d, causal, sqrt_d, dq, dk, dv,
                                     delta, stream);
+}
+
+// The four entries above with attention-probability dropout: o = ((M s) . softmax(S)) V with the keep
+// mask M of csrc/dropout_philox.h, regenerated by the two backward passes; lse is that of the undropped softmax.
+// threshold and scale as for qarig_dropout, site < 256, key = DEVICE uint32[4] {seed_lo, seed_hi, step, rank}.
+// Head dim 128 is refused.
+extern "C" int qarig_attention_dropout_fwd(const float* q, const float* k, const float* v, int N, int Sq, int Sk,
+                                           int H, int d, int causal, float sqrt_d, float* o, float* lse,
+                                           void* stream, uint32_t threshold, float scale, uint32_t site,
+                                           const uint32_t* key) {
+    const AttnDropArgs dr{threshold, scale, site, key};
+    return attention_fwd_impl<false, true>(q, k, v, N, Sq, Sk, H, d, causal, sqrt_d, o, lse, stream, &dr);
+}
+extern "C" int qarig_attention_dropout_bwd(const float* q, const float* k, const float* v, const float* o,
+                                           const float* dO, const float* lse, int N, int Sq, int Sk, int H, int d,
+                                           int causal, float sqrt_d, float* dq, float* dk, float* dv, float* delta,
+                                           void* stream, uint32_t threshold, float scale, uint32_t site,
+                                           const uint32_t* key) {
+    const AttnDropArgs dr{threshold, scale, site, key};
+    return attention_bwd_impl<false, true>(q, k, v, o, dO, lse, N, Sq, Sk, H, d, causal, sqrt_d, dq, dk, dv, delta,
+                                           stream, &dr);
+}
+extern "C" int qarig_attention_dropout_lp_fwd(const float* q, const float* k, const float* v, int N, int Sq, int Sk,
+                                              int H, int d, int causal, float sqrt_d, float* o, float* lse,
+                                              void* stream, uint32_t threshold, float scale, uint32_t site,
+                                              const uint32_t* key) {
+    const AttnDropArgs dr{threshold, scale, site, key};
+    return attention_fwd_impl<true, true>(q, k, v, N, Sq, Sk, H, d, causal, sqrt_d, o, lse, stream, &dr);
+}
+extern "C" int qarig_attention_dropout_lp_bwd(const float* q, const float* k, const float* v, const float* o,
+                                              const float* dO, const float* lse, int N, int Sq, int Sk, int H, int d,
+                                              int causal, float sqrt_d, float* dq, float* dk, float* dv,
+                                              float* delta, void* stream, uint32_t threshold, float scale,
+                                              uint32_t site, const uint32_t* key) {
+    const AttnDropArgs dr{threshold, scale, site, key};
+    return attention_bwd_impl<true, true>(q, k, v, o, dO, lse, N, Sq, Sk, H, d, causal, sqrt_d, dq, dk, dv, delta,
+                                          stream, &dr);
 }
 
 // One decode step with a KV cache (generation; no reference counterpart - the reference

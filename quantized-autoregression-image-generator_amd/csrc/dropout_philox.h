@@ -1,6 +1,8 @@
 // Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11) and the
 // keep rule of csrc/dropout.hip, in plain C++ for host and device: tests/test_dropout_host.py compiles this
 // header for the host alone and checks the known answers and the element layout against the NumPy reference.
+// The attention-probability counters and keep rule of csrc/attention.hip follow the same way
+// (tests/test_attn_dropout_host.py).
 #pragma once
 #include <stdint.h>
 
@@ -13,6 +15,8 @@
 #define QARIG_DROPOUT_MAX_THRESHOLD 58982u   // round(0.9 * 65536)
 #define QARIG_DROPOUT_BLOCK 256              // threads per workgroup, eight elements per thread-iteration
 #define QARIG_DROPOUT_MAX_BLOCKS 8192        // grid cap: larger launches wrap the grid-stride loop
+#define QARIG_ATTN_DROPOUT_SITES 256u        // attention sites 0 ... 255: eight bits of the second counter word
+#define QARIG_ATTN_DROPOUT_MAX_SK (1 << 26)  // key index >> 3 fits the 23 bits below the site
 
 namespace qarig {
 
@@ -41,6 +45,32 @@ QARIG_HD inline void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32
 // 16 bits when j is even, the high 16 when odd; kept iff that value >= threshold.
 QARIG_HD inline bool dropout_value(uint32_t w, int j, uint32_t threshold) {
     return ((j & 1) ? (w >> 16) : (w & 0xffffu)) >= threshold;
+}
+
+// ---- attention-probability dropout --------------------------------------------------------------------------
+// Element (n, h, i, j) = query i against key j in head h of sequence n, at attention site `site`: the call
+// philox4x32_10(c0, c1, step, rank, seed_lo, seed_hi) with c0 = (n H + h) Sq + i and c1 = 2^31 | site << 23 | j >> 3
+// serves the eight keys j & ~7 ... j | 7 of one query, 16 bits each by the rule above.  The set high bit of c1
+// keeps these counters apart from those of csrc/dropout.hip, whose second word is a small site ordinal.
+QARIG_HD inline uint32_t attn_dropout_c0(uint32_t n, uint32_t H, uint32_t h, uint32_t Sq, uint32_t i) {
+    return (n * H + h) * Sq + i;
+}
+QARIG_HD inline uint32_t attn_dropout_c1(uint32_t site, uint32_t j) {
+    return 0x80000000u | (site << 23) | (j >> 3);
+}
+// The keep bits of the eight keys of one call: bit b = key (j & ~7) + b.
+QARIG_HD inline uint32_t attn_dropout_keep8(const uint32_t out[4], uint32_t threshold) {
+    uint32_t m = 0;
+#pragma unroll
+    for (int b = 0; b < 8; ++b) m |= (uint32_t)dropout_value(out[b >> 1], b, threshold) << b;
+    return m;
+}
+QARIG_HD inline bool attn_dropout_keep(uint32_t n, uint32_t H, uint32_t h, uint32_t Sq, uint32_t i, uint32_t j,
+                                       uint32_t site, uint32_t threshold, uint32_t step, uint32_t rank,
+                                       uint32_t seed_lo, uint32_t seed_hi) {
+    uint32_t out[4];
+    philox4x32_10(attn_dropout_c0(n, H, h, Sq, i), attn_dropout_c1(site, j), step, rank, seed_lo, seed_hi, out);
+    return dropout_value(out[(j & 7) >> 1], (int)(j & 7), threshold);
 }
 
 }  // namespace qarig

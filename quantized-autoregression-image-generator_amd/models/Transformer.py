@@ -58,6 +58,7 @@ class Transformer(nn.Module):
                         use_activation=False))
         self._pe_cache = {}
         self._dropout = None        # (p, key) while enable_dropout is in force
+        self._attn_dropout = None   # (p, key) while enable_attention_dropout is in force
 
     def custom_load_state_dict(self, state_dict):
         load_matching(self, state_dict)
@@ -86,12 +87,12 @@ class Transformer(nn.Module):
         if p == 0:
             self.disable_dropout()
             return None
-        from qarig.dropout import DropoutKey, threshold_and_scale
+        from qarig.dropout import threshold_and_scale
         threshold_and_scale(p)      # ValueError outside (0, 0.9]
         device = self.dec_embedding.weight.device
         if device.type != "cuda":
             raise RuntimeError("Transformer.enable_dropout needs the model on the GPU (call model.to(device) first)")
-        key = DropoutKey(seed, rank, device)
+        key = self._shared_key(self._attn_dropout, seed, rank, device)
         self._dropout = (float(p), key)
         for i, res in enumerate(self._residual_layers()):
             res._dropout = (float(p), 2 + i, key)
@@ -102,10 +103,76 @@ class Transformer(nn.Module):
         for res in self._residual_layers():
             res._dropout = None
 
+    @staticmethod
+    def _shared_key(other, seed, rank, device):
+        """The model holds one DropoutKey: whichever of enable_dropout and enable_attention_dropout comes second
+        reuses the first one's (`other` = the other feature's state), and must name the same seed and rank."""
+        from qarig.dropout import DropoutKey
+        if other is None:
+            return DropoutKey(seed, rank, device)
+        key = other[1]
+        if (key.seed, key.rank) != (int(seed), int(rank)):
+            raise ValueError(f"the model's dropout key has seed {key.seed}, rank {key.rank}; residual and attention "
+                             f"dropout share it, got seed {int(seed)}, rank {int(rank)}")
+        return key
+
     @property
     def dropout_key(self):
-        """The DropoutKey whose step word the training step sets, or None while dropout is off."""
-        return self._dropout[1] if self._dropout is not None else None
+        """The DropoutKey whose step word the training step sets, or None while both dropouts are off."""
+        for state in (self._dropout, self._attn_dropout):
+            if state is not None:
+                return state[1]
+        return None
+
+    # -- attention-probability dropout (additive; DESIGN 9.36) --------------------------------------------
+    def _attention_layers(self):
+        """Every AttentionLayer in evaluation order: the encoder's self-attention, then per decoder block
+        self-attention followed by cross-attention.  Their ordinals are a namespace of their own (the mask's
+        second counter word carries a high bit that no residual or embedding site has)."""
+        out = []
+        if self.use_encoder:
+            out += [layer.self_attn_block.self_attn for layer in self.encoder_layers]
+        for layer in self.decoder_layers:
+            out.append(layer.self_attn_block.self_attn)
+            if layer.use_cross_attn:
+                out.append(layer.cross_attn_block.cross_attn)
+        return out
+
+    def enable_attention_dropout(self, p, seed, rank=0):
+        """Dropout of the attention probabilities with probability p (0 < p <= 0.9; 0 disables) in training
+        steps (train mode and gradients enabled; nowhere else): the fused attention kernels regenerate the mask
+        in registers in the forward and both backward passes, nothing is stored.  The mask is a pure function
+        of (seed, rank, step, attention site, sequence, head, query, key); the key is the one enable_dropout
+        uses (same seed and rank, ValueError otherwise), so the training step needs to know of one step word.
+        Served in the fp32 and the reduced-precision attention; a model whose attention runs on the head-dim-128
+        kernel is refused here.  Returns the key."""
+        if p == 0:
+            self.disable_attention_dropout()
+            return None
+        from qarig import ops
+        from qarig.dropout import threshold_and_scale
+        threshold_and_scale(p)      # ValueError outside (0, 0.9]
+        device = self.dec_embedding.weight.device
+        if device.type != "cuda":
+            raise RuntimeError("Transformer.enable_attention_dropout needs the model on the GPU "
+                               "(call model.to(device) first)")
+        layers = self._attention_layers()
+        for at in layers:
+            if ops.attention_head_dim(at.head_dim) == ops.ATTENTION_HEAD_DIMS[-1]:
+                raise ValueError(f"attention dropout: head dim {at.head_dim} runs on the head-dim-"
+                                 f"{ops.ATTENTION_HEAD_DIMS[-1]} kernel, which has no dropout form")
+        if len(layers) > ops.ATTN_DROPOUT_SITES:
+            raise ValueError(f"attention dropout: {len(layers)} attention layers, at most {ops.ATTN_DROPOUT_SITES}")
+        key = self._shared_key(self._dropout, seed, rank, device)
+        self._attn_dropout = (float(p), key)
+        for i, at in enumerate(layers):
+            at._attn_dropout = (float(p), i, key)
+        return key
+
+    def disable_attention_dropout(self):
+        self._attn_dropout = None
+        for at in self._attention_layers():
+            at._attn_dropout = None
 
     def _embedding_dropout(self, x, site):
         if self._dropout is not None and dropout_active(self):

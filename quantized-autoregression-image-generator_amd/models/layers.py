@@ -270,6 +270,16 @@ class AttentionLayer(nn.Module):
         self.q_block = block(in_dim)
         self.k_block = block(cross_cond_dim)
         self.v_block = block(cross_cond_dim)
+        self._attn_dropout = None    # (p, site, key) while models.Transformer.enable_attention_dropout is in force
+
+    def _dropout_args(self):
+        """QF.attention's dropout argument: set in training steps alone (dropout_active), None everywhere else --
+        evaluation, validation, generation and the cached decode paths run the plain kernels."""
+        if self._attn_dropout is None or not dropout_active(self):
+            return None
+        from qarig.dropout import threshold_and_scale
+        p, site, key = self._attn_dropout
+        return (*threshold_and_scale(p), site, key.buffer)
 
     def kv_params(self):
         """((w1, b1, w2, b2) of k_block, the same of v_block, act1, act2) when the two blocks can
@@ -289,7 +299,7 @@ class AttentionLayer(nn.Module):
             if len({(b[0]._act, b[1]._act) for b in blocks}) == 1:
                 params = [(*_lin_params(b[0]), *_lin_params(b[1])) for b in blocks]
                 q, k, v = QF.mlp2x3(x, params, blocks[0][0]._act, blocks[0][1]._act)
-                return QF.attention(q, k, v, self.heads, self.use_masked_attn)
+                return QF.attention(q, k, v, self.heads, self.use_masked_attn, self._dropout_args())
         src = cross_cond if self.use_cross_attn else x
         q = _mlp2_forward(self.q_block, x)
         if kv is not None:
@@ -301,7 +311,7 @@ class AttentionLayer(nn.Module):
             else:
                 k = _mlp2_forward(self.k_block, src)
                 v = _mlp2_forward(self.v_block, src)
-        return QF.attention(q, k, v, self.heads, self.use_masked_attn)
+        return QF.attention(q, k, v, self.heads, self.use_masked_attn, self._dropout_args())
 
 
 class SelfAttentionBlock(nn.Module):

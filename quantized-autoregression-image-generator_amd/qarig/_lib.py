@@ -90,6 +90,10 @@ SIGNATURES = {
     "qarig_attention_fwd": (I, [P, P, P, I, I, I, I, I, I, F, P, P, P]),
     "qarig_attention_lp_fwd": (I, [P, P, P, I, I, I, I, I, I, F, P, P, P]),
     "qarig_attention_lp_bwd": (I, [P, P, P, P, P, P, I, I, I, I, I, I, F, P, P, P, P, P]),
+    "qarig_attention_dropout_fwd": (I, [P, P, P, I, I, I, I, I, I, F, P, P, P, U, F, U, P]),
+    "qarig_attention_dropout_bwd": (I, [P, P, P, P, P, P, I, I, I, I, I, I, F, P, P, P, P, P, U, F, U, P]),
+    "qarig_attention_dropout_lp_fwd": (I, [P, P, P, I, I, I, I, I, I, F, P, P, P, U, F, U, P]),
+    "qarig_attention_dropout_lp_bwd": (I, [P, P, P, P, P, P, I, I, I, I, I, I, F, P, P, P, P, P, U, F, U, P]),
     "qarig_attention_decode": (I, [P, P, P, P, P, I, I, I, I, P, I, L, F, P, P, P]),
     "qarig_gemm_grouped_skinny_f32": (I, [P, L, L, P, L, L, P, L, L, P, L, I, I, I, I, I, P]),
     "qarig_gemm_skinny_ln_f32": (I, [P, L, F, P, P, P, P, L, P, L, L, P, L, L, P, L, P, L, I, I, I, I, I, P]),

@@ -213,6 +213,54 @@ def check_dropout_args(dropout, dropout_seed):
     return p, seed
 
 
+def attn_dropout_arg(text):
+    """argparse type of --attn-dropout: 0 (off) or a probability qarig.dropout.threshold_and_scale accepts."""
+    import argparse
+    from .dropout import threshold_and_scale
+    try:
+        v = float(text)
+        if v != 0.0:
+            threshold_and_scale(v)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--attn-dropout must be 0 or lie in (0, 0.9], got {text}")
+    return v
+
+
+def add_attn_dropout_args(p):
+    """--attn-dropout of a Transformer training command line (additive, 0 by default; shares --dropout-seed)."""
+    p.add_argument("--attn-dropout", type=attn_dropout_arg, default=0.0,
+                   help="(additive; the reference has no dropout) drop probability P in (0, 0.9] of the attention "
+                        "probabilities (0 = off: the plain attention kernels, nothing else is launched or allocated): "
+                        "every softmax row of every attention layer loses each entry with probability P and the kept "
+                        "ones are scaled by 1 / (1 - P), in training steps only.  The mask is generated inside the fused "
+                        "attention kernels from (--dropout-seed, rank, optimizer step, layer, sequence, head, query, "
+                        "key) and never stored; it is independent of the --dropout masks under the same seed.  Not "
+                        "available for models whose head dim runs on the head-dim-128 kernel")
+
+
+def check_attn_dropout_args(attn_dropout, dropout_seed, sites=1, batch=1, heads=1, seq_q=1, seq_k=1):
+    """(p, seed) once more before anything is launched with them, or ValueError.  With p > 0 also what the
+    attention entry points would refuse at the first step (include/qarig.h qarig_attention_dropout_fwd): more
+    than 256 attention layers (the site is eight bits of a counter word), more than 2^26 keys, and
+    batch * heads * queries not below 2^32 (one counter word)."""
+    from .dropout import ATTN_DROPOUT_MAX_KEYS, ATTN_DROPOUT_SITES, MAX_THRESHOLD, threshold_and_scale
+    p, seed = float(attn_dropout), int(dropout_seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"--dropout-seed must be an integer in [0, 2^64), got {dropout_seed}")
+    if p == 0.0:
+        return p, seed
+    t, _ = threshold_and_scale(p)
+    assert 1 <= t <= MAX_THRESHOLD
+    if not 1 <= int(sites) <= ATTN_DROPOUT_SITES:
+        raise ValueError(f"--attn-dropout: {sites} attention layers; the mask numbers at most {ATTN_DROPOUT_SITES}")
+    if int(seq_k) > ATTN_DROPOUT_MAX_KEYS:
+        raise ValueError(f"--attn-dropout: {seq_k} keys per sequence, at most 2^26")
+    if int(batch) * int(heads) * int(seq_q) >= 1 << 32:
+        raise ValueError(f"--attn-dropout: batch * heads * queries = {int(batch) * int(heads) * int(seq_q)} must stay "
+                         "below 2^32")
+    return p, seed
+
+
 def weight_decay_arg(text):
     """argparse type of --weight-decay: 0 (off) or a float in (0, 1]."""
     import argparse

@@ -9,6 +9,10 @@ import struct
 import torch
 
 MAX_THRESHOLD = 58982       # round(0.9 * 65536)
+# attention-probability dropout (csrc/dropout_philox.h QARIG_ATTN_DROPOUT_SITES / _MAX_SK; tests/test_attn_dropout_host.py
+# compares them with the header): the site is eight bits of the second counter word, the key index >> 3 the 23 below
+ATTN_DROPOUT_SITES = 256
+ATTN_DROPOUT_MAX_KEYS = 1 << 26
 
 
 def threshold_and_scale(p):

@@ -621,19 +621,20 @@ class _Attention(torch.autograd.Function):
     zero-padded to a kernel head dim (see `attention`)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, heads, causal, scale_dim=None):
+    def forward(ctx, q, k, v, heads, causal, scale_dim=None, dropout=None):
         require_cuda(q, k, v)
         q, k, v = f32c(q), f32c(k), f32c(v)
-        o, lse = ops.attention_fwd(q, k, v, heads, causal, scale_dim)
+        o, lse = ops.attention_fwd(q, k, v, heads, causal, scale_dim, dropout)
         ctx.save_for_backward(q, k, v, o, lse)
         ctx.heads, ctx.causal, ctx.scale_dim = heads, causal, scale_dim
+        ctx.dropout = dropout           # (T, s, site, key buffer): the backward passes regenerate the mask
         return o
 
     @staticmethod
     def backward(ctx, do):
         q, k, v, o, lse = ctx.saved_tensors
-        dq, dk, dv = ops.attention_bwd(q, k, v, o, f32c(do), lse, ctx.heads, ctx.causal, ctx.scale_dim)
-        return dq, dk, dv, None, None, None
+        dq, dk, dv = ops.attention_bwd(q, k, v, o, f32c(do), lse, ctx.heads, ctx.causal, ctx.scale_dim, ctx.dropout)
+        return dq, dk, dv, None, None, None, None
 
 
 def _pad_heads(t, heads, d, dp):
@@ -642,8 +643,11 @@ def _pad_heads(t, heads, d, dp):
     return torch.nn.functional.pad(t.reshape(N, S, heads, d), (0, dp - d)).reshape(N, S, heads * dp)
 
 
-def attention(q, k, v, heads, causal):
-    """The reference accepts any `heads` that divides the model width (models/layers.py:433); the kernels
+def attention(q, k, v, heads, causal, dropout=None):
+    """dropout: None, or (T, s, site, key buffer) -- attention-probability dropout on the training path (the
+    no-grad branch ignores it; head dim 128 is refused by the entry point).
+
+    The reference accepts any `heads` that divides the model width (models/layers.py:433); the kernels
     are instantiated for head dims 4, 8, 16, 32, 64 (MFMA, csrc/attention.hip) and 128 (vector-ALU fma chains,
     csrc/attention_wide.hip: the rare few-heads model).  Any other head dim up to 128 runs on the next
     instantiated one with every head zero-padded: the extra columns add exact zeros to q.k and produce
@@ -660,12 +664,14 @@ def attention(q, k, v, heads, causal):
             require_cuda(q, k, v)
             o = ops.attention_fwd(f32c(qp), f32c(kp), f32c(vp), heads, causal, d)[0]
         else:
-            o = _Attention.apply(qp, kp, vp, heads, causal, d)
+            o = _Attention.apply(qp, kp, vp, heads, causal, d, dropout)
         N, S, _ = o.shape
         return o.reshape(N, S, heads, dp)[..., :d].reshape(N, S, heads * d)
     if _no_grad():
         require_cuda(q, k, v)
         return ops.attention_fwd(f32c(q), f32c(k), f32c(v), heads, causal)[0]
+    if dropout is not None:
+        return _Attention.apply(q, k, v, heads, causal, None, dropout)
     return _Attention.apply(q, k, v, heads, causal)
 
 

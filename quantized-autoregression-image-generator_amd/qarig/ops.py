@@ -11,6 +11,7 @@ import torch
 
 from . import _lib
 from ._lib import check, f32c, ptr, require_cuda, stream, workspace
+from .dropout import ATTN_DROPOUT_SITES      # attention sites the mask numbers (one definition)
 
 ACT_IDS = {None: 0, "none": 0, "silu": 1, "tanh": 2, "sigmoid": 3}
 
@@ -1213,14 +1214,34 @@ def attention_head_dim(d):
     return None
 
 
-def attention_fwd(q, k, v, heads, causal, scale_dim=None):
-    """scale_dim: the model's head dim when the tensors carry zero-padded heads (softmax scale 1/sqrt(scale_dim))."""
+def _attention_dropout_args(dropout):
+    """(threshold, scale, site, key pointer) of attention_fwd / attention_bwd's dropout = (T, s, site, key buffer):
+    the checks that need the tensor; the entry point refuses the rest."""
+    threshold, scale, site, key = dropout
+    require_cuda(key)
+    if key.dtype != torch.int32 or key.numel() != 4 or not key.is_contiguous():
+        raise TypeError("attention dropout: key is a contiguous int32 tensor of 4 words {seed_lo, seed_hi, step, rank}")
+    threshold, site = int(threshold), int(site)
+    if not 0 <= threshold < 2 ** 32 or not 0 <= site < 2 ** 32:
+        raise ValueError(f"attention dropout: threshold and site must fit 32 bits, got {threshold}, {site}")
+    return threshold, float(scale), site, ptr(key)
+
+
+def attention_fwd(q, k, v, heads, causal, scale_dim=None, dropout=None):
+    """scale_dim: the model's head dim when the tensors carry zero-padded heads (softmax scale 1/sqrt(scale_dim)).
+    dropout: None, or (T, s, site, key buffer) -- attention-probability dropout, include/qarig.h
+    qarig_attention_dropout_fwd."""
     N, Sq, D = q.shape
     Sk = k.shape[1]
     d = D // heads
     o = torch.empty_like(q)
     lse = torch.empty((N, heads, Sq), dtype=torch.float32, device=q.device)
     lib = _lib.load()
+    if dropout is not None:
+        fn = lib.qarig_attention_dropout_lp_fwd if lp_mode() else lib.qarig_attention_dropout_fwd
+        check(fn(ptr(q), ptr(k), ptr(v), N, Sq, Sk, heads, d, int(causal), float((scale_dim or d) ** 0.5), ptr(o),
+                 ptr(lse), stream(), *_attention_dropout_args(dropout)), "qarig_attention_dropout_fwd")
+        return o, lse
     fn = lib.qarig_attention_lp_fwd if lp_mode() else lib.qarig_attention_fwd
     check(fn(ptr(q), ptr(k), ptr(v), N, Sq, Sk, heads, d, int(causal), float((scale_dim or d) ** 0.5), ptr(o),
              ptr(lse), stream()), "qarig_attention_fwd")
@@ -1437,7 +1458,8 @@ def window_append(ctl, ring, ids):
                                           ptr(_bad_flag(ring.device)), stream()), "qarig_window_append")
 
 
-def attention_bwd(q, k, v, o, dO, lse, heads, causal, scale_dim=None):
+def attention_bwd(q, k, v, o, dO, lse, heads, causal, scale_dim=None, dropout=None):
+    """dropout: what attention_fwd took for the same (q, k, v): the backward passes regenerate its mask."""
     N, Sq, D = q.shape
     Sk = k.shape[1]
     d = D // heads
@@ -1446,6 +1468,12 @@ def attention_bwd(q, k, v, o, dO, lse, heads, causal, scale_dim=None):
     dv = torch.empty_like(v)
     delta = torch.empty_like(lse)
     lib = _lib.load()
+    if dropout is not None:
+        fn = lib.qarig_attention_dropout_lp_bwd if lp_mode() else lib.qarig_attention_dropout_bwd
+        check(fn(ptr(q), ptr(k), ptr(v), ptr(o), ptr(dO), ptr(lse), N, Sq, Sk, heads, d, int(causal),
+                 float((scale_dim or d) ** 0.5), ptr(dq), ptr(dk), ptr(dv), ptr(delta), stream(),
+                 *_attention_dropout_args(dropout)), "qarig_attention_dropout_bwd")
+        return dq, dk, dv
     fn = lib.qarig_attention_lp_bwd if lp_mode() else lib.qarig_attention_bwd
     check(fn(ptr(q), ptr(k), ptr(v), ptr(o), ptr(dO), ptr(lse), N, Sq, Sk, heads, d, int(causal),
              float((scale_dim or d) ** 0.5), ptr(dq), ptr(dk), ptr(dv), ptr(delta), stream()), "qarig_attention_bwd")

@@ -87,6 +87,13 @@ def set_dropout_step(model, optim):
         key.set_step(optim.step_count + 1)
 
 
+def _dropout_state(model):
+    """What a captured step's launches depend on: the key and the (re-created on every enable) states of residual
+    and attention-probability dropout, compared by identity."""
+    return (getattr(model, "dropout_key", None), getattr(model, "_dropout", None),
+            getattr(model, "_attn_dropout", None))
+
+
 def train_step(model, optim, hr_input, lr_input, hr_target, pos_idx, dp=True, pos_bound=None,
                label_smoothing=0.0, z_loss=0.0):
     """forward + CE + backward + gradient all-reduce + Adam.  Returns the loss tensor
@@ -281,11 +288,11 @@ class GraphedTrainStep:
         set_dropout_step(self.model, self.optim)
         if self.calls <= self.warmup:
             return self._body(z, rand.to(z.device), captured=False)
-        if self.graph is not None and getattr(self.model, "dropout_key", None) is not self._dropout_key:
+        if self.graph is not None and any(a is not b for a, b in zip(_dropout_state(self.model), self._dropout_key)):
             raise RuntimeError("GraphedTrainStep: dropout was enabled, disabled or re-keyed after the step was "
                                "captured; the graph holds the launches and the key of its capture")
         if self.graph is None:
-            self._dropout_key = getattr(self.model, "dropout_key", None)
+            self._dropout_key = _dropout_state(self.model)
             self._z = z.clone()
             self._rand = rand.to(z.device).clone()
             self.optim._dev_step_buffer()      # must exist BEFORE capture: created inside, its

@@ -94,6 +94,7 @@ def parse_args():
                    help="(additive) score only the first batches of --val-dataset-path.")
     cc.add_regulariser_args(p)
     cc.add_dropout_args(p)
+    cc.add_attn_dropout_args(p)
     cc.add_optimizer_args(p)
     cc.add_grad_clip_args(p)
     args = vars(p.parse_args())
@@ -191,6 +192,18 @@ def main():
     if dropout > 0:
         # the step word of the mask key follows optim.step_count: with --load-optim the sequence continues
         model.enable_dropout(dropout, dropout_seed, rank=parallel.rank())
+    # the longest query and key extents an attention layer of this run can meet: the window (or the whole
+    # sequence: LR tokens, <start>, HR tokens), and the LR tokens for cross-attention
+    lr_seq = (lr_d["image_dim"][0] // lr_d["patch_dim"][0]) * (lr_d["image_dim"][1] // lr_d["patch_dim"][1])
+    longest = lr_seq + total_hr_Seq + 1
+    if use_sliding_window:
+        longest = min(longest, sliding_window)
+    attn_dropout, _ = cc.check_attn_dropout_args(
+        args["attn_dropout"], dropout_seed, sites=len(model._attention_layers()), batch=args["batch_size"],
+        heads=max(hp["self_attn_heads"], cross_attn_heads or 1), seq_q=longest, seq_k=max(longest, lr_seq))
+    if attn_dropout > 0:
+        # the same key (seed, rank, step word) as --dropout; the attention sites are a namespace of their own
+        model.enable_attention_dropout(attn_dropout, dropout_seed, rank=parallel.rank())
 
     dataset = FeatureMapDataset(dataset_path=args["dataset_path"], load_image=False,
                                 return_filepaths=False)
@@ -251,6 +264,10 @@ def main():
     if dropout > 0:
         info(f"Dropout: {dropout}")
         info(f"Dropout Seed: {dropout_seed}")
+    if attn_dropout > 0:
+        info(f"Attention Dropout: {attn_dropout}")
+        if not dropout > 0:
+            info(f"Dropout Seed: {dropout_seed}")
     if weight_decay > 0:
         info(f"Weight Decay: {weight_decay}")
     if schedule is not None:
@@ -288,6 +305,9 @@ def main():
             model_dict["z_loss"] = z_loss
         if dropout > 0:             # informational likewise
             model_dict["dropout"] = dropout
+            model_dict["dropout_seed"] = dropout_seed
+        if attn_dropout > 0:        # informational likewise
+            model_dict["attn_dropout"] = attn_dropout
             model_dict["dropout_seed"] = dropout_seed
         if weight_decay > 0:        # informational likewise
             model_dict["weight_decay"] = weight_decay
