@@ -2,15 +2,20 @@
 // allocation; so do their gradients and moments): one launch per step, and the same
 // flat gradient buffer is what the DP all-reduce moves.  Semantics of
 // torch.optim.Adam(lr, betas) without weight decay / amsgrad
-// (train_quantized_transformer.py:317-320; train_autoencoder.py:133-136).  Additive: adamw_kernel, the same update
-// behind a decoupled weight decay of the groups a mask selects (torch.optim.AdamW with two parameter groups).
+// (train_quantized_transformer.py:317-320; train_autoencoder.py:133-136).  Additive: a decoupled weight decay of
+// the groups a mask selects (torch.optim.AdamW with two parameter groups), an EMA of the parameters and a
+// global-norm gradient clip with a skipped-step guard, all from the same launch.
+// The update of one element is stated once, in adam_element.h.  Two kernel bodies call it: adam_kernel (one element
+// per thread-iteration, any 4-byte alignment: the plain and the EMA entry) and adam_groups_kernel (groups of 8,
+// 16-byte accesses: the AdamW and the clip entry).  adam_launch is the host side of all four entries.
+#include "adam_element.h"
 #include "qarig_common.h"
 
 namespace qarig {
 
 // EMA: the same pass also moves an exponential moving average of the parameters, e <- lerp(e, pn, ema_w),
-// one more read and one more write stream on the launch (7 -> 9), no further launch.  p, m, v and the shadow
-// are computed by the very expressions of the plain instantiation.
+// one more read and one more write stream on the launch (7 -> 9), no further launch.  The loads stay in this
+// order (g, m, v, then p, then ema): the compiler's schedule of the benchmarked launch follows it.
 template <bool EMA>
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                             float* __restrict__ m, float* __restrict__ v, float* __restrict__ ema,
@@ -24,71 +29,41 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
     }
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * blockDim.x) {
-        const float gi = g[i] * grad_scale;
-        // exp_avg.lerp_(grad, 1 - beta1), torch's two-branch lerp
-        const float w = 1.0f - beta1;
-        const float mi = m[i];
-        const float mn = w < 0.5f ? mi + w * (gi - mi) : gi - (gi - mi) * (1.0f - w);
-        // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
-        const float vn = v[i] * beta2 + (1.0f - beta2) * gi * gi;
-        const float denom = sqrtf(vn) / bc2_sqrt + eps;
-        const float pn = p[i] - step_size * (mn / denom);
+        const float gi = g[i];
+        float mi = m[i], vi = v[i];
+        const float pi = p[i];
+        float ei = EMA ? ema[i] : 0.0f;
+        const float pn = adam_element<EMA>(pi, gi, mi, vi, ei, /*decayed*/ false, beta1, beta2, eps, step_size,
+                                           bc2_sqrt, ema_w, /*decay*/ 0.0f, grad_scale);
         p[i] = pn;
-        m[i] = mn;
-        v[i] = vn;
-        if (EMA) {
-            // the two-branch lerp again: ema_w = 1 yields pn, ema_w = 0 keeps e, and e == pn stays, all exactly
-            const float ei = ema[i];
-            ema[i] = ema_w < 0.5f ? ei + ema_w * (pn - ei) : pn - (pn - ei) * (1.0f - ema_w);
-        }
-        if (shadow) {       // reduced-precision mode: the bf16 copy the GEMMs read, from the same pass
-            typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-            typedef float f32x2_t __attribute__((ext_vector_type(2)));
-            const f32x2_t f = {pn, 0.0f};
-            shadow[i] = (unsigned short)(__builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2_t)) & 0xffffu);
-        }
+        m[i] = mi;
+        v[i] = vi;
+        if (EMA) ema[i] = ei;
+        // reduced-precision mode: the bf16 copy the GEMMs read, from the same pass
+        if (shadow) shadow[i] = (unsigned short)(pack_bf16x2(pn, 0.0f) & 0xffffu);
     }
 }
 
-// AdamW: decoupled weight decay in front of the same update, on groups of 8 elements.  One element's arithmetic:
-// pd = fma(-decay, p, p) where the element is decayed (one rounding; decay = fp32(lr * lambda)), p's own bits
-// where it is not, then adam_kernel's expressions with pd in the place of p[i].  Returns the new parameter.
-template <bool EMA>
-__device__ __forceinline__ float adamw_element(float pi, float graw, float& mi, float& vi, float& ei, bool decayed,
-                                               float beta1, float beta2, float eps, float step_size,
-                                               float bc2_sqrt, float ema_w, float decay, float grad_scale) {
-    const float pd = decayed ? __builtin_fmaf(-decay, pi, pi) : pi;
-    const float gi = graw * grad_scale;
-    const float w = 1.0f - beta1;
-    const float mn = w < 0.5f ? mi + w * (gi - mi) : gi - (gi - mi) * (1.0f - w);
-    const float vn = vi * beta2 + (1.0f - beta2) * gi * gi;
-    const float denom = sqrtf(vn) / bc2_sqrt + eps;
-    const float pn = pd - step_size * (mn / denom);
-    mi = mn;
-    vi = vn;
-    if (EMA) ei = ema_w < 0.5f ? ei + ema_w * (pn - ei) : pn - (pn - ei) * (1.0f - ema_w);
-    return pn;
-}
-
-// two floats -> two nearest-even bf16 in one dword (low half: a), the conversion of adam_kernel's shadow
-__device__ __forceinline__ unsigned pack_bf16x2(float a, float b) {
-    typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-    typedef float f32x2_t __attribute__((ext_vector_type(2)));
-    const f32x2_t f = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2_t));
-}
-
-// One thread-iteration = one group of 8 elements = one mask byte: two 16-byte loads per input stream, all of them
-// ahead of the first store, two 16-byte stores per fp32 output stream and one for the 8 bf16 of the shadow.  The
-// last group of an n that is no multiple of 8 goes element by element and touches nothing at or behind n.
-// 7 (9 with the EMA) streams of 4 bytes per element as adam_kernel, plus n / 8 mask bytes.
-template <bool EMA>
-__global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                             float* __restrict__ v, float* __restrict__ ema,
-                             const unsigned char* __restrict__ mask, int64_t n, float beta1, float beta2,
-                             float eps, float step_size, float bc2_sqrt, float ema_w, float decay,
-                             float grad_scale, const float* __restrict__ dev_step,
-                             unsigned short* __restrict__ shadow) {
+// AdamW and the clip.  One thread-iteration = one group of 8 elements = one mask byte: two 16-byte loads per input
+// stream, all of them ahead of the first store, two 16-byte stores per fp32 output stream and one for the 8 bf16 of
+// the shadow.  The last group of an n that is no multiple of 8 goes element by element and touches nothing at or
+// behind n.  7 (9 with the EMA) streams of 4 bytes per element as adam_kernel, plus n / 8 mask bytes.
+// CLIP: gi = fp32(fp32(g * grad_scale) * coef), norm and coef read from clip_state by every thread; a norm that is
+// not finite ends the kernel before it loads or stores anything else (the step is skipped); mask may be NULL
+// (nothing decayed).  A template parameter: without it no clip_state read, early return or second multiply is left.
+template <bool EMA, bool CLIP>
+__global__ void adam_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                   float* __restrict__ v, float* __restrict__ ema,
+                                   const unsigned char* __restrict__ mask, int64_t n, float beta1, float beta2,
+                                   float eps, float step_size, float bc2_sqrt, float ema_w, float decay,
+                                   float grad_scale, const float* __restrict__ dev_step,
+                                   unsigned short* __restrict__ shadow, const double* __restrict__ clip_state) {
+    float scale = grad_scale;       // the element's scale argument; behind the clip coef, on fp32(g * grad_scale)
+    if (CLIP) {
+        const double norm = clip_state[0];
+        scale = (float)clip_state[1];
+        if (!(__builtin_fabs(norm) <= 1.7976931348623157e308)) return;
+    }
     if (dev_step) {     // captured-graph replay: always four floats {step_size, bc2_sqrt, ema_w, decay}
         step_size = dev_step[0];
         bc2_sqrt = dev_step[1];
@@ -98,7 +73,7 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
     const int64_t full = n >> 3, groups = (n + 7) >> 3;
     for (int64_t gr = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; gr < groups;
          gr += (int64_t)gridDim.x * blockDim.x) {
-        const bool decayed = mask[gr] != 0;
+        const bool decayed = (!CLIP || mask) ? mask[gr] != 0 : false;
         const int64_t base = gr << 3;
         if (gr < full) {
             f32x4 pv[2], gv[2], mv[2], vv[2], ev[2];
@@ -115,8 +90,8 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     float mi = mv[h][k], vi = vv[h][k], ei = EMA ? ev[h][k] : 0.0f;
-                    pv[h][k] = adamw_element<EMA>(pv[h][k], gv[h][k], mi, vi, ei, decayed, beta1, beta2, eps,
-                                                  step_size, bc2_sqrt, ema_w, decay, grad_scale);
+                    pv[h][k] = adam_element<EMA>(pv[h][k], CLIP ? gv[h][k] * grad_scale : gv[h][k], mi, vi, ei,
+                                                 decayed, beta1, beta2, eps, step_size, bc2_sqrt, ema_w, decay, scale);
                     mv[h][k] = mi;
                     vv[h][k] = vi;
                     if (EMA) ev[h][k] = ei;
@@ -140,8 +115,8 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
         } else {
             for (int64_t i = base; i < n; ++i) {
                 float mi = m[i], vi = v[i], ei = EMA ? ema[i] : 0.0f;
-                const float pn = adamw_element<EMA>(p[i], g[i], mi, vi, ei, decayed, beta1, beta2, eps, step_size,
-                                                    bc2_sqrt, ema_w, decay, grad_scale);
+                const float pn = adam_element<EMA>(p[i], CLIP ? g[i] * grad_scale : g[i], mi, vi, ei, decayed, beta1,
+                                                   beta2, eps, step_size, bc2_sqrt, ema_w, decay, scale);
                 p[i] = pn;
                 m[i] = mi;
                 v[i] = vi;
@@ -231,84 +206,6 @@ __global__ __launch_bounds__(GRAD_NORM_BLOCK) void grad_clip_coef_kernel(const d
     }
 }
 
-// Adam / AdamW behind the clip: adamw_kernel's structure (groups of 8, 16-byte accesses, all loads ahead of the
-// first store) with gi = fp32(fp32(g * grad_scale) * coef), norm and coef read from clip_state by every thread.  A
-// norm that is not finite ends the kernel before it loads or stores anything else: the step is skipped.  mask may
-// be NULL (nothing decayed).  The element arithmetic is adamw_element's, fed the scaled gradient and coef in the
-// places of the raw gradient and grad_scale.
-template <bool EMA>
-__global__ void adam_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                 float* __restrict__ v, float* __restrict__ ema,
-                                 const unsigned char* __restrict__ mask, int64_t n, float beta1, float beta2,
-                                 float eps, float step_size, float bc2_sqrt, float ema_w, float decay,
-                                 float grad_scale, const float* __restrict__ dev_step,
-                                 unsigned short* __restrict__ shadow, const double* __restrict__ clip_state) {
-    const double norm = clip_state[0];
-    const float coef = (float)clip_state[1];
-    if (!(__builtin_fabs(norm) <= 1.7976931348623157e308)) return;
-    if (dev_step) {     // captured-graph replay: always four floats {step_size, bc2_sqrt, ema_w, decay}
-        step_size = dev_step[0];
-        bc2_sqrt = dev_step[1];
-        if (EMA) ema_w = dev_step[2];
-        decay = dev_step[3];
-    }
-    const int64_t full = n >> 3, groups = (n + 7) >> 3;
-    for (int64_t gr = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; gr < groups;
-         gr += (int64_t)gridDim.x * blockDim.x) {
-        const bool decayed = mask ? mask[gr] != 0 : false;
-        const int64_t base = gr << 3;
-        if (gr < full) {
-            f32x4 pv[2], gv[2], mv[2], vv[2], ev[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                pv[h] = *(const f32x4*)(p + base + 4 * h);
-                gv[h] = *(const f32x4*)(g + base + 4 * h);
-                mv[h] = *(const f32x4*)(m + base + 4 * h);
-                vv[h] = *(const f32x4*)(v + base + 4 * h);
-                if (EMA) ev[h] = *(const f32x4*)(ema + base + 4 * h);
-            }
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    float mi = mv[h][k], vi = vv[h][k], ei = EMA ? ev[h][k] : 0.0f;
-                    pv[h][k] = adamw_element<EMA>(pv[h][k], gv[h][k] * grad_scale, mi, vi, ei, decayed, beta1, beta2,
-                                                  eps, step_size, bc2_sqrt, ema_w, decay, coef);
-                    mv[h][k] = mi;
-                    vv[h][k] = vi;
-                    if (EMA) ev[h][k] = ei;
-                }
-            }
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                *(f32x4*)(p + base + 4 * h) = pv[h];
-                *(f32x4*)(m + base + 4 * h) = mv[h];
-                *(f32x4*)(v + base + 4 * h) = vv[h];
-                if (EMA) *(f32x4*)(ema + base + 4 * h) = ev[h];
-            }
-            if (shadow) {
-                uint4 s;
-                s.x = pack_bf16x2(pv[0][0], pv[0][1]);
-                s.y = pack_bf16x2(pv[0][2], pv[0][3]);
-                s.z = pack_bf16x2(pv[1][0], pv[1][1]);
-                s.w = pack_bf16x2(pv[1][2], pv[1][3]);
-                *(uint4*)(shadow + base) = s;
-            }
-        } else {
-            for (int64_t i = base; i < n; ++i) {
-                float mi = m[i], vi = v[i], ei = EMA ? ema[i] : 0.0f;
-                const float pn = adamw_element<EMA>(p[i], g[i] * grad_scale, mi, vi, ei, decayed, beta1, beta2, eps,
-                                                    step_size, bc2_sqrt, ema_w, decay, coef);
-                p[i] = pn;
-                m[i] = mi;
-                v[i] = vi;
-                if (EMA) ema[i] = ei;
-                if (shadow) shadow[i] = (unsigned short)(pack_bf16x2(pn, 0.0f) & 0xffffu);
-            }
-        }
-    }
-}
-
 // Exchanges two fp32 buffers in place, as bit patterns (no arithmetic touches the values): 16-byte body where
 // both buffers are 16-byte aligned, scalar tail behind it.
 __global__ void swap_f32_kernel(unsigned* __restrict__ a, unsigned* __restrict__ b, int64_t nvec, int64_t n) {
@@ -332,71 +229,69 @@ __global__ void swap_f32_kernel(unsigned* __restrict__ a, unsigned* __restrict__
 
 using namespace qarig;
 
-// step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t), both computed by the
-// host in double as torch does.  grad_scale multiplies g first (1/world after a sum
-// all-reduce; 1 otherwise).  dev_step (optional, device, 2 floats {step_size, bc2_sqrt}) overrides
-// the two per-step scalars, so that a captured graph of the training step can be replayed while
-// the host refreshes them between replays.  shadow_bf16 (optional, n bf16 values): receives the updated
-// parameters rounded to nearest-even bf16 -- the operands of the reduced-precision GEMMs -- so that no
-// per-weight cast launch follows an optimiser step.
-extern "C" int qarig_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float beta1,
-                               float beta2, float eps, float step_size, float bc2_sqrt,
-                               float grad_scale, const float* dev_step, void* shadow_bf16, void* stream) {
-    QARIG_CHECK_ARG(p && g && m && v && n > 0 && n <= (1LL << 40), "adam: bad arguments");
-    int64_t b = (n + 255) / 256;
+// The host side of the four Adam entries (include/qarig.h documents their arguments and what they refuse): each
+// checks the one pointer that is its own and calls this; `who` prefixes every message.  grouped: adam_groups_kernel,
+// whose 16-byte accesses need aligned buffers and an ema and a shadow that do not overlap p, with the clip where
+// clip_state is given; otherwise adam_kernel, which takes any 4-byte-aligned view.  The EMA instantiation where ema
+// is given; decay is looked at only where there is a mask.  A refused call launches nothing.
+static int adam_launch(const char* who, bool grouped, float* p, const float* g, float* m, float* v, float* ema,
+                       const unsigned char* mask, int64_t n, float beta1, float beta2, float eps, float step_size,
+                       float bc2_sqrt, float ema_w, float decay, float grad_scale, const float* dev_step,
+                       void* shadow_bf16, const double* clip_state, void* stream) {
+    QARIG_CHECK_ARG(p && g && m && v && n > 0 && n <= (1LL << 40), "%s: bad arguments", who);
+    if (grouped) {
+        const uintptr_t up = (uintptr_t)p, ue = (uintptr_t)ema, us = (uintptr_t)shadow_bf16;
+        QARIG_CHECK_ARG(up % 16 == 0 && (uintptr_t)g % 16 == 0 && (uintptr_t)m % 16 == 0 && (uintptr_t)v % 16 == 0 &&
+                            ue % 16 == 0 && us % 16 == 0,
+                        "%s: p, g, m, v, ema and shadow_bf16 must be 16-byte aligned", who);
+        QARIG_CHECK_ARG((uintptr_t)clip_state % 8 == 0, "%s: clip_state must be 8-byte aligned", who);
+        QARIG_CHECK_ARG(!mask || (decay >= 0.0f && decay < 1.0f), "%s: decay must lie in [0, 1)", who);  // (NaN fails)
+        const uint64_t bytes = 4 * (uint64_t)n;
+        QARIG_CHECK_ARG(!ema || ue + bytes <= up || up + bytes <= ue, "%s: ema overlaps p", who);
+        QARIG_CHECK_ARG(!shadow_bf16 || us + bytes / 2 <= up || up + bytes <= us, "%s: shadow_bf16 overlaps p", who);
+    }
+    int64_t b = ((grouped ? (n + 7) / 8 : n) + 255) / 256;
     if (b > 8192) b = 8192;
-    hipLaunchKernelGGL(adam_kernel<false>, dim3((int)b), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
-                       (float*)nullptr, n, beta1, beta2, eps, step_size, bc2_sqrt, 0.0f, grad_scale, dev_step,
-                       (unsigned short*)shadow_bf16);
-    QARIG_CHECK_LAUNCH("adam");
+    unsigned short* shadow = (unsigned short*)shadow_bf16;
+    if (grouped) {
+        const auto kernel = clip_state ? (ema ? adam_groups_kernel<true, true> : adam_groups_kernel<false, true>)
+                                       : (ema ? adam_groups_kernel<true, false> : adam_groups_kernel<false, false>);
+        hipLaunchKernelGGL(kernel, dim3((int)b), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, mask, n, beta1,
+                           beta2, eps, step_size, bc2_sqrt, ema_w, decay, grad_scale, dev_step, shadow, clip_state);
+    } else {
+        const auto kernel = ema ? adam_kernel<true> : adam_kernel<false>;
+        hipLaunchKernelGGL(kernel, dim3((int)b), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n, beta1, beta2,
+                           eps, step_size, bc2_sqrt, ema_w, grad_scale, dev_step, shadow);
+    }
+    QARIG_CHECK_LAUNCH(who);
     return QARIG_OK;
 }
 
-// The same step with an exponential moving average of the parameters kept from the same pass:
-// ema <- lerp(ema, p_new, ema_w), n floats, updated in place.  dev_step here holds 3 floats,
-// {step_size, bc2_sqrt, ema_w}.  p, m, v and shadow_bf16 come out as qarig_adam_step leaves them.
+extern "C" int qarig_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float beta1,
+                               float beta2, float eps, float step_size, float bc2_sqrt,
+                               float grad_scale, const float* dev_step, void* shadow_bf16, void* stream) {
+    return adam_launch("adam", false, p, g, m, v, nullptr, nullptr, n, beta1, beta2, eps, step_size, bc2_sqrt, 0.0f,
+                       0.0f, grad_scale, dev_step, shadow_bf16, nullptr, stream);
+}
+
+// dev_step here holds 3 floats, {step_size, bc2_sqrt, ema_w}
 extern "C" int qarig_adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, int64_t n,
                                    float beta1, float beta2, float eps, float step_size, float bc2_sqrt,
                                    float ema_w, float grad_scale, const float* dev_step, void* shadow_bf16,
                                    void* stream) {
-    QARIG_CHECK_ARG(p && g && m && v && ema && n > 0 && n <= (1LL << 40), "adam_ema: bad arguments");
-    int64_t b = (n + 255) / 256;
-    if (b > 8192) b = 8192;
-    hipLaunchKernelGGL(adam_kernel<true>, dim3((int)b), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n,
-                       beta1, beta2, eps, step_size, bc2_sqrt, ema_w, grad_scale, dev_step,
-                       (unsigned short*)shadow_bf16);
-    QARIG_CHECK_LAUNCH("adam_ema");
-    return QARIG_OK;
+    QARIG_CHECK_ARG(ema, "adam_ema: bad arguments");
+    return adam_launch("adam_ema", false, p, g, m, v, ema, nullptr, n, beta1, beta2, eps, step_size, bc2_sqrt, ema_w,
+                       0.0f, grad_scale, dev_step, shadow_bf16, nullptr, stream);
 }
 
-// AdamW (include/qarig.h has the normative arithmetic): decay_mask holds one byte per group of 8 elements,
-// ceil(n / 8) of them; ema may be NULL (the plain instantiation); dev_step, when given, is always four floats
-// {step_size, bc2_sqrt, ema_w, decay} and the host's values of the four are ignored.
+// ema may be NULL; dev_step, when given, is always four floats {step_size, bc2_sqrt, ema_w, decay}, here and below
 extern "C" int qarig_adamw_step(float* p, const float* g, float* m, float* v, float* ema,
                                 const unsigned char* decay_mask, int64_t n, float beta1, float beta2, float eps,
                                 float step_size, float bc2_sqrt, float ema_w, float decay, float grad_scale,
                                 const float* dev_step, void* shadow_bf16, void* stream) {
-    QARIG_CHECK_ARG(p && g && m && v && decay_mask && n > 0 && n <= (1LL << 40), "adamw: bad arguments");
-    const uintptr_t up = (uintptr_t)p, ue = (uintptr_t)ema, us = (uintptr_t)shadow_bf16;
-    QARIG_CHECK_ARG(up % 16 == 0 && (uintptr_t)g % 16 == 0 && (uintptr_t)m % 16 == 0 && (uintptr_t)v % 16 == 0 &&
-                        ue % 16 == 0 && us % 16 == 0,
-                    "adamw: p, g, m, v, ema and shadow_bf16 must be 16-byte aligned");
-    QARIG_CHECK_ARG(decay >= 0.0f && decay < 1.0f, "adamw: decay must lie in [0, 1)");      // (NaN fails both)
-    const uint64_t bytes = 4 * (uint64_t)n;
-    QARIG_CHECK_ARG(!ema || ue + bytes <= up || up + bytes <= ue, "adamw: ema overlaps p");
-    QARIG_CHECK_ARG(!shadow_bf16 || us + bytes / 2 <= up || up + bytes <= us, "adamw: shadow_bf16 overlaps p");
-    int64_t b = ((n + 7) / 8 + 255) / 256;
-    if (b > 8192) b = 8192;
-    if (ema)
-        hipLaunchKernelGGL(adamw_kernel<true>, dim3((int)b), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema,
-                           decay_mask, n, beta1, beta2, eps, step_size, bc2_sqrt, ema_w, decay, grad_scale,
-                           dev_step, (unsigned short*)shadow_bf16);
-    else
-        hipLaunchKernelGGL(adamw_kernel<false>, dim3((int)b), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
-                           (float*)nullptr, decay_mask, n, beta1, beta2, eps, step_size, bc2_sqrt, 0.0f, decay,
-                           grad_scale, dev_step, (unsigned short*)shadow_bf16);
-    QARIG_CHECK_LAUNCH("adamw");
-    return QARIG_OK;
+    QARIG_CHECK_ARG(decay_mask, "adamw: bad arguments");
+    return adam_launch("adamw", true, p, g, m, v, ema, decay_mask, n, beta1, beta2, eps, step_size, bc2_sqrt, ema_w,
+                       decay, grad_scale, dev_step, shadow_bf16, nullptr, stream);
 }
 
 // Global gradient norm and clip coefficient (include/qarig.h has the normative arithmetic): two launches, the
@@ -422,36 +317,15 @@ extern "C" int qarig_grad_clip_coef(const float* g, int64_t n, float grad_scale,
     return QARIG_OK;
 }
 
-// qarig_adamw_step behind the clip: the gradient is scaled by clip_state[1] as well, and a non-finite
-// clip_state[0] skips the step on the device.  decay_mask may be NULL here (no decay: the host decay is not looked
-// at); everything else as qarig_adamw_step.
+// decay_mask may be NULL here (no decay: the host decay is not looked at)
 extern "C" int qarig_adam_clip_step(float* p, const float* g, float* m, float* v, float* ema,
                                     const unsigned char* decay_mask, int64_t n, float beta1, float beta2, float eps,
                                     float step_size, float bc2_sqrt, float ema_w, float decay, float grad_scale,
                                     const float* dev_step, void* shadow_bf16, const double* clip_state,
                                     void* stream) {
-    QARIG_CHECK_ARG(p && g && m && v && clip_state && n > 0 && n <= (1LL << 40), "adam_clip: bad arguments");
-    const uintptr_t up = (uintptr_t)p, ue = (uintptr_t)ema, us = (uintptr_t)shadow_bf16;
-    QARIG_CHECK_ARG(up % 16 == 0 && (uintptr_t)g % 16 == 0 && (uintptr_t)m % 16 == 0 && (uintptr_t)v % 16 == 0 &&
-                        ue % 16 == 0 && us % 16 == 0,
-                    "adam_clip: p, g, m, v, ema and shadow_bf16 must be 16-byte aligned");
-    QARIG_CHECK_ARG((uintptr_t)clip_state % 8 == 0, "adam_clip: clip_state must be 8-byte aligned");
-    QARIG_CHECK_ARG(!decay_mask || (decay >= 0.0f && decay < 1.0f), "adam_clip: decay must lie in [0, 1)");
-    const uint64_t bytes = 4 * (uint64_t)n;
-    QARIG_CHECK_ARG(!ema || ue + bytes <= up || up + bytes <= ue, "adam_clip: ema overlaps p");
-    QARIG_CHECK_ARG(!shadow_bf16 || us + bytes / 2 <= up || up + bytes <= us, "adam_clip: shadow_bf16 overlaps p");
-    int64_t b = ((n + 7) / 8 + 255) / 256;
-    if (b > 8192) b = 8192;
-    if (ema)
-        hipLaunchKernelGGL(adam_clip_kernel<true>, dim3((int)b), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema,
-                           decay_mask, n, beta1, beta2, eps, step_size, bc2_sqrt, ema_w, decay, grad_scale,
-                           dev_step, (unsigned short*)shadow_bf16, clip_state);
-    else
-        hipLaunchKernelGGL(adam_clip_kernel<false>, dim3((int)b), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
-                           (float*)nullptr, decay_mask, n, beta1, beta2, eps, step_size, bc2_sqrt, 0.0f, decay,
-                           grad_scale, dev_step, (unsigned short*)shadow_bf16, clip_state);
-    QARIG_CHECK_LAUNCH("adam_clip");
-    return QARIG_OK;
+    QARIG_CHECK_ARG(clip_state, "adam_clip: bad arguments");
+    return adam_launch("adam_clip", true, p, g, m, v, ema, decay_mask, n, beta1, beta2, eps, step_size, bc2_sqrt,
+                       ema_w, decay, grad_scale, dev_step, shadow_bf16, clip_state, stream);
 }
 
 // a <-> b, n floats each, bit-exact.  The buffers must not overlap (refused).

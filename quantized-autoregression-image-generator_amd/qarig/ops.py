@@ -1657,9 +1657,22 @@ def ssim_bwd(a, b, maps, g, data_range=2.0, sigma=1.5, taps=11, k1=0.01, k2=0.03
     return da
 
 
+def _adam_asserts(p, shadow, ema=None, decay_mask=None, dev_step=None, dev_floats=None, clip_state=None):
+    """What the four Adam wrappers ask of their optional tensors.  dev_floats: the (least, most) floats dev_step may
+    hold."""
+    n = p.numel()
+    assert shadow is None or (shadow.dtype == torch.bfloat16 and shadow.numel() == n)
+    assert ema is None or (ema.dtype == torch.float32 and ema.numel() == n and ema.is_contiguous())
+    assert decay_mask is None or (decay_mask.dtype == torch.uint8 and decay_mask.is_contiguous()
+                                  and decay_mask.is_cuda and decay_mask.numel() == (n + 7) // 8)
+    assert dev_step is None or dev_floats is None or dev_floats[0] <= dev_step.numel() <= dev_floats[1]
+    assert clip_state is None or (clip_state.dtype == torch.float64 and clip_state.is_cuda
+                                  and clip_state.numel() == 4)
+
+
 def adam_step(p, g, m, v, beta1, beta2, eps, step_size, bc2_sqrt, grad_scale=1.0, dev_step=None, shadow=None):
     """shadow: optional bf16 tensor of p's numel that receives the updated parameters (reduced precision)."""
-    assert shadow is None or (shadow.dtype == torch.bfloat16 and shadow.numel() == p.numel())
+    _adam_asserts(p, shadow)
     check(_lib.load().qarig_adam_step(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), beta1, beta2, eps,
                                       step_size, bc2_sqrt, grad_scale, ptr(dev_step), ptr(shadow), stream()),
           "qarig_adam_step")
@@ -1669,9 +1682,8 @@ def adam_ema_step(p, g, m, v, ema, beta1, beta2, eps, step_size, bc2_sqrt, ema_w
                   shadow=None):
     """adam_step that also moves `ema` (fp32, p's numel) towards the updated parameters by weight ema_w.
     dev_step, when given, holds three floats: {step_size, bc2_sqrt, ema_w}."""
-    assert shadow is None or (shadow.dtype == torch.bfloat16 and shadow.numel() == p.numel())
-    assert ema.dtype == torch.float32 and ema.numel() == p.numel() and ema.is_contiguous()
-    assert dev_step is None or dev_step.numel() >= 3
+    assert ema is not None
+    _adam_asserts(p, shadow, ema, dev_step=dev_step, dev_floats=(3, math.inf))
     check(_lib.load().qarig_adam_ema_step(ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), p.numel(), beta1, beta2, eps,
                                           step_size, bc2_sqrt, ema_w, grad_scale, ptr(dev_step), ptr(shadow),
                                           stream()),
@@ -1683,11 +1695,8 @@ def adamw_step(p, g, m, v, ema, decay_mask, beta1, beta2, eps, step_size, bc2_sq
     """adam_step / adam_ema_step (ema may be None) behind a decoupled weight decay: the elements of the groups of 8
     whose byte in `decay_mask` (uint8, ceil(numel / 8) entries) is non-zero are first moved to fma(-decay, p, p),
     decay = fp32(lr * lambda).  dev_step, when given, holds four floats: {step_size, bc2_sqrt, ema_w, decay}."""
-    assert shadow is None or (shadow.dtype == torch.bfloat16 and shadow.numel() == p.numel())
-    assert ema is None or (ema.dtype == torch.float32 and ema.numel() == p.numel() and ema.is_contiguous())
-    assert decay_mask.dtype == torch.uint8 and decay_mask.is_contiguous() and decay_mask.is_cuda \
-        and decay_mask.numel() == (p.numel() + 7) // 8
-    assert dev_step is None or dev_step.numel() == 4
+    assert decay_mask is not None
+    _adam_asserts(p, shadow, ema, decay_mask, dev_step, (4, 4))
     check(_lib.load().qarig_adamw_step(ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), ptr(decay_mask), p.numel(), beta1,
                                        beta2, eps, step_size, bc2_sqrt, ema_w, decay, grad_scale, ptr(dev_step),
                                        ptr(shadow), stream()),
@@ -1715,12 +1724,8 @@ def adam_clip_step(p, g, m, v, ema, decay_mask, beta1, beta2, eps, step_size, bc
     """adamw_step with the gradient also scaled by clip_state[1], skipped on the device when clip_state[0] is not
     finite (clip_state: the four doubles grad_clip_coef leaves).  ema and decay_mask may be None.  dev_step, when
     given, holds four floats: {step_size, bc2_sqrt, ema_w, decay}."""
-    assert shadow is None or (shadow.dtype == torch.bfloat16 and shadow.numel() == p.numel())
-    assert ema is None or (ema.dtype == torch.float32 and ema.numel() == p.numel() and ema.is_contiguous())
-    assert decay_mask is None or (decay_mask.dtype == torch.uint8 and decay_mask.is_contiguous()
-                                  and decay_mask.is_cuda and decay_mask.numel() == (p.numel() + 7) // 8)
-    assert dev_step is None or dev_step.numel() == 4
-    assert clip_state.dtype == torch.float64 and clip_state.is_cuda and clip_state.numel() == 4
+    assert clip_state is not None
+    _adam_asserts(p, shadow, ema, decay_mask, dev_step, (4, 4), clip_state)
     check(_lib.load().qarig_adam_clip_step(ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), ptr(decay_mask), p.numel(),
                                            beta1, beta2, eps, step_size, bc2_sqrt, ema_w, decay, grad_scale,
                                            ptr(dev_step), ptr(shadow), ptr(clip_state), stream()),

@@ -86,6 +86,36 @@ def test_tolerances_reject_the_mutant(mutant):
             assert case["id"] in dict(rejected), (mutant, case["id"])
 
 
+# ---- the emulation is the source: csrc/adam_element.h on the host, bit for bit ---------------------------------
+@pytest.fixture(scope="module")
+def element_exe(tmp_path_factory):
+    return C.build_element_program(tmp_path_factory.mktemp("adam_element"))
+
+
+@pytest.mark.parametrize("with_ema", [True, False], ids=["ema", "plain"])
+@pytest.mark.parametrize("case", CASES, ids=[c["id"] for c in CASES])
+def test_kernel_element_on_the_host_is_the_emulation(case, with_ema, element_exe):
+    """The element function every kernel of csrc/optim.hip calls, compiled for the host and chained over the steps
+    for each element (decayed by element_mask, the raw gradient and grad_scale as adam_kernel and the grouped
+    kernel without the clip pass them): p, m, v and ema after every step carry adamw_emulate32's bits, and the
+    shadow's conversion gives torch's bf16 of p."""
+    x = C.make_inputs(case)
+    ema = x["ema"] if with_ema else None
+    want = C.adamw_emulate32(x["p"], x["grads"], x["mask"], x["scalars"], x["beta1"], x["beta2"], x["eps"],
+                             x["grad_scale"], ema=ema)
+    got = C.run_element_program(element_exe, x["p"], ema, C.element_mask(x["mask"], x["p"].shape[0]), x["beta1"],
+                                x["beta2"], x["eps"],
+                                [dict(s, g=g, scale=x["grad_scale"]) for g, s in zip(x["grads"], x["scalars"])])
+    assert len(got) == len(want) == C.STEPS
+    for t, (a, b) in enumerate(zip(got, want)):
+        for k in ("p", "m", "v") + (("ema",) if with_ema else ()):
+            assert np.array_equal(a[k], b[k].view(np.uint32)), (t, k)
+        # the shadow: p rounded to nearest-even bf16, as torch rounds it
+        bf16 = torch.from_numpy(b["p"]).to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16)
+        assert np.array_equal(a["shadow"], bf16.astype(np.uint32)), t
+    assert not np.array_equal(got[-1]["p"], x["p"].view(np.uint32))
+
+
 def test_fma_form_against_the_rounded_factor():
     """Why fma(-c, p, p): below 1 fp32 steps by 2^-24 = 6e-8, so at lr lambda = 1e-6 the factor fp32(1 - c) is
     1 - 17 x 2^-24 -- a decay of 1.0133e-6, off by 1.3 % (up to 3 % at other values, more for smaller c) -- while

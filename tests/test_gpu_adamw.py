@@ -1,5 +1,5 @@
-"""qarig_adamw_step (csrc/optim.hip adamw_kernel) against its fp64 definition and against the plain Adam entries:
-tolerances, inputs and masks from tests/adamw_cases.py, where the bounds are derived (and
+"""qarig_adamw_step (csrc/optim.hip adam_groups_kernel) against its fp64 definition and against the plain Adam
+entries: tolerances, inputs and masks from tests/adamw_cases.py, where the bounds are derived (and
 tests/test_adamw_host.py shows the specified arithmetic meets them and seven wrong AdamWs do not)."""
 import pytest
 import torch

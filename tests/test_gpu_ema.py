@@ -113,6 +113,50 @@ def test_ema_launch_leaves_adam_bit_identical(n, with_dev_step, with_shadow):
 SENTINEL = 0x7FC0BEEF      # a NaN with a payload
 
 
+@pytest.mark.parametrize("with_ema", [False, True], ids=["adam", "adam_ema"])
+@pytest.mark.parametrize("off", [1, 3])
+@pytest.mark.parametrize("n", [1, 7, 9, 257, 2049])
+def test_plain_entries_take_views_of_any_4_byte_alignment(n, off, with_ema):
+    """ops.adam_step and ops.adam_ema_step on views that start `off` floats into 16-byte-aligned buffers (the shadow
+    `off` bf16 into its own), shadow on: the same bits as the same call on aligned copies, and the sentinels on both
+    sides of every view keep theirs.  The grouped entries, with which these two share the host side, demand 16-byte
+    alignment; these two must not."""
+    from qarig import ops
+    pad = 8
+    gen = torch.Generator(device="cuda").manual_seed(100 * n + off)
+    vals = [torch.randn(n, device="cuda", generator=gen), torch.randn(n, device="cuda", generator=gen),
+            torch.randn(n, device="cuda", generator=gen) * 0.1, torch.rand(n, device="cuda", generator=gen) * 0.01,
+            torch.randn(n, device="cuda", generator=gen)]                          # p, g, m, v, ema
+
+    def view_into(dtype, fill, as_dtype):
+        buf = torch.full((off + n + pad,), fill, dtype=dtype, device="cuda")
+        view = buf[off:off + n].view(as_dtype)
+        assert buf.data_ptr() % 16 == 0 and view.data_ptr() == buf.data_ptr() + off * buf.element_size()
+        return buf, view
+
+    bufs, views = zip(*(view_into(torch.int32, SENTINEL, torch.float32) for _ in vals))
+    for view, x in zip(views, vals):
+        view.copy_(x)
+    sbuf, sview = view_into(torch.int16, 0x7FC1, torch.bfloat16)
+    aligned = [x.clone() for x in vals]
+    shadow = torch.zeros(n, dtype=torch.bfloat16, device="cuda")
+    assert all(x.data_ptr() % 16 == 0 for x in aligned + [shadow])
+    for (p, g, m, v, e), sh in ((views, sview), (aligned, shadow)):
+        if with_ema:
+            ops.adam_ema_step(p, g, m, v, e, B1, B2, EPS, 2e-3, 0.0316, 0.25, 0.5, shadow=sh)
+        else:
+            ops.adam_step(p, g, m, v, B1, B2, EPS, 2e-3, 0.0316, 0.5, shadow=sh)
+    torch.cuda.synchronize()
+    for k, (view, x, x0) in enumerate(zip(views, aligned, vals)):
+        assert _same_bits(view, x), k
+        assert _same_bits(x, x0) == (k == 1 or (k == 4 and not with_ema)), k      # all moved but g (and an unused ema)
+    assert torch.equal(sview.view(torch.int16), shadow.view(torch.int16))
+    assert torch.equal(shadow, aligned[0].to(torch.bfloat16))
+    for buf in bufs:
+        assert bool((buf[:off] == SENTINEL).all()) and bool((buf[off + n:] == SENTINEL).all())
+    assert bool((sbuf[:off] == 0x7FC1).all()) and bool((sbuf[off + n:] == 0x7FC1).all())
+
+
 @pytest.mark.parametrize("off", [0, 4, 1])         # 0 and 4: 16-byte aligned views; 1: the scalar form
 @pytest.mark.parametrize("n", [1, 3, 4, 1023, 2 ** 20 + 1])
 def test_swap_is_bit_exact_and_stays_inside_its_views(n, off):

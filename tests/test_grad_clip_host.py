@@ -164,6 +164,33 @@ def test_emulation_meets_the_tolerances(case, nan_step):
             assert np.array_equal(got[0][k].view(np.int32), got[1][k].view(np.int32))
 
 
+# ---- the emulation is the source: csrc/adam_element.h on the host, called as the clip instantiation calls it -----
+@pytest.fixture(scope="module")
+def element_exe(tmp_path_factory):
+    return A.build_element_program(tmp_path_factory.mktemp("adam_element"))
+
+
+@pytest.mark.parametrize("nan_step", [None, 1])
+@pytest.mark.parametrize("case", CASES, ids=[c["id"] for c in CASES])
+def test_kernel_element_on_the_host_is_the_emulation(case, nan_step, element_exe):
+    """The kernels' element function compiled for the host, fed what adam_groups_kernel<*, true> feeds it: the
+    gradient argument fp32(g * grad_scale), the scale argument coef, norm and coef those of clip_emulate32's own
+    step; a step with a norm that is not finite leaves the state alone.  p, m, v and ema after every step carry
+    clip_emulate32's bits."""
+    x = C.make_inputs(case, nan_step=nan_step)
+    want = C.clip_emulate32(x["p"], x["grads"], x["mask"], x["scalars"], x["beta1"], x["beta2"], x["eps"],
+                            x["grad_scale"], x["max_norm"], ema=x["ema"])
+    steps = [dict(s, g=g, pre=x["grad_scale"], scale=w["coef"], skipped=not math.isfinite(w["norm"]))
+             for g, s, w in zip(x["grads"], x["scalars"], want)]
+    assert [s["skipped"] for s in steps] == [t == nan_step for t in range(C.STEPS)]
+    got = A.run_element_program(element_exe, x["p"], x["ema"], A.element_mask(x["mask"], x["p"].shape[0]),
+                                x["beta1"], x["beta2"], x["eps"], steps, clip=True)
+    for t, (a, b) in enumerate(zip(got, want)):
+        for k in ("p", "m", "v", "ema"):
+            assert np.array_equal(a[k], b[k].view(np.uint32)), (t, k)
+    assert not np.array_equal(got[-1]["p"], x["p"].view(np.uint32))
+
+
 def _rejected(case, mutant):
     """Does the mutant leave a tolerance on this case?  The norm's for the accumulation mutant, the chain's for
     the others (with a NaN in the second step for the two skip mutants)."""
