@@ -148,6 +148,44 @@ def _zero_padded_rows(dy, M, N, ld):
     return out
 
 
+def _layer_grads(dT, X, w, b, need_w, need_b):
+    """(dW, db) of one Linear layer from its pre-activation gradient dT and its input X: the bias gradient rides
+    on the weight-gradient launch when both are wanted."""
+    if need_w:
+        return _wgrad(dT, X, w, b, need_b)
+    return None, (_bgrad(dT, b) if need_b else None)
+
+
+def _mlp_fwd(x2, w1, b1, w2, b2, act1, act2):
+    """The two forward products of one fp32 MLP: (y, t2 or None, t1, h)."""
+    h, t1 = ops.gemm(x2, w1, bias=b1, want_preact=True, act=act1)
+    if act2:
+        y, t2 = ops.gemm(h, w2, bias=b2, want_preact=True, act=act2)
+    else:
+        y, t2 = ops.gemm(h, w2, bias=b2), None
+    return y, t2, t1, h
+
+
+def _mlp_layer1_bwd(dT1, x2, w1, params, need, dx=None):
+    """Backward of an fp32 MLP's first layer from dT1; w1: the product's operand, params = (w1, b1) as the
+    parameters that own the gradients, need = needs_input_grad of (x, w1, b1).  dx: the input gradient so far
+    (the blocks of a shared input accumulate into the first one's).  Returns (dx, dw1, db1)."""
+    if need[0]:
+        if dx is None:
+            dx = ops.gemm(dT1, w1, a_kcontig=True, b_kcontig=False)
+        else:
+            ops.gemm(dT1, w1, a_kcontig=True, b_kcontig=False, out=dx, accumulate=True, splitk=1)
+    return (dx, *_layer_grads(dT1, x2, *params, need[1], need[2]))
+
+
+def _mlp_bwd(dT2, x2, w1, b1, w2, b2, t1, h, act1, need, dx=None):
+    """Backward of one fp32 MLP from dT2; need = needs_input_grad of (x, w1, b1, w2, b2), dx as in
+    _mlp_layer1_bwd.  Returns (dx, dw1, db1, dw2, db2)."""
+    dT1 = ops.gemm(dT2, w2, a_kcontig=True, b_kcontig=False, gradz=t1, gact=act1)
+    dw2, db2 = _layer_grads(dT2, h, w2, b2, need[3], need[4])
+    return (*_mlp_layer1_bwd(dT1, x2, w1, (w1, b1), need, dx), dw2, db2)
+
+
 class _MLP2(torch.autograd.Function):
     """y = act2(act1(x W1^T + b1) W2^T + b2): the two-layer MLPs that make up q/k/v
     blocks, the FFN, the pos-cond MLP and the classifier (reference
@@ -167,10 +205,11 @@ class _MLP2(torch.autograd.Function):
         require_cuda(x, w1, w2)
         shp = x.shape
         x2 = _2d(f32c(x))
-        h, t1 = ops.gemm(x2, w1, bias=b1, want_preact=True, act=act1)
         N, K = w2.shape
         ctx.pad = _MLP2._padded_out(x2.shape[0], N, K, act2, b2)
         ctx.native = ctx.pad and ops.ragged_output_native(x2.shape[0], N, K)
+        if ctx.pad:
+            h, t1 = ops.gemm(x2, w1, bias=b1, want_preact=True, act=act1)
         if ctx.native:
             # the GEMM entry takes the true width: ring on the first 128 q columns, tail kernel on the rest,
             # into rows of whole 16-float groups; only the backward's zero-row-padded weight image is built
@@ -192,10 +231,7 @@ class _MLP2(torch.autograd.Function):
             y, t2 = ops.gemm(h, w2p, bias=b2p, flop_frac=N / Np)[:, :N].contiguous(), None
             ctx.save_for_backward(x2, w1, w2p, t1, h, t2)
         else:
-            if act2:
-                y, t2 = ops.gemm(h, w2, bias=b2, want_preact=True, act=act2)
-            else:
-                y, t2 = ops.gemm(h, w2, bias=b2), None
+            y, t2, t1, h = _mlp_fwd(x2, w1, b1, w2, b2, act1, act2)
             ctx.save_for_backward(x2, w1, w2, t1, h, t2)
         ctx.act1, ctx.act2 = act1, act2
         ctx.params = (w1, b1, w2, b2)
@@ -243,23 +279,17 @@ class _MLP2(torch.autograd.Function):
                         db2 = dbp[:N]
         else:
             dT2 = ops.act_bwd(dy2, t2, ctx.act2) if ctx.act2 else dy2
-            dT1 = ops.gemm(dT2, w2, a_kcontig=True, b_kcontig=False, gradz=t1, gact=ctx.act1)
-            if ctx.needs_input_grad[3]:
-                dw2, db2 = _wgrad(dT2, h, ctx.params[2], ctx.params[3], ctx.needs_input_grad[4])
-            elif ctx.needs_input_grad[4]:
-                db2 = _bgrad(dT2, ctx.params[3])
+            dx, *grads = _mlp_bwd(dT2, x2, *ctx.params, t1, h, ctx.act1, ctx.needs_input_grad)
+            if dx is not None:
+                dx = dx.reshape(*dy.shape[:-1], w1.shape[1])
+            return (dx, *grads, None, None)
         return (*_MLP2._backward_layer1(ctx, dy, dT1, x2, w1), dw2, db2, None, None)
 
     @staticmethod
     def _backward_layer1(ctx, dy, dT1, x2, w1):
-        dx = dw1 = db1 = None
-        if ctx.needs_input_grad[0]:
-            dx = ops.gemm(dT1, w1, a_kcontig=True, b_kcontig=False).reshape(
-                *dy.shape[:-1], w1.shape[1])
-        if ctx.needs_input_grad[1]:
-            dw1, db1 = _wgrad(dT1, x2, ctx.params[0], ctx.params[1], ctx.needs_input_grad[2])
-        elif ctx.needs_input_grad[2]:
-            db1 = _bgrad(dT1, ctx.params[1])
+        dx, dw1, db1 = _mlp_layer1_bwd(dT1, x2, w1, ctx.params[:2], ctx.needs_input_grad)
+        if dx is not None:
+            dx = dx.reshape(*dy.shape[:-1], w1.shape[1])
         return dx, dw1, db1
 
 
@@ -286,14 +316,9 @@ class _MLP2x3(torch.autograd.Function):
         x2 = _2d(f32c(x))
         outs, saved = [], [x2]
         for i in range(3):
-            w1, b1, w2, b2 = params[4 * i:4 * i + 4]
-            h, t1 = ops.gemm(x2, w1, bias=b1, want_preact=True, act=act1)
-            if act2:
-                y, t2 = ops.gemm(h, w2, bias=b2, want_preact=True, act=act2)
-            else:
-                y, t2 = ops.gemm(h, w2, bias=b2), None
-            outs.append(y.reshape(*shp[:-1], w2.shape[0]))
-            saved += [t1, h, t2 if t2 is not None else x2.new_empty(0)]
+            y, t2, t1, h = _mlp_fwd(x2, *params[4 * i:4 * i + 4], act1, act2)
+            outs.append(y.reshape(*shp[:-1], y.shape[1]))
+            saved += [t1, h, t2]
         ctx.save_for_backward(*saved)
         ctx.act1, ctx.act2 = act1, act2
         ctx.params = params
@@ -306,27 +331,13 @@ class _MLP2x3(torch.autograd.Function):
         grads = []
         dx = None
         for i in range(3):
-            w1, b1, w2, b2 = ctx.params[4 * i:4 * i + 4]
             t1, h, t2 = saved[1 + 3 * i:4 + 3 * i]
             dy2 = _2d(f32c(dys[i]))
             dT2 = ops.act_bwd(dy2, t2, ctx.act2) if ctx.act2 else dy2
-            dT1 = ops.gemm(dT2, w2, a_kcontig=True, b_kcontig=False, gradz=t1, gact=ctx.act1)
             ni = 3 + 4 * i          # needs_input_grad index of w1
-            dw1 = db1 = dw2 = db2 = None
-            if ctx.needs_input_grad[ni + 2]:
-                dw2, db2 = _wgrad(dT2, h, w2, b2, ctx.needs_input_grad[ni + 3])
-            elif ctx.needs_input_grad[ni + 3]:
-                db2 = _bgrad(dT2, b2)
-            if ctx.needs_input_grad[0]:
-                if dx is None:
-                    dx = ops.gemm(dT1, w1, a_kcontig=True, b_kcontig=False)
-                else:
-                    ops.gemm(dT1, w1, a_kcontig=True, b_kcontig=False, out=dx, accumulate=True, splitk=1)
-            if ctx.needs_input_grad[ni]:
-                dw1, db1 = _wgrad(dT1, x2, w1, b1, ctx.needs_input_grad[ni + 1])
-            elif ctx.needs_input_grad[ni + 1]:
-                db1 = _bgrad(dT1, b1)
-            grads += [dw1, db1, dw2, db2]
+            need = (ctx.needs_input_grad[0], *ctx.needs_input_grad[ni:ni + 4])
+            dx, *block = _mlp_bwd(dT2, x2, *ctx.params[4 * i:4 * i + 4], t1, h, ctx.act1, need, dx)
+            grads += block
         if dx is not None:
             dx = dx.reshape(*dys[0].shape[:-1], x2.shape[1])
         return (dx, None, None, *grads)
@@ -455,25 +466,25 @@ def _mlp_group_ok(x, blocks_params, M):
 
 
 def mlp2xg(x, blocks_params, act1, act2=0):
-    """blocks_params: G (w1, b1, w2, b2) tuples of one shape, all applied to x.  Returns G tensors."""
-    M = x.numel() // x.shape[-1]
-    if not _no_grad() and _mlp_group_ok(x, blocks_params, M):
-        return _MLP2xG.apply(x, act1, act2, *[t for p in blocks_params for t in p])
-    if len(blocks_params) == 3:
-        return mlp2x3(x, blocks_params, act1, act2, _grouped=False)
+    """blocks_params: G (w1, b1, w2, b2) tuples of one shape, all applied to x.  Returns G tensors.
+    In order: without grad mode the plain products; one grouped launch per product where _mlp_group_ok holds; for
+    G = 3 the three-block node on the shared input -- the reduced-precision one where the mode supports the shapes
+    at 128-multiple widths, else the fp32 one; otherwise (the cross-attention k / v pair) G single nodes."""
+    if not _no_grad():
+        flat = [t for p in blocks_params for t in p]
+        if _mlp_group_ok(x, blocks_params, x.numel() // x.shape[-1]):
+            return _MLP2xG.apply(x, act1, act2, *flat)
+        if len(blocks_params) == 3:
+            if ops.lp_mode() and all(_lp().mlp2_supported(x, p[0], p[2]) and p[2].shape[0] % 128 == 0
+                                     for p in blocks_params):
+                return _lp().mlp2x3_node(x, act1, act2, flat)
+            return _MLP2x3.apply(x, act1, act2, *flat)
     return tuple(mlp2(x, *p, act1, act2) for p in blocks_params)
 
 
-def mlp2x3(x, blocks_params, act1, act2=0, _grouped=True):
+def mlp2x3(x, blocks_params, act1, act2=0):
     """blocks_params: three (w1, b1, w2, b2) tuples (q, k, v).  Returns (q, k, v)."""
-    if _no_grad():
-        return tuple(mlp2(x, *p, act1, act2) for p in blocks_params)
-    if _grouped and _mlp_group_ok(x, blocks_params, x.numel() // x.shape[-1]):
-        return _MLP2xG.apply(x, act1, act2, *[t for p in blocks_params for t in p])
-    if ops.lp_mode() and all(_lp().mlp2_supported(x, p[0], p[2]) and p[2].shape[0] % 128 == 0
-                                       for p in blocks_params):
-        return _lp().mlp2x3_node(x, act1, act2, [t for p in blocks_params for t in p])
-    return _MLP2x3.apply(x, act1, act2, *[t for p in blocks_params for t in p])
+    return mlp2xg(x, blocks_params, act1, act2)
 
 
 class _Mul(torch.autograd.Function):

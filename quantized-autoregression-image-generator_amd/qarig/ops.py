@@ -277,20 +277,30 @@ def _lp_put(key, src, value):
     _lp_cache[key] = (weakref.ref(src), value)
 
 
+def _lp_image(head, x, build, extras=(), tail=()):
+    """The cached image of weight x under the key (head, address, shape, *extras, version, LP_EPOCH, *tail):
+    build() makes it on a miss, and it is kept for -- and only served to -- the tensor x stands for (x._qarig_src
+    when x is a detached alias of a parameter, else x).  Under stream capture there is no lookup and no store:
+    the image is rebuilt, so that a replayed graph reads the weights the optimiser has just written and holds no
+    address that an invalidation can free."""
+    if torch.cuda.is_current_stream_capturing():
+        return build()
+    src = getattr(x, "_qarig_src", x)
+    key = (head, x.data_ptr(), tuple(x.shape), *extras, x._version, LP_EPOCH, *tail)
+    hit = _lp_get(key, src)
+    if hit is None:
+        hit = build()
+        _lp_put(key, src, hit)
+    return hit
+
+
 def cast_bf16(x, cache=False):
     """bf16 copy (torch.bfloat16, same shape) of a dense fp32 tensor, rounded to nearest even."""
     assert x.dtype == torch.float32 and x.is_contiguous()
-    key = None
-    if cache and not torch.cuda.is_current_stream_capturing():
-        src = getattr(x, "_qarig_src", x)
-        key = ("n", x.data_ptr(), tuple(x.shape), x._version, LP_EPOCH)
-        hit = _lp_get(key, src)
-        if hit is not None:
-            return hit
+    if cache:
+        return _lp_image("n", x, lambda: cast_bf16(x))
     out = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
     check(_lib.load().qarig_cast_bf16(ptr(x), ptr(out), x.numel(), stream()), "qarig_cast_bf16")
-    if key is not None:
-        _lp_put(key, src, out)
     return out
 
 
@@ -299,22 +309,14 @@ def cast_fp8(x, cache=False, want_bf16=False):
     [, bf16 copy of x from the same pass]) of a dense fp32 tensor: one scale for the tensor, 448 / max|x| (include/qarig.h
     qarig_cast_fp8).  The factor stays on the device; the GEMM epilogue multiplies by it."""
     assert x.dtype == torch.float32 and x.is_contiguous() and x.numel() % 4 == 0
-    key = None
-    if cache and not torch.cuda.is_current_stream_capturing():
-        src = getattr(x, "_qarig_src", x)
-        key = ("f8", x.data_ptr(), tuple(x.shape), x._version, LP_EPOCH)
-        hit = _lp_get(key, src)
-        if hit is not None:
-            return hit
+    if cache:
+        return _lp_image("f8", x, lambda: cast_fp8(x, want_bf16=want_bf16))
     out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
     aux = torch.empty(2, dtype=torch.float32, device=x.device)     # [0] inv_scale, [1] amax bits
     xb = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if want_bf16 else None
     check(_lib.load().qarig_cast_fp8(ptr(x), x.numel(), ptr(out), ptr(aux), aux.data_ptr() + 4, ptr(xb),
                                      stream()), "qarig_cast_fp8")
-    res = (out, aux[:1], xb) if want_bf16 else (out, aux[:1])
-    if key is not None:
-        _lp_put(key, src, res)
-    return res
+    return (out, aux[:1], xb) if want_bf16 else (out, aux[:1])
 
 
 def f8_supported(M, N, K):
@@ -442,41 +444,28 @@ def mx_weight(w, pad_rows=0):
     given -- cached until the next optimiser step under the keys of the bf16 shadows (address,
     shape, version, LP_EPOCH); rebuilt on every call under stream capture, so that a replayed
     graph quantises the weights the optimiser has just written."""
-    src = getattr(w, "_qarig_src", w)
     Np = pad_rows or w.shape[0]
-    capturing = torch.cuda.is_current_stream_capturing()
-    key = ("mx", w.data_ptr(), tuple(w.shape), Np, w._version, LP_EPOCH)
-    if not capturing:
-        hit = _lp_get(key, src)
-        if hit is not None:
-            return hit
-    wd = w.detach()
-    if Np != w.shape[0]:
-        wp = torch.zeros((Np, w.shape[1]), dtype=torch.float32, device=w.device)
-        wp[:w.shape[0]].copy_(wd)
-        wd = wp
-    out = mx_quant(wd if wd.is_contiguous() else wd.contiguous(), row=True, transposed=True)
-    if not capturing:
-        _lp_put(key, src, out)
-    return out
+
+    def quantised():
+        wd = w.detach()
+        if Np != w.shape[0]:
+            wp = torch.zeros((Np, w.shape[1]), dtype=torch.float32, device=w.device)
+            wp[:w.shape[0]].copy_(wd)
+            wd = wp
+        return mx_quant(wd if wd.is_contiguous() else wd.contiguous(), row=True, transposed=True)
+
+    return _lp_image("mx", w, quantised, extras=(Np,))
 
 
 def cast_transpose_bf16(x, cache=False):
     """bf16 (C, R) transpose of a row-contiguous fp32 (R, C) matrix."""
     assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
-    key = None
-    if cache and not torch.cuda.is_current_stream_capturing():
-        src = getattr(x, "_qarig_src", x)
-        key = ("t", x.data_ptr(), tuple(x.shape), x.stride(0), x._version, LP_EPOCH)
-        hit = _lp_get(key, src)
-        if hit is not None:
-            return hit
+    if cache:
+        return _lp_image("t", x, lambda: cast_transpose_bf16(x), extras=(x.stride(0),))
     R, Cc = x.shape
     out = torch.empty((Cc, R), dtype=torch.bfloat16, device=x.device)
     check(_lib.load().qarig_cast_transpose_bf16(ptr(x), x.stride(0), R, Cc, ptr(out), stream()),
           "qarig_cast_transpose_bf16")
-    if key is not None:
-        _lp_put(key, src, out)
     return out
 
 
@@ -1816,13 +1805,14 @@ def _conv_workspace(weight, nbytes, geom, tag, inference):
     must not hold the address of a cache entry that an invalidation can free."""
     if not inference or torch.cuda.is_current_stream_capturing():
         return workspace(nbytes, weight.device, tag), 0
-    key = (tag, weight.data_ptr(), tuple(weight.shape), weight._version, LP_EPOCH, _lib.OPTION_EPOCH, geom)
-    hit = _lp_get(key, weight)
-    if hit is not None:
-        return hit, 1
-    ws = torch.empty(max(16, nbytes), dtype=torch.uint8, device=weight.device)
-    _lp_put(key, weight, ws)
-    return ws, 0
+    fresh = []
+
+    def scratch():
+        fresh.append(torch.empty(max(16, nbytes), dtype=torch.uint8, device=weight.device))
+        return fresh[0]
+
+    ws = _lp_image(tag, weight, scratch, tail=(_lib.OPTION_EPOCH, geom))
+    return ws, int(not fresh)
 
 
 def conv2d_fwd(x, weight, bias, stride, pad, act, want_preact=False, inference=False):
