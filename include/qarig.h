@@ -531,6 +531,32 @@ int qarig_assemble_tokens(const int64_t* lr, int S_lr, const int64_t* hr, int S_
                           int k_lr, int k_hr, const int64_t* offs, int W, int64_t* hr_in,
                           int64_t* hr_tg, int64_t* pos, int* bad_flag, void* stream);
 
+/* Token noise (additive: the reference has none): a training-time corruption of the tokens a stage
+ * READS -- the teacher-forced hr tokens of the decoder input (stream 0) and the lr tokens an encoder conditions on
+ * (stream 1) -- with the targets left clean.  Token j of the full, un-windowed stream (S tokens) of sample n makes
+ * one Philox4x32-10 call (that of qarig_dropout below) with key (seed_lo, seed_hi) and counter
+ * (n S + j, 2^30 | stream, step, rank); bit 30 set and bit 31 clear keeps the counters apart from residual dropout
+ * (small site ordinals) and attention dropout (bit 31 set) under the same key.  With out[4] the call's result the
+ * token is unchanged iff (out[0] & 0xffff) >= threshold (replace rate threshold / 65536) and otherwise becomes
+ * lo + ((uint64)out[1] span >> 32): range == 0 draws from the whole codebook (lo = 0, span = K), range > 0 from
+ * the SOM neighbourhood [lo, hi] = [max(0, id - range), min(K - 1, id + range)], span = hi - lo + 1.  The draw may
+ * return the id itself: the effective change rate is threshold / 65536 (1 - 1 / span).  An id outside [0, K)
+ * passes through (qarig_embedding_fwd flags it).  key: DEVICE uint32[4] {seed_lo, seed_hi, step, rank}.
+ *
+ * qarig_assemble_tokens_noise is qarig_assemble_tokens with stream 0 applied to the hr tokens of hr_in, in the hr
+ * codebook's range (K = k_hr) and before the base model's + k_lr; j is the index into hr, so a token's noise does
+ * not depend on the window that shows it.  <start> and the base model's leading lr tokens are never corrupted;
+ * hr_tg and pos are the plain entry's bits.  qarig_token_noise corrupts a whole (N,S) tensor (out may be ids
+ * itself; any other overlap is refused) and agrees with the fused entry for stream 0 over hr.  Refused (-1)
+ * without a launch: null pointers, threshold outside [1, 58982], range < 0, K < 1, N S >= 2^31 (N S_hr for the
+ * fused entry), stream_id outside {0, 1}. */
+int qarig_assemble_tokens_noise(const int64_t* lr, int S_lr, const int64_t* hr, int S_hr, int N, int base,
+                                int k_lr, int k_hr, const int64_t* offs, int W, int64_t* hr_in,
+                                int64_t* hr_tg, int64_t* pos, int* bad_flag, uint32_t threshold, int range,
+                                const uint32_t* key, void* stream);
+int qarig_token_noise(const int64_t* ids, int64_t* out, int N, int S, int K, uint32_t threshold, int range,
+                      int stream_id, const uint32_t* key, void* stream);
+
 /* nn.Embedding + additive position table -- models/Transformer.py:127-139,154-167.
  * ids int64 (M = N*S); pe (S,D) or NULL; out (M,D). */
 int qarig_embedding_fwd(const int64_t* ids, int M, int S, int D, int V, const float* table,

@@ -73,4 +73,35 @@ QARIG_HD inline bool attn_dropout_keep(uint32_t n, uint32_t H, uint32_t h, uint3
     return dropout_value(out[(j & 7) >> 1], (int)(j & 7), threshold);
 }
 
+// ---- token noise --------------------------------------------------------------------------------
+// Token j of the full, un-windowed stream (S tokens) of sample n: one call philox4x32_10(c0, c1, step, rank,
+// seed_lo, seed_hi) with c0 = n S + j and c1 = 2^30 | stream (0: the decoder's hr tokens, j the index into hr;
+// 1: the encoder's lr tokens).  Bit 30 set and bit 31 clear keeps these counters apart from the other two
+// domains under the same key: the second word of a model's residual dropout is a site ordinal below 2 + (number
+// of residual layers), a few hundred at most (models.Transformer.enable_dropout refuses one at or past 2^30; the
+// bare qarig_dropout entry takes any 32-bit site), and the attention domain above sets bit 31.
+// The token is unchanged iff (out[0] & 0xffff) >= threshold -- the sense of dropout_value, replace rate
+// threshold / 65536 -- and otherwise becomes lo + ((uint64)out[1] span >> 32), where range == 0 draws from the
+// whole codebook (lo = 0, span = K) and range > 0 from the SOM neighbourhood [max(0, id - range),
+// min(K - 1, id + range)], clamped at the ends of the axis.  The draw may return id itself: the effective change
+// rate is threshold / 65536 (1 - 1 / span).  An id outside [0, K) passes through (the embedding kernel flags it).
+#define QARIG_TOKEN_NOISE_DOMAIN 0x40000000u
+#define QARIG_TOKEN_NOISE_STREAMS 2u         // 0: decoder input (hr), 1: encoder input (lr)
+
+QARIG_HD inline uint32_t token_noise_c1(uint32_t stream) { return QARIG_TOKEN_NOISE_DOMAIN | stream; }
+QARIG_HD inline int64_t token_noise_id(int64_t id, uint32_t c0, uint32_t stream, int K, uint32_t threshold, int range,
+                                       uint32_t step, uint32_t rank, uint32_t seed_lo, uint32_t seed_hi) {
+    if (id < 0 || id >= K) return id;
+    uint32_t out[4];
+    philox4x32_10(c0, token_noise_c1(stream), step, rank, seed_lo, seed_hi, out);
+    if (dropout_value(out[0], 0, threshold)) return id;
+    int64_t lo = 0, span = K;
+    if (range > 0) {
+        lo = id - range > 0 ? id - range : 0;
+        const int64_t hi = id + range < K - 1 ? id + range : K - 1;
+        span = hi - lo + 1;
+    }
+    return lo + (int64_t)(((uint64_t)out[1] * (uint64_t)span) >> 32);
+}
+
 }  // namespace qarig

@@ -1,5 +1,6 @@
 // Token embedding + sinusoidal positions (reference models/Transformer.py:127-167,
 // models/layers.py:83-96) and the embedding-weight gradient.
+#include "dropout_philox.h"
 #include "qarig_common.h"
 
 namespace qarig {
@@ -48,14 +49,28 @@ __global__ void embedding_fwd_kernel(const int64_t* __restrict__ ids, int M, int
 // are never materialised; window w of sample n starts at offs[n] and the kernel writes
 // hr_in (N,W), hr_tg (N,W) and the absolute positions pos (N,W) = offs[n] + w directly.
 // window == 0: no sliding window, the whole sequences (W = S_in) and no positions.
-__global__ void assemble_tokens_kernel(const int64_t* __restrict__ lr, int S_lr,
-                                       const int64_t* __restrict__ hr, int S_hr, int N, int base,
-                                       int k_lr, int k_hr, const int64_t* __restrict__ offs, int W,
-                                       int64_t* __restrict__ hr_in, int64_t* __restrict__ hr_tg,
-                                       int64_t* __restrict__ pos, int* __restrict__ bad_flag) {
+// NOISE: hr token j' = j - lead is first passed through token_noise_id (csrc/dropout_philox.h) in the
+// hr codebook's own range, before the base model's + k_lr -- stream 0, counter n S_hr + j', i.e. keyed on the token's
+// place in hr, not on the window that shows it.  <start>, the base model's leading lr tokens, hr_tg and pos are the
+// plain kernel's.
+struct TokenNoise {
+    uint32_t threshold;
+    int range;
+    const uint32_t* key;        // DEVICE {seed_lo, seed_hi, step, rank}
+};
+
+template <bool NOISE>
+__device__ __forceinline__ void assemble_tokens_body(const int64_t* __restrict__ lr, int S_lr,
+                                                     const int64_t* __restrict__ hr, int S_hr, int N, int base,
+                                                     int k_lr, int k_hr, const int64_t* __restrict__ offs, int W,
+                                                     int64_t* __restrict__ hr_in, int64_t* __restrict__ hr_tg,
+                                                     int64_t* __restrict__ pos, int* __restrict__ bad_flag,
+                                                     const TokenNoise noise) {
     const int lead = base ? S_lr : 1;          // tokens in front of the HR tokens of the input
     const int64_t total = (int64_t)N * W;
     const int64_t o_max = (int64_t)lead + S_hr - W;   // last valid window start
+    uint32_t k0 = 0, k1 = 0, step = 0, rank = 0;
+    if (NOISE) k0 = noise.key[0], k1 = noise.key[1], step = noise.key[2], rank = noise.key[3];
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
          idx += (int64_t)gridDim.x * blockDim.x) {
         const int n = (int)(idx / W), w = (int)(idx - (int64_t)n * W);
@@ -67,11 +82,43 @@ __global__ void assemble_tokens_kernel(const int64_t* __restrict__ lr, int S_lr,
         const int64_t j = o + w;                                   // index in the full sequences
         int64_t vin;
         if (j < lead) vin = base ? lr[(int64_t)n * S_lr + j] : (int64_t)k_hr;
-        else vin = hr[(int64_t)n * S_hr + (j - lead)] + (base ? k_lr : 0);
+        else {
+            const int64_t e = (int64_t)n * S_hr + (j - lead);
+            int64_t id = hr[e];
+            if (NOISE) id = token_noise_id(id, (uint32_t)e, 0u, k_hr, noise.threshold, noise.range, step, rank, k0, k1);
+            vin = id + (base ? k_lr : 0);
+        }
         hr_in[idx] = vin;
         hr_tg[idx] = j < S_hr ? hr[(int64_t)n * S_hr + j] : (int64_t)k_hr;
         if (pos) pos[idx] = j;
     }
+}
+
+__global__ void assemble_tokens_kernel(const int64_t* __restrict__ lr, int S_lr,
+                                       const int64_t* __restrict__ hr, int S_hr, int N, int base,
+                                       int k_lr, int k_hr, const int64_t* __restrict__ offs, int W,
+                                       int64_t* __restrict__ hr_in, int64_t* __restrict__ hr_tg,
+                                       int64_t* __restrict__ pos, int* __restrict__ bad_flag) {
+    assemble_tokens_body<false>(lr, S_lr, hr, S_hr, N, base, k_lr, k_hr, offs, W, hr_in, hr_tg, pos, bad_flag,
+                                TokenNoise{0u, 0, nullptr});
+}
+
+__global__ void assemble_tokens_noise_kernel(const int64_t* __restrict__ lr, int S_lr,
+                                             const int64_t* __restrict__ hr, int S_hr, int N, int base,
+                                             int k_lr, int k_hr, const int64_t* __restrict__ offs, int W,
+                                             int64_t* __restrict__ hr_in, int64_t* __restrict__ hr_tg,
+                                             int64_t* __restrict__ pos, int* __restrict__ bad_flag,
+                                             TokenNoise noise) {
+    assemble_tokens_body<true>(lr, S_lr, hr, S_hr, N, base, k_lr, k_hr, offs, W, hr_in, hr_tg, pos, bad_flag, noise);
+}
+
+// out[n][j] = token_noise_id(ids[n][j]) of stream `stream_id` over a whole (N,S) tensor: one token per
+// thread-iteration; out may be ids itself (each thread reads its own element before it writes it).
+__global__ void token_noise_kernel(const int64_t* ids, int64_t* out, int total, int K, uint32_t threshold, int range,
+                                   uint32_t stream_id, const uint32_t* __restrict__ key) {
+    const uint32_t k0 = key[0], k1 = key[1], step = key[2], rank = key[3];
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x)
+        out[e] = token_noise_id(ids[e], (uint32_t)e, stream_id, K, threshold, range, step, rank, k0, k1);
 }
 
 // dtable[v][:] = sum over m with ids[m]==v of dy[m][:], m ascending (deterministic, no
@@ -205,14 +252,10 @@ extern "C" int qarig_embedding_bwd(const int64_t* ids, int M, int D, int V, cons
     return QARIG_OK;
 }
 
-// hr_in / hr_tg / pos (N,W) int64 from the BMU indices (see assemble_tokens_kernel).  lr (N,S_lr)
-// is read by the base model only; offs (N) int64 window starts or NULL (then W must be the
-// input length S_lr + S_hr (base) / 1 + S_hr and pos may be NULL).  An offset outside [0, S_in - W]
-// sets *bad_flag (device int, may be NULL) and is clamped, as the other index-consuming kernels do.
-extern "C" int qarig_assemble_tokens(const int64_t* lr, int S_lr, const int64_t* hr, int S_hr, int N,
-                                     int base, int k_lr, int k_hr, const int64_t* offs, int W,
-                                     int64_t* hr_in, int64_t* hr_tg, int64_t* pos, int* bad_flag,
-                                     void* stream) {
+// The argument checks and the grid of both assemble entries: QARIG_OK and the workgroup count in *blocks.
+static int assemble_tokens_plan(const int64_t* lr, int S_lr, const int64_t* hr, int S_hr, int N, int base,
+                                const int64_t* offs, int W, const int64_t* hr_in, const int64_t* hr_tg,
+                                int* blocks) {
     QARIG_CHECK_ARG(hr && hr_in && hr_tg && (lr || !base), "assemble_tokens: null pointer");
     QARIG_CHECK_ARG(N > 0 && S_hr > 0 && W > 0 && (!base || S_lr > 0), "assemble_tokens: bad extents");
     QARIG_CHECK_DIMS("assemble_tokens", N, S_hr);
@@ -224,10 +267,79 @@ extern "C" int qarig_assemble_tokens(const int64_t* lr, int S_lr, const int64_t*
     // targets line up only for S_lr == 1 -- as in the reference, longer LR
     // sequences simply run out of target (guarded: <end> is written past it)
     const int64_t total = (int64_t)N * W;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
+    const int64_t b = (total + 255) / 256;
+    *blocks = b > 2048 ? 2048 : (int)b;
+    return QARIG_OK;
+}
+
+// hr_in / hr_tg / pos (N,W) int64 from the BMU indices (see assemble_tokens_kernel).  lr (N,S_lr)
+// is read by the base model only; offs (N) int64 window starts or NULL (then W must be the
+// input length S_lr + S_hr (base) / 1 + S_hr and pos may be NULL).  An offset outside [0, S_in - W]
+// sets *bad_flag (device int, may be NULL) and is clamped, as the other index-consuming kernels do.
+extern "C" int qarig_assemble_tokens(const int64_t* lr, int S_lr, const int64_t* hr, int S_hr, int N,
+                                     int base, int k_lr, int k_hr, const int64_t* offs, int W,
+                                     int64_t* hr_in, int64_t* hr_tg, int64_t* pos, int* bad_flag,
+                                     void* stream) {
+    int blocks = 0;
+    if (assemble_tokens_plan(lr, S_lr, hr, S_hr, N, base, offs, W, hr_in, hr_tg, &blocks) != QARIG_OK)
+        return QARIG_ERR_ARG;
     hipLaunchKernelGGL(assemble_tokens_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, lr, S_lr,
                        hr, S_hr, N, base, k_lr, k_hr, offs, W, hr_in, hr_tg, pos, bad_flag);
     QARIG_CHECK_LAUNCH("assemble_tokens");
+    return QARIG_OK;
+}
+
+// What both token-noise entries ask of (threshold, range, K, N S, key).
+static int token_noise_args_ok(const char* who, uint32_t threshold, int range, int K, int N, int S,
+                               const uint32_t* key) {
+    QARIG_CHECK_ARG(key, "%s: null pointer", who);
+    QARIG_CHECK_ARG(threshold >= 1 && threshold <= QARIG_DROPOUT_MAX_THRESHOLD,
+                    "%s: threshold must lie in [1, 58982] (0 < p <= 0.9)", who);
+    QARIG_CHECK_ARG(range >= 0, "%s: range must be >= 0 (0 = the whole codebook), got %d", who, range);
+    QARIG_CHECK_ARG(K >= 1, "%s: the vocabulary needs at least one code, got %d", who, K);
+    QARIG_CHECK_ARG((int64_t)N * S < (1LL << 31), "%s: N S must stay below 2^31 (one counter word)", who);
+    return QARIG_OK;
+}
+
+// qarig_assemble_tokens with token noise on the hr tokens of hr_in (csrc/dropout_philox.h token_noise_id, stream 0,
+// vocabulary k_hr): threshold in [1, 58982], range >= 0 (0 = the whole codebook), key DEVICE uint32[4]
+// {seed_lo, seed_hi, step, rank}.  hr_tg and pos are the plain entry's bits; <start> and the base model's lr tokens
+// are never corrupted.
+extern "C" int qarig_assemble_tokens_noise(const int64_t* lr, int S_lr, const int64_t* hr, int S_hr, int N,
+                                           int base, int k_lr, int k_hr, const int64_t* offs, int W,
+                                           int64_t* hr_in, int64_t* hr_tg, int64_t* pos, int* bad_flag,
+                                           uint32_t threshold, int range, const uint32_t* key, void* stream) {
+    int blocks = 0;
+    if (assemble_tokens_plan(lr, S_lr, hr, S_hr, N, base, offs, W, hr_in, hr_tg, &blocks) != QARIG_OK)
+        return QARIG_ERR_ARG;
+    if (token_noise_args_ok("assemble_tokens_noise", threshold, range, k_hr, N, S_hr, key) != QARIG_OK)
+        return QARIG_ERR_ARG;
+    hipLaunchKernelGGL(assemble_tokens_noise_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, lr, S_lr,
+                       hr, S_hr, N, base, k_lr, k_hr, offs, W, hr_in, hr_tg, pos, bad_flag,
+                       TokenNoise{threshold, range, key});
+    QARIG_CHECK_LAUNCH("assemble_tokens_noise");
+    return QARIG_OK;
+}
+
+// out = token noise of ids (N,S) int64 over the vocabulary [0, K): stream_id 0 (the decoder's hr tokens; agrees with
+// qarig_assemble_tokens_noise token for token) or 1 (the encoder's lr tokens).  out may be ids itself; any other
+// overlap is refused.
+extern "C" int qarig_token_noise(const int64_t* ids, int64_t* out, int N, int S, int K, uint32_t threshold,
+                                 int range, int stream_id, const uint32_t* key, void* stream) {
+    QARIG_CHECK_ARG(ids && out, "token_noise: null pointer");
+    QARIG_CHECK_ARG(N > 0 && S > 0, "token_noise: bad extents");
+    if (token_noise_args_ok("token_noise", threshold, range, K, N, S, key) != QARIG_OK) return QARIG_ERR_ARG;
+    QARIG_CHECK_ARG(stream_id >= 0 && stream_id < (int)QARIG_TOKEN_NOISE_STREAMS,
+                    "token_noise: stream_id must be 0 (decoder input) or 1 (encoder input), got %d", stream_id);
+    const int total = (int)((int64_t)N * S);
+    const uintptr_t ui = (uintptr_t)ids, uo = (uintptr_t)out;
+    const uint64_t bytes = 8 * (uint64_t)total;
+    QARIG_CHECK_ARG(ui == uo || ui + bytes <= uo || uo + bytes <= ui,
+                    "token_noise: ids and out overlap without being the same buffer");
+    int blocks = (int)(((int64_t)total + 255) / 256);
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(token_noise_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, ids, out, total, K,
+                       threshold, range, (uint32_t)stream_id, key);
+    QARIG_CHECK_LAUNCH("token_noise");
     return QARIG_OK;
 }

@@ -35,6 +35,17 @@ def parse_args(argv=None):
                    help="Score the exponential moving average of the weights (the checkpoint's 'model_ema', "
                         "written with --ema-decay) instead of the last-step weights.")
     p.add_argument("--topk", type=int, default=5, help="k of the top-k accuracy.")
+    p.add_argument("--input-noise", type=cc.input_noise_arg, default=0.0,
+                   help="Score under the token noise of training (train_quantized_transformer.py --input-noise): each HR "
+                        "token the decoder reads is replaced with probability P in (0, 0.9]; the targets stay clean.  "
+                        "0 = off.")
+    p.add_argument("--cond-noise", type=cc.cond_noise_arg, default=0.0,
+                   help="The same for the LR tokens an encoder-decoder stage conditions on.  0 = off.")
+    p.add_argument("--noise-range", type=int, default=0,
+                   help="Replacements are drawn from the codes within R of the token's own; 0 = the whole codebook.")
+    p.add_argument("--noise-seed", type=cc.dropout_seed_arg, default=0,
+                   help="64-bit seed of the noise; the step word is the batch number, so the result is a function of "
+                        "the dataset order.")
     p.add_argument("--out-json", type=pathlib.Path, default=None, help="Where the result is written as JSON.")
     return vars(p.parse_args(argv))
 
@@ -59,14 +70,26 @@ def main():
         transformer_hidden_dim=md["transformer_hidden_dim"], hidden_activation=md["hidden_activation"])
     model.custom_load_state_dict(md["model_ema" if args["use_ema"] else "model"])
     model = model.to(device).eval()
+    try:
+        input_noise, cond_noise, noise_range, noise_seed = cc.check_token_noise_args(
+            args["input_noise"], args["cond_noise"], args["noise_range"], args["noise_seed"],
+            train_base_model=md["train_base_model"], k_lr=lr_codebook.num_embeddings, k_hr=hr_codebook.num_embeddings)
+    except ValueError as e:
+        raise SystemExit(str(e))
 
     dataset = FeatureMapDataset(dataset_path=args["dataset_path"], load_image=False, return_filepaths=False)
     loader = torch.utils.data.DataLoader(dataset, batch_size=args["batch_size"], num_workers=2, shuffle=False)
     scorer = evaluate.TokenScorer(model, lr_codebook, hr_codebook, md["train_base_model"],
-                                  md["sliding_window"] if md["use_sliding_window"] else None, topk=args["topk"])
+                                  md["sliding_window"] if md["use_sliding_window"] else None, topk=args["topk"],
+                                  input_noise=input_noise, cond_noise=cond_noise,
+                                  noise_range=noise_range if input_noise or cond_noise else 0,
+                                  noise_seed=noise_seed if input_noise or cond_noise else 0)
     evaluate.score_loader(scorer, loader, device, args["max_batches"])
     result = scorer.result()
     result["weights"] = "model_ema" if args["use_ema"] else "model"
+    for k, v in (("input_noise", input_noise), ("cond_noise", cond_noise), ("noise_range", noise_range),
+                 ("noise_seed", noise_seed)):
+        result.setdefault(k, v)         # the four values are recorded with and without noise
     logging.info(evaluate.summary_line("Eval", result) + f" | images: {result['images']:,}")
     if args["out_json"] is not None:
         args["out_json"].parent.mkdir(parents=True, exist_ok=True)

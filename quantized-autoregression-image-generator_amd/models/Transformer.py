@@ -59,6 +59,7 @@ class Transformer(nn.Module):
         self._pe_cache = {}
         self._dropout = None        # (p, key) while enable_dropout is in force
         self._attn_dropout = None   # (p, key) while enable_attention_dropout is in force
+        self._token_noise = None    # qarig.dropout.TokenNoise (a tuple, the key second) while enable_token_noise is
 
     def custom_load_state_dict(self, state_dict):
         load_matching(self, state_dict)
@@ -92,7 +93,10 @@ class Transformer(nn.Module):
         device = self.dec_embedding.weight.device
         if device.type != "cuda":
             raise RuntimeError("Transformer.enable_dropout needs the model on the GPU (call model.to(device) first)")
-        key = self._shared_key(self._attn_dropout, seed, rank, device)
+        # the site ordinals stay far below 2^30, where the token-noise counters begin (csrc/dropout_philox.h)
+        if 2 + len(self._residual_layers()) >= 1 << 30:
+            raise ValueError("dropout: too many residual layers for the site word of the mask's counter")
+        key = self._shared_key(self._held_key("_dropout"), seed, rank, device)
         self._dropout = (float(p), key)
         for i, res in enumerate(self._residual_layers()):
             res._dropout = (float(p), 2 + i, key)
@@ -103,14 +107,24 @@ class Transformer(nn.Module):
         for res in self._residual_layers():
             res._dropout = None
 
+    _KEY_HOLDERS = ("_dropout", "_attn_dropout", "_token_noise")
+
+    def _held_key(self, but=None):
+        """The DropoutKey held by the features other than `but` (each state carries it second), or None."""
+        for name in self._KEY_HOLDERS:
+            state = getattr(self, name)
+            if name != but and state is not None:
+                return state[1]
+        return None
+
     @staticmethod
-    def _shared_key(other, seed, rank, device):
-        """The model holds one DropoutKey: whichever of enable_dropout and enable_attention_dropout comes second
-        reuses the first one's (`other` = the other feature's state), and must name the same seed and rank."""
+    def _shared_key(key, seed, rank, device):
+        """The model holds one DropoutKey: whichever of enable_dropout, enable_attention_dropout and
+        enable_token_noise comes later reuses the first one's (`key` = what the other features hold), and must name
+        the same seed and rank."""
         from qarig.dropout import DropoutKey
-        if other is None:
+        if key is None:
             return DropoutKey(seed, rank, device)
-        key = other[1]
         if (key.seed, key.rank) != (int(seed), int(rank)):
             raise ValueError(f"the model's dropout key has seed {key.seed}, rank {key.rank}; residual and attention "
                              f"dropout share it, got seed {int(seed)}, rank {int(rank)}")
@@ -118,11 +132,40 @@ class Transformer(nn.Module):
 
     @property
     def dropout_key(self):
-        """The DropoutKey whose step word the training step sets, or None while both dropouts are off."""
-        for state in (self._dropout, self._attn_dropout):
-            if state is not None:
-                return state[1]
-        return None
+        """The DropoutKey whose step word the training step sets, or None while both dropouts and the token noise
+        are off."""
+        return self._held_key()
+
+    # -- token noise (additive; DESIGN 9.39) ----------------------------------------------------------------
+    def enable_token_noise(self, p_input, p_cond, seed, rank=0, neighbour_range=0):
+        """Token noise for cascade training: in training steps the decoder's teacher-forced hr tokens are replaced
+        with probability p_input and the encoder's lr tokens with probability p_cond (each 0 or in (0, 0.9]; both 0
+        disables), the targets staying clean.  neighbour_range 0 draws the replacement from the whole codebook,
+        R > 0 from the codes within R of the token's own on the SOM axis.  The model only holds the state:
+        qarig.pipeline.tokenize_window(token_noise=model.token_noise) applies it where the tokens are assembled, so
+        scoring, sampling and generation, which never pass it, never see noise.  The decision for a token is a pure
+        function of (seed, rank, step, stream, sample, absolute position); the key is the one enable_dropout and
+        enable_attention_dropout use (same seed and rank, ValueError otherwise).  Returns the key."""
+        if p_input == 0 and p_cond == 0:
+            self.disable_token_noise()
+            return None
+        from qarig.dropout import TokenNoise
+        if p_cond != 0 and not self.use_encoder:
+            raise ValueError("token noise: p_cond > 0 needs an encoder (a base model's lr tokens are its start tokens)")
+        device = self.dec_embedding.weight.device
+        if device.type != "cuda":
+            raise RuntimeError("Transformer.enable_token_noise needs the model on the GPU (call model.to(device) first)")
+        noise = TokenNoise.probabilities(p_input, p_cond, neighbour_range)      # ValueError outside (0, 0.9] / R < 0
+        self._token_noise = noise.with_key(self._shared_key(self._held_key("_token_noise"), seed, rank, device))
+        return self._token_noise.key
+
+    def disable_token_noise(self):
+        self._token_noise = None
+
+    @property
+    def token_noise(self):
+        """The qarig.dropout.TokenNoise state tokenize_window takes, or None while token noise is off."""
+        return self._token_noise
 
     # -- attention-probability dropout (additive; DESIGN 9.36) --------------------------------------------
     def _attention_layers(self):
@@ -163,7 +206,7 @@ class Transformer(nn.Module):
                                  f"{ops.ATTENTION_HEAD_DIMS[-1]} kernel, which has no dropout form")
         if len(layers) > ops.ATTN_DROPOUT_SITES:
             raise ValueError(f"attention dropout: {len(layers)} attention layers, at most {ops.ATTN_DROPOUT_SITES}")
-        key = self._shared_key(self._dropout, seed, rank, device)
+        key = self._shared_key(self._held_key("_attn_dropout"), seed, rank, device)
         self._attn_dropout = (float(p), key)
         for i, at in enumerate(layers):
             at._attn_dropout = (float(p), i, key)

@@ -76,6 +76,8 @@ SIGNATURES = {
     "qarig_index_histogram": (I, [P, L, I, P, P, P]),
     "qarig_posemb_fwd": (I, [P, I, I, P, P, P]),
     "qarig_assemble_tokens": (I, [P, I, P, I, I, I, I, I, P, I, P, P, P, P, P]),
+    "qarig_assemble_tokens_noise": (I, [P, I, P, I, I, I, I, I, P, I, P, P, P, P, U, I, P, P]),
+    "qarig_token_noise": (I, [P, P, I, I, I, U, I, I, P, P]),
     "qarig_embedding_fwd": (I, [P, I, I, I, I, P, P, P, P, P]),
     "qarig_embedding_bwd": (I, [P, I, I, I, P, P, P]),
     "qarig_layernorm_fwd": (I, [P, I, I, F, P, P, P, P, P, P, P, P, P]),

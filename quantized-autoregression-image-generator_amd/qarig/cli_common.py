@@ -261,6 +261,74 @@ def check_attn_dropout_args(attn_dropout, dropout_seed, sites=1, batch=1, heads=
     return p, seed
 
 
+def _noise_arg(flag):
+    def parse(text):
+        import argparse
+        from .dropout import threshold_and_scale
+        try:
+            v = float(text)
+            if v != 0.0:
+                threshold_and_scale(v)
+        except ValueError:
+            raise argparse.ArgumentTypeError(f"{flag} must be 0 or lie in (0, 0.9], got {text}")
+        return v
+    return parse
+
+
+input_noise_arg = _noise_arg("--input-noise")
+cond_noise_arg = _noise_arg("--cond-noise")
+
+
+def add_token_noise_args(p):
+    """--input-noise / --cond-noise / --noise-range of a Transformer training command line (additive, all 0 by
+    default; they share --dropout-seed)."""
+    p.add_argument("--input-noise", type=input_noise_arg, default=0.0,
+                   help="(additive; the reference trains on clean tokens) probability P in (0, 0.9] with which each "
+                        "teacher-forced HR token the decoder reads is replaced in training steps (0 = off: the plain "
+                        "token-assembly launch, nothing else is launched or allocated); the targets stay clean.  "
+                        "Models the sampling mistakes a stage meets in generation, where every token it reads was "
+                        "drawn by the model.  The decision is a counter-based function of (--dropout-seed, rank, "
+                        "optimizer step, sample, absolute token position), made inside the token-assembly kernel: "
+                        "the same tokens with --graph-step, and --load-optim continues the sequence.  Sampling, "
+                        "validation and generation never see it")
+    p.add_argument("--cond-noise", type=cond_noise_arg, default=0.0,
+                   help="(additive) the same for the LR tokens an encoder-decoder stage conditions on (in generation: "
+                        "the previous stage's samples): one small launch per step.  Not with --train-base-model, "
+                        "whose LR tokens are its start tokens and are drawn at random in generation")
+    p.add_argument("--noise-range", type=_steps_arg("--noise-range", 0), default=0,
+                   help="(additive) R >= 0: a replaced token is drawn from the codes within R of its own index -- the "
+                        "codebooks are SOMs, neighbouring indices are similar codes -- clamped at the ends of the "
+                        "axis; 0 (default) draws from the whole codebook.  The draw may return the token itself: the "
+                        "effective change rate is P (1 - 1 / span)")
+
+
+def check_token_noise_args(input_noise, cond_noise, noise_range, dropout_seed, train_base_model=False, k_lr=None,
+                           k_hr=None):
+    """(p_input, p_cond, range, seed) once more before anything is launched with them, or ValueError: either
+    probability outside (0, 0.9], a negative range, --cond-noise for a base model, and a range that reaches across
+    the smaller codebook (k_lr, k_hr: the vocabulary sizes, when known)."""
+    from .dropout import TokenNoise
+    seed = int(dropout_seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"--dropout-seed must be an integer in [0, 2^64), got {dropout_seed}")
+    for flag, p in (("--input-noise", input_noise), ("--cond-noise", cond_noise)):
+        try:
+            TokenNoise.probabilities(p, 0.0)
+        except ValueError:
+            raise ValueError(f"{flag} must be 0 or lie in (0, 0.9], got {p}")
+    if isinstance(noise_range, bool) or int(noise_range) != noise_range or noise_range < 0:
+        raise ValueError(f"--noise-range must be an integer >= 0, got {noise_range}")
+    p_input, p_cond, r = float(input_noise), float(cond_noise), int(noise_range)
+    if p_cond > 0 and train_base_model:
+        raise ValueError("--cond-noise does not go with --train-base-model: the base stage's LR tokens are its start "
+                         "tokens, and its generation draws them at random")
+    sizes = [int(k) for k in (k_lr, k_hr) if k is not None]
+    if r > 0 and sizes and r >= min(sizes):
+        raise ValueError(f"--noise-range {r} reaches across the smaller codebook ({min(sizes)} codes): use 0 to draw "
+                         "from the whole codebook")
+    return p_input, p_cond, r, seed
+
+
 def weight_decay_arg(text):
     """argparse type of --weight-decay: 0 (off) or a float in (0, 1]."""
     import argparse

@@ -4,6 +4,7 @@ four-word device key {seed_lo, seed_hi, step, rank} every launch of a model read
 Nothing here draws a random number: the keep-bit of an element is a pure function of (seed, rank, step, site,
 element index), so the only per-step state is the step word, which the training step writes before its forward
 (pipeline.train_step / GraphedTrainStep) from the optimizer's step count."""
+import collections
 import struct
 
 import torch
@@ -26,6 +27,38 @@ def threshold_and_scale(p):
     if not 0 < t <= MAX_THRESHOLD:
         raise ValueError(f"dropout probability must lie in (0, 0.9] and be at least 1/131072, got {p}")
     return t, struct.unpack("f", struct.pack("f", 65536.0 / (65536.0 - t)))[0]
+
+
+class TokenNoise(collections.namedtuple("TokenNoise", "p_input key p_cond neighbour_range t_input t_cond")):
+    """The token-noise state of a model or a scorer (the key second, like the dropout states):
+    replace probabilities of the decoder's hr tokens (p_input) and the encoder's lr tokens (p_cond), their
+    thresholds (0 = that stream is off) and the neighbour range (0 = the whole codebook)."""
+    __slots__ = ()
+
+    @classmethod
+    def probabilities(cls, p_input, p_cond, neighbour_range=0):
+        """The state without a key yet.  Each probability is 0 or one threshold_and_scale accepts (the scale is
+        unused); ValueError otherwise, and for a negative or non-integer range."""
+        p_input, p_cond = float(p_input), float(p_cond)
+        if isinstance(neighbour_range, bool) or int(neighbour_range) != neighbour_range or neighbour_range < 0:
+            raise ValueError(f"token noise: the neighbour range must be an integer >= 0, got {neighbour_range}")
+        t_input = threshold_and_scale(p_input)[0] if p_input != 0.0 else 0
+        t_cond = threshold_and_scale(p_cond)[0] if p_cond != 0.0 else 0
+        return cls(p_input, None, p_cond, int(neighbour_range), t_input, t_cond)
+
+    def with_key(self, key):
+        return self._replace(key=key)
+
+    def input_args(self):
+        """ops.assemble_tokens(noise=...) of the decoder's hr tokens, or None while p_input is 0."""
+        return (self.t_input, self.neighbour_range, self.key.buffer) if self.t_input else None
+
+    def corrupt_cond(self, lr_idx, k_lr):
+        """The encoder's lr tokens: one ops.token_noise launch (stream 1), or lr_idx itself while p_cond is 0."""
+        if not self.t_cond:
+            return lr_idx
+        from . import ops
+        return ops.token_noise(lr_idx, k_lr, self.t_cond, self.neighbour_range, 1, self.key.buffer)
 
 
 def _i32(word):

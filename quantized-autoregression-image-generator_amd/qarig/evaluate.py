@@ -16,9 +16,25 @@ IGNORE_INDEX = -100
 
 
 class TokenScorer:
-    def __init__(self, model, lr_codebook, hr_codebook, train_base_model, window, topk=5):
+    def __init__(self, model, lr_codebook, hr_codebook, train_base_model, window, topk=5, input_noise=0,
+                 cond_noise=0, noise_range=0, noise_seed=0):
+        """input_noise / cond_noise / noise_range / noise_seed: the held-out nll under the token noise of training
+         -- the decoder's hr tokens and the encoder's lr tokens corrupted, the targets clean -- from a
+        key of the scorer's own (rank 0) whose step word is the number of the batch, counted from 0: a
+        deterministic function of the dataset order.  All four 0 (the default): no key, today's calls and bits."""
         if int(topk) < 1:
             raise ValueError(f"topk must be at least 1, got {topk}")
+        self.noise = None
+        self.noise_seed = int(noise_seed)
+        self._noise_args = (input_noise, cond_noise, noise_range)
+        if input_noise != 0 or cond_noise != 0:
+            from .dropout import TokenNoise
+            if cond_noise != 0 and train_base_model:
+                raise ValueError("TokenScorer: cond_noise needs an encoder-decoder stage")
+            self.noise = TokenNoise.probabilities(input_noise, cond_noise, noise_range)     # the key: at the first batch
+        elif noise_range != 0 or self.noise_seed != 0:
+            raise ValueError("TokenScorer: noise_range / noise_seed without input_noise or cond_noise")
+        self._batches = 0
         self.model = model
         self.lr_cb, self.hr_cb = lr_codebook, hr_codebook
         self.base, self.window, self.topk = bool(train_base_model), window, int(topk)
@@ -48,8 +64,17 @@ class TokenScorer:
             self._pos_nll = torch.zeros(seq, dtype=torch.float64, device=dev)
             self._pos_cnt = torch.zeros(seq, dtype=torch.int64, device=dev)
             self._totals = torch.zeros(3, dtype=torch.int64, device=dev)
+            if self.noise is not None:
+                from .dropout import DropoutKey
+                self.noise = self.noise.with_key(DropoutKey(self.noise_seed, 0, dev))
         elif seq != self.seq_len:
             raise ValueError(f"TokenScorer: sequences of {seq} tokens after sequences of {self.seq_len}")
+        noise_args = None
+        if self.noise is not None:
+            self.noise.key.set_step(self._batches)
+            noise_args = self.noise.input_args()
+            lr_idx = self.noise.corrupt_cond(lr_idx, self.lr_cb.num_embeddings)     # before model.encode
+        self._batches += 1
         was_training = model.training
         model.eval()
         try:
@@ -61,7 +86,7 @@ class TokenScorer:
                 W = seq if start is None or self.window is None else min(int(self.window), seq)
                 offs = None if start is None else self._starts(N, start)
                 hr_in, hr_tg, pos = ops.assemble_tokens(lr_idx, hr_idx, self.base, self.lr_cb.num_embeddings,
-                                                        self.hr_cb.num_embeddings, offs, W)
+                                                        self.hr_cb.num_embeddings, offs, W, noise=noise_args)
                 if skip:
                     hr_tg[:, :skip] = IGNORE_INDEX      # counted by the window before
                 logits = model.decode(hr_in, enc, pos, seq)
@@ -89,7 +114,10 @@ class TokenScorer:
                 "perplexity": math.exp(mean) if mean < 700.0 else math.inf,
                 "top1": totals[1] / max(tokens, 1), "topk": totals[2] / max(tokens, 1), "k": self.topk,
                 "per_position_nll": pos.tolist(), "per_position_count": self._pos_cnt.cpu().tolist(),
-                "per_image_nll": img.tolist()}
+                "per_image_nll": img.tolist(),
+                **({} if self.noise is None else
+                   {"input_noise": self.noise.p_input, "cond_noise": self.noise.p_cond,
+                    "noise_range": self.noise.neighbour_range, "noise_seed": self.noise_seed})}
 
 
 def score_loader(scorer, batches, device, max_batches=None):

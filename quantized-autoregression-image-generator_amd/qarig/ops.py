@@ -1004,10 +1004,44 @@ def posemb(pos, D):
     return out
 
 
-def assemble_tokens(lr_idx, hr_idx, base, k_lr, k_hr, offs=None, window=None):
+TOKEN_NOISE_STREAMS = 2        # 0: the decoder's hr tokens, 1: the encoder's lr tokens (csrc/dropout_philox.h)
+
+
+def _token_noise_args(threshold, neighbour_range, key, what):
+    threshold, neighbour_range = int(threshold), int(neighbour_range)
+    if not 1 <= threshold <= DROPOUT_MAX_THRESHOLD:
+        raise ValueError(f"{what}: threshold must lie in [1, {DROPOUT_MAX_THRESHOLD}], got {threshold}")
+    if neighbour_range < 0:
+        raise ValueError(f"{what}: the neighbour range must be >= 0 (0 = the whole codebook), got {neighbour_range}")
+    if key.dtype != torch.int32 or key.numel() != 4 or not key.is_contiguous():
+        raise TypeError(f"{what}: key is a contiguous int32 tensor of 4 words {{seed_lo, seed_hi, step, rank}}")
+    return threshold, neighbour_range
+
+
+def token_noise(ids, k, threshold, neighbour_range, stream_id, key, out=None):
+    """Token noise over a whole (N,S) int64 tensor (include/qarig.h qarig_token_noise): token (n, j) is replaced with
+    probability threshold / 65536 by a draw from the whole codebook [0, k) (neighbour_range 0) or from the ids within
+    neighbour_range of its own, a pure function of (key = device int32[4] {seed_lo, seed_hi, step, rank}, stream_id,
+    n, j).  out: None (a new tensor) or ids itself (in place)."""
+    require_cuda(ids, key, out)
+    if ids.dtype != torch.int64 or ids.dim() != 2 or not ids.is_contiguous():
+        raise TypeError("token_noise: ids must be a contiguous int64 (N,S) tensor")
+    threshold, neighbour_range = _token_noise_args(threshold, neighbour_range, key, "token_noise")
+    y = torch.empty_like(ids) if out is None else out
+    if y.dtype != torch.int64 or y.shape != ids.shape or not y.is_contiguous():
+        raise TypeError("token_noise: out must be a contiguous int64 tensor of ids' shape")
+    N, S = ids.shape
+    check(_lib.load().qarig_token_noise(ptr(ids), ptr(y), N, S, int(k), threshold, neighbour_range, int(stream_id),
+                                        ptr(key), stream()), "qarig_token_noise")
+    return y
+
+
+def assemble_tokens(lr_idx, hr_idx, base, k_lr, k_hr, offs=None, window=None, noise=None):
     """(hr_in, hr_tg, pos) int64 (N,W) from the BMU indices: token assembly + window slicing of
     the training loop (reference train_quantized_transformer.py:423-484) in one launch.
-    offs: int64 (N,) window starts on the device, or None for the whole sequence (pos None)."""
+    offs: int64 (N,) window starts on the device, or None for the whole sequence (pos None).
+    noise: None, or (threshold, neighbour_range, key) -- the hr tokens of hr_in pass through the token noise of
+    stream 0 (qarig_assemble_tokens_noise replaces the plain entry; hr_tg and pos are unchanged)."""
     require_cuda(hr_idx, lr_idx, offs)
     hr_idx = _i64c(hr_idx)
     N, S_hr = hr_idx.shape
@@ -1024,6 +1058,15 @@ def assemble_tokens(lr_idx, hr_idx, base, k_lr, k_hr, offs=None, window=None):
     if offs is not None:
         offs = _i64c(offs)
         assert offs.shape == (N,)
+    if noise is not None:
+        require_cuda(noise[2])
+        threshold, neighbour_range = _token_noise_args(noise[0], noise[1], noise[2], "assemble_tokens")
+        check(_lib.load().qarig_assemble_tokens_noise(ptr(lr_idx) if base else None, S_lr, ptr(hr_idx), S_hr, N,
+                                                      int(base), int(k_lr), int(k_hr), ptr(offs), W, ptr(hr_in),
+                                                      ptr(hr_tg), ptr(pos), ptr(_bad_flag(dev)), threshold,
+                                                      neighbour_range, ptr(noise[2]), stream()),
+              "qarig_assemble_tokens_noise")
+        return hr_in, hr_tg, pos
     check(_lib.load().qarig_assemble_tokens(ptr(lr_idx) if base else None, S_lr, ptr(hr_idx), S_hr, N,
                                             int(base), int(k_lr), int(k_hr), ptr(offs), W, ptr(hr_in),
                                             ptr(hr_tg), ptr(pos), ptr(_bad_flag(dev)), stream()),

@@ -37,10 +37,15 @@ def slide(hr_input, hr_target, window, rand_indices):
     return hr_input.gather(1, offs), hr_target.gather(1, offs), offs
 
 
-def tokenize_window(feature_map, lr_codebook, hr_codebook, train_base_model, window, rand_indices):
+def tokenize_window(feature_map, lr_codebook, hr_codebook, train_base_model, window, rand_indices,
+                    token_noise=None):
     """tokenize + slide fused: BMU indices -> (hr_input, lr_input, hr_target, pos) of ONE window
     per sample, assembled by one kernel (no cat / full / gather / arange launches and no
-    full-length sequences in HBM).  rand_indices None: no sliding window (pos None)."""
+    full-length sequences in HBM).  rand_indices None: no sliding window (pos None).
+    token_noise: a model's noise state (models.Transformer.token_noise) or None.  With p_input > 0 the
+    assembling launch is the noise entry (the hr tokens of hr_input corrupted, hr_target clean); with p_cond > 0 an
+    encoder-decoder stage's lr_input goes through one token-noise launch.  The key's step word must have been
+    written for this step (set_dropout_step).  None: the calls of a run without the feature."""
     from . import ops
     lr_idx = lr_codebook.get_patches_bmu(feature_map, reshape=True)
     hr_idx = hr_codebook.get_patches_bmu(feature_map, reshape=True)
@@ -49,8 +54,13 @@ def tokenize_window(feature_map, lr_codebook, hr_codebook, train_base_model, win
         # pinned + non-blocking: a copy from pageable memory would make the host wait for the device
         offs = offs.pin_memory().to(feature_map.device, non_blocking=True)
     hr_in, hr_tg, pos = ops.assemble_tokens(lr_idx, hr_idx, train_base_model, lr_codebook.num_embeddings,
-                                            hr_codebook.num_embeddings, offs, window)
-    return hr_in, (None if train_base_model else lr_idx), hr_tg, pos
+                                            hr_codebook.num_embeddings, offs, window,
+                                            noise=None if token_noise is None else token_noise.input_args())
+    if train_base_model:        # its lr tokens are the start tokens inside hr_in: never corrupted
+        return hr_in, None, hr_tg, pos
+    if token_noise is not None:
+        lr_idx = token_noise.corrupt_cond(lr_idx, lr_codebook.num_embeddings)
+    return hr_in, lr_idx, hr_tg, pos
 
 
 def num_windows(seq_len, window):
@@ -78,10 +88,12 @@ def loss_pair(loss):
 
 
 def set_dropout_step(model, optim):
-    """With dropout enabled on the model (models.Transformer.enable_dropout): the number of the optimizer step
-    this forward belongs to goes into the mask key's step word -- a non-blocking copy on the current stream,
-    ahead of the forward, eager or replayed.  The step number is the optimizer's, so a run resumed with its
-    optimizer state continues the mask sequence.  Without dropout: nothing."""
+    """With dropout or token noise enabled on the model (models.Transformer.enable_dropout / enable_attention_dropout
+    / enable_token_noise: whichever holds the key): the number of the optimizer step this forward belongs to goes
+    into the mask key's step word -- a non-blocking copy on the current stream, ahead of the forward, eager or
+    replayed.  The step number is the optimizer's, so a run resumed with its optimizer state continues the mask
+    sequence.  Token noise reads the key where the tokens are assembled: an eager loop calls this before
+    tokenize_window (train_step's own call then writes the same word again).  Without any of them: nothing."""
     key = getattr(model, "dropout_key", None)
     if key is not None:
         key.set_step(optim.step_count + 1)
@@ -89,9 +101,9 @@ def set_dropout_step(model, optim):
 
 def _dropout_state(model):
     """What a captured step's launches depend on: the key and the (re-created on every enable) states of residual
-    and attention-probability dropout, compared by identity."""
+    dropout, attention-probability dropout and token noise, compared by identity."""
     return (getattr(model, "dropout_key", None), getattr(model, "_dropout", None),
-            getattr(model, "_attn_dropout", None))
+            getattr(model, "_attn_dropout", None), getattr(model, "_token_noise", None))
 
 
 def train_step(model, optim, hr_input, lr_input, hr_target, pos_idx, dp=True, pos_bound=None,
@@ -248,7 +260,8 @@ class GraphedTrainStep:
 
     def _body(self, z, rand, captured):
         hr_in, lr_in, hr_tg, pos = tokenize_window(z, self.lr_cb, self.hr_cb, self.base, self.window,
-                                                   rand if self.window is not None else None)
+                                                   rand if self.window is not None else None,
+                                                   token_noise=getattr(self.model, "_token_noise", None))
         lr_seq = (z.shape[2] // self.lr_cb.patch_dim[0]) * (z.shape[3] // self.lr_cb.patch_dim[1])
         seq = (z.shape[2] // self.hr_cb.patch_dim[0]) * (z.shape[3] // self.hr_cb.patch_dim[1]) + \
             (lr_seq if self.base else 1)

@@ -95,6 +95,7 @@ def parse_args():
     cc.add_regulariser_args(p)
     cc.add_dropout_args(p)
     cc.add_attn_dropout_args(p)
+    cc.add_token_noise_args(p)
     cc.add_optimizer_args(p)
     cc.add_grad_clip_args(p)
     args = vars(p.parse_args())
@@ -102,6 +103,8 @@ def parse_args():
         cc.check_optimizer_args(args["weight_decay"], args["lr_schedule"], args["lr_warmup_steps"],
                                 args["lr_decay_steps"], args["lr_min_ratio"])
         cc.check_grad_clip_args(args["clip_grad_norm"], args["max_skipped_steps"])
+        cc.check_token_noise_args(args["input_noise"], args["cond_noise"], args["noise_range"], args["dropout_seed"],
+                                  train_base_model=args["train_base_model"])
     except ValueError as e:
         p.error(str(e))
     return args
@@ -204,6 +207,17 @@ def main():
     if attn_dropout > 0:
         # the same key (seed, rank, step word) as --dropout; the attention sites are a namespace of their own
         model.enable_attention_dropout(attn_dropout, dropout_seed, rank=parallel.rank())
+    try:        # (the codebook sizes are known only here)
+        input_noise, cond_noise, noise_range, _ = cc.check_token_noise_args(
+            args["input_noise"], args["cond_noise"], args["noise_range"], dropout_seed,
+            train_base_model=train_base_model, k_lr=lr_num_embeddings, k_hr=hr_num_embeddings)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    token_noise = input_noise > 0 or cond_noise > 0
+    if token_noise:
+        # the same key once more; the tokens are corrupted where they are assembled (pipeline.tokenize_window)
+        model.enable_token_noise(input_noise, cond_noise, dropout_seed, rank=parallel.rank(),
+                                 neighbour_range=noise_range)
 
     dataset = FeatureMapDataset(dataset_path=args["dataset_path"], load_image=False,
                                 return_filepaths=False)
@@ -268,6 +282,12 @@ def main():
         info(f"Attention Dropout: {attn_dropout}")
         if not dropout > 0:
             info(f"Dropout Seed: {dropout_seed}")
+    if token_noise:
+        info(f"Input Noise: {input_noise}")
+        info(f"Cond Noise: {cond_noise}")
+        info(f"Noise Range: {noise_range}")
+        if not (dropout > 0 or attn_dropout > 0):
+            info(f"Dropout Seed: {dropout_seed}")
     if weight_decay > 0:
         info(f"Weight Decay: {weight_decay}")
     if schedule is not None:
@@ -308,6 +328,14 @@ def main():
             model_dict["dropout_seed"] = dropout_seed
         if attn_dropout > 0:        # informational likewise
             model_dict["attn_dropout"] = attn_dropout
+            model_dict["dropout_seed"] = dropout_seed
+        if token_noise:             # informational likewise: the non-zero values
+            if input_noise > 0:
+                model_dict["input_noise"] = input_noise
+            if cond_noise > 0:
+                model_dict["cond_noise"] = cond_noise
+            if noise_range > 0:
+                model_dict["noise_range"] = noise_range
             model_dict["dropout_seed"] = dropout_seed
         if weight_decay > 0:        # informational likewise
             model_dict["weight_decay"] = weight_decay
@@ -417,9 +445,11 @@ def main():
                     nwin = pipeline.num_windows(seq_total, sliding_window)
                     rand = torch.randint(low=0, high=nwin, size=(N * world,))   # CPU global RNG
                     rand = parallel.shard(parallel.broadcast_host_tensor(rand))
+                if token_noise:      # the assembling launch reads the step word (train_step writes it again)
+                    pipeline.set_dropout_step(model, optim)
                 hr_in, lr_in, hr_tg, pos_idx = pipeline.tokenize_window(
                     feature_map, lr_codebook, hr_codebook, train_base_model,
-                    sliding_window if use_sliding_window else None, rand)
+                    sliding_window if use_sliding_window else None, rand, token_noise=model.token_noise)
                 loss = pipeline.train_step(model, optim, hr_in, lr_in, hr_tg, pos_idx,
                                            pos_bound=seq_total, label_smoothing=label_smoothing,
                                            z_loss=z_loss)
