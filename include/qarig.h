@@ -704,6 +704,26 @@ int qarig_cross_entropy_ld_fwd(const float* logits, int64_t ld_logits, const int
 int qarig_cross_entropy_reg_fwd(const float* logits, const int64_t* target, int M, int C, float label_smoothing,
                                 float z_loss, float* loss, float* dlogits, float* row_ws, int* bad_flag,
                                 void* stream);
+/* The same with SOM-neighbour soft targets (additive): the codebooks are one-dimensional self-organising maps, code
+ * t +- 1 decodes to almost the patch of code t, and part of the smoothing mass goes there.  The leading `codes`
+ * classes lie on the SOM axis; classes codes .. C - 1 are special (<end>) and are nobody's neighbour.  For a row with
+ * target t < codes, with w = weights (DEVICE, range + 1 floats of the index distance, weights[0] = 1):
+ *   lo = max(0, t - range), hi = min(codes - 1, t + range),  q[j] = w[|j - t|] / sum_{i = lo .. hi} w[|i - t|]
+ *   h = logs - sum_j q[j] (x[j] - mx)            (cross-entropy against q, from the shifted logits as u is)
+ *   obj = (1 - eps - nu) nll + eps u + nu h + zeta lse^2
+ *   d obj / d x[c] = p[c] (1 + 2 zeta lse) - (1 - eps - nu) [c == t] - eps / C - nu q[c]
+ * -- the window is clamped at the ends of the axis and renormalised.  A row whose target is special takes nu = 0:
+ * the objective and gradient of qarig_cross_entropy_reg_fwd, bit for bit.  neighbour_smoothing in [0, 1),
+ * label_smoothing + neighbour_smoothing < 1 (as fp32), 0 < codes <= C, and with neighbour_smoothing > 0:
+ * 1 <= range <= 31 and weights non-NULL; anything else is refused before a launch.  At neighbour_smoothing = 0 the
+ * call is qarig_cross_entropy_reg_fwd (range and weights are not looked at) and returns its bits.  loss[1] and the
+ * second half of row_ws stay the plain nll.  A window column holding -inf makes the row objective +inf (as u does);
+ * its gradient element is the finite (-eps / C - nu q[c]) / M.  A table entry of exactly 0 takes its column out of the
+ * window.  Everything else as qarig_cross_entropy_reg_fwd states it. */
+int qarig_cross_entropy_soft_fwd(const float* logits, const int64_t* target, int M, int C, int codes,
+                                 float label_smoothing, float z_loss, float neighbour_smoothing, int range,
+                                 const float* weights, float* loss, float* dlogits, float* row_ws, int* bad_flag,
+                                 void* stream);
 
 /* Held-out evaluation (additive; the reference has none), csrc/score.hip.
  * qarig_token_score: logits (M,C) fp32 contiguous, target int64 (M).  Per row, in the shifted form of the

@@ -122,6 +122,7 @@ SIGNATURES = {
     "qarig_cross_entropy_fwd": (I, [P, P, I, I, P, P, P, P, P]),
     "qarig_cross_entropy_ld_fwd": (I, [P, L, P, I, I, P, P, L, P, P, P]),
     "qarig_cross_entropy_reg_fwd": (I, [P, P, I, I, F, F, P, P, P, P, P]),
+    "qarig_cross_entropy_soft_fwd": (I, [P, P, I, I, I, F, F, F, I, P, P, P, P, P, P]),
     "qarig_token_score": (I, [P, P, I, I, L, P, P, P, P]),
     "qarig_score_reduce": (I, [P, P, I, I, I, I, I, P, P, P, P, P]),
     "qarig_pair_error_workspace_bytes": (Z, [I, L]),

@@ -163,6 +163,74 @@ def add_regulariser_args(p):
                         "Logged and evaluated as --label-smoothing describes")
 
 
+def neighbour_smoothing_arg(text):
+    """argparse type of --neighbour-smoothing: a float in [0, 1)."""
+    import argparse
+    try:
+        v = float(text)
+    except ValueError:
+        v = float("nan")
+    if not 0.0 <= v < 1.0:
+        raise argparse.ArgumentTypeError(f"--neighbour-smoothing must lie in [0, 1), got {text}")
+    return v
+
+
+def neighbour_range_arg(text):
+    """argparse type of --neighbour-range: an integer in 1 .. 31."""
+    import argparse
+    try:
+        v = int(text)
+    except ValueError:
+        v = 0
+    if not 1 <= v <= 31:
+        raise argparse.ArgumentTypeError(f"--neighbour-range must be an integer in 1 .. 31, got {text}")
+    return v
+
+
+def neighbour_sigma_arg(text):
+    """argparse type of --neighbour-sigma: a finite float > 0."""
+    import argparse
+    try:
+        v = float(text)
+    except ValueError:
+        v = float("nan")
+    if not 0.0 < v < float("inf"):
+        raise argparse.ArgumentTypeError(f"--neighbour-sigma must be finite and > 0, got {text}")
+    return v
+
+
+def add_neighbour_args(p):
+    """--neighbour-smoothing / --neighbour-range / --neighbour-sigma of a Transformer training command line (additive,
+    off by default)."""
+    p.add_argument("--neighbour-smoothing", type=neighbour_smoothing_arg, default=0.0,
+                   help="(additive) nu in [0, 1), nu + --label-smoothing < 1: that much of the target's mass goes to "
+                        "the HR codes within --neighbour-range of the target's index -- the codebooks are SOMs, "
+                        "neighbouring indices decode to similar patches -- by a Gaussian of the index distance, clamped "
+                        "at the ends of the axis and renormalised; <end> is nobody's neighbour and an <end> target is "
+                        "not smoothed.  0 = off.  One more term of the fused cross-entropy launch.  Logged and "
+                        "evaluated as --label-smoothing describes")
+    p.add_argument("--neighbour-range", type=neighbour_range_arg, default=None,
+                   help="(additive) R in 1 .. 31: the codes either side of the target that share "
+                        "--neighbour-smoothing; required with it, refused without it")
+    p.add_argument("--neighbour-sigma", type=neighbour_sigma_arg, default=None,
+                   help="(additive) width > 0 of the Gaussian of the index distance (default R / 2)")
+
+
+def check_neighbour_args(label_smoothing, z_loss, neighbour_smoothing, neighbour_range, neighbour_sigma, codes=None):
+    """(nu, R, sigma) once more before anything is launched with them, or ValueError, worded by flag: what holds
+    between the flags (nu + --label-smoothing < 1, nu > 0 needs R, R or sigma need nu > 0).  Off: (0.0, None, None)."""
+    from . import ops
+    try:
+        _, _, nu, R, sigma = ops.check_ce_soft(label_smoothing, z_loss, neighbour_smoothing, neighbour_range,
+                                               neighbour_sigma, 1 if codes is None else codes)
+    except ValueError as e:
+        text = str(e)
+        for name in ("label_smoothing", "neighbour_smoothing", "neighbour_range", "neighbour_sigma", "z_loss"):
+            text = text.replace(name, "--" + name.replace("_", "-"))
+        raise ValueError(text)
+    return nu, R, sigma
+
+
 def dropout_arg(text):
     """argparse type of --dropout: 0 (off) or a probability qarig.dropout.threshold_and_scale accepts."""
     import argparse

@@ -764,16 +764,20 @@ class _CrossEntropy(torch.autograd.Function):
 
 class _CrossEntropyReg(torch.autograd.Function):
     """mean CE with label smoothing and z-loss over rows (ops.cross_entropy_reg_fwd): the objective, and the
-    {objective, plain nll} pair as a second, non-differentiable output."""
+    {objective, plain nll} pair as a second, non-differentiable output.  soft: None, or the (neighbour_smoothing,
+    range, sigma, codes) of SOM-neighbour soft targets (ops.cross_entropy_soft_fwd, the same launch)."""
 
     @staticmethod
-    def forward(ctx, logits, target, label_smoothing, z_loss):
+    def forward(ctx, logits, target, label_smoothing, z_loss, soft=None):
         require_cuda(logits, target)
         l2 = _2d(f32c(logits))
         t = target.reshape(-1)
         if t.dtype != torch.int64:
             t = t.long()
-        pair, dl = ops.cross_entropy_reg_fwd(l2, t.contiguous(), label_smoothing, z_loss, want_grad=True)
+        if soft is None:
+            pair, dl = ops.cross_entropy_reg_fwd(l2, t.contiguous(), label_smoothing, z_loss, want_grad=True)
+        else:
+            pair, dl = ops.cross_entropy_soft_fwd(l2, t.contiguous(), label_smoothing, z_loss, *soft, want_grad=True)
         ctx.save_for_backward(dl)
         ctx.shape = logits.shape
         ctx.mark_non_differentiable(pair)
@@ -783,18 +787,27 @@ class _CrossEntropyReg(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dloss, _dpair):
         (dl,) = ctx.saved_tensors
-        return ops.scale_by(dl, f32c(dloss).reshape(1)).reshape(ctx.shape), None, None, None
+        return ops.scale_by(dl, f32c(dloss).reshape(1)).reshape(ctx.shape), None, None, None, None
 
 
-def cross_entropy(logits, target, label_smoothing=0.0, z_loss=0.0):
+def cross_entropy(logits, target, label_smoothing=0.0, z_loss=0.0, *, neighbour_smoothing=0.0, neighbour_range=None,
+                  neighbour_sigma=None, codes=None):
     """Mean cross-entropy over rows.  With label_smoothing = z_loss = 0 (the default) the plain node and launch.
     Otherwise F.cross_entropy(..., label_smoothing=...) + z_loss * mean(logsumexp^2) from the fused launch; the
     returned objective then carries `.pair`, the detached device tensor {objective, plain mean nll}, and `.nll`,
-    its second element (what validation and evaluate_transformer.py report), for logging."""
-    eps, zeta = ops.check_ce_regularisers(label_smoothing, z_loss)
-    if eps == 0.0 and zeta == 0.0:
-        return _CrossEntropy.apply(logits, target)
-    loss, pair = _CrossEntropyReg.apply(logits, target, eps, zeta)
+    its second element (what validation and evaluate_transformer.py report), for logging.
+    neighbour_smoothing > 0 (keyword-only, off by default; ops.check_ce_soft): that much of the target mass goes to
+    the codes within neighbour_range of the target among the leading `codes` classes -- the SOM axis of the
+    codebook -- by a Gaussian of the index distance of width neighbour_sigma (default range / 2), in the same launch
+    and node; `.pair` and `.nll` as with the regularisers.  With neighbour_smoothing = 0 the two branches above."""
+    eps, zeta, nu, R, sigma = ops.check_ce_soft(label_smoothing, z_loss, neighbour_smoothing, neighbour_range,
+                                                neighbour_sigma, codes, logits.shape[-1])
+    if nu == 0.0:
+        if eps == 0.0 and zeta == 0.0:
+            return _CrossEntropy.apply(logits, target)
+        loss, pair = _CrossEntropyReg.apply(logits, target, eps, zeta)
+    else:
+        loss, pair = _CrossEntropyReg.apply(logits, target, eps, zeta, (nu, R, sigma, int(codes)))
     loss.pair = pair
     loss.nll = pair[1]
     return loss

@@ -1572,6 +1572,91 @@ def cross_entropy_reg_fwd(logits2d, target, label_smoothing, z_loss, want_grad=T
     return loss, dl
 
 
+NEIGHBOUR_RANGE_MAX = 31        # a window of 2 R + 1 <= 63 columns: one per lane of the row's wave
+_NEIGHBOUR_WEIGHTS = {}
+
+
+def _f32(v):
+    """The fp32 value a float argument of the C entry arrives as."""
+    import struct
+    return struct.unpack("f", struct.pack("f", v))[0]
+
+
+def neighbour_table(R, sigma):
+    """w[d] = exp(-d^2 / (2 sigma^2)), d = 0 .. R, of the INDEX distance on the SOM axis (not of a distance between
+    the codes' latents): computed in fp64, rounded once to fp32; w[0] = 1.  A host tensor."""
+    d = torch.arange(int(R) + 1, dtype=torch.float64)
+    return torch.exp(-(d * d) / (2.0 * float(sigma) ** 2)).to(torch.float32)
+
+
+def neighbour_weights(R, sigma, device):
+    """neighbour_table(R, sigma) on `device`, made once per (device, R, sigma): a captured step holds its address."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (device, int(R), float(sigma))
+    w = _NEIGHBOUR_WEIGHTS.get(key)
+    if w is None:
+        w = _NEIGHBOUR_WEIGHTS[key] = neighbour_table(R, sigma).to(device)
+    return w
+
+
+def check_ce_soft(label_smoothing=0.0, z_loss=0.0, neighbour_smoothing=0.0, neighbour_range=None,
+                  neighbour_sigma=None, codes=None, classes=None):
+    """(label_smoothing, z_loss, neighbour_smoothing, range, sigma) as qarig_cross_entropy_soft_fwd accepts them, or
+    ValueError.  neighbour_smoothing = 0 gives (eps, zeta, 0.0, None, None) and refuses a range or a sigma: they
+    would do nothing.  neighbour_smoothing > 0 needs a range in 1 .. 31; sigma defaults to range / 2.  codes (the
+    classes on the SOM axis) and classes are checked against each other when both are given."""
+    eps, zeta = check_ce_regularisers(label_smoothing, z_loss)
+    nu = float(neighbour_smoothing)
+    if not 0.0 <= nu < 1.0:
+        raise ValueError(f"neighbour_smoothing must lie in [0, 1), got {neighbour_smoothing}")
+    if not _f32(_f32(eps) + _f32(nu)) < 1.0:
+        raise ValueError(f"label_smoothing + neighbour_smoothing must stay below 1, got {eps} + {nu}")
+    if nu == 0.0:
+        if neighbour_range is not None or neighbour_sigma is not None:
+            raise ValueError("neighbour_range / neighbour_sigma do nothing without neighbour_smoothing > 0")
+        return eps, zeta, 0.0, None, None
+    if neighbour_range is None:
+        raise ValueError("neighbour_smoothing > 0 needs neighbour_range")
+    if isinstance(neighbour_range, bool) or int(neighbour_range) != neighbour_range or \
+            not 1 <= neighbour_range <= NEIGHBOUR_RANGE_MAX:
+        raise ValueError(f"neighbour_range must be an integer in 1 .. {NEIGHBOUR_RANGE_MAX}, got {neighbour_range}")
+    R = int(neighbour_range)
+    sigma = R / 2.0 if neighbour_sigma is None else float(neighbour_sigma)
+    if not 0.0 < sigma < float("inf"):
+        raise ValueError(f"neighbour_sigma must be finite and > 0, got {neighbour_sigma}")
+    if codes is None:
+        raise ValueError("neighbour_smoothing > 0 needs codes, the number of classes on the SOM axis")
+    if isinstance(codes, bool) or int(codes) != codes or codes < 1 or (classes is not None and codes > classes):
+        raise ValueError(f"codes must be an integer in 1 .. C = {classes}, got {codes}")
+    return eps, zeta, nu, R, sigma
+
+
+def cross_entropy_soft_fwd(logits2d, target, label_smoothing=0.0, z_loss=0.0, neighbour_smoothing=0.0,
+                           neighbour_range=None, neighbour_sigma=None, codes=None, want_grad=True):
+    """cross_entropy_reg_fwd with SOM-neighbour soft targets (include/qarig.h qarig_cross_entropy_soft_fwd):
+    neighbour_smoothing of the target mass goes to the codes within neighbour_range of the target among the leading
+    `codes` classes, by a Gaussian of the index distance with width neighbour_sigma (default range / 2), clamped at
+    the ends of the axis and renormalised.  (loss, dlogits) as cross_entropy_reg_fwd; with neighbour_smoothing = 0
+    its bits."""
+    require_cuda(logits2d, target)
+    assert logits2d.dtype == torch.float32 and logits2d.dim() == 2 and logits2d.is_contiguous()
+    assert target.dtype == torch.int64 and target.is_contiguous() and target.numel() == logits2d.shape[0]
+    M, C = logits2d.shape
+    eps, zeta, nu, R, sigma = check_ce_soft(label_smoothing, z_loss, neighbour_smoothing, neighbour_range,
+                                            neighbour_sigma, codes, C)
+    w = neighbour_weights(R, sigma, logits2d.device) if nu > 0 else None
+    loss = torch.empty(2, dtype=torch.float32, device=logits2d.device)
+    dl = torch.empty_like(logits2d) if want_grad else None
+    rows = torch.empty(2 * M, dtype=torch.float32, device=logits2d.device)
+    check(_lib.load().qarig_cross_entropy_soft_fwd(ptr(logits2d), ptr(target), M, C, C if codes is None else int(codes),
+                                                   eps, zeta, nu, R or 0, ptr(w), ptr(loss), ptr(dl), ptr(rows),
+                                                   ptr(_bad_flag(logits2d.device)), stream()),
+          "qarig_cross_entropy_soft_fwd")
+    return loss, dl
+
+
 def token_score(logits2d, target, ignore_index=-100):
     """(row_nll fp32 (M,), row_rank int32 (M,)) of logits (M,C) against int64 targets: the negative
     log-likelihood in nats and the number of classes ranked before the target (0: arg-max, ties to the smaller

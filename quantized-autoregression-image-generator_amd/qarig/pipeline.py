@@ -107,16 +107,21 @@ def _dropout_state(model):
 
 
 def train_step(model, optim, hr_input, lr_input, hr_target, pos_idx, dp=True, pos_bound=None,
-               label_smoothing=0.0, z_loss=0.0):
+               label_smoothing=0.0, z_loss=0.0, neighbour_smoothing=0.0, neighbour_range=None, neighbour_sigma=None,
+               codes=None):
     """forward + CE + backward + gradient all-reduce + Adam.  Returns the loss tensor
     (device scalar; callers decide when to .item()).  pos_bound: exclusive upper bound of
     pos_idx (the un-windowed sequence length) -- sizes the model's position table without
     a device read-back.  label_smoothing, z_loss: the regularisers of QF.cross_entropy (0, 0: the
-    plain loss and launch); the returned objective then has the plain nll beside it, loss_pair()."""
+    plain loss and launch); the returned objective then has the plain nll beside it, loss_pair().
+    neighbour_smoothing, neighbour_range, neighbour_sigma, codes: the SOM-neighbour soft targets of QF.cross_entropy
+    (off by default: the calls above)."""
     set_dropout_step(model, optim)
     optim.zero_grad()
     logits = model(x_dec=hr_input, x_enc=lr_input, pos_cond=pos_idx, pos_bound=pos_bound)
-    loss = QF.cross_entropy(logits.view(-1, logits.shape[-1]), hr_target.flatten(), label_smoothing, z_loss)
+    loss = QF.cross_entropy(logits.view(-1, logits.shape[-1]), hr_target.flatten(), label_smoothing, z_loss,
+                            neighbour_smoothing=neighbour_smoothing, neighbour_range=neighbour_range,
+                            neighbour_sigma=neighbour_sigma, codes=codes)
     loss.backward()
     w = parallel.world_size() if dp else 1
     if dp and not optim.finish_allreduce() and w > 1:   # overlapped buckets, else one exchange
@@ -246,9 +251,18 @@ class GraphedTrainStep:
     launch behind them."""
 
     def __init__(self, model, optim, lr_codebook, hr_codebook, train_base_model, window, warmup=2,
-                 label_smoothing=0.0, z_loss=0.0):
+                 label_smoothing=0.0, z_loss=0.0, neighbour_smoothing=0.0, neighbour_range=None, neighbour_sigma=None,
+                 codes=None):
         from . import ops
-        self.label_smoothing, self.z_loss = ops.check_ce_regularisers(label_smoothing, z_loss)   # fixed at capture
+        # fixed at capture
+        self.label_smoothing, self.z_loss, nu, R, sigma = ops.check_ce_soft(
+            label_smoothing, z_loss, neighbour_smoothing, neighbour_range, neighbour_sigma, codes)
+        self.soft = dict(neighbour_smoothing=nu, neighbour_range=R, neighbour_sigma=sigma,
+                         codes=codes if nu > 0 else None)
+        if nu > 0:
+            # the weight table must exist BEFORE capture, for the reason _dev_step_buffer() must: made inside, its
+            # upload would be part of the graph.  The captured launch finds it in ops' cache and holds its address
+            self._neighbour_weights = ops.neighbour_weights(R, sigma, optim.flat_param.device)
         self.segmented = parallel.world_size() > 1 or optim._overlap
         self.model, self.optim = model, optim
         self.lr_cb, self.hr_cb = lr_codebook, hr_codebook
@@ -268,7 +282,7 @@ class GraphedTrainStep:
         self.optim.zero_grad()
         logits = self.model(x_dec=hr_in, x_enc=lr_in, pos_cond=pos, pos_bound=seq)
         loss = QF.cross_entropy(logits.view(-1, logits.shape[-1]), hr_tg.flatten(), self.label_smoothing,
-                                self.z_loss)
+                                self.z_loss, **self.soft)
         loss.backward()
         if self.segmented:
             if not captured:

@@ -93,6 +93,7 @@ def parse_args():
     p.add_argument("--val-batches", type=int, default=None,
                    help="(additive) score only the first batches of --val-dataset-path.")
     cc.add_regulariser_args(p)
+    cc.add_neighbour_args(p)
     cc.add_dropout_args(p)
     cc.add_attn_dropout_args(p)
     cc.add_token_noise_args(p)
@@ -103,6 +104,8 @@ def parse_args():
         cc.check_optimizer_args(args["weight_decay"], args["lr_schedule"], args["lr_warmup_steps"],
                                 args["lr_decay_steps"], args["lr_min_ratio"])
         cc.check_grad_clip_args(args["clip_grad_norm"], args["max_skipped_steps"])
+        cc.check_neighbour_args(args["label_smoothing"], args["z_loss"], args["neighbour_smoothing"],
+                                args["neighbour_range"], args["neighbour_sigma"])
         cc.check_token_noise_args(args["input_noise"], args["cond_noise"], args["noise_range"], args["dropout_seed"],
                                   train_base_model=args["train_base_model"])
     except ValueError as e:
@@ -190,7 +193,13 @@ def main():
         optim.enable_grad_clip(clip_grad_norm)
     # argparse has checked both; once more before anything is launched with them
     label_smoothing, z_loss = ops.check_ce_regularisers(args["label_smoothing"], args["z_loss"])
-    regularised = label_smoothing > 0 or z_loss > 0
+    # the HR codes are the classes on the SOM axis; <end>, the class behind them, is nobody's neighbour
+    neighbour_smoothing, neighbour_range, neighbour_sigma = cc.check_neighbour_args(
+        label_smoothing, z_loss, args["neighbour_smoothing"], args["neighbour_range"], args["neighbour_sigma"],
+        codes=hr_codebook.num_embeddings)
+    soft = dict(neighbour_smoothing=neighbour_smoothing, neighbour_range=neighbour_range,
+                neighbour_sigma=neighbour_sigma, codes=hr_codebook.num_embeddings if neighbour_smoothing > 0 else None)
+    regularised = label_smoothing > 0 or z_loss > 0 or neighbour_smoothing > 0
     dropout, dropout_seed = cc.check_dropout_args(args["dropout"], args["dropout_seed"])
     if dropout > 0:
         # the step word of the mask key follows optim.step_count: with --load-optim the sequence continues
@@ -275,6 +284,10 @@ def main():
     if regularised:
         info(f"Label Smoothing: {label_smoothing}")
         info(f"Z-Loss: {z_loss}")
+    if neighbour_smoothing > 0:
+        info(f"Neighbour Smoothing: {neighbour_smoothing}")
+        info(f"Neighbour Range: {neighbour_range}")
+        info(f"Neighbour Sigma: {neighbour_sigma}")
     if dropout > 0:
         info(f"Dropout: {dropout}")
         info(f"Dropout Seed: {dropout_seed}")
@@ -323,6 +336,10 @@ def main():
             model_dict["label_smoothing"] = label_smoothing
         if z_loss > 0:
             model_dict["z_loss"] = z_loss
+        if neighbour_smoothing > 0:     # informational likewise
+            model_dict["neighbour_smoothing"] = neighbour_smoothing
+            model_dict["neighbour_range"] = neighbour_range
+            model_dict["neighbour_sigma"] = neighbour_sigma
         if dropout > 0:             # informational likewise
             model_dict["dropout"] = dropout
             model_dict["dropout_seed"] = dropout_seed
@@ -417,7 +434,7 @@ def main():
     if args["graph_step"]:
         graphed = pipeline.GraphedTrainStep(model, optim, lr_codebook, hr_codebook, train_base_model,
                                             sliding_window if use_sliding_window else None,
-                                            label_smoothing=label_smoothing, z_loss=z_loss)
+                                            label_smoothing=label_smoothing, z_loss=z_loss, **soft)
     global_steps = 0
     done = False
     skipped_before, skipped_run = 0, 0      # --clip-grad-norm: the device's count so far, consecutive skips
@@ -452,7 +469,7 @@ def main():
                     sliding_window if use_sliding_window else None, rand, token_noise=model.token_noise)
                 loss = pipeline.train_step(model, optim, hr_in, lr_in, hr_tg, pos_idx,
                                            pos_bound=seq_total, label_smoothing=label_smoothing,
-                                           z_loss=z_loss)
+                                           z_loss=z_loss, **soft)
             nll_val = 0.0
             if regularised:                                          # one read-back for the two numbers
                 loss_val, nll_val = pipeline.loss_pair(loss).tolist()
