@@ -672,54 +672,61 @@ int qarig_attention_decode(const float* q, const float* k_new, const float* v_ne
                            int max_len, int64_t batch_stride, float sqrt_d, const float* o_mul,
                            float* o, void* stream);
 
-/* nn.CrossEntropyLoss() mean over rows + d/dlogits --
- * train_quantized_transformer.py:337,496-502.  row_ws: M floats. */
-int qarig_cross_entropy_fwd(const float* logits, const int64_t* target, int M, int C, float* loss,
-                            float* dlogits, float* row_ws, int* bad_flag, void* stream);
-/* The same loss (train_quantized_transformer.py:337,496-502) on rows with leading dimensions: logits rows at
- * ld_logits >= C, whose columns C .. ld_logits - 1 are never read; dlogits rows at ld_dlogits >= C, whose
- * columns C .. ld_dlogits - 1 receive exact zeros (the classifier's logits stay in their (M, 528) GEMM output
- * buffer and the input-gradient GEMM reduces over the zero columns); nothing behind row M - 1's ld_dlogits
- * columns is written.  loss, row_ws and dlogits[:, :C] carry the bits of qarig_cross_entropy_fwd, which is
- * the ld == C case.  The regularised entry below has no such form: a step with label smoothing or z-loss
- * passes dense logits. */
-int qarig_cross_entropy_ld_fwd(const float* logits, int64_t ld_logits, const int64_t* target, int M, int C,
-                               float* loss, float* dlogits, int64_t ld_dlogits, float* row_ws, int* bad_flag,
-                               void* stream);
-
-/* Cross-entropy with label smoothing and z-loss (additive; the reference trains with neither):
- * F.cross_entropy(logits, target, label_smoothing = eps) + zeta mean_r(logsumexp(logits[r])^2), in one rows
- * launch and one mean launch.  Per row, mx = max x, s = sum exp(x - mx), logs = log s, lse = mx + logs:
+/* Cross-entropy, mean over rows, fused with d/dlogits: one rows launch and one mean launch (csrc/loss.hip).
+ * qarig_cross_entropy_fused_fwd states the whole contract; the four entries behind it are its special cases, kept
+ * with their signatures, and every one of them writes the bits the superset writes for the same numbers.
+ *
+ * logits fp32, rows at ld_logits >= C (columns C .. ld_logits - 1 are never read); target int64 (M).  With all three
+ * numbers 0: nn.CrossEntropyLoss() as the reference trains with (train_quantized_transformer.py:337,496-502).
+ * Otherwise (additive; the reference trains with none of them) F.cross_entropy(logits, target, label_smoothing = eps)
+ * + zeta mean_r(logsumexp(logits[r])^2), and SOM-neighbour soft targets.  Per row, mx = max x, s = sum exp(x - mx),
+ * logs = log s, lse = mx + logs, p[c] = exp((x[c] - mx) - logs):
  *   nll = logs - (x[t] - mx),  u = logs - (1 / C) sum_c (x[c] - mx),  obj = (1 - eps) nll + eps u + zeta lse^2,
- *   d obj / d x[c] = exp((x[c] - mx) - logs) (1 + 2 zeta lse) - (1 - eps) [c == t] - eps / C.
- * label_smoothing in [0, 1), z_loss finite and >= 0, anything else is refused.  loss: 2 floats = {mean obj, mean
- * plain nll}.  dlogits (M,C) or NULL = d(mean obj)/d(logits); NULL leaves the losses bit for bit.  row_ws: 2 M
- * floats, the row objectives then the row nlls.  A term whose coefficient is 0 is not evaluated: with both 0 every
- * output carries the bits qarig_cross_entropy_fwd writes (both halves of row_ws its row losses), and
- * label_smoothing = 0 never forms 0 * inf on rows with -inf entries.  With label_smoothing > 0 such a row's
- * objective, and loss[0], are +inf as torch's are; its nll and its gradient stay finite, the -inf columns getting
- * (-eps / C) / M.  A target outside [0,C) sets *bad_flag and its row adds 0 to both means.  A row's outputs depend
- * on that row alone (no floating-point atomics, one fixed summation order, 4-byte loads at every alignment); a row
- * holding NaN is undefined in that row alone. */
-int qarig_cross_entropy_reg_fwd(const float* logits, const int64_t* target, int M, int C, float label_smoothing,
-                                float z_loss, float* loss, float* dlogits, float* row_ws, int* bad_flag,
-                                void* stream);
-/* The same with SOM-neighbour soft targets (additive): the codebooks are one-dimensional self-organising maps, code
- * t +- 1 decodes to almost the patch of code t, and part of the smoothing mass goes there.  The leading `codes`
- * classes lie on the SOM axis; classes codes .. C - 1 are special (<end>) and are nobody's neighbour.  For a row with
- * target t < codes, with w = weights (DEVICE, range + 1 floats of the index distance, weights[0] = 1):
+ *   d obj / d x[c] = p[c] (1 + 2 zeta lse) - (1 - eps) [c == t] - eps / C.
+ * Soft targets: the codebooks are one-dimensional self-organising maps, code t +- 1 decodes to almost the patch of
+ * code t, and part of the smoothing mass goes there.  The leading `codes` classes lie on the SOM axis; classes
+ * codes .. C - 1 are special (<end>) and are nobody's neighbour.  For a row with target t < codes, with w = weights
+ * (DEVICE, range + 1 floats of the index distance, weights[0] = 1) and nu = neighbour_smoothing:
  *   lo = max(0, t - range), hi = min(codes - 1, t + range),  q[j] = w[|j - t|] / sum_{i = lo .. hi} w[|i - t|]
  *   h = logs - sum_j q[j] (x[j] - mx)            (cross-entropy against q, from the shifted logits as u is)
  *   obj = (1 - eps - nu) nll + eps u + nu h + zeta lse^2
  *   d obj / d x[c] = p[c] (1 + 2 zeta lse) - (1 - eps - nu) [c == t] - eps / C - nu q[c]
- * -- the window is clamped at the ends of the axis and renormalised.  A row whose target is special takes nu = 0:
- * the objective and gradient of qarig_cross_entropy_reg_fwd, bit for bit.  neighbour_smoothing in [0, 1),
- * label_smoothing + neighbour_smoothing < 1 (as fp32), 0 < codes <= C, and with neighbour_smoothing > 0:
- * 1 <= range <= 31 and weights non-NULL; anything else is refused before a launch.  At neighbour_smoothing = 0 the
- * call is qarig_cross_entropy_reg_fwd (range and weights are not looked at) and returns its bits.  loss[1] and the
- * second half of row_ws stay the plain nll.  A window column holding -inf makes the row objective +inf (as u does);
- * its gradient element is the finite (-eps / C - nu q[c]) / M.  A table entry of exactly 0 takes its column out of the
- * window.  Everything else as qarig_cross_entropy_reg_fwd states it. */
+ * -- the window is clamped at the ends of the axis and renormalised.  A row whose target is special takes nu = 0: the
+ * objective and gradient at neighbour_smoothing = 0, bit for bit.  A table entry of exactly 0 takes its column out of
+ * the window.
+ * Accepted: M, C positive, at most 2^24 each, product at most 2^40; C <= ld_logits <= 2^31, and with dlogits
+ * C <= ld_dlogits <= 2^31; label_smoothing in [0, 1); z_loss finite and >= 0; neighbour_smoothing in [0, 1);
+ * label_smoothing + neighbour_smoothing < 1 (as fp32); 0 < codes <= C; with neighbour_smoothing > 0: 1 <= range <= 31
+ * and weights non-NULL (at neighbour_smoothing = 0 range and weights are not looked at).  Anything else is refused
+ * before a launch.
+ * loss: 2 floats = {mean obj, mean plain nll}.  row_ws: 2 M floats, the row objectives then the row nlls.  dlogits:
+ * NULL, or rows at ld_dlogits = d(mean obj)/d(logits), columns C .. ld_dlogits - 1 written as exact +0 (the
+ * classifier's logits stay in their (M, 528) GEMM output buffer and the input-gradient GEMM reduces over the zero
+ * columns); nothing behind row M - 1's ld_dlogits columns is written; NULL leaves the losses bit for bit.
+ * A term whose coefficient is 0 is not evaluated: with all three 0 both losses are the plain mean loss and both halves
+ * of row_ws its row losses, and label_smoothing = 0 never forms 0 * inf on rows with -inf entries.  With
+ * label_smoothing > 0 such a row's objective, and loss[0], are +inf as torch's are; its nll and its gradient stay
+ * finite, the -inf columns getting (-eps / C) / M.  A window column holding -inf makes the row objective +inf (as u
+ * does); its gradient element is the finite (-eps / C - nu q[c]) / M.  A target outside [0,C) sets *bad_flag and its
+ * row adds 0 to both means.  A row's outputs depend on that row alone (no floating-point atomics, one fixed summation
+ * order, 4-byte loads at every alignment); a row holding NaN is undefined in that row alone. */
+int qarig_cross_entropy_fused_fwd(const float* logits, int64_t ld_logits, const int64_t* target, int M, int C,
+                                  int codes, float label_smoothing, float z_loss, float neighbour_smoothing, int range,
+                                  const float* weights, float* loss, float* dlogits, int64_t ld_dlogits, float* row_ws,
+                                  int* bad_flag, void* stream);
+/* The superset at (0, 0, 0) on dense rows, with the plain ABI: loss 1 float (the mean loss), row_ws M floats (the row
+ * losses); neither the second loss nor a second half of row_ws is written. */
+int qarig_cross_entropy_fwd(const float* logits, const int64_t* target, int M, int C, float* loss,
+                            float* dlogits, float* row_ws, int* bad_flag, void* stream);
+/* The same with the superset's leading dimensions; qarig_cross_entropy_fwd is its ld == C case. */
+int qarig_cross_entropy_ld_fwd(const float* logits, int64_t ld_logits, const int64_t* target, int M, int C,
+                               float* loss, float* dlogits, int64_t ld_dlogits, float* row_ws, int* bad_flag,
+                               void* stream);
+/* The superset on dense rows (ld = C) at neighbour_smoothing = 0: label smoothing and z-loss. */
+int qarig_cross_entropy_reg_fwd(const float* logits, const int64_t* target, int M, int C, float label_smoothing,
+                                float z_loss, float* loss, float* dlogits, float* row_ws, int* bad_flag,
+                                void* stream);
+/* The superset on dense rows (ld = C). */
 int qarig_cross_entropy_soft_fwd(const float* logits, const int64_t* target, int M, int C, int codes,
                                  float label_smoothing, float z_loss, float neighbour_smoothing, int range,
                                  const float* weights, float* loss, float* dlogits, float* row_ws, int* bad_flag,

@@ -3,6 +3,7 @@
 // accumulators that stay on the device for a whole dataset (score_reduce_kernel).  One wave per row /
 // per output element; no floating-point atomics, so two runs over the same rows are bit-identical.
 #include "qarig_common.h"
+#include "row_sweep.h"
 
 namespace qarig {
 
@@ -17,8 +18,9 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     return v;
 }
 
-// The arithmetic of ce_rows_kernel (loss.hip): lane partial sums in ascending trips, the 64-lane butterfly,
-// nll = log s - (x[t] - mx).  x[t] is read first, so the rank is counted in the sweep that finds the maximum.
+// The arithmetic of the cross-entropy row kernel (loss.hip) on its sweeps (row_sweep.h): lane partial sums in
+// ascending trips, the 64-lane butterfly, nll = log s - (x[t] - mx).  x[t] is read first, so the rank is counted in
+// the sweep that finds the maximum (neither depends on the order).
 __global__ __launch_bounds__(256) void token_score_kernel(const float* __restrict__ logits,
                                                           const int64_t* __restrict__ target, int M, int C,
                                                           int64_t ignore_index, float* __restrict__ row_nll,
@@ -40,33 +42,14 @@ __global__ __launch_bounds__(256) void token_score_kernel(const float* __restric
     const int ti = (int)t;
     float mx = -INFINITY;
     int above = 0;
-    // four trips' loads in flight at a time in both sweeps (left alone, hipcc waits for every load before it
-    // issues the next); the maximum and the count do not depend on the order, the sum keeps its own:
-    // lane partial sums in ascending trips
-    int c = lane;
-    for (; c + 192 < C; c += 256) {
-        const float v0 = x[c], v1 = x[c + 64], v2 = x[c + 128], v3 = x[c + 192];
-        mx = fmaxf(fmaxf(mx, v0), fmaxf(fmaxf(v1, v2), v3));
-        above += ((v0 > xt || (v0 == xt && c < ti)) ? 1 : 0) + ((v1 > xt || (v1 == xt && c + 64 < ti)) ? 1 : 0) +
-                 ((v2 > xt || (v2 == xt && c + 128 < ti)) ? 1 : 0) + ((v3 > xt || (v3 == xt && c + 192 < ti)) ? 1 : 0);
-    }
-    for (; c < C; c += 64) {
-        const float v = x[c];
+    row_sweep(x, C, lane, [&](float v, int col) {
         mx = fmaxf(mx, v);
-        above += (v > xt || (v == xt && c < ti)) ? 1 : 0;
-    }
+        above += (int)((v > xt) | ((v == xt) & (col < ti)));        // | and &: selects, no branch per column
+    });
     mx = wave_max(mx);
     above = wave_sum_i(above);
     float s = 0.0f;
-    c = lane;
-    for (; c + 192 < C; c += 256) {
-        const float v0 = x[c], v1 = x[c + 64], v2 = x[c + 128], v3 = x[c + 192];
-        s += expf(v0 - mx);
-        s += expf(v1 - mx);
-        s += expf(v2 - mx);
-        s += expf(v3 - mx);
-    }
-    for (; c < C; c += 64) s += expf(x[c] - mx);
+    row_sweep(x, C, lane, [&](float v, int) { s += expf(v - mx); });
     s = wave_sum(s);
     if (lane == 0) {
         row_nll[row] = logf(s) - (xt - mx);

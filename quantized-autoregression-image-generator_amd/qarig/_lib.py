@@ -119,6 +119,7 @@ SIGNATURES = {
     "qarig_window_attention": (I, [P, P, P, I, I, I, I, I, L, P, L, P, P]),
     "qarig_window_append": (I, [P, P, P, I, L, P, P]),
     "qarig_attention_bwd": (I, [P, P, P, P, P, P, I, I, I, I, I, I, F, P, P, P, P, P]),
+    "qarig_cross_entropy_fused_fwd": (I, [P, L, P, I, I, I, F, F, F, I, P, P, P, L, P, P, P]),
     "qarig_cross_entropy_fwd": (I, [P, P, I, I, P, P, P, P, P]),
     "qarig_cross_entropy_ld_fwd": (I, [P, L, P, I, I, P, P, L, P, P, P]),
     "qarig_cross_entropy_reg_fwd": (I, [P, P, I, I, F, F, P, P, P, P, P]),

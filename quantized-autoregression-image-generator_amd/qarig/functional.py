@@ -730,64 +730,57 @@ def _strided_rows(logits):
     return l2
 
 
+def _ce_forward(ctx, logits, target, label_smoothing=0.0, z_loss=0.0, soft=None):
+    """The {objective, plain nll} pair of ops.cross_entropy_fwd; the logits gradient is produced here, in the forward
+    pass, and saved.  soft: None, or the (neighbour_smoothing, range, sigma, codes) of SOM-neighbour soft targets."""
+    require_cuda(logits, target)
+    t = target.reshape(-1)
+    if t.dtype != torch.int64:
+        t = t.long()
+    l2 = _strided_rows(logits)
+    if l2 is not None:
+        # logits left in a wider buffer by their producer (the classifier's (M, 528) GEMM output): read at their row
+        # stride; the gradient goes back in rows of the same stride, zero behind the classes
+        ops.RAGGED_CALLS["ce_ld"] += 1
+    else:
+        l2 = _2d(f32c(logits))
+    pair, dl = ops.cross_entropy_fwd(l2, t.contiguous(), label_smoothing, z_loss, *(soft or ()), want_grad=True)
+    ctx.save_for_backward(dl)
+    ctx.shape = logits.shape
+    return pair
+
+
+def _ce_backward(ctx, dloss):
+    (dl,) = ctx.saved_tensors
+    return ops.scale_by(dl, f32c(dloss).reshape(1))[:, :ctx.shape[-1]].reshape(ctx.shape)
+
+
 class _CrossEntropy(torch.autograd.Function):
-    """mean CE over rows; the logits gradient is produced in the forward pass."""
+    """mean CE over rows: one output."""
 
     @staticmethod
     def forward(ctx, logits, target):
-        require_cuda(logits, target)
-        t = target.reshape(-1)
-        if t.dtype != torch.int64:
-            t = t.long()
-        ctx.shape = logits.shape
-        ctx.cols = None
-        l2 = _strided_rows(logits)
-        if l2 is not None:
-            # logits left in a wider buffer by their producer (the classifier's (M, 528) GEMM output): read at
-            # their row stride; the gradient goes back in rows of the same stride, zero behind the classes
-            loss, dl = ops.cross_entropy_ld_fwd(l2, t.contiguous(), want_grad=True)
-            ops.RAGGED_CALLS["ce_ld"] += 1
-            ctx.cols = l2.shape[1]
-        else:
-            loss, dl = ops.cross_entropy_fwd(_2d(f32c(logits)), t.contiguous(), want_grad=True)
-        ctx.save_for_backward(dl)
-        return loss
+        return _ce_forward(ctx, logits, target)[0]
 
     @staticmethod
     def backward(ctx, dloss):
-        (dl,) = ctx.saved_tensors
-        g = ops.scale_by(dl, f32c(dloss).reshape(1))
-        if ctx.cols is not None:
-            return g[:, :ctx.cols].reshape(ctx.shape), None
-        return g.reshape(ctx.shape), None
+        return _ce_backward(ctx, dloss), None
 
 
 class _CrossEntropyReg(torch.autograd.Function):
-    """mean CE with label smoothing and z-loss over rows (ops.cross_entropy_reg_fwd): the objective, and the
-    {objective, plain nll} pair as a second, non-differentiable output.  soft: None, or the (neighbour_smoothing,
-    range, sigma, codes) of SOM-neighbour soft targets (ops.cross_entropy_soft_fwd, the same launch)."""
+    """mean CE with label smoothing, z-loss and (soft) SOM-neighbour soft targets over rows: the objective, and the
+    {objective, plain nll} pair as a second, non-differentiable output."""
 
     @staticmethod
     def forward(ctx, logits, target, label_smoothing, z_loss, soft=None):
-        require_cuda(logits, target)
-        l2 = _2d(f32c(logits))
-        t = target.reshape(-1)
-        if t.dtype != torch.int64:
-            t = t.long()
-        if soft is None:
-            pair, dl = ops.cross_entropy_reg_fwd(l2, t.contiguous(), label_smoothing, z_loss, want_grad=True)
-        else:
-            pair, dl = ops.cross_entropy_soft_fwd(l2, t.contiguous(), label_smoothing, z_loss, *soft, want_grad=True)
-        ctx.save_for_backward(dl)
-        ctx.shape = logits.shape
+        pair = _ce_forward(ctx, logits, target, label_smoothing, z_loss, soft)
         ctx.mark_non_differentiable(pair)
         ctx.set_materialize_grads(False)
         return pair[0], pair
 
     @staticmethod
     def backward(ctx, dloss, _dpair):
-        (dl,) = ctx.saved_tensors
-        return ops.scale_by(dl, f32c(dloss).reshape(1)).reshape(ctx.shape), None, None, None, None
+        return _ce_backward(ctx, dloss), None, None, None, None
 
 
 def cross_entropy(logits, target, label_smoothing=0.0, z_loss=0.0, *, neighbour_smoothing=0.0, neighbour_range=None,

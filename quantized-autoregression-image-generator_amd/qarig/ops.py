@@ -1512,64 +1512,14 @@ def attention_bwd(q, k, v, o, dO, lse, heads, causal, scale_dim=None, dropout=No
     return dq, dk, dv
 
 
-def cross_entropy_fwd(logits2d, target, want_grad=True):
-    M, C = logits2d.shape
-    loss = torch.empty((), dtype=torch.float32, device=logits2d.device)
-    dl = torch.empty_like(logits2d) if want_grad else None
-    rows = torch.empty(M, dtype=torch.float32, device=logits2d.device)
-    check(_lib.load().qarig_cross_entropy_fwd(ptr(logits2d), ptr(target), M, C, ptr(loss), ptr(dl),
-                                              ptr(rows), ptr(_bad_flag(logits2d.device)), stream()),
-          "qarig_cross_entropy_fwd")
-    return loss, dl
-
-
-def cross_entropy_ld_fwd(logits2d, target, ld_grad=None, want_grad=True):
-    """cross_entropy_fwd on logits rows with a leading dimension (a column slice of a wider buffer; the columns
-    behind the slice are never read): (loss, dlogits), dlogits an (M, ld_grad) buffer (ld_grad >= C, default the
-    logits' row stride) whose columns C .. ld_grad - 1 are exact zeros.  include/qarig.h
-    qarig_cross_entropy_ld_fwd; the bits of cross_entropy_fwd on a dense copy."""
-    require_cuda(logits2d, target)
-    assert logits2d.dtype == torch.float32 and logits2d.dim() == 2 and logits2d.stride(1) == 1
-    assert target.dtype == torch.int64 and target.is_contiguous() and target.numel() == logits2d.shape[0]
-    M, C = logits2d.shape
-    ld = logits2d.stride(0) if M > 1 else max(C, logits2d.stride(0))
-    ld_grad = ld if ld_grad is None else int(ld_grad)
-    assert ld >= C and ld_grad >= C
-    loss = torch.empty((), dtype=torch.float32, device=logits2d.device)
-    dl = torch.empty((M, ld_grad), dtype=torch.float32, device=logits2d.device) if want_grad else None
-    rows = torch.empty(M, dtype=torch.float32, device=logits2d.device)
-    check(_lib.load().qarig_cross_entropy_ld_fwd(ptr(logits2d), ld, ptr(target), M, C, ptr(loss), ptr(dl), ld_grad,
-                                                 ptr(rows), ptr(_bad_flag(logits2d.device)), stream()),
-          "qarig_cross_entropy_ld_fwd")
-    return loss, dl
-
-
 def check_ce_regularisers(label_smoothing, z_loss):
-    """(label_smoothing, z_loss) as floats, or ValueError: what qarig_cross_entropy_reg_fwd accepts."""
+    """(label_smoothing, z_loss) as floats, or ValueError: what the cross-entropy entries accept."""
     eps, zeta = float(label_smoothing), float(z_loss)
     if not 0.0 <= eps < 1.0:
         raise ValueError(f"label_smoothing must lie in [0, 1), got {label_smoothing}")
     if not (0.0 <= zeta < float("inf")):
         raise ValueError(f"z_loss must be finite and >= 0, got {z_loss}")
     return eps, zeta
-
-
-def cross_entropy_reg_fwd(logits2d, target, label_smoothing, z_loss, want_grad=True):
-    """F.cross_entropy(logits2d, target, label_smoothing=...) + z_loss * mean(logsumexp(logits2d)^2) in the fused
-    launch: (loss, dlogits), loss = {mean objective, mean plain nll} as one (2,) tensor, dlogits the gradient of
-    the objective (None unless want_grad).  With both numbers 0 the bits of cross_entropy_fwd."""
-    require_cuda(logits2d, target)
-    assert logits2d.dtype == torch.float32 and logits2d.dim() == 2 and logits2d.is_contiguous()
-    assert target.dtype == torch.int64 and target.is_contiguous() and target.numel() == logits2d.shape[0]
-    eps, zeta = check_ce_regularisers(label_smoothing, z_loss)
-    M, C = logits2d.shape
-    loss = torch.empty(2, dtype=torch.float32, device=logits2d.device)
-    dl = torch.empty_like(logits2d) if want_grad else None
-    rows = torch.empty(2 * M, dtype=torch.float32, device=logits2d.device)
-    check(_lib.load().qarig_cross_entropy_reg_fwd(ptr(logits2d), ptr(target), M, C, eps, zeta, ptr(loss), ptr(dl),
-                                                  ptr(rows), ptr(_bad_flag(logits2d.device)), stream()),
-          "qarig_cross_entropy_reg_fwd")
-    return loss, dl
 
 
 NEIGHBOUR_RANGE_MAX = 31        # a window of 2 R + 1 <= 63 columns: one per lane of the row's wave
@@ -1603,7 +1553,7 @@ def neighbour_weights(R, sigma, device):
 
 def check_ce_soft(label_smoothing=0.0, z_loss=0.0, neighbour_smoothing=0.0, neighbour_range=None,
                   neighbour_sigma=None, codes=None, classes=None):
-    """(label_smoothing, z_loss, neighbour_smoothing, range, sigma) as qarig_cross_entropy_soft_fwd accepts them, or
+    """(label_smoothing, z_loss, neighbour_smoothing, range, sigma) as qarig_cross_entropy_fused_fwd accepts them, or
     ValueError.  neighbour_smoothing = 0 gives (eps, zeta, 0.0, None, None) and refuses a range or a sigma: they
     would do nothing.  neighbour_smoothing > 0 needs a range in 1 .. 31; sigma defaults to range / 2.  codes (the
     classes on the SOM axis) and classes are checked against each other when both are given."""
@@ -1633,28 +1583,36 @@ def check_ce_soft(label_smoothing=0.0, z_loss=0.0, neighbour_smoothing=0.0, neig
     return eps, zeta, nu, R, sigma
 
 
-def cross_entropy_soft_fwd(logits2d, target, label_smoothing=0.0, z_loss=0.0, neighbour_smoothing=0.0,
-                           neighbour_range=None, neighbour_sigma=None, codes=None, want_grad=True):
-    """cross_entropy_reg_fwd with SOM-neighbour soft targets (include/qarig.h qarig_cross_entropy_soft_fwd):
-    neighbour_smoothing of the target mass goes to the codes within neighbour_range of the target among the leading
-    `codes` classes, by a Gaussian of the index distance with width neighbour_sigma (default range / 2), clamped at
-    the ends of the axis and renormalised.  (loss, dlogits) as cross_entropy_reg_fwd; with neighbour_smoothing = 0
-    its bits."""
+def cross_entropy_fwd(logits2d, target, label_smoothing=0.0, z_loss=0.0, neighbour_smoothing=0.0,
+                      neighbour_range=None, neighbour_sigma=None, codes=None, ld_grad=None, want_grad=True):
+    """Mean cross-entropy of logits (M, C) against int64 targets in the fused launch (include/qarig.h
+    qarig_cross_entropy_fused_fwd): F.cross_entropy(logits2d, target, label_smoothing=...) + z_loss *
+    mean(logsumexp(logits2d)^2), and with neighbour_smoothing > 0 that much of the target mass on the codes within
+    neighbour_range of the target among the leading `codes` classes, by a Gaussian of the index distance with width
+    neighbour_sigma (default range / 2), clamped at the ends of the axis and renormalised (check_ce_soft).
+    logits2d: dense, or a column slice of a wider buffer (unit column stride, row stride >= C; the columns behind the
+    slice are never read).  Returns (pair, dlogits): pair = {mean objective, mean plain nll} as one (2,) tensor, the
+    plain loss twice with all three numbers 0; dlogits an (M, ld_grad) buffer (ld_grad >= C, default the logits' row
+    stride) holding the gradient of the objective, its columns C .. ld_grad - 1 exact zeros (None unless want_grad)."""
     require_cuda(logits2d, target)
-    assert logits2d.dtype == torch.float32 and logits2d.dim() == 2 and logits2d.is_contiguous()
+    assert logits2d.dtype == torch.float32 and logits2d.dim() == 2 and logits2d.stride(1) == 1
     assert target.dtype == torch.int64 and target.is_contiguous() and target.numel() == logits2d.shape[0]
     M, C = logits2d.shape
+    ld = logits2d.stride(0) if M > 1 else max(C, logits2d.stride(0))
+    ld_grad = ld if ld_grad is None else int(ld_grad)
+    assert ld >= C and ld_grad >= C
     eps, zeta, nu, R, sigma = check_ce_soft(label_smoothing, z_loss, neighbour_smoothing, neighbour_range,
                                             neighbour_sigma, codes, C)
     w = neighbour_weights(R, sigma, logits2d.device) if nu > 0 else None
-    loss = torch.empty(2, dtype=torch.float32, device=logits2d.device)
-    dl = torch.empty_like(logits2d) if want_grad else None
+    pair = torch.empty(2, dtype=torch.float32, device=logits2d.device)
+    dl = torch.empty((M, ld_grad), dtype=torch.float32, device=logits2d.device) if want_grad else None
     rows = torch.empty(2 * M, dtype=torch.float32, device=logits2d.device)
-    check(_lib.load().qarig_cross_entropy_soft_fwd(ptr(logits2d), ptr(target), M, C, C if codes is None else int(codes),
-                                                   eps, zeta, nu, R or 0, ptr(w), ptr(loss), ptr(dl), ptr(rows),
-                                                   ptr(_bad_flag(logits2d.device)), stream()),
-          "qarig_cross_entropy_soft_fwd")
-    return loss, dl
+    check(_lib.load().qarig_cross_entropy_fused_fwd(ptr(logits2d), ld, ptr(target), M, C,
+                                                    C if codes is None else int(codes), eps, zeta, nu, R or 0, ptr(w),
+                                                    ptr(pair), ptr(dl), ld_grad, ptr(rows),
+                                                    ptr(_bad_flag(logits2d.device)), stream()),
+          "qarig_cross_entropy_fused_fwd")
+    return pair, dl
 
 
 def token_score(logits2d, target, ignore_index=-100):

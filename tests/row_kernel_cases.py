@@ -3,8 +3,9 @@
 MI355X) and tests/test_row_kernels_host.py (the same pieces on the CPU).
 
 WHAT IS UNDER TEST.  layernorm_fwd_kernel / layernorm_bwd_kernel (one wave per row, two-pass variance, a register
-form for D = 256 NV and a scalar form for every other D or a pointer off 16 bytes), ce_rows_kernel + mean_kernel
-(cross-entropy and its gradient; the per-row losses land in `row_ws`), mse_partial_kernel + mean_kernel, and the
+form for D = 256 NV and a scalar form for every other D or a pointer off 16 bytes), ce_reg_rows_kernel<false, false,
+false> + mean2_kernel (cross-entropy and its gradient; the per-row losses land in `row_ws`), mse_partial_kernel +
+mean2_kernel, and the
 LayerNorm the decode step's Linear kernels apply on the way in.  Unit-scale Gaussian rows judged by one global
 max|err| / max|ref| cannot see a one-pass variance, a loss rounded at the magnitude of the logits, a row that is only
 wrong next to a larger one, or a loop that never takes its second trip.  The families below can.
@@ -37,7 +38,7 @@ dpred takes the derived 2 u: a - b rounds once and the quotient of 2 (a - b) by 
 rounded 1 / n would round three times and reach 2.77 u on these inputs; the kernel corrects it by a Newton step).
 
 MUTANTS (`MUTANTS`; the host test proves each is rejected on the GPU test's own inputs, and by which family):
-one-pass variance (offset), loss = (mx + log s) - x[t] with p = exp(x - lse) -- ce_rows_kernel before this file
+one-pass variance (offset), loss = (mx + log s) - x[t] with p = exp(x - lse) -- the row kernel before this file
 existed -- (CE offset), a dropped last partial 64-chunk, a mean that stops at 256 rows, an MSE of one grid trip.
 
 Measured on an MI355X (profiles/row_kernels_measured.txt):
@@ -527,7 +528,7 @@ def ce_ref(x, t):
 
 
 def mean_emulate(v, inv, stop_at_256=False):
-    """mean_kernel: 256 strided partial sums, a tree, times inv.  The mutant never takes a second trip."""
+    """mean2_kernel, one block: 256 strided partial sums, a tree, times inv.  The mutant never takes a second trip."""
     n = v.shape[0]
     trips = -(-n // 256)
     pad = torch.zeros(trips * 256)
@@ -544,7 +545,7 @@ def mean_emulate(v, inv, stop_at_256=False):
 
 
 def ce_emulate(x, t, mutant=None):
-    """ce_rows_kernel + mean_kernel in fp32 on the CPU, the shifted form: loss = log s - (x[t] - mx),
+    """The plain cross-entropy (ce_reg_rows_kernel<false, false, false> + mean2_kernel) in fp32 on the CPU, the shifted form: loss = log s - (x[t] - mx),
     p = exp((x - mx) - log s).  mutant "lse": loss = (mx + log s) - x[t], p = exp(x - (mx + log s));
     "drop_tail", "mean_256" as named.  Returns row losses, dlogits, the mean loss."""
     M, C = x.shape
@@ -637,7 +638,7 @@ def mse_ref(a, b):
 
 
 def mse_emulate(a, b, mutant=None):
-    """mse_partial_kernel + mean_kernel: 1024 x 256 threads, one fmaf per element in ascending grid trips, a tree
+    """mse_partial_kernel + mean2_kernel: 1024 x 256 threads, one fmaf per element in ascending grid trips, a tree
     per block, then the mean of the 1024 partial sums.  mutant "one_trip": elements past the first trip are lost."""
     n = a.numel()
     inv_n = torch.tensor(1.0) / torch.tensor(float(n))

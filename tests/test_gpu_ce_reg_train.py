@@ -73,9 +73,9 @@ def test_autograd_node():
     g = torch.Generator().manual_seed(11)
     x = (2.0 * torch.randn((6, 12, 33), generator=g)).cuda()
     t = torch.randint(0, 33, (6, 12), generator=g).cuda()
-    pair, dl = ops.cross_entropy_reg_fwd(x.view(-1, 33), t.flatten(), EPS, ZETA)
+    pair, dl = ops.cross_entropy_fwd(x.view(-1, 33), t.flatten(), EPS, ZETA)
     assert pair.shape == (2,) and dl.shape == (72, 33)
-    pair0, none = ops.cross_entropy_reg_fwd(x.view(-1, 33), t.flatten(), EPS, ZETA, want_grad=False)
+    pair0, none = ops.cross_entropy_fwd(x.view(-1, 33), t.flatten(), EPS, ZETA, want_grad=False)
     assert none is None and torch.equal(pair0, pair)
     logits = x.clone().requires_grad_(True)
     loss = QF.cross_entropy(logits, t, EPS, ZETA)

@@ -35,10 +35,9 @@ def test_autograd_node():
     x = (2.0 * torch.randn((6, 12, 33), generator=g)).cuda()
     t = torch.randint(0, 33, (6, 12), generator=g).cuda()
     assert int((t == 32).sum()) > 0          # <end> targets among them
-    pair, dl = ops.cross_entropy_soft_fwd(x.view(-1, 33), t.flatten(), EPS, ZETA, NU, RANGE, None, CODES)
+    pair, dl = ops.cross_entropy_fwd(x.view(-1, 33), t.flatten(), EPS, ZETA, NU, RANGE, None, CODES)
     assert pair.shape == (2,) and dl.shape == (72, 33)
-    pair0, none = ops.cross_entropy_soft_fwd(x.view(-1, 33), t.flatten(), EPS, ZETA, NU, RANGE, SIGMA, CODES,
-                                             want_grad=False)
+    pair0, none = ops.cross_entropy_fwd(x.view(-1, 33), t.flatten(), EPS, ZETA, NU, RANGE, SIGMA, CODES, want_grad=False)
     assert none is None and torch.equal(pair0, pair)            # sigma defaults to range / 2
     logits = x.clone().requires_grad_(True)
     loss = QF.cross_entropy(logits, t, EPS, ZETA, neighbour_smoothing=NU, neighbour_range=RANGE, codes=CODES)
@@ -80,14 +79,16 @@ def test_autograd_node():
 
 
 def _eager_counted(n, monkeypatch, **kw):
-    """T._eager with the C-ABI calls of each step counted and the new entry watched."""
+    """T._eager with the C-ABI calls of each step counted and the cross-entropy entry watched: a hit is a call that
+    passes neighbour_smoothing > 0 (argument 8 of qarig_cross_entropy_fused_fwd)."""
     from qarig import _lib, pipeline
     lib = _lib.load()
     hits, counts = [], []
-    real_entry, real_step = lib.qarig_cross_entropy_soft_fwd, pipeline.train_step
+    real_entry, real_step = lib.qarig_cross_entropy_fused_fwd, pipeline.train_step
 
     def entry(*a):
-        hits.append(1)
+        if a[8] > 0:
+            hits.append(1)
         return real_entry(*a)
 
     def step(*a, **k):
@@ -96,13 +97,13 @@ def _eager_counted(n, monkeypatch, **kw):
         counts.append(_lib.N_CALLS - before)
         return out
 
-    monkeypatch.setattr(lib, "qarig_cross_entropy_soft_fwd", entry)
+    monkeypatch.setattr(lib, "qarig_cross_entropy_fused_fwd", entry)
     monkeypatch.setattr(pipeline, "train_step", step)
     try:
         res = T._eager(n, **kw)
     finally:
         monkeypatch.setattr(pipeline, "train_step", real_step)
-        monkeypatch.setattr(lib, "qarig_cross_entropy_soft_fwd", real_entry)
+        monkeypatch.setattr(lib, "qarig_cross_entropy_fused_fwd", real_entry)
     return res, counts, len(hits)
 
 
@@ -115,8 +116,8 @@ def test_train_step_defaults_unchanged_and_pair_against_fp64(monkeypatch):
     assert torch.equal(default, zero) and losses_d == losses_z
     assert pairs_d == [[v, v] for v in losses_d] == pairs_z
     assert calls_d == calls_z and len(calls_d) == 3 and min(calls_d) > 0
-    assert hits_d == hits_z == 0             # neither path reaches the new entry
-    # the regularisers alone do not reach it either, and make the calls they made
+    assert hits_d == hits_z == 0             # neither path asks for soft targets
+    # the regularisers alone do not either, and make the calls they made
     (reg, _, pairs_reg), calls_reg, hits_reg = _eager_counted(3, monkeypatch, label_smoothing=EPS, z_loss=ZETA)
     assert hits_reg == 0
     seen = []

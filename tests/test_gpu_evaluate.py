@@ -95,8 +95,8 @@ def test_scorer_counts_every_token_once_and_agrees_with_cross_entropy(tag):
     assert r["bits_per_token"] == pytest.approx(r["nll_mean"] / 0.6931471805599453, rel=1e-15)
     assert 0.0 <= r["top1"] <= r["topk"] <= 1.0
 
-    # the same windows one at a time through the existing cross-entropy entry.  Its row losses are ce_rows_kernel's,
-    # whose arithmetic token_score_kernel repeats on the same logits; what differs is the mean (fp32, mean_kernel,
+    # the same windows one at a time through the existing cross-entropy entry.  Its row losses are the row kernel's,
+    # whose arithmetic token_score_kernel repeats on the same logits; what differs is the mean (fp32, mean2_kernel,
     # within CE_MEAN_TOL_U = 4 u of the rows' mean) against the scorer's fp64 sums: inside CE_TOL_U's 8 u for unit rows
     lr_idx = lr_cb.get_patches_bmu(z, reshape=True)
     hr_idx = hr_cb.get_patches_bmu(z, reshape=True)
@@ -108,8 +108,8 @@ def test_scorer_counts_every_token_once_and_agrees_with_cross_entropy(tag):
                                                     offs, window)
             logits = m(x_dec=hr_in, x_enc=None if base else lr_idx, pos_cond=pos, pos_bound=seq)
             keep = logits[:, skip:].reshape(-1, logits.shape[-1]).contiguous()
-            loss, _ = ops.cross_entropy_fwd(keep, hr_tg[:, skip:].reshape(-1).contiguous(), want_grad=False)
-            total += float(loss) * keep.shape[0]
+            pair, _ = ops.cross_entropy_fwd(keep, hr_tg[:, skip:].reshape(-1).contiguous(), want_grad=False)
+            total += float(pair[0]) * keep.shape[0]
             rows += keep.shape[0]
     assert rows == N * seq
     want = total / rows

@@ -265,6 +265,85 @@ def test_cross_entropy_with_leading_dimensions_carries_the_dense_bits(M, C):
         assert int(_ce_call("ld", buf, ld, bad, M, C, ld)[3]) == 1
 
 
+def _ce_pair_call(entry, logits, ld, target, M, C, ld_grad, eps, zeta, nu=0.0, R=0, w=None, guard=64):
+    """One launch of a two-loss cross-entropy entry ("fused", or "reg" / "soft" on dense logits) through the C ABI:
+    (loss (2,), row_ws incl. guard, dlogits buffer incl. guard, flag)."""
+    from qarig import _lib, ops
+    lib = _lib.load()
+    loss = torch.full((2,), float("nan"), device="cuda")
+    rows = torch.full((2 * M + guard,), float("nan"), device="cuda")
+    dl = torch.full((M * ld_grad + guard,), float("nan"), device="cuda")
+    flag = torch.zeros(1, dtype=torch.int32, device="cuda")
+    wp = None if w is None else w.data_ptr()
+    tail = (loss.data_ptr(), dl.data_ptr(), rows.data_ptr(), flag.data_ptr(), ops.stream())
+    if entry == "fused":
+        rc = lib.qarig_cross_entropy_fused_fwd(logits.data_ptr(), ld, target.data_ptr(), M, C, C - 1, eps, zeta, nu, R,
+                                               wp, loss.data_ptr(), dl.data_ptr(), ld_grad, rows.data_ptr(),
+                                               flag.data_ptr(), ops.stream())
+    elif entry == "soft":
+        rc = lib.qarig_cross_entropy_soft_fwd(logits.data_ptr(), target.data_ptr(), M, C, C - 1, eps, zeta, nu, R, wp,
+                                              *tail)
+    else:
+        rc = lib.qarig_cross_entropy_reg_fwd(logits.data_ptr(), target.data_ptr(), M, C, eps, zeta, *tail)
+    assert rc == 0, _lib.last_error()
+    return loss, rows, dl, flag
+
+
+@pytest.mark.parametrize("C", [5, 65, 513])
+@pytest.mark.parametrize("M", [1, 7])
+def test_regularised_cross_entropy_with_leading_dimensions_carries_the_dense_bits(M, C):
+    """qarig_cross_entropy_fused_fwd on rows with a leading dimension, with label smoothing and z-loss and with
+    soft targets on top (codes = C - 1): the bits of the reg / soft entry on the dense copy, exact +0 pads, nothing
+    read or written outside."""
+    from qarig import ops
+    g = torch.Generator().manual_seed(10 * M + C)
+    dense = (torch.randn((M, C), generator=g) * 3).cuda()
+    target = torch.randint(0, C, (M,), generator=g).cuda()
+    R = 1 if C == 5 else 2                  # codes = 4 holds no window of 2 R + 1 = 5
+    w = ops.neighbour_weights(R, R / 2.0, "cuda")
+    for entry, nu in (("reg", 0.0), ("soft", 0.2)):
+        extra = (nu, R, w) if nu else ()
+        loss0, rows0, dl0, flag0 = _ce_pair_call(entry, dense, C, target, M, C, C, 0.1, 1e-4, *extra)
+        assert int(flag0) == 0
+        for ld in sorted({C, C + 3} | ({528} if C == 513 else set())):
+            buf = torch.full((M, ld), float("nan"), device="cuda")     # NaN pads: a read of them would show
+            buf[:, :C].copy_(dense)
+            loss, rows, dl, flag = _ce_pair_call("fused", buf, ld, target, M, C, ld, 0.1, 1e-4, *extra)
+            assert int(flag) == 0
+            assert torch.equal(loss, loss0) and not torch.equal(loss[0], loss[1])
+            assert torch.equal(rows[:M], rows0[:M]) and torch.equal(rows[M:2 * M], rows0[M:2 * M])
+            d2 = dl[:M * ld].view(M, ld)
+            assert torch.equal(d2[:, :C], dl0[:M * C].view(M, C))
+            assert (d2[:, C:] == 0).all() and not torch.signbit(d2[:, C:]).any()      # exact +0
+            assert torch.isnan(dl[M * ld:]).all() and torch.isnan(rows[2 * M:]).all()  # nothing past ld * M, 2 M
+            assert torch.isnan(buf[:, C:]).all()
+
+
+def test_regularised_autograd_node_reads_the_logits_where_they_lie():
+    """QF.cross_entropy with regularisers on the [:, :513] slice of a (64, 528) buffer: one strided launch, and the
+    loss, the pair and the gradient of the dense call bit for bit."""
+    from qarig import functional as QF
+    from qarig import ops
+    M, C = 64, 513
+    g = torch.Generator().manual_seed(33)
+    x = (torch.randn((M, C), generator=g) * 3).cuda()
+    t = torch.randint(0, C, (M,), generator=g).cuda()
+    dense = x.clone().requires_grad_(True)
+    want = QF.cross_entropy(dense, t, 0.1, 1e-4)
+    want.backward()
+    buf = torch.full((M, 528), float("nan"), device="cuda")
+    buf[:, :C].copy_(x)
+    buf.requires_grad_(True)
+    before = ops.RAGGED_CALLS["ce_ld"]
+    loss = QF.cross_entropy(buf[:, :C], t, 0.1, 1e-4)
+    assert ops.RAGGED_CALLS["ce_ld"] == before + 1
+    loss.backward()
+    assert torch.equal(loss.detach(), want.detach()) and torch.equal(loss.pair, want.pair)
+    assert not torch.equal(loss.pair[0], loss.pair[1])
+    assert torch.equal(buf.grad[:, :C], dense.grad)
+    assert (buf.grad[:, C:] == 0).all()
+
+
 def test_input_gradient_over_the_zero_columns_the_loss_writes():
     """dX = dlogits W with K' = K rounded up to 16 (513 -> 528): A is the (M, 528) gradient buffer of the
     cross-entropy entry, its pad columns written by that entry, B a zero-row-padded image of W; against fp64."""
@@ -277,7 +356,7 @@ def test_input_gradient_over_the_zero_columns_the_loss_writes():
     W = (torch.randn((C, Nout), generator=g) * 0.1).cuda()
     Wp = torch.zeros((528, Nout), device="cuda")
     Wp[:C].copy_(W)
-    _, dl = ops.cross_entropy_ld_fwd(buf[:, :C], target)
+    _, dl = ops.cross_entropy_fwd(buf[:, :C], target)
     assert dl.shape == (M, 528)
     dX = ops.gemm(dl, Wp, a_kcontig=True, b_kcontig=False)
     ref = dl[:, :C].double().cpu() @ W.double().cpu()

@@ -51,7 +51,7 @@ def rank_by_argsort(x, t):
 
 
 def score_emulate(x, t, mutant=None):
-    """token_score_kernel on the CPU: the nll of row_kernel_cases.ce_emulate (ce_rows_kernel's fp32 arithmetic,
+    """token_score_kernel on the CPU: the nll of row_kernel_cases.ce_emulate (the cross-entropy row kernel's fp32 arithmetic,
     which the kernel repeats) and the rank as the sweep counts it; `mutant` one of MUTANTS."""
     drop = mutant == "drop_tail"
     nll = R.ce_emulate(x, t, "drop_tail" if drop else None)[0]

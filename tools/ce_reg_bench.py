@@ -3,10 +3,13 @@ its arms alternating in one process, medians of 7 after warm-up.  Nothing is gat
 measured.
 
 (a) kernels, with dlogits as the training step calls them, at 16,384 x 513 (config 2: 64 windows of 256 tokens) and
-    32,768 x 8,193 (config 5's vocabulary: 8 x 4,096): qarig_cross_entropy_fwd (ce_rows_kernel + mean_kernel, one load
-    waited for at a time) against qarig_cross_entropy_reg_fwd (ce_reg_rows_kernel + mean2_kernel, four trips' loads
-    in flight) at (0, 0) -- the same bits, checked here -- and at (0.1, 1e-4).  Achieved GB/s counts one read of the
-    logits and one write of dlogits (the second and third sweep may hit in cache).
+    32,768 x 8,193 (config 5's vocabulary: 8 x 4,096): qarig_cross_entropy_fwd against qarig_cross_entropy_reg_fwd
+    at (0, 0) and at (0.1, 1e-4).  Since the loss path has one row kernel the first two arms launch the
+    same ce_reg_rows_kernel<false, false, false> -- the plain entry without the row nlls and with a one-block mean --
+    so "plain against reg(0, 0)" compares a kernel with itself (the same bits, still checked here) and measures the
+    run-to-run spread; against a build of an earlier commit it is the plain entry's own before and after
+    (profiles/r33_ce_one_kernel.json).  Achieved GB/s counts one read of the logits and one write of dlogits (the
+    second and third sweep may hit in cache).
 (b) the config-2 step (bench.py's model builder), pipeline.train_step with the regularisers off and on.
 
     python tools/ce_reg_bench.py --out profiles/r23_ce_reg.json

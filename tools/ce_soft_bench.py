@@ -4,8 +4,9 @@ is gated: the numbers are recorded as measured.
 
 (a) kernels, with dlogits as the training step calls them, at 16,384 x 513 (config 2: 64 windows of 256 tokens) and
     32,768 x 8,193 (config 5's vocabulary: 8 x 4,096): qarig_cross_entropy_reg_fwd at (0.1, 1e-4) against
-    qarig_cross_entropy_soft_fwd at (0.1, 1e-4, 0.2), R = 4, sigma = 2, codes = C - 1, and the new entry at
-    neighbour_smoothing = 0, which must write the regularised entry's bits (checked here).  Achieved GB/s counts one
+    qarig_cross_entropy_soft_fwd at (0.1, 1e-4, 0.2), R = 4, sigma = 2, codes = C - 1, and the soft entry at
+    neighbour_smoothing = 0, which must write the regularised entry's bits (checked here; since DESIGN 9.41 both
+    entries fill the same launcher's arguments, so that arm compares a launch with itself).  Achieved GB/s counts one
     read of the logits and one write of dlogits (the second and third sweep may hit in cache).
 (b) the config-2 step (bench.py's model builder), pipeline.train_step with the soft targets off and on (no other
     regulariser in either arm: off is the default step).

@@ -2,7 +2,8 @@
 alternating in one process, medians of 7 after warm-up.
 
 (a) kernels: qarig_token_score + qarig_score_reduce against the existing pair behind
-    qarig_cross_entropy_fwd(dlogits = NULL) (ce_rows_kernel + mean_kernel) on the same logits and targets, at
+    qarig_cross_entropy_fwd(dlogits = NULL) (ce_reg_rows_kernel<false, false, false> + mean2_kernel, whose two sweeps
+    are token_score_kernel's: csrc/row_sweep.h) on the same logits and targets, at
     16,384 x 513 (config 2: 64 windows of 256 tokens) and 32,768 x 8,193 (config 5's vocabulary: 8 x 4,096).  Both
     arms sweep the logits twice; achieved GB/s counts one read of the logits (the second sweep may hit in cache).
 (b) pipeline: TokenScorer.add_batch against pipeline.train_step at config 2's shapes (bench.py's model builder), in
