@@ -793,6 +793,24 @@ int qarig_ssim_fwd_maps(const float* a, const float* b, int N, int C, int H, int
 int qarig_ssim_bwd(const float* a, const float* b, const double* maps, const double* g, int N, int C, int H, int W,
                    const double* win, int taps, float* da, void* stream);
 
+/* Generation evaluation (additive; the reference has none), csrc/moments.hip: the features and moments behind a
+ * Frechet distance between two sample sets in latent space (qarig/gen_eval.py).  No floating-point atomics, one
+ * fixed summation order: equal inputs and an equal call sequence give equal bits.
+ * qarig_pool_features: z (N,C,H,W) fp32 contiguous; f (N, D) fp64, D = C (H/P) (W/P), written in full.  Feature
+ * (c, i, j) of a sample is the mean of its P x P block: the block summed in fp64 in raster order, divided by P^2
+ * once (P = 1: a conversion).  Refused: P not dividing H and W, D outside 1 ... 1024, null pointers, N < 1, f
+ * overlapping z.
+ * qarig_moments_add: f (n, D) fp64 with ld = D; shift (D) fp64, NULL = zeros.  With a_r = f_r - shift (fp64), ADDED
+ * into accumulators the caller zeroed once: count (int64) += n, sum (D) += sum_r a_r, gram (D,D) row-major
+ * (i, j) += sum_r a_ri a_rj for every (i, j) with floor(j/16) >= floor(i/16) -- the upper triangle of 16 x 16
+ * tiles, diagonal tiles whole; every other element of gram keeps its bits (the host mirrors the result).  The
+ * products run on v_mfma_f64_16x16x4_f64, rows in ascending steps of four; each tile belongs to one wave, which
+ * loads it, accumulates and stores it.  A NaN feature stays in its row and column of gram.  Refused: D outside
+ * 1 ... 1024, n outside 1 ... 2^20, null f / count / sum / gram, accumulators that alias f. */
+int qarig_pool_features(const float* z, int N, int C, int H, int W, int P, double* f, void* stream);
+int qarig_moments_add(const double* f, int n, int D, const double* shift, int64_t* count, double* sum, double* gram,
+                      void* stream);
+
 /* F.mse_loss (mean) + d/dpred -- train_autoencoder.py:215-217, train_codebook.py:233-235. */
 size_t qarig_mse_workspace_bytes(void);
 int qarig_mse_fwd(const float* pred, const float* target, int64_t n, float* loss, float* dpred,

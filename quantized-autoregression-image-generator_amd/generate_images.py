@@ -10,6 +10,7 @@ import argparse
 import os
 import pathlib
 
+import numpy as np
 import torch
 
 from models.Transformer import Transformer
@@ -84,6 +85,10 @@ def parse_args(argv=None):
                    help="(additive) every Transformer stage loads the exponential moving average of its weights "
                         "(the checkpoint's 'model_ema', written by train_quantized_transformer.py --ema-decay) "
                         "instead of the last-step weights; a stage file without one is an error.")
+    p.add_argument("--save-latents", type=pathlib.Path, default=argparse.SUPPRESS,
+                   help="(additive) rank 0 writes the last stage's quantised latents -- the tensors the decoder turns "
+                        "into recon_model_<last> -- for all --num-images as one fp32 (N,C,H,W) .npy file: the input of "
+                        "evaluate_generation.py.")
     return vars(p.parse_args(argv))
 
 
@@ -197,8 +202,13 @@ def main():
                 log(f"Prompt: completions {'keep' if same else 'DO NOT keep'} the {kept:,} prompt tokens of "
                     f"{num_images:,} images")
             if rank == 0:
-                recon = decoder_model(hr_codebook.get_quantized_image(indices=all_tokens, unpatchify_input=True))
+                latents = hr_codebook.get_quantized_image(indices=all_tokens, unpatchify_input=True)
+                recon = decoder_model(latents)
                 ops.check_index_flag(device, f"stage {index} tokens")
+                if args.get("save_latents") is not None and index == list(config)[-1]:
+                    args["save_latents"].parent.mkdir(parents=True, exist_ok=True)
+                    with open(args["save_latents"], "wb") as f:      # (a file object: np.save appends no ".npy")
+                        np.save(f, latents.detach().float().cpu().numpy())
                 save_images(images=recon, file_name=f"recon_model_{index}", dest_path=out_dir, logging=print)
         sampling.decode_cache_clear()        # (the stage's decode caches hold its model: let both go, as the reference does)
         del model

@@ -133,6 +133,8 @@ SIGNATURES = {
     "qarig_ssim_maps_bytes": (Z, [I, I, I, I, I]),
     "qarig_ssim_fwd_maps": (I, [P, P, I, I, I, I, P, I, D, D, P, P, P, Z, P]),
     "qarig_ssim_bwd": (I, [P, P, P, P, I, I, I, I, P, I, P, P]),
+    "qarig_pool_features": (I, [P, I, I, I, I, I, P, P]),
+    "qarig_moments_add": (I, [P, I, I, P, P, P, P, P]),
     "qarig_mse_workspace_bytes": (Z, []),
     "qarig_mse_fwd": (I, [P, P, L, P, P, P, P]),
     "qarig_adam_step": (I, [P, P, P, P, L, F, F, F, F, F, F, P, P, P]),

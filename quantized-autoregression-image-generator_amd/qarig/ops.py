@@ -1732,6 +1732,41 @@ def ssim_bwd(a, b, maps, g, data_range=2.0, sigma=1.5, taps=11, k1=0.01, k2=0.03
     return da
 
 
+def pool_features(z, pool):
+    """(N, D) fp64 features of an (N,C,H,W) fp32 batch, D = C (H/pool) (W/pool): the mean of every pool x pool
+    block, summed in fp64 in raster order (pool 1: a conversion).  D is at most 1024."""
+    require_cuda(z)
+    if z.dim() != 4 or z.numel() == 0:
+        raise ValueError(f"pool_features: need a non-empty (N,C,H,W) batch, got {tuple(z.shape)}")
+    z = f32c(z)
+    N, C, H, W = z.shape
+    pool = int(pool)
+    D = C * (H // pool) * (W // pool) if pool >= 1 else 0
+    f = torch.empty((N, max(D, 1)), dtype=torch.float64, device=z.device)
+    check(_lib.load().qarig_pool_features(ptr(z), N, C, H, W, pool, ptr(f), stream()), "qarig_pool_features")
+    return f
+
+
+def moments_add(f, state, shift=None):
+    """Adds the rows of f (n, D) fp64 into state = (count int64 (1,), sum fp64 (D,), gram fp64 (D,D)), which the
+    caller zeroed once: count += n, sum += sum_r a_r, gram += sum_r a_r a_r^T on the upper triangle of 16 x 16
+    tiles (diagonal tiles whole; the rest of gram is left alone), a_r = f_r - shift.  fp64 MFMA, one fixed order,
+    no atomics: deterministic."""
+    count, total, gram = state
+    require_cuda(f, count, total, gram, shift)
+    if f.dim() != 2 or f.dtype != torch.float64 or f.numel() == 0:
+        raise ValueError(f"moments_add: need non-empty (n, D) fp64 features, got {tuple(f.shape)} {f.dtype}")
+    f = f.contiguous()
+    n, D = f.shape
+    assert count.dtype == torch.int64 and count.numel() == 1
+    assert total.dtype == gram.dtype == torch.float64 and total.is_contiguous() and gram.is_contiguous()
+    assert total.shape == (D,) and gram.shape == (D, D), (tuple(total.shape), tuple(gram.shape), D)
+    if shift is not None:
+        assert shift.dtype == torch.float64 and shift.shape == (D,) and shift.is_contiguous()
+    check(_lib.load().qarig_moments_add(ptr(f), n, D, ptr(shift), ptr(count), ptr(total), ptr(gram), stream()),
+          "qarig_moments_add")
+
+
 def _adam_asserts(p, shadow, ema=None, decay_mask=None, dev_step=None, dev_floats=None, clip_state=None):
     """What the four Adam wrappers ask of their optional tensors.  dev_floats: the (least, most) floats dev_step may
     hold."""

@@ -35,7 +35,7 @@ _FUNC = re.compile(r"^[0-9a-f]+ <(.+)>:$")
 
 # passes of an MFMA from its shape and input type (gfx950): cycles = flop / (flop per cycle per SIMD
 # of the type's dense peak), a pass = 4 cycles
-_MFMA_NAME = re.compile(r"v_mfma(?:_scale)?_f32_(\d+)x(\d+)x(\d+)(?:_(\d+)b)?_?(\w+)$")
+_MFMA_NAME = re.compile(r"v_mfma(?:_scale)?_f(?:32|64)_(\d+)x(\d+)x(\d+)(?:_(\d+)b)?_?(\w+)$")
 
 
 def _mfma_passes(mn):
@@ -46,6 +46,8 @@ def _mfma_passes(mn):
     flop = 2 * M * N * K * blocks
     if typ == "f32":
         rate = 64               # 157.3 TF dense
+    elif typ == "f64":
+        rate = 32               # 78.6 TF dense: v_mfma_f64_16x16x4_f64 is 16 passes (csrc/moments.hip)
     elif typ in ("bf16", "f16"):
         rate = 1024             # 2.5 PF
     elif "f8" in typ or "bf8" in typ or typ in ("i8", "f8f6f4"):
