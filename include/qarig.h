@@ -811,6 +811,36 @@ int qarig_pool_features(const float* z, int N, int C, int H, int W, int P, doubl
 int qarig_moments_add(const double* f, int n, int D, const double* shift, int64_t* count, double* sum, double* gram,
                       void* stream);
 
+/* Generation evaluation, k-nearest-neighbour statistics (additive; the reference has none), csrc/knn.hip: the two
+ * primitives behind precision / recall, density / coverage and nearest-real-neighbour distances (qarig/gen_eval.py
+ * manifold_metrics, nearest_real).  q (nq, D) and x (nx, D) fp64 with ld = D; shift (D) fp64, NULL = zeros.  With
+ * a_i = q_i - shift and b_j = x_j - shift (fp64),
+ *   d2(i, j) = (|a_i|^2 + |b_j|^2) - 2 sum_c a_ic b_jc:
+ * the inner product on v_mfma_f64_16x16x4_f64, the feature index ascending in steps of four from a zero
+ * accumulator, operands zero past D after the subtraction; |.|^2 in one order that depends on D alone (lane l of a
+ * wave sums the features l, l + 64, ... ascending, then a butterfly).  d2 is a function of the unordered pair of rows
+ * and the shift: its bits do not depend on which row is the query, on a row's position, on the tile or on how the
+ * queries are split over calls; both entries take it from one device function.  |got - exact| <=
+ * (D + 8) 2^-53 (|a_i|^2 + |b_j|^2 + 2 sum_c |a_ic| |b_jc|): choose the shift near the data.  No floating-point
+ * atomics; equal inputs give equal bits.
+ * qarig_knn_smallest: for every query row the k smallest d2 over the rows of x, ascending, into d2_out (nq, k) with
+ * their x indices in idx_out (nq, k).  Order by (value, index): equal values go to the lower index.  self_offset >= 0:
+ * query i IS x row self_offset + i, and that one row is no candidate -- by index, never by value (a duplicate at
+ * distance 0 is a neighbour); -1: no row is excluded.  Comparisons are ordinary < on doubles: a NaN distance never
+ * enters a list; slots no candidate qualified for hold +inf and index -1.
+ * qarig_ball_count: count_out[i] = the number of x rows j (row self_offset + i excluded when self_offset >= 0) with
+ * d2(i, j) <= r2[j], r2 (nx) fp64: the radius belongs to the x row.  NaN is never inside.
+ * Both need a workspace of qarig_knn_workspace_bytes(nq, nx, D, k) bytes (the norms and, where the x axis is split
+ * over workgroups, per-split partial lists; 0: bad extents; ball_count: any k).  Refused: D outside 1 ... 1024, nq or
+ * nx outside 1 ... 2^20, k outside 1 ... 8, self_offset neither -1 nor in 0 ... nx - nq, fewer than k candidates
+ * (nx - (self_offset >= 0) < k), null pointers (shift excepted), outputs or the workspace overlapping an input, a
+ * workspace that is too small (QARIG_ERR_WORKSPACE). */
+size_t qarig_knn_workspace_bytes(int nq, int nx, int D, int k);
+int qarig_knn_smallest(const double* q, int nq, const double* x, int nx, int D, const double* shift, int k,
+                       int self_offset, double* d2_out, int* idx_out, void* ws, size_t ws_bytes, void* stream);
+int qarig_ball_count(const double* q, int nq, const double* x, int nx, int D, const double* shift, const double* r2,
+                     int self_offset, int* count_out, void* ws, size_t ws_bytes, void* stream);
+
 /* F.mse_loss (mean) + d/dpred -- train_autoencoder.py:215-217, train_codebook.py:233-235. */
 size_t qarig_mse_workspace_bytes(void);
 int qarig_mse_fwd(const float* pred, const float* target, int64_t n, float* loss, float* dpred,

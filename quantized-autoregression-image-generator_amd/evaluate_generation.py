@@ -4,7 +4,9 @@ no evaluation): the Frechet distance between the pooled latents of the dataset a
 generate_images.py --save-latents wrote -- or between their decoded images with --space image -- next to two floors:
 what hard quantisation with the HR codebook alone costs, and the distance between two halves of the real set (the
 sampling noise of this many samples) (qarig/gen_eval.py).  The number is NOT FID: it is comparable only between
-runs that share the autoencoder, --feature-pool and --space.  Single-process only."""
+runs that share the autoencoder, --feature-pool and --space.  --knn K adds k-nearest-neighbour precision, recall,
+density and coverage and the generated samples' distances to their nearest real sample, beside the same statistics of
+the two real halves; --save-neighbours writes every generated sample's nearest real sample.  Single-process only."""
 import argparse
 import json
 import logging
@@ -41,11 +43,25 @@ def parse_args(argv=None):
     p.add_argument("--batch-size", type=int, default=64, help="Batch size for both sets.")
     p.add_argument("--max-batches", type=int, default=None, help="Score the first batches of the real set only.")
     p.add_argument("--out-json", type=pathlib.Path, default=None, help="Where the result is written as JSON.")
+    p.add_argument("--knn", type=int, default=0,
+                   help="k of the k-nearest-neighbour precision / recall / density / coverage (0 = off; 3 and 5 are "
+                        "the usual values, at most 8).  The values depend on k and on both sample counts.")
+    p.add_argument("--knn-max-samples", type=int, default=gen_eval.KNN_MAX_SAMPLES,
+                   help="With --knn: the first N samples of each set are kept for the neighbour statistics.")
+    p.add_argument("--save-neighbours", type=pathlib.Path, default=None,
+                   help="With --knn: write an .npz with, per generated sample, the index (dataset order) of its "
+                        "nearest real sample and the distance to it.")
     args = vars(p.parse_args(argv))
     if args["space"] == "image" and args["decoder_path"] is None:
         p.error("--space image needs --decoder-path")
     if args["feature_pool"] < 1 or args["batch_size"] < 1:
         p.error("--feature-pool and --batch-size must be positive")
+    if not 0 <= args["knn"] <= gen_eval.MAX_KNN:
+        p.error(f"--knn must be 0 (off) ... {gen_eval.MAX_KNN}")
+    if args["knn_max_samples"] < 1:
+        p.error("--knn-max-samples must be positive")
+    if args["save_neighbours"] is not None and args["knn"] == 0:
+        p.error("--save-neighbours needs --knn")
     return args
 
 
@@ -59,6 +75,15 @@ def feature_dim(shape, pool):
         raise SystemExit(f"{C} x {H // pool} x {W // pool} = {D:,} features per sample exceed {gen_eval.MAX_DIM:,}: "
                          f"pass a larger --feature-pool")
     return D
+
+
+def check_knn_counts(k, n_real, n_generated):
+    """SystemExit unless real, its two halves and the generated set all hold at least k + 1 samples."""
+    sets = {"real": n_real, "real_a": (n_real + 1) // 2, "real_b": n_real // 2, "generated": n_generated}
+    small = [f"{name} ({n})" for name, n in sets.items() if n < k + 1]
+    if small:
+        raise SystemExit(f"--knn {k} needs at least {k + 1} samples in every set (the real set is also split into "
+                         f"halves): too few in {', '.join(small)}")
 
 
 def main():
@@ -86,7 +111,14 @@ def main():
         shape = real_shape
     D = feature_dim(shape, pool)
 
-    scorer = gen_eval.GenerationScorer(pool, space=args["space"], decoder=decoder, hr_codebook=hr_codebook)
+    if args["knn"]:
+        n_real = len(dataset)
+        if args["max_batches"] is not None:
+            n_real = min(n_real, args["max_batches"] * args["batch_size"])
+        check_knn_counts(args["knn"], min(n_real, args["knn_max_samples"]),
+                         min(generated.shape[0], args["knn_max_samples"]))
+    scorer = gen_eval.GenerationScorer(pool, space=args["space"], decoder=decoder, hr_codebook=hr_codebook,
+                                       knn=args["knn"], knn_max_samples=args["knn_max_samples"])
     loader = torch.utils.data.DataLoader(dataset, batch_size=args["batch_size"], num_workers=2, shuffle=False)
     for i, batch in enumerate(loader):
         if args["max_batches"] is not None and i >= args["max_batches"]:
@@ -100,6 +132,20 @@ def main():
             logging.warning(f"Warning: set '{name}' has {n:,} samples for D = {D:,} features (fewer than 2 D): its "
                             f"covariance is rank-deficient or poorly estimated and the distance is biased upward")
     logging.info(gen_eval.summary_line("Eval generation", result))
+    if args["knn"]:
+        m = result["manifold"]
+        for name, n in m["dropped"].items():
+            if n:
+                logging.warning(f"Warning: --knn-max-samples {args['knn_max_samples']:,} dropped {n:,} samples of set "
+                                f"'{name}' from the neighbour statistics (the Frechet distance uses all of them)")
+        for key in ("nn_generated_real", "nn_real_split"):
+            logging.info(f"Eval generation nearest-neighbour distance {key[3:]} | " +
+                         " ".join(f"{q}={v:.6g}" for q, v in m[key].items()))
+    if args["save_neighbours"] is not None:
+        idx, d2 = gen_eval.nearest_real(scorer.bank("generated"), scorer.bank("real"), scorer.shift)
+        args["save_neighbours"].parent.mkdir(parents=True, exist_ok=True)
+        with open(args["save_neighbours"], "wb") as f:      # a file object: np.savez would append .npz to a path
+            np.savez(f, index=idx.cpu().numpy(), distance=np.sqrt(np.maximum(d2.cpu().numpy(), 0.0)))
     if args["out_json"] is not None:
         args["out_json"].parent.mkdir(parents=True, exist_ok=True)
         with open(args["out_json"], "w") as f:

@@ -135,6 +135,9 @@ SIGNATURES = {
     "qarig_ssim_bwd": (I, [P, P, P, P, I, I, I, I, P, I, P, P]),
     "qarig_pool_features": (I, [P, I, I, I, I, I, P, P]),
     "qarig_moments_add": (I, [P, I, I, P, P, P, P, P]),
+    "qarig_knn_workspace_bytes": (Z, [I, I, I, I]),
+    "qarig_knn_smallest": (I, [P, I, P, I, I, P, I, I, P, P, P, Z, P]),
+    "qarig_ball_count": (I, [P, I, P, I, I, P, P, I, P, P, Z, P]),
     "qarig_mse_workspace_bytes": (Z, []),
     "qarig_mse_fwd": (I, [P, P, L, P, P, P, P]),
     "qarig_adam_step": (I, [P, P, P, P, L, F, F, F, F, F, F, P, P, P]),

@@ -7,7 +7,13 @@ stay on the device in fp64 (ops.moments_add: fp64 MFMA, one fixed order, no atom
 result().  Means, covariances and the distance itself are host arithmetic in fp64 NumPy.
 
 THE NUMBER IS NOT FID.  It is comparable only between runs that share the autoencoder (and, in image space, the
-decoder), the pool and the space; the results carry a note saying so."""
+decoder), the pool and the space; the results carry a note saying so.
+
+Optional (GenerationScorer(knn=k)): k-nearest-neighbour manifold statistics over the same features -- improved precision
+and recall (Kynkaanniemi et al. 2019), density and coverage (Naeem et al. 2020) and every generated sample's distance to
+its nearest real one.  The feature rows of a set stay on the device (FeatureBank); the squared distances, the k
+smallest per row and the ball memberships come from ops.knn_smallest / ops.ball_count (fp64 MFMA, deterministic), and
+only a handful of integers and quantiles are read back."""
 import numpy as np
 import torch
 
@@ -17,6 +23,13 @@ TILE = 16       # moments_add maintains the upper triangle of TILE x TILE tiles 
 MAX_DIM = 1024
 NOTE = ("Frechet distance between pooled autoencoder features -- NOT FID: no Inception network is involved, and "
         "values are comparable only between runs that share the autoencoder, the feature pool and the space.")
+MANIFOLD_NOTE = ("k-nearest-neighbour precision / recall / density / coverage over the same pooled features: the "
+                 "values depend on k and on both sample counts and are comparable only between runs that share them "
+                 "(and the autoencoder, the feature pool and the space); real_split is what two real samples of this "
+                 "size reach.")
+MAX_KNN = 8
+KNN_MAX_SAMPLES = 16384          # default per-set cap of the feature banks
+NN_QUANTILES = (("min", 0.0), ("q01", 0.01), ("q10", 0.10), ("q50", 0.50))
 
 
 def mirror_triangle(gram):
@@ -85,6 +98,86 @@ class FeatureMoments:
         return {"count": count, "mean": mean, "cov": cov}
 
 
+class FeatureBank:
+    """The first `capacity` feature rows of a set, kept on the device in one (capacity, dim) fp64 buffer in the order
+    they were added.  Rows past the capacity are counted (`dropped`) and ignored."""
+
+    def __init__(self, dim, capacity):
+        dim, capacity = int(dim), int(capacity)
+        if not 1 <= dim <= MAX_DIM:
+            raise ValueError(f"FeatureBank: dim {dim} outside 1 ... {MAX_DIM}")
+        if not 1 <= capacity <= 1 << 20:
+            raise ValueError(f"FeatureBank: capacity {capacity} outside 1 ... 2^20")
+        self.dim, self.capacity = dim, capacity
+        self.count = 0
+        self.dropped = 0
+        self._buf = None
+
+    def add(self, features):
+        """Copies the rows of features (n, dim) fp64 in, as far as there is room; nothing is read back."""
+        if features.dim() != 2 or features.shape[1] != self.dim or features.dtype != torch.float64:
+            raise ValueError(f"FeatureBank.add: features {tuple(features.shape)} {features.dtype}, need "
+                             f"(n, {self.dim}) fp64")
+        ops.require_cuda(features)
+        if self._buf is None:
+            self._buf = torch.empty((self.capacity, self.dim), dtype=torch.float64, device=features.device)
+        take = min(features.shape[0], self.capacity - self.count)
+        if take > 0:
+            self._buf[self.count:self.count + take].copy_(features[:take])
+        self.count += take
+        self.dropped += features.shape[0] - take
+
+    def rows(self):
+        """(count, dim) fp64: a view of the rows held."""
+        if self._buf is None:
+            raise ValueError("FeatureBank.rows: no row was added")
+        return self._buf[:self.count]
+
+
+def _rows(s):
+    return s.rows() if isinstance(s, FeatureBank) else s
+
+
+def manifold_metrics(real, generated, k, shift=None):
+    """{"precision", "recall", "density", "coverage"} of `generated` (m, D) against `real` (n, D) -- fp64 device
+    tensors or FeatureBanks -- as Python floats after ONE read-back of four integers.  With r2_real[j] the k-th
+    smallest squared distance from real j to the other real rows (r2_gen likewise):
+      precision = mean_i [generated i lies in some real ball],      density = sum_i #(real balls holding i) / (k m),
+      recall    = mean_j [real j lies in some generated ball],      coverage = mean_j [some generated i in j's ball].
+    Each set needs at least k + 1 rows.  The values depend on k, n and m."""
+    real, generated, k = _rows(real), _rows(generated), int(k)
+    if not 1 <= k <= MAX_KNN:
+        raise ValueError(f"manifold_metrics: k = {k}, need 1 ... {MAX_KNN}")
+    n, m = real.shape[0], generated.shape[0]
+    if n < k + 1 or m < k + 1:
+        raise ValueError(f"manifold_metrics: k = {k} needs at least {k + 1} rows per set, got {n} and {m}")
+    r2_real = ops.knn_smallest(real, real, k, shift, 0)[0][:, k - 1].contiguous()
+    r2_gen = ops.knn_smallest(generated, generated, k, shift, 0)[0][:, k - 1].contiguous()
+    in_real = ops.ball_count(generated, real, r2_real, shift)            # (m,): real balls around generated i
+    in_gen = ops.ball_count(real, generated, r2_gen, shift)              # (n,): generated balls around real j
+    nearest = ops.knn_smallest(real, generated, 1, shift)[0][:, 0]       # (n,): real j's nearest generated sample
+    counts = torch.stack(((in_real > 0).sum(), in_real.sum(dtype=torch.int64), (in_gen > 0).sum(),
+                          (nearest <= r2_real).sum())).cpu().tolist()
+    return {"precision": counts[0] / m, "recall": counts[2] / n, "density": counts[1] / (k * m),
+            "coverage": counts[3] / n}
+
+
+def nearest_real(generated, real, shift=None):
+    """(idx (m,) int32, d2 (m,) fp64) on the device: for every generated row the index of its nearest real row (ties
+    to the lower index) and the SQUARED distance to it."""
+    d2, idx = ops.knn_smallest(_rows(generated), _rows(real), 1, shift)
+    return idx[:, 0], d2[:, 0]
+
+
+def nn_quantiles(d2):
+    """{"min", "q01", "q10", "q50"} of the distances sqrt(max(d2, 0)): order statistics floor(p (m - 1)) of the
+    sorted device vector, one read-back of four values, the square root on the host."""
+    s = torch.sort(d2).values
+    at = torch.tensor([int(p * (s.numel() - 1)) for _, p in NN_QUANTILES], device=s.device)
+    host = s[at].cpu().numpy()
+    return {name: float(np.sqrt(max(v, 0.0))) for (name, _), v in zip(NN_QUANTILES, host)}
+
+
 def _psd_sqrt(c):
     """(c^1/2, sum of the negative eigenvalues that were clipped to 0) of a symmetric matrix."""
     w, v = np.linalg.eigh((c + c.T) / 2.0)
@@ -113,16 +206,25 @@ def frechet_distance(m1, c1, m2, c2):
 class GenerationScorer:
     """Moments of the sets `real`, `real_a` / `real_b` (alternate real samples), `generated` and, with a codebook,
     `quantised` (the hard-quantised real latents), all about one shift -- the mean feature of the first real batch --
-    so that the sets' means are differences of comparable sums."""
+    so that the sets' means are differences of comparable sums.  knn = k > 0 also keeps the first knn_max_samples
+    feature rows of real / generated (half as many of real_a / real_b) in FeatureBanks, and result() gains
+    "manifold"; with knn = 0 no bank exists and nothing else changes."""
     SETS = ("real", "real_a", "real_b", "quantised", "generated")
 
-    def __init__(self, pool, space="latent", decoder=None, hr_codebook=None):
+    BANKS = ("real", "real_a", "real_b", "generated")
+
+    def __init__(self, pool, space="latent", decoder=None, hr_codebook=None, knn=0, knn_max_samples=KNN_MAX_SAMPLES):
         if space not in ("latent", "image"):
             raise ValueError(f"GenerationScorer: space must be 'latent' or 'image', got {space!r}")
         if space == "image" and decoder is None:
             raise ValueError("GenerationScorer: the image space needs a decoder")
         if int(pool) < 1:
             raise ValueError(f"GenerationScorer: pool must be positive, got {pool}")
+        if not 0 <= int(knn) <= MAX_KNN or int(knn_max_samples) < 1:
+            raise ValueError(f"GenerationScorer: knn = {knn} outside 0 ... {MAX_KNN} (0 = off) or knn_max_samples = "
+                             f"{knn_max_samples} not positive")
+        self.knn, self.knn_max_samples = int(knn), int(knn_max_samples)
+        self._banks = {}
         self.pool, self.space, self.decoder, self.hr_codebook = int(pool), space, decoder, hr_codebook
         self.dim = None
         self.shift = None
@@ -148,6 +250,33 @@ class GenerationScorer:
         if m is None:
             m = self._sets[name] = FeatureMoments(self.dim, self.shift)
         m.add(f)
+        if self.knn and name in self.BANKS:
+            b = self._banks.get(name)
+            if b is None:      # the halves of the real set hold half of what the whole may
+                cap = self.knn_max_samples if name in ("real", "generated") else (self.knn_max_samples + 1) // 2
+                b = self._banks[name] = FeatureBank(self.dim, cap)
+            b.add(f)
+
+    def bank(self, name):
+        """The FeatureBank of a set (knn > 0 only); KeyError for a set nothing was added to."""
+        return self._banks[name]
+
+    def manifold(self):
+        """The "manifold" entry of result(): the k-NN statistics of (real, generated) and, as the ceiling two real
+        samples of this size reach, of (real_a, real_b), with nearest-neighbour distance quantiles."""
+        k = self.knn
+        small = [n for n in self.BANKS if n not in self._banks or self._banks[n].count < k + 1]
+        if small:
+            raise ValueError(f"GenerationScorer: knn = {k} needs at least {k + 1} samples per set; too few in "
+                             f"{', '.join(small)}")
+        b = self._banks
+        return {"k": k, "counts": {n: b[n].count for n in self.BANKS},
+                "dropped": {n: b[n].dropped for n in self.BANKS},
+                "real_generated": manifold_metrics(b["real"], b["generated"], k, self.shift),
+                "real_split": manifold_metrics(b["real_a"], b["real_b"], k, self.shift),
+                "nn_generated_real": nn_quantiles(nearest_real(b["generated"], b["real"], self.shift)[1]),
+                "nn_real_split": nn_quantiles(nearest_real(b["real_b"], b["real_a"], self.shift)[1]),
+                "note": MANIFOLD_NOTE}
 
     @torch.no_grad()
     def add(self, z, which="real"):
@@ -200,6 +329,8 @@ class GenerationScorer:
                           ("fd_real_quantised", "real", "quantised"), ("fd_real_split", "real_a", "real_b")):
             if a in stats and b in stats:
                 r[key] = frechet_distance(stats[a]["mean"], stats[a]["cov"], stats[b]["mean"], stats[b]["cov"])
+        if self.knn:
+            r["manifold"] = self.manifold()
         return r
 
 
@@ -208,5 +339,11 @@ def summary_line(tag, result):
     for key in ("fd_real_generated", "fd_quantised_generated", "fd_real_quantised", "fd_real_split"):
         if key in result:
             parts.append("{}: {:.6g}".format(key[3:], result[key]["fd"]))
-    return "{} latent-space Frechet distance (not FID) | {} | D: {} | {}".format(
+    line = "{} latent-space Frechet distance (not FID) | {} | D: {} | {}".format(
         tag, " | ".join(parts), result["dim"], " ".join(f"{k}={v}" for k, v in result["counts"].items()))
+    if "manifold" in result:
+        m = result["manifold"]
+        for key in ("real_generated", "real_split"):
+            line += " | {} k={}: ".format(key, m["k"]) + " ".join(
+                "{}={:.4f}".format(name, m[key][name]) for name in ("precision", "recall", "density", "coverage"))
+    return line

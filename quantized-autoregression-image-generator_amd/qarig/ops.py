@@ -1767,6 +1767,61 @@ def moments_add(f, state, shift=None):
           "qarig_moments_add")
 
 
+def _knn_args(what, q, x, shift, self_offset, k):
+    """The checks knn_smallest and ball_count share; returns (q, x, shift, nq, nx, D, workspace)."""
+    require_cuda(q, x, shift)
+    for name, f in (("q", q), ("x", x)):
+        if f.dim() != 2 or f.dtype != torch.float64 or f.numel() == 0:
+            raise ValueError(f"{what}: need non-empty (n, D) fp64 rows for {name}, got {tuple(f.shape)} {f.dtype}")
+    if q.shape[1] != x.shape[1]:
+        raise ValueError(f"{what}: q has {q.shape[1]} features per row, x has {x.shape[1]}")
+    q, x = q.contiguous(), x.contiguous()
+    (nq, D), nx = q.shape, x.shape[0]
+    if shift is not None:
+        if shift.dtype != torch.float64 or tuple(shift.shape) != (D,):
+            raise ValueError(f"{what}: shift must be ({D},) fp64, got {tuple(shift.shape)} {shift.dtype}")
+        shift = shift.contiguous()
+    self_offset = int(self_offset)
+    if self_offset != -1 and not 0 <= self_offset <= nx - nq:
+        raise ValueError(f"{what}: self_offset {self_offset} is neither -1 nor in 0 ... nx - nq = {nx - nq}")
+    if nx - (self_offset >= 0) < k:
+        raise ValueError(f"{what}: {nx - (self_offset >= 0)} candidates per query, fewer than k = {k}")
+    nb = _lib.load().qarig_knn_workspace_bytes(nq, nx, D, k)
+    if nb == 0:
+        raise ValueError(f"{what}: nq = {nq}, nx = {nx}, D = {D}, k = {k} outside what the kernel supports")
+    return q, x, shift, nq, nx, D, torch.empty(nb, dtype=torch.uint8, device=q.device)
+
+
+def knn_smallest(q, x, k, shift=None, self_offset=-1):
+    """(d2 (nq, k) fp64, idx (nq, k) int32): for every row of q (nq, D) fp64 the k smallest squared distances to the
+    rows of x (nx, D) fp64, ascending, ties to the lower index, and their x indices.  Distances are taken about
+    `shift` ((D,) fp64 or None) in the Gram form on fp64 MFMA (include/qarig.h).  self_offset >= 0: query i is x row
+    self_offset + i, which is no candidate.  1 <= k <= 8.  Deterministic; nothing is read back."""
+    k = int(k)
+    if not 1 <= k <= 8:
+        raise ValueError(f"knn_smallest: k = {k}, need 1 ... 8")
+    q, x, shift, nq, nx, D, ws = _knn_args("knn_smallest", q, x, shift, self_offset, k)
+    d2 = torch.empty((nq, k), dtype=torch.float64, device=q.device)
+    idx = torch.empty((nq, k), dtype=torch.int32, device=q.device)
+    check(_lib.load().qarig_knn_smallest(ptr(q), nq, ptr(x), nx, D, ptr(shift), k, int(self_offset), ptr(d2),
+                                         ptr(idx), ptr(ws), ws.numel(), stream()), "qarig_knn_smallest")
+    return d2, idx
+
+
+def ball_count(q, x, r2, shift=None, self_offset=-1):
+    """count (nq,) int32: the number of rows j of x (row self_offset + i excluded when self_offset >= 0) with
+    d2(q_i, x_j) <= r2[j], r2 (nx,) fp64 -- the radius belongs to the x row; d2 as in knn_smallest, bit for bit."""
+    q, x, shift, nq, nx, D, ws = _knn_args("ball_count", q, x, shift, self_offset, 1)
+    require_cuda(r2)
+    if r2.dtype != torch.float64 or tuple(r2.shape) != (nx,):
+        raise ValueError(f"ball_count: r2 must be ({nx},) fp64, got {tuple(r2.shape)} {r2.dtype}")
+    r2 = r2.contiguous()
+    count = torch.empty(nq, dtype=torch.int32, device=q.device)
+    check(_lib.load().qarig_ball_count(ptr(q), nq, ptr(x), nx, D, ptr(shift), ptr(r2), int(self_offset), ptr(count),
+                                       ptr(ws), ws.numel(), stream()), "qarig_ball_count")
+    return count
+
+
 def _adam_asserts(p, shadow, ema=None, decay_mask=None, dev_step=None, dev_floats=None, clip_state=None):
     """What the four Adam wrappers ask of their optional tensors.  dev_floats: the (least, most) floats dev_step may
     hold."""

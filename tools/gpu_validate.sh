@@ -30,3 +30,4 @@ step 200 $O/${TAG}_ssim_loss.json python tools/ssim_loss_bench.py; tail -12 $O/$
 step 300 $O/${TAG}_ce_reg.json python tools/ce_reg_bench.py; tail -12 $O/${TAG}_ce_reg.json
 step 300 $O/${TAG}_ce_soft.json python tools/ce_soft_bench.py; tail -12 $O/${TAG}_ce_soft.json
 step 200 $O/${TAG}_gen_eval.json python tools/gen_eval_bench.py; tail -12 $O/${TAG}_gen_eval.json
+step 400 $O/${TAG}_gen_knn.json python tools/gen_knn_bench.py; tail -12 $O/${TAG}_gen_knn.json
