@@ -102,6 +102,35 @@ int qarig_bmu_fwd_coarse_ws(const float* x, int N, int C, int H, int W, int pH, 
 size_t qarig_bmu_prepare_bytes(int K, int D);
 int qarig_bmu_prepare(const float* codebook, int K, int D, void* image, void* stream);
 
+/* ---- SOM topology evaluation (additive, no reference counterpart) -------------- */
+
+/* The two best-matching units of every patch row.  x, patch dims and codebook as qarig_bmu_fwd; 2 <= K <= 16384
+ * (else QARIG_ERR_ARG), any D.  Per row r of N*(H/pH)*(W/pW): idx1, idx2 int64, d1, d2 fp32.  d(r,k) is the literal
+ * definition of the search (fp32 fma chains for |w|^2 and |x|^2, the ascending chain of -2 w x, then
+ * sqrtf(max((acc + w2) + x2, 0))); candidates are ordered by (d, k) lexicographically, (d1, idx1) is the minimum
+ * and (d2, idx2) the minimum over k != idx1.  So idx1 equals qarig_bmu_fwd's index on every input that search
+ * takes by this definition (more than 25 rows or more than 25 codes; with at most 25 of both qarig_bmu_fwd follows
+ * torch.cdist into the direct form sqrt(sum (x - w)^2), this entry does not), duplicate
+ * codes give d2 == d1 with idx2 > idx1, a row equal to a code gives d1 == 0.  Indices are always in [0, K): a NaN
+ * distance is never taken and an unfilled slot reports d = +inf.  Every output element is written once, the
+ * result of a row does not depend on N or on the other rows, no atomics. */
+int qarig_bmu_top2(const float* x, int N, int C, int H, int W, int pH, int pW, const float* codebook, int K, int D,
+                   int64_t* idx1, int64_t* idx2, float* d1, float* d2, void* stream);
+/* Reduction of one qarig_bmu_top2 call of N images of seq rows each (N seq < 2^31, 2 <= K <= 2^24).
+ * img_sums (N,3) fp64, written: {sum d1, sum d2, sum d1^2} per image, fp64 throughout in one fixed order (thread t
+ * of 256 adds rows t, t + 256, ... in ascending order, then a 64-lane butterfly, then the four waves in order),
+ * so an image's bits do not depend on its batch.  gap_hist int64 [K] += histogram of |idx1 - idx2|; ratio_hist
+ * int64 [32] += histogram of min(31, floor(32 (double)d1 / (double)d2)), bin 31 where d2 == 0 (integer atomics;
+ * both caller-initialised).  A row with an index outside [0, K) sets *bad_flag and is left out of gap_hist. */
+int qarig_topology_rows(const int64_t* idx1, const int64_t* idx2, const float* d1, const float* d2, int N, int seq,
+                        int K, double* img_sums, int64_t* gap_hist, int64_t* ratio_hist, int* bad_flag,
+                        void* stream);
+/* lag_sum fp64 [K]: lag_sum[r] = sum_{t=0}^{K-1-r} |w_t - w_{t+r}|_2 for r = 1 ... K-1 ([0] is not written);
+ * codebook (K,D) fp32, K >= 2.  Differences, squares (fma, e ascending), sqrt and sums in fp64; one workgroup per
+ * lag, thread t of 256 adds t, t + 256, ... in ascending order, then the butterfly and the four waves in order.
+ * No atomics. */
+int qarig_code_lag_profile(const float* codebook, int K, int D, double* lag_sum, void* stream);
+
 /* ---- Linear algebra core ----------------------------------------------------- */
 
 /* C[M,N] = epilogue(sum_k A(m,k) B(n,k)).  a_kcontig: A stored [M][K] (1) or

@@ -213,19 +213,27 @@ __device__ __forceinline__ int64_t bmu_pick_index(BmuPick p) { return p.idx == I
 //   Codes: at(k) returns code k as {m2(e) = -2 w[k][e], w2 = |w[k]|^2 by its chain}; UNROLL codes in flight per thread
 //          (2 where they come from memory one wave per row, so that the loads of two codes overlap).
 // Rows and codes held in registers are zero past D: fmaf(-0, 0, acc) = acc, the chains are the definition's.
-template <class Row, class Codes>
-__device__ __forceinline__ BmuPick bmu_rescan(const Row& row, const Codes& codes, int first, int stride, int K) {
+// bmu_literal walks the candidates and hands each (d, k) to `take`; bmu_rescan keeps the first minimum, the top-2
+// search (further down) the two smallest.
+template <class Row, class Codes, class Take>
+__device__ __forceinline__ void bmu_literal(const Row& row, const Codes& codes, int first, int stride, int K,
+                                            Take&& take) {
     float x2 = 0.0f;
     row.each([&](int, float xe) { x2 = fmaf(xe, xe, x2); });
-    BmuPick best{INFINITY, INT_MAX};
 #pragma unroll Codes::UNROLL
     for (int k = first; k < K; k += stride) {
         const auto c = codes.at(k);
         float acc = 0.0f;
         row.each([&](int e, float xe) { acc = fmaf(c.m2(e), xe, acc); });
-        const float d = sqrtf(fmaxf((acc + c.w2) + x2, 0.0f));
-        if (d < best.d) best = BmuPick{d, k};
+        take(sqrtf(fmaxf((acc + c.w2) + x2, 0.0f)), k);
     }
+}
+template <class Row, class Codes>
+__device__ __forceinline__ BmuPick bmu_rescan(const Row& row, const Codes& codes, int first, int stride, int K) {
+    BmuPick best{INFINITY, INT_MAX};
+    bmu_literal(row, codes, first, stride, K, [&](float d, int k) {
+        if (d < best.d) best = BmuPick{d, k};
+    });
     return best;
 }
 // Rows: NE elements in registers (NE >= D, zero past D), of which the chains take the first n (D <= n <= NE: the
@@ -2034,4 +2042,184 @@ extern "C" int qarig_bmu_fwd(const float* x, int N, int C, int H, int W, int pH,
                              const float* codebook, int K, int D, int64_t* out_idx,
                              void* workspace, size_t ws_bytes, void* stream) {
     return qarig_bmu_fwd_prepared(x, N, C, H, W, pH, pW, codebook, K, D, out_idx, workspace, ws_bytes, nullptr, stream);
+}
+
+// ---------------------------------------------------------------------------------
+// Top-2 search (qarig_bmu_top2): the two smallest (d, k) of every patch row, d the literal definition at the head
+// of this file (bmu_literal), candidates ordered by (d, k) lexicographically.  (d1, idx1) is the minimum -- the
+// first index of the minimal d, which is what every matmul-form search above returns -- and (d2, idx2) the minimum over
+// k != idx1.  The second has to be chosen in the d order, not the t order of the branch-free scans: the add of
+// |x|^2, the clamp and the sqrt map neighbouring t to one d, and among codes of one d the lower index comes first
+// whatever their t were.  The topographic error counts |idx1 - idx2| != 1, so a second picked by t would move it.
+//
+// Form: a workgroup owns 64 patch rows, one per lane, the row's patch in registers; the codebook (or a chunk of
+// it) sits in LDS as -2 w and |w|^2; wave v of the NW evaluates codes v, v + NW, ... of the chunk, every lane of
+// a wave reading the same code (an LDS broadcast).  Each lane keeps two (d, k) pairs; the waves' pairs of a row
+// meet through LDS.  NW = 16 in the chunked form where the row takes at most 16 registers (few rows against many
+// codes -- 8,192 rows x 8,192 codes are 128 workgroups -- then still fill the chip: 469 -> 167 us there, 475 ->
+// 270 us at 32,768 rows), 4 otherwise (65,536 rows x 512 resident codes: 84 us with 4 waves, 97 with 16).
+// A minimum under a total order does not depend on who saw which candidate, so the result depends neither on N
+// nor on the rows that share a workgroup.  No atomics, every output element written once.
+// A NaN distance is never taken; a slot no candidate filled reports d = +inf and the lowest index that keeps
+// idx1 != idx2, so indices stay in [0, K) on any input.
+namespace qarig {
+
+struct BmuTop2 {
+    float d1; int i1;
+    float d2; int i2;
+};
+__device__ __forceinline__ bool bmu_before(float d, int k, float e, int j) { return d < e || (d == e && k < j); }
+__device__ __forceinline__ void bmu_top2_take(BmuTop2& s, float d, int k) {
+    const bool a = bmu_before(d, k, s.d1, s.i1), b = bmu_before(d, k, s.d2, s.i2);
+    s.d2 = a ? s.d1 : (b ? d : s.d2);
+    s.i2 = a ? s.i1 : (b ? k : s.i2);
+    s.d1 = a ? d : s.d1;
+    s.i1 = a ? k : s.i1;
+}
+
+// Codes k0 ... of a staged chunk: -2 w [n][S] (S = D rounded up to 4, zero past D), |w|^2 [n].
+template <int NE>
+struct BmuCodesLds {
+    static constexpr int UNROLL = 2;
+    const float* m;
+    const float* w2;
+    int S, k0;
+    __device__ __forceinline__ BmuCodeRegs<NE> at(int k) const {
+        const float4* p = reinterpret_cast<const float4*>(m + (k - k0) * S);
+        BmuCodeRegs<NE> c;
+#pragma unroll
+        for (int q = 0; q < NE / 4; ++q) {
+            const float4 t = 4 * q < S ? p[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+            c.m[4 * q] = t.x; c.m[4 * q + 1] = t.y; c.m[4 * q + 2] = t.z; c.m[4 * q + 3] = t.w;
+        }
+        c.w2 = w2[k - k0];
+        return c;
+    }
+};
+
+template <int NE, bool RESIDENT>
+constexpr int top2_waves() { return NE > 0 && NE <= 16 && !RESIDENT ? 16 : 4; }
+template <int NE, bool RESIDENT>
+constexpr int top2_merge_floats() { return top2_waves<NE, RESIDENT>() * 4 * 64; }    // [wave][d1, i1, d2, i2][lane]
+
+// NE > 0: D <= NE, the row in NE registers, the codes through LDS in chunks of `chunk` (RESIDENT: chunk >= K, one
+// staging, no loop).  NE == 0: any D, the row gathered from the latent and the codes read from memory per candidate.
+template <int NE, bool RESIDENT>
+__global__ __launch_bounds__((top2_waves<NE, RESIDENT>() * 64)) void bmu_top2_kernel(PatchGeom g,
+                                                                                   const float* __restrict__ w, int K,
+                                                                                   int chunk,
+                                                                                   int64_t* __restrict__ idx1,
+                                                                                   int64_t* __restrict__ idx2,
+                                                                                   float* __restrict__ d1,
+                                                                                   float* __restrict__ d2) {
+    constexpr int NW = top2_waves<NE, RESIDENT>();
+    extern __shared__ float4 top2_lds[];
+    float* merge = reinterpret_cast<float*>(top2_lds);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int row = blockIdx.x * 64 + lane;
+    const bool valid = row < g.R;
+    const int64_t base = valid ? patch_row_base(g, row) : 0;
+    BmuTop2 s{INFINITY, INT_MAX, INFINITY, INT_MAX};
+    auto take = [&](float d, int k) { bmu_top2_take(s, d, k); };
+    if constexpr (NE > 0) {
+        const int D = g.D, S = (D + 3) & ~3;
+        float* cm = merge + top2_merge_floats<NE, RESIDENT>();
+        float* cw2 = cm + (int64_t)chunk * S;
+        BmuRowRegs<NE> r;
+        r.n = D;
+        {
+            int j = 0, i = 0, c = 0;
+#pragma unroll
+            for (int e = 0; e < NE; ++e) {
+                r.x[e] = (valid && e < D) ? g.x[base + ((int64_t)c * g.H + i) * g.W + j] : 0.0f;
+                if (++j == g.pW) {
+                    j = 0;
+                    if (++i == g.pH) { i = 0; ++c; }
+                }
+            }
+        }
+        for (int k0 = 0; k0 < K; k0 += chunk) {
+            const int n = min(chunk, K - k0);
+            if (!RESIDENT && k0) __syncthreads();      // every wave has scanned the previous chunk
+            for (int c = tid; c < n; c += NW * 64) {
+                const float* wk = w + (int64_t)(k0 + c) * D;
+                float w2 = 0.0f;
+                for (int e = 0; e < S; ++e) {
+                    const float v = e < D ? wk[e] : 0.0f;
+                    if (e < D) w2 = fmaf(v, v, w2);
+                    cm[c * S + e] = -2.0f * v;
+                }
+                cw2[c] = w2;
+            }
+            __syncthreads();
+            bmu_literal(r, BmuCodesLds<NE>{cm, cw2, S, k0}, k0 + wave, NW, k0 + n, take);
+            if (RESIDENT) break;
+        }
+    } else {
+        bmu_literal(BmuRowGather{g, base}, BmuCodesMemory{w, g.D}, wave, NW, K, take);
+    }
+    int* mi = reinterpret_cast<int*>(merge);
+    merge[(wave * 4 + 0) * 64 + lane] = s.d1;
+    mi[(wave * 4 + 1) * 64 + lane] = s.i1;
+    merge[(wave * 4 + 2) * 64 + lane] = s.d2;
+    mi[(wave * 4 + 3) * 64 + lane] = s.i2;
+    __syncthreads();
+    if (wave != 0 || !valid) return;
+#pragma unroll
+    for (int v = 1; v < NW; ++v) {
+        bmu_top2_take(s, merge[(v * 4 + 0) * 64 + lane], mi[(v * 4 + 1) * 64 + lane]);
+        bmu_top2_take(s, merge[(v * 4 + 2) * 64 + lane], mi[(v * 4 + 3) * 64 + lane]);
+    }
+    if (s.i1 == INT_MAX) s.i1 = 0;
+    if (s.i2 == INT_MAX) s.i2 = s.i1 == 0 ? 1 : 0;
+    idx1[row] = s.i1;
+    idx2[row] = s.i2;
+    d1[row] = s.d1;
+    d2[row] = s.d2;
+}
+
+}  // namespace qarig
+
+static constexpr size_t TOP2_LDS_MAX = 160 * 1024;
+
+template <int NE>
+static void bmu_top2_launch(const PatchGeom& g, const float* codebook, int K, int64_t* idx1, int64_t* idx2, float* d1,
+                            float* d2, hipStream_t st) {
+    static size_t raised[2] = {0, 0};
+    const int S = (g.D + 3) & ~3;
+    const size_t per_code = (size_t)(S + 1) * 4;
+    const dim3 grid((g.R + 63) / 64);
+    if (K <= 1024 && top2_merge_floats<NE, true>() * 4 + K * per_code <= TOP2_LDS_MAX) {
+        const size_t shm = top2_merge_floats<NE, true>() * 4 + K * per_code;
+        const dim3 block(top2_waves<NE, true>() * 64);
+        bmu_lds_attr((const void*)bmu_top2_kernel<NE, true>, shm, raised[0]);
+        hipLaunchKernelGGL((bmu_top2_kernel<NE, true>), grid, block, shm, st, g, codebook, K, K, idx1, idx2, d1, d2);
+    } else {
+        const int chunk = S <= 16 ? 512 : S <= 36 ? 256 : 128;     // 33 - 38 KB of codes
+        const size_t shm = top2_merge_floats<NE, false>() * 4 + chunk * per_code;
+        const dim3 block(top2_waves<NE, false>() * 64);
+        bmu_lds_attr((const void*)bmu_top2_kernel<NE, false>, shm, raised[1]);
+        hipLaunchKernelGGL((bmu_top2_kernel<NE, false>), grid, block, shm, st, g, codebook, K, chunk, idx1, idx2, d1,
+                           d2);
+    }
+}
+
+extern "C" int qarig_bmu_top2(const float* x, int N, int C, int H, int W, int pH, int pW, const float* codebook, int K,
+                              int D, int64_t* idx1, int64_t* idx2, float* d1, float* d2, void* stream) {
+    PatchGeom g;
+    const int rc = bmu_geom("bmu_top2", x, N, C, H, W, pH, pW, codebook, K, D, idx1, nullptr, g);
+    if (rc != QARIG_OK) return rc;
+    QARIG_CHECK_ARG(idx2 && d1 && d2, "bmu_top2: null pointer");
+    QARIG_CHECK_ARG(K >= 2 && K <= BMU_K_MAX, "bmu_top2: K = %d, need 2 <= K <= %d", K, BMU_K_MAX);
+    hipStream_t st = (hipStream_t)stream;
+    if (D <= 4) bmu_top2_launch<4>(g, codebook, K, idx1, idx2, d1, d2, st);
+    else if (D <= 16) bmu_top2_launch<16>(g, codebook, K, idx1, idx2, d1, d2, st);
+    else if (D <= 64) bmu_top2_launch<64>(g, codebook, K, idx1, idx2, d1, d2, st);
+    else {
+        constexpr int threads = top2_waves<0, true>() * 64, shm = top2_merge_floats<0, true>() * 4;
+        hipLaunchKernelGGL((bmu_top2_kernel<0, true>), dim3((g.R + 63) / 64), dim3(threads), shm, st, g, codebook, K,
+                           K, idx1, idx2, d1, d2);
+    }
+    QARIG_CHECK_LAUNCH("bmu_top2");
+    return QARIG_OK;
 }

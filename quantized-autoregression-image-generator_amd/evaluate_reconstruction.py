@@ -34,6 +34,10 @@ def parse_args(argv=None):
     p.add_argument("--max-batches", type=int, default=None, help="Score the first batches only.")
     p.add_argument("--data-range", type=float, default=2.0,
                    help="Peak-to-peak range of the images for PSNR and SSIM (pixels in [-1, 1]: 2).")
+    p.add_argument("--topology", action="store_true",
+                   help="(additive, not in the reference) also measure every codebook's SOM topology "
+                        "(qarig/topology.py): topographic error, index-gap shares and the lag profile, as a "
+                        "\"topology\" block per codebook and one Topology line each.")
     p.add_argument("--out-json", type=pathlib.Path, default=None, help="Where the result is written as JSON.")
     return vars(p.parse_args(argv))
 
@@ -63,7 +67,7 @@ def main():
     dataset = FeatureMapDataset(dataset_path=args["dataset_path"], load_image=args["with_images"],
                                 return_filepaths=False)
     loader = torch.utils.data.DataLoader(dataset, batch_size=args["batch_size"], num_workers=2, shuffle=False)
-    scorer = recon_eval.ReconScorer(decoder, codebooks, data_range=args["data_range"])
+    scorer = recon_eval.ReconScorer(decoder, codebooks, data_range=args["data_range"], topology=args["topology"])
     recon_eval.score_loader(scorer, loader, device, args["max_batches"])
     result = scorer.result()
     if "autoencoder" in result:
@@ -71,6 +75,9 @@ def main():
                      f" | images: {result['images']:,}")
     for name, block in result["codebooks"].items():
         logging.info(recon_eval.recon_summary_line(f"Eval {name}", block) + f" | images: {result['images']:,}")
+        if "topology" in block:
+            from qarig.topology import topology_summary_line
+            logging.info(topology_summary_line(name, block["topology"]))
     if args["out_json"] is not None:
         args["out_json"].parent.mkdir(parents=True, exist_ok=True)
         with open(args["out_json"], "w") as f:

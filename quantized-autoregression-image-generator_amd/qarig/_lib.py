@@ -36,6 +36,9 @@ SIGNATURES = {
     "qarig_bmu_fwd_coarse_ws": (I, [P, I, I, I, I, I, I, P, I, I, P, P, P, P, Z, P]),
     "qarig_bmu_prepare_bytes": (Z, [I, I]),
     "qarig_bmu_prepare": (I, [P, I, I, P, P]),
+    "qarig_bmu_top2": (I, [P, I, I, I, I, I, I, P, I, I, P, P, P, P, P]),
+    "qarig_topology_rows": (I, [P, P, P, P, I, I, I, P, P, P, P, P]),
+    "qarig_code_lag_profile": (I, [P, I, I, P, P]),
     "qarig_gemm_ragged_tn": (I, [I, I, I]),
     "qarig_gemm_ragged_nt": (I, [I, I, I]),
     "qarig_gemm_workspace_bytes": (Z, [I, I, I]),

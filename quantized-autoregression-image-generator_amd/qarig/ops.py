@@ -143,6 +143,60 @@ def bmu_coarse(x, codebook, patch_dim, prepared=False):
 BMU_COARSE_PHASES = False      # tools: return all eight counters
 
 
+# ------------------------------------------------------------- SOM topology
+def bmu_top2(x, codebook, patch_dim):
+    """(idx1, idx2, d1, d2) of every patch of x (N,C,H,W): the two best-matching units under the (d, k) order of
+    include/qarig.h qarig_bmu_top2 (int64, int64, fp32, fp32; N*Seq each).  idx1 equals `bmu` (beyond the 25 rows
+    x 25 codes up to which `bmu` takes torch.cdist's direct form); 2 <= K <= 16384."""
+    require_cuda(x, codebook)
+    x = f32c(x)
+    cb = f32c(codebook)
+    N, C, H, W = x.shape
+    pH, pW = patch_dim
+    K, D = cb.shape
+    rows = N * (H // pH) * (W // pW)
+    idx = torch.empty((2, rows), dtype=torch.int64, device=x.device)
+    d = torch.empty((2, rows), dtype=torch.float32, device=x.device)
+    check(_lib.load().qarig_bmu_top2(ptr(x), N, C, H, W, pH, pW, ptr(cb), K, D, ptr(idx[0]), ptr(idx[1]), ptr(d[0]),
+                                     ptr(d[1]), stream()), "qarig_bmu_top2")
+    return idx[0], idx[1], d[0], d[1]
+
+
+def topology_rows(idx1, idx2, d1, d2, images, gap_hist, ratio_hist, img_sums=None):
+    """Reduces one bmu_top2 call of `images` images: returns img_sums (images,3) fp64 = per-image {sum d1, sum d2,
+    sum d1^2} (written into `img_sums` when given) and adds the histograms of |idx1 - idx2| and of
+    min(31, floor(32 d1 / d2)) to gap_hist (int64 [K]) and ratio_hist (int64 [32]), all on the device
+    (include/qarig.h qarig_topology_rows).  Every tensor must be contiguous."""
+    require_cuda(idx1, idx2, d1, d2, gap_hist, ratio_hist, img_sums)
+    rows = idx1.numel()
+    if images < 1 or rows % images or not (idx2.numel() == d1.numel() == d2.numel() == rows):
+        raise ValueError(f"topology_rows: {rows} rows do not make {images} images of equal length")
+    if img_sums is None:
+        img_sums = torch.empty((images, 3), dtype=torch.float64, device=idx1.device)
+    for name, t, dt in (("idx1", idx1, torch.int64), ("idx2", idx2, torch.int64), ("d1", d1, torch.float32),
+                        ("d2", d2, torch.float32), ("gap_hist", gap_hist, torch.int64),
+                        ("ratio_hist", ratio_hist, torch.int64), ("img_sums", img_sums, torch.float64)):
+        if t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"topology_rows: {name} must be a contiguous {dt} tensor")
+    if ratio_hist.numel() != 32 or img_sums.numel() != images * 3:
+        raise ValueError("topology_rows: ratio_hist has 32 bins, img_sums is (images, 3)")
+    check(_lib.load().qarig_topology_rows(ptr(idx1), ptr(idx2), ptr(d1), ptr(d2), images, rows // images,
+                                          gap_hist.numel(), ptr(img_sums), ptr(gap_hist), ptr(ratio_hist),
+                                          ptr(_bad_flag(idx1.device)), stream()), "qarig_topology_rows")
+    return img_sums
+
+
+def code_lag_profile(codebook):
+    """fp64 [K]: [r] = sum_t |w_t - w_{t+r}| over the codebook's index axis, r = 1 ... K-1; [0] = 0
+    (include/qarig.h qarig_code_lag_profile)."""
+    require_cuda(codebook)
+    cb = f32c(codebook)
+    K, D = cb.shape
+    out = torch.zeros(K, dtype=torch.float64, device=cb.device)
+    check(_lib.load().qarig_code_lag_profile(ptr(cb), K, D, ptr(out), stream()), "qarig_code_lag_profile")
+    return out
+
+
 # -------------------------------------------------------------------------- GEMM
 # bench.py sets this to a list to bracket every GEMM launch with HIP events on the
 # launch stream: entries are (flops, start_event, end_event).

@@ -49,7 +49,9 @@ def usage_block(counts):
 
 
 class ReconScorer:
-    def __init__(self, decoder, codebooks, data_range=2.0):
+    def __init__(self, decoder, codebooks, data_range=2.0, topology=False):
+        """topology: also measure every codebook's SOM topology on the same latents (qarig.topology) and add a
+        "topology" key to its block."""
         if not float(data_range) > 0.0:
             raise ValueError(f"data_range must be positive, got {data_range}")
         self.decoder = decoder
@@ -59,6 +61,10 @@ class ReconScorer:
         self._err = {}       # (block, comparison) -> [elements per image, [pair_error (N,3)], [ssim (N,)] or None]
         self._counts = {}    # codebook name -> int64 (K,) on the device
         self._images = 0
+        self._topology = None
+        if topology:
+            from .topology import TopologyScorer
+            self._topology = TopologyScorer(self.codebooks)
 
     def _score(self, block, comparison, got, want, with_ssim):
         entry = self._err.get((block, comparison))
@@ -101,6 +107,8 @@ class ReconScorer:
                     counts = self._counts[name] = torch.zeros(cb.num_embeddings, dtype=torch.int64,
                                                               device=latent.device)
                 ops.index_histogram(ids, counts)
+            if self._topology is not None:
+                self._topology.add_batch(latent)
             self._images += latent.shape[0]
         finally:
             for m, mode in zip(modules, modes):
@@ -124,9 +132,12 @@ class ReconScorer:
         if ("autoencoder", "vs_image") in self._err:
             r["autoencoder"] = self._block("autoencoder")
         r["codebooks"] = {}
+        topology = self._topology.result() if self._topology is not None else {}
         for name in self.codebooks:
             block = self._block(name)
             block["usage"] = usage_block(self._counts[name].cpu().tolist())
+            if name in topology:
+                block["topology"] = topology[name]
             r["codebooks"][name] = block
         return r
 

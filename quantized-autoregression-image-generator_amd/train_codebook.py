@@ -37,7 +37,14 @@ def parse_args():
                         "SSIM | used | perplexity and appends one JSON line to <out-dir>/val_log.jsonl")
     p.add_argument("--val-step", type=int, default=None, help="Steps between evaluations (default: --checkpoint-step).")
     p.add_argument("--val-batches", type=int, default=None, help="Score the first batches of the held-out set only.")
-    return vars(p.parse_args())
+    p.add_argument("--val-topology", action="store_true",
+                   help="(additive, not in the reference) the validation pass also measures the codebook's SOM topology "
+                        "(qarig/topology.py): a \"topology\" block in val_log.jsonl and ' | TE: <topographic error>' on "
+                        "the Val line.  Needs --val-dataset-path.")
+    args = p.parse_args()
+    if args.val_topology and args.val_dataset_path is None:
+        p.error("--val-topology needs --val-dataset-path")
+    return vars(args)
 
 
 def main():
@@ -80,11 +87,13 @@ def main():
     def validate(global_steps):
         """Rank 0 alone, like the checkpoint: the other ranks wait at their next exchange."""
         from qarig import recon_eval
-        scorer = recon_eval.ReconScorer(decoder_model, {"codebook": codebook})
+        scorer = recon_eval.ReconScorer(decoder_model, {"codebook": codebook}, topology=args["val_topology"])
         recon_eval.score_loader(scorer, val_loader, device, args["val_batches"])
         block = recon_eval.without_per_image(scorer.result()["codebooks"]["codebook"])
-        cc.validate(out_dir, {"step": global_steps, "codebook": block},
-                    [recon_eval.recon_summary_line("Val", block)], info)
+        line = recon_eval.recon_summary_line("Val", block)
+        if args["val_topology"]:
+            line += " | TE: {:.4f}".format(block["topology"]["topographic_error"])
+        cc.validate(out_dir, {"step": global_steps, "codebook": block}, [line], info)
 
     info(f"{project_name}")
     info(f"Output Dir: {out_dir}")
